@@ -13,6 +13,10 @@ boards (masked no-ops are not counted); they are counted on the device.
     python bench.py --gpus N ...         # N GPUs of this node: starts its own N ranks as child processes
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W      # ... or runs as one of a launcher's ranks
+    python bench.py --dump-outputs DIR   # ... and writes the last timed step's rewards to DIR/rewards.npy (float32)
+
+The timed steps' seeds depend on the arguments only (the time-bound pre-warm runs on an executor of its own), so two
+builds given the same arguments play the same games and their dumps compare element for element.
 
 The loop itself is native (csrc/bgs_pipeline.hip, `simulator.pipeline.RolloutExecutor`): one library call enqueues the
 timed region's K steps on `--inflight` batches / HIP streams in rotation; the hand-over (`--handover codes`, default) is
@@ -595,6 +599,28 @@ def gpu_single_game_latency():
     return us
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, rewards) -> dict:
+    """`--dump-outputs`: the last timed step's rewards int8[rows, 2] as DIR/rewards.npy (float32).  Above 64 MB, a sample of
+    rows drawn with a fixed seed (DIR/rewards_rows.npy: their indices, float64) -- the same rows for the same arguments."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    out = np.asarray(rewards, dtype=np.float32)
+    files = {}
+    if out.nbytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (out.itemsize * out.shape[1] + 8)   # (room for the row indices and the headers)
+        rows = np.sort(np.random.default_rng(SEED).choice(out.shape[0], size=keep, replace=False))
+        out = out[rows]
+        np.save(os.path.join(directory, "rewards_rows.npy"), rows.astype(np.float64))
+        files["rewards_rows"] = [int(rows.size)]
+    np.save(os.path.join(directory, "rewards.npy"), out)
+    files["rewards"] = list(out.shape)
+    return files
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -634,6 +660,9 @@ def main() -> int:
                     "the cost of the strict contract is on the line")
     ap.add_argument("--only-depth", type=int, default=0, help="with --only: batches in flight instead of the config's own")
     ap.add_argument("--only", choices=sorted(OTHER_CONFIGS), help="measure one of the other BASELINE configs and print its JSON object")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rewards of the last timed step (rank 0's host array, float32) to "
+                    "DIR/rewards.npy, a fixed seeded sample of its rows if it exceeds 64 MB: two builds compare output for output")
     args = ap.parse_args()
     if args.gather not in ("shm", "rccl", "both"):
         print("bench.py: --gather must be shm, rccl or both", file=sys.stderr)
@@ -824,13 +853,20 @@ def main() -> int:
             timed_region.rank_spread = (dt_fastest, dt)
             return dt, steps_total, steps_local, kernel_ms
 
-        # untimed: bring the device to its loaded power state (and RCCL to connected peers), then the W warm-up steps
+        # untimed: bring the device to its loaded power state (and RCCL to connected peers), then the W warm-up steps.
+        # The time-bound part runs on an executor of its own (seeds of their own), so that the timed steps' seeds -- seed0 +
+        # step index on `exe` -- do not depend on how many steps the pre-warm took: the same arguments give the same inputs
+        # (--dump-outputs).  One GPU: it hands over through the same sink and host arrays; a shared array or a gather
+        # counts its hand-overs, so there it runs without one and `exe` makes a fixed number of hand-overs behind it.
         prewarm_steps = 0
         if args.prewarm_ms > 0:
+            plain = kind == "sink" and sink is not None
+            warm = RolloutExecutor(batches, sink=sink if plain else None, host_arrays=host_rewards if plain else (),
+                                   seed0=SEED + (1 << 40))
             t_end = time.perf_counter() + args.prewarm_ms * 1e-3
             while True:
-                exe.enqueue(4 * depth, handover != "none")
-                exe.drain()
+                warm.enqueue(4 * depth, plain)
+                warm.drain()
                 prewarm_steps += 4 * depth
                 go_on = time.perf_counter() < t_end
                 if dist is not None:  # every rank makes the same number of (collective) steps
@@ -839,6 +875,10 @@ def main() -> int:
                     go_on = bool(flag.item())
                 if not go_on:
                     break
+            warm.close()
+            exe.enqueue(4 * depth, handover != "none")
+            exe.drain()
+            prewarm_steps += 4 * depth
         exe.enqueue(args.warmup, handover != "none")
         exe.drain()
         elapsed, steps_total, steps_local, kernel_ms = timed_region(args.steps, True, stride)
@@ -849,6 +889,11 @@ def main() -> int:
         final_host = None
         if owner and handover != "none":
             final_host = np.array(ring.array((exe.handovers - 1) % host_slots)) if ring is not None else np.array(exe.last_host_array())
+        # what --dump-outputs writes: the rewards of the last timed step as its caller has them (the host array; without a
+        # hand-over, the batch's own rewards on the device)
+        last_rewards = final_host
+        if owner and last_rewards is None and args.dump_outputs:
+            last_rewards = batches[last % depth].reward
 
         gather_ok = None
         if dist is not None and owner and final_host is not None:
@@ -920,7 +965,7 @@ def main() -> int:
             for b in batches:   # (the launch shape follows the launches in flight: back to the pipeline's)
                 b.set_launches_in_flight(depth)
         result = {"kind": kind, "elapsed": elapsed, "steps_total": steps_total, "steps_local": steps_local, "kernel_ms": kernel_ms,
-                  "last": last, "final_host": final_host, "gather_ok": gather_ok, "repeats": repeats, "solo": solo, "rng_other": rng_other,
+                  "last": last, "final_host": final_host, "last_rewards": last_rewards, "gather_ok": gather_ok, "repeats": repeats, "solo": solo, "rng_other": rng_other,
                   "device_resident": device_resident, "prewarm_steps": prewarm_steps, "host_slots": host_slots,
                   "host_threads": host_threads, "rows": rows, "note": note, "rank_spread": rank_spread}
         exe.close()
@@ -1132,6 +1177,11 @@ def main() -> int:
             extra["other_configs"] = early_other if early_other is not None else other_configs()
     if failed:
         extra["failed_handovers"] = failed
+    if args.dump_outputs and rank == 0:
+        good = [r for r in results if "error" not in r]
+        primary = next((r for r in good if r["kind"] == "rccl"), good[0])   # (the hand-over that carries `value`)
+        extra["dump_outputs"] = {"dir": args.dump_outputs, "seed": SEED + primary["last"],
+                                 "shapes": dump_outputs(args.dump_outputs, primary["last_rewards"])}
     emit(extra)
     if dist is not None:
         # The ranks part company here.  If a hand-over failed on some rank only, the others may never reach this barrier:

@@ -266,3 +266,26 @@ def test_round6_rehearsals_value_is_the_rccl_gathers():
         assert d["value"] == pytest.approx(d["gather_rccl"]["value"]) and "failed_handovers" not in d
         assert d["gather_shm"]["gathered_rewards_verified"] is True and d["gather_rccl"]["gathered_rewards_verified"] is True
         assert 0 < d["ms_per_step_fastest_rank"] <= d["ms_per_step_slowest_rank"]
+
+
+def test_dump_outputs_writes_float32_within_64_mb(tmp_path):
+    """bench.dump_outputs: the rewards as they are when they fit, a seeded sample of rows (the same every time, with their
+    indices) when they do not -- never more than 64 MB."""
+    import numpy as np
+
+    sys.path[:0] = [ROOT]
+    import bench
+
+    small = np.random.default_rng(3).integers(-1, 2, size=(1 << 12, 2)).astype(np.int8)
+    assert bench.dump_outputs(str(tmp_path / "a"), small) == {"rewards": [1 << 12, 2]}
+    got = np.load(tmp_path / "a" / "rewards.npy")
+    assert got.dtype == np.float32 and (got == small).all() and not (tmp_path / "a" / "rewards_rows.npy").exists()
+
+    big = np.random.default_rng(4).integers(-1, 2, size=(9 << 20, 2)).astype(np.int8)
+    for name in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / name), big)
+        assert sum(f.stat().st_size for f in (tmp_path / name).iterdir()) <= 64 << 20
+    rows = np.load(tmp_path / "b" / "rewards_rows.npy")
+    assert rows.dtype == np.float64 and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(rows, np.load(tmp_path / "c" / "rewards_rows.npy"))
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "rewards.npy"), big[rows.astype(np.int64)])

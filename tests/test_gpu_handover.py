@@ -945,3 +945,29 @@ def test_bench_under_the_strict_rng_contract():
     other = d["rng_other"]
     assert other["rng"].startswith("per-block") and other["parity_with_oracle_first_4096"] is True and other["value"] > 0
     assert d["value"] > 0 and d["rccl_ranks"] is None
+
+
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """`bench.py --dump-outputs DIR`: the rewards of the last timed step, as rank 0's host array holds them, in float32 --
+    the same from run to run with the same arguments (the time-bound pre-warm does not move the timed steps' seeds) and the
+    oracle's for that step's seed."""
+    dumps, lines = [], []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--batch", str(1 << 16),
+               "--prewarm-ms", "30", "--no-cpu-baseline", "--no-other-configs", "--no-repeats", "--no-device-resident",
+               "--dump-outputs", str(out)]
+        proc = subprocess.run(cmd, env=product_env(BGS_BENCH_SOLO="0"), capture_output=True, text=True, timeout=300)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        lines.append(json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1]))
+        dumps.append(np.load(out / "rewards.npy"))
+    d = lines[0]
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["dump_outputs"]["shapes"] == {"rewards": [1 << 16, 2]}
+    assert lines[1]["dump_outputs"]["seed"] == d["dump_outputs"]["seed"]
+    # the timed steps follow one fixed chunk of 4 x 3 hand-overs behind the pre-warm and the warm-up step
+    assert d["dump_outputs"]["seed"] == SEED + 4 * d["config"]["inflight_batches"] + 1 + 5 - 1
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (1 << 16, 2)
+    np.testing.assert_array_equal(dumps[0], dumps[1])
+    orc = oracle.ConnectOracle(6, 7, 4, 1 << 16)
+    orc.rollout(d["dump_outputs"]["seed"])
+    np.testing.assert_array_equal(dumps[0], orc.reward.astype(np.float32))
