@@ -22,6 +22,7 @@
 extern "C" const char bgs_tu_id_connect[];
 extern "C" const char bgs_tu_id_bounce[];
 extern "C" const char bgs_tu_id_generic[];
+extern "C" const char bgs_tu_id_evaluate[];
 
 namespace {
 thread_local char g_error[512] = "";
@@ -646,14 +647,14 @@ extern "C" {
 
 int bgs_version(void) { return 200; }
 
-// The identity of the kernels this library was LINKED with: the three units' own ids folded into 16 hex digits (the same
+// The identity of the kernels this library was LINKED with: the four units' own ids folded into 16 hex digits (the same
 // fold as `make print-id`: h = id_0; h = h * 0x100000001b3 ^ id_k, 64-bit wrap-around).  "unknown..." when a unit was
 // compiled outside the Makefile.
 const char* bgs_build_id(void) {
     static const std::string id = [] {
         uint64_t h = 0;
         bool first = true;
-        for (const char* tu : {bgs_tu_id_connect, bgs_tu_id_bounce, bgs_tu_id_generic}) {
+        for (const char* tu : {bgs_tu_id_connect, bgs_tu_id_bounce, bgs_tu_id_generic, bgs_tu_id_evaluate}) {
             char* end = nullptr;
             const uint64_t v = strtoull(tu, &end, 16);
             if (end == tu || *end != 0) return std::string("unknown");
@@ -672,6 +673,7 @@ const char* bgs_kernel_unit_id(int unit) {
         case 0: return bgs_tu_id_connect;
         case 1: return bgs_tu_id_bounce;
         case 2: return bgs_tu_id_generic;
+        case 3: return bgs_tu_id_evaluate;
         default: return nullptr;
     }
 }
@@ -1021,6 +1023,35 @@ int bgs_rollout(bgs_batch* b, uint64_t seed, int32_t max_plies, uint32_t flags) 
     else if (b->game == BGS_GAME_CONNECT) (void)bgs::connect_rollout(b, seed, max_plies, flags, nullptr);
     else bgs::bounce_rollout(b, seed, max_plies, flags);
     return finish_launch();
+}
+
+int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
+                                 int counts_on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(counts != nullptr, "counts is NULL");
+    NEED(b->game == BGS_GAME_CONNECT, "evaluate_actions: Connect batches only (Bounce boards are not supported yet)");
+    NEED(!b->generic, "evaluate_actions: bit-packed Connect boards only (up to %d bits a plane); %dx%d boards are generic",
+         64 * BGS_CONNECT_MAX_WORDS, b->cg.h, b->cg.w);
+    NEED(playouts >= 1, "playouts must be >= 1 (got %d)", playouts);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    NEED(!counts_on_device || (reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
+    NEED(b->n <= INT64_MAX / b->cg.w / playouts, "n * width * playouts overflows int64 (%lld x %d x %d)", (long long)b->n,
+         b->cg.w, playouts);
+    const size_t bytes = (size_t)b->n * b->cg.w * 3 * sizeof(int32_t);
+    if (counts_on_device) {
+        bgs::connect_evaluate(b, seed, playouts, max_plies, counts);
+        return finish_launch();
+    }
+    int32_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
+    bgs::connect_evaluate(b, seed, playouts, max_plies, d);
+    rc = finish_launch();
+    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, bytes);
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
 }
 
 int bgs_steps(bgs_batch* b, uint64_t* steps) {

@@ -131,6 +131,10 @@ void connect_legal(const bgs_batch* b, uint8_t* d_legal, int32_t* d_count);
 void connect_pack(const bgs_batch* b, const int8_t* d_grid, const int8_t* d_player, const int8_t* d_winner,
                   int32_t* d_status_out);
 
+// ---- flat Monte-Carlo evaluation of packed Connect boards (evaluate_kernels.hip): counts int32[n][w][3] on the device,
+// 16-byte aligned; enqueued on the batch's stream ----
+void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts);
+
 // ---- Bounce (bounce_kernels.hip) ----
 void bounce_reset(const bgs_batch* b);
 void bounce_step_random(const bgs_batch* b, uint64_t seed, uint32_t count);

@@ -781,6 +781,31 @@ class ConnectBatch(_Batch):
         """columns int32[n]; a negative entry skips the board.  Returns per-board status (0 / -2 illegal)."""
         return self._step_actions(columns, 1, want_status)
 
+    def evaluate_actions(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1) -> np.ndarray:
+        """Flat Monte-Carlo evaluation of every column of every board (bgs_connect_evaluate_actions), one launch:
+        int32[n, width, 3] = (wins, draws, losses) of the player to move, over `playouts` games that start with that
+        column and continue by the uniform random policy until they end or hold `max_plies` plies (a capped game counts in
+        none of the three).  Illegal columns and ended boards give 0, 0, 0.  The boards are not modified.  Playout p of
+        column c of board i is game ((first_game + i) * width + c) * playouts + p of the batch's RNG contract."""
+        out = np.empty((self.n, self.width, 3), dtype=np.int32)
+        _abi.check(_abi.lib().bgs_connect_evaluate_actions(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
+                                                           ctypes.c_int32(max_plies), ctypes.c_void_p(out.ctypes.data), 0))
+        return out
+
+    def evaluate_actions_tensor(self, out=None, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1):
+        """`evaluate_actions` into a device tensor int32[n, width, 3] (allocated when None), enqueued on the batch's stream
+        with no synchronisation.  Every entry is written."""
+        t = self._need_torch("evaluate_actions_tensor")
+        shape = (self.n, self.width, 3)
+        if out is None:
+            out = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
+        if not (out.is_cuda and out.dtype == t.int32 and tuple(out.shape) == shape and out.is_contiguous()
+                and out.data_ptr() % 16 == 0):
+            raise TypeError(f"out must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        _abi.check(_abi.lib().bgs_connect_evaluate_actions(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
+                                                           ctypes.c_int32(max_plies), ctypes.c_void_p(out.data_ptr()), 1))
+        return out
+
     @property
     def legal(self) -> np.ndarray:
         out = np.empty((self.n, self.width), dtype=np.uint8)
@@ -858,6 +883,12 @@ class BounceBatch(_Batch):
         )
         self._cells = tuple((c % self.width, c // self.width) for c in range(self.height * self.width))
         self._after_create()
+
+    def evaluate_actions(self, *args, **kwargs):
+        """Not available for Bounce: flat Monte-Carlo evaluation covers bit-packed Connect boards only."""
+        raise ValueError("evaluate_actions: Connect batches only (Bounce boards are not supported yet)")
+
+    evaluate_actions_tensor = evaluate_actions
 
     def step_actions(self, moves, want_status: bool = True):
         """moves int32[n, 4] = source x, y, target x, y; a negative first entry skips the board."""

@@ -72,6 +72,9 @@ SIGNATURES = {
     "bgs_step_random_n": (ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32]),
     "bgs_step_actions": (ctypes.c_int, [c_handle, ctypes.c_void_p, ctypes.c_int, _i32p]),
     "bgs_rollout": (ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32]),
+    "bgs_connect_evaluate_actions": (
+        ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int]
+    ),
     "bgs_steps": (ctypes.c_int, [c_handle, _u64p]),
     "bgs_reset_steps": (ctypes.c_int, [c_handle]),
     "bgs_read_grid": (ctypes.c_int, [c_handle, _i8p]),
@@ -311,6 +314,15 @@ def unit_ids() -> dict:
     its own unit header and the compile flags).  Counter files under profiles/ name the unit id of the kernel they
     describe; an edit to one unit leaves the others' counters quotable."""
     return {name: (lib().bgs_kernel_unit_id(k) or b"unknown").decode("ascii") for k, name in enumerate(UNITS)}
+
+
+# kernel units beyond UNITS (bench.py records UNITS alone, and its line stays as it was): index -> name
+EXTRA_UNITS = {3: "evaluate"}
+
+
+def extra_unit_ids() -> dict:
+    """{"evaluate": id}: the ids of the kernel units that are not in UNITS (bgs_kernel_unit_id(3) on)."""
+    return {name: (lib().bgs_kernel_unit_id(k) or b"unknown").decode("ascii") for k, name in EXTRA_UNITS.items()}
 
 
 def device_count() -> int:

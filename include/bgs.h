@@ -92,11 +92,12 @@ BGS_API int bgs_version(void);
 BGS_API const char* bgs_last_error(void);
 BGS_API int bgs_device_count(int* count);
 /* identity of the kernels this library was LINKED with (16 hex digits): every kernel translation unit embeds the hash of
- * its own source, the kernel headers and the compile flags when it is compiled, and this folds the three.  Measurement
+ * its own source, the kernel headers and the compile flags when it is compiled, and this folds the four.  Measurement
  * files under profiles/ carry the id of the build they were taken on, and bench.py refuses to quote instruction counts
  * of another build.  `make -C csrc print-id` gives the id the sources in the tree would produce. */
 BGS_API const char* bgs_build_id(void);
-/* the id one kernel unit was compiled with: 0 connect_kernels, 1 bounce_kernels, 2 generic_kernels; NULL otherwise */
+/* the id one kernel unit was compiled with: 0 connect_kernels, 1 bounce_kernels, 2 generic_kernels, 3 evaluate_kernels;
+ * NULL otherwise */
 BGS_API const char* bgs_kernel_unit_id(int unit);
 
 /* ---- configuration + batch lifetime ------------------------------------------------------------- */
@@ -169,6 +170,19 @@ BGS_API int bgs_step_actions(bgs_batch* b, const int32_t* actions, int actions_o
 /* plies until every board ended or holds max_plies plies (README.md:52 `while not state.has_ended`), fused in
  * one launch with the board in registers */
 BGS_API int bgs_rollout(bgs_batch* b, uint64_t seed, int32_t max_plies, uint32_t flags);
+/* Flat Monte-Carlo evaluation of every legal column of every board (Connect, bit-packed boards only).
+ * counts int32[n][width][3] = (wins, draws, losses) of the player to move at board i, over `playouts` games that
+ * start with column c and then continue by the batch's uniform random policy and RNG contract until they end or
+ * hold max_plies plies; a capped game is counted in none of the three.  Illegal columns and ended boards: 0, 0, 0.
+ * The batch's boards are not modified; the transitions played are added to bgs_steps.  counts_on_device != 0: a
+ * device pointer (16-byte aligned), enqueued on the batch's stream, no synchronisation, no allocation; otherwise a
+ * host buffer and the call returns when it is filled.
+ * RNG: playout p of column c of board i is the game with global id G = ((first_game + i) * width + c) * playouts + p
+ * (mod 2^64), played from board i after column c, its draws keyed by (seed, G, ply) under the batch's contract, ply the
+ * board's absolute ply count: the playouts of board i in (c, p) order are a bgs_rollout(seed) with first_game =
+ * first_game * width * playouts over the boards replicated width * playouts times and stepped by their column. */
+BGS_API int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies,
+                                         int32_t* counts, int counts_on_device);
 /* env-steps (transitions applied to running boards) since the last bgs_reset / bgs_reset_steps */
 BGS_API int bgs_steps(bgs_batch* b, uint64_t* steps);
 BGS_API int bgs_reset_steps(bgs_batch* b);
