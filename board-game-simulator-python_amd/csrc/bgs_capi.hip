@@ -376,6 +376,11 @@ int device_facts(bgs_batch* b) {
         const int v = atoi(env);
         if (v >= 1 && v <= 8) b->bounce_flat_wps = v;
     }
+    b->bounce_eval_wps = 0;
+    if (const char* env = bgs::experiment("bounce_eval_wps")) {
+        const int v = atoi(env);
+        if (v >= 1 && v <= 8) b->bounce_eval_wps = v;
+    }
     // multi-pass Bounce rollout (bounce_kernels.hip, bounce_rollout): "cap:lanes,..."; the last entry's cap is the
     // caller's max_plies whatever it says; "single" = one launch that plays every game to the end
     {
@@ -1046,6 +1051,41 @@ int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, 
     int32_t* d = nullptr;
     HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
     bgs::connect_evaluate(b, seed, playouts, max_plies, d);
+    rc = finish_launch();
+    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, bytes);
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
+int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
+                              int counts_on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(counts != nullptr, "counts is NULL");
+    NEED(b->game == BGS_GAME_BOUNCE, "evaluate_moves: Bounce batches only (Connect boards: bgs_connect_evaluate_actions)");
+    NEED(!b->generic, "evaluate_moves: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
+         BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
+    NEED(playouts >= 1, "playouts must be >= 1 (got %d)", playouts);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    NEED(!counts_on_device || (reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
+    const int64_t slots = (int64_t)b->bg.w * b->bg.h * b->bg.w;
+    NEED(b->n <= INT64_MAX / slots / playouts, "n * width * height * width * playouts overflows int64 (%lld x %lld x %d)",
+         (long long)b->n, (long long)slots, playouts);
+    // scratch: the roots' legal-move prefix and the workgroups' totals, in the staging region (ordered on the stream)
+    Stage st(b);
+    uint64_t* d_ends = st.take<uint64_t>((size_t)b->n);
+    uint64_t* d_totals = st.take<uint64_t>((size_t)(b->n + BGS_BLOCK - 1) / BGS_BLOCK);
+    NEED(d_ends && d_totals, "staging region too small");
+    const size_t bytes = (size_t)b->n * (size_t)slots * 3 * sizeof(int32_t);
+    if (counts_on_device) {
+        bgs::bounce_evaluate(b, seed, playouts, max_plies, counts, d_ends, d_totals);
+        return finish_launch();
+    }
+    int32_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
+    bgs::bounce_evaluate(b, seed, playouts, max_plies, d, d_ends, d_totals);
     rc = finish_launch();
     if (rc == BGS_OK) rc = copy_to_host(b, counts, d, bytes);
     const hipError_t e = hipFreeAsync(d, b->stream);

@@ -35,6 +35,7 @@ struct bgs_batch {
     int bounce_pieces;       // 1: from-initial flat rollouts run on the piece list (K3p; experiment bounce_pieces=0: K3f)
     int bounce_block;        // K3p: threads per workgroup, 256 / 512 / 1024 (experiment bounce_block): the waves of a workgroup share their drain
     int bounce_flat_wps;     // waves per SIMD of a flat Bounce rollout launch (experiment bounce_flat_wps)
+    int bounce_eval_wps;     // waves per SIMD of bgs_bounce_evaluate_moves (0: the evaluate unit's default; experiment bounce_eval_wps)
     int bounce_flat_waves;   // > 0: that many waves per launch instead (experiment bounce_flat_waves)
     int bounce_pool;         // K3p: the last wave of a workgroup parks its boards for other workgroups (experiment bounce_pool=0: off)
     int bounce_pieces_park;  // K3p: a draining wave parks its boards at this many or fewer (0..63; experiment bounce_pieces_park, else experiment bounce_park, else -1 = bounce_shape().park)
@@ -134,6 +135,10 @@ void connect_pack(const bgs_batch* b, const int8_t* d_grid, const int8_t* d_play
 // ---- flat Monte-Carlo evaluation of packed Connect boards (evaluate_kernels.hip): counts int32[n][w][3] on the device,
 // 16-byte aligned; enqueued on the batch's stream ----
 void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts);
+// ... of packed Bounce boards: counts int32[n][w][h * w][3] on the device (zeroed and filled here, 16-byte aligned);
+// d_ends uint64[n] and d_totals uint64[(n + 255) / 256] are scratch (the batch's staging region); enqueued on the stream
+void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts, uint64_t* d_ends,
+                     uint64_t* d_totals);
 
 // ---- Bounce (bounce_kernels.hip) ----
 void bounce_reset(const bgs_batch* b);

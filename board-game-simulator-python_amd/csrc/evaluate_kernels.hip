@@ -1,5 +1,6 @@
 // evaluate_kernels.hip -- flat Monte-Carlo evaluation of every column of a batch of packed Connect boards
-// (bgs_connect_evaluate_actions): for board i and column c, `playouts` games that start with column c on board i and
+// (bgs_connect_evaluate_actions), and of every move of a batch of packed Bounce boards (bgs_bounce_evaluate_moves, the
+// second half of this file).  Connect: for board i and column c, `playouts` games that start with column c on board i and
 // continue by the uniform random policy, reduced on the device to (wins, draws, losses) of the player to move at board i.
 //
 // Game ids (include/bgs.h): playout p of column c of board i is global game
@@ -415,7 +416,494 @@ void launch_evaluate(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint3
     }
 }
 
+// ================================================================================================================
+// Bounce (bgs_bounce_evaluate_moves): for root i and slot s = x * H * W + c -- the move of the piece in column x of the
+// active row to cell c, bit c of the root's targets[x] -- `playouts` games that start with that move and continue by the
+// uniform random policy, reduced to (wins, draws, losses) of the player to move at root i.  Playout p of slot s of root i
+// is global game ((first_game + i) * S + s) * P + p, S = W * H * W, drawn under Bounce's contract (a philox word per ply,
+// keyed by the board's absolute ply): an oracle rollout(seed, first_game * S * P) over the roots replicated S * P times
+// and stepped by their slot's move, illegal slots dropped.
+//
+// The ply below restates, on the Bounce unit's packing (bounce_kernels.hip: four value bit-planes, cell y * W + x), what
+// its `movable` / `reach` / `enumerate_flat` / `pick_flat` / `move_piece` do -- the one-lane-per-board ply of K3f, whose
+// target masks live in a per-lane dword column of LDS.  It reads boards from memory and never assumes they descend from
+// the configured start position (K3p's piece list does).
+//
+// Shape.  A first pass counts the legal moves of every root and scans them (uint64 inclusive prefix `ends` in the
+// staging region): the legal (root, slot) segments are numbered 0 .. ends[n-1] - 1 in (root, slot) order, their playouts
+// 0 .. ends[n-1] * P - 1 in (segment, playout) order.  Persistent waves draw chunks of that sequence from a device-wide
+// counter and refill their idle lanes from it at ply boundaries (K3f's refill loop): a lane plays one game at a time,
+// keeps the stepped board of its current segment in registers for every playout of that segment it takes, and counts
+// W/D/L in registers.  A lane flushes its counts when it changes segment: into the wave's LDS tally when the segment
+// lies in the window of its current chunk (a chunk spans at most kBounceEvalWindow segments), by global atomics
+// otherwise; the window goes out by one atomic per segment and counter when the wave takes its next chunk.  Counts are
+// zeroed by the launcher.  Games that never end stay in the bulk kernel up to the cap: the dynamic queue keeps the other
+// lanes of their wave busy until it runs dry (docs/EXPERIMENTS.md: the tail's share of a launch).
+// ================================================================================================================
+constexpr uint32_t kBounceEvalWindow = 64;        // segments of a wave's LDS tally = most segments a chunk spans
+constexpr uint32_t kBounceEvalChunk = 512;        // playouts a wave draws at a time (fewer when P is small: <= 63 * P)
+constexpr uint32_t kBounceMaxPlies = 65535u;      // plies are uint16 (the Bounce unit's kMaxPlies)
+// persistent waves per SIMD (the kernel holds 5 by its registers).  Default board, max_plies 1024, 10^9 env-steps/s at
+// 256 roots x 256 playouts / 4096 x 64: 1 wave 2.01 / 2.47, 2 waves 2.71 / 4.09, 4 waves 2.88 / 5.13 (docs/EXPERIMENTS.md §16)
+constexpr int kBounceEvalWps = 4;
+
+struct BBoard {
+    uint64_t v[4];
+};
+
+__device__ __forceinline__ uint64_t b_occupancy(const BBoard& b) { return b.v[0] | b.v[1] | b.v[2] | b.v[3]; }
+
+__device__ __forceinline__ uint32_t b_value_at(const BBoard& b, int c) {
+    return (uint32_t)((b.v[0] >> c) & 1ull) | ((uint32_t)((b.v[1] >> c) & 1ull) << 1) |
+           ((uint32_t)((b.v[2] >> c) & 1ull) << 2) | ((uint32_t)((b.v[3] >> c) & 1ull) << 3);
+}
+
+// pieces the side to move may pick: the occupied non-goal row nearest its own side
+template <class GEO>
+__device__ __forceinline__ uint64_t b_movable(const GEO& g, uint64_t occ, uint32_t player) {
+    const uint64_t oi = occ & g.interior;
+    if (!oi) return 0;
+    const int cell = player ? 63 - __clzll((long long)oi) : __ffsll((unsigned long long)oi) - 1;
+    const int row = (int)(((uint32_t)cell * g.inv_w) >> 16);
+    return oi & (((1ull << g.w) - 1ull) << (row * g.w));
+}
+
+// one segment of v steps from cell c (the frontier walk of the Bounce unit's reach): the cells it ends on
+template <class GEO>
+__device__ __forceinline__ uint64_t b_segment(const GEO& g, uint32_t v, int c, uint64_t empty_interior, uint32_t up, uint32_t down) {
+    uint64_t a0 = 1ull << c, al = 0, ar = 0, land = 0;
+    for (uint32_t s = 1; s <= v; ++s) {
+        const uint64_t via_left = a0 | al, via_right = a0 | ar;   // no immediate left <-> right reversal
+        const uint64_t nf = ((via_left | ar) << up) >> down;
+        const uint64_t nl = (via_left & g.not_col0) >> 1;
+        const uint64_t nr = (via_right & g.not_collast) << 1;
+        if (s < v) {
+            a0 = nf & empty_interior;
+            al = nl & empty_interior;
+            ar = nr & empty_interior;
+            if (!(a0 | al | ar)) break;
+        } else {
+            land = nf | nl | nr;
+        }
+    }
+    return land;
+}
+
+// every legal landing cell of the piece on `src` for `player` (a lane's own loop: roots only)
+template <class GEO>
+__device__ __forceinline__ uint64_t b_reach(const GEO& g, const BBoard& b, uint64_t occ, uint32_t player, int src) {
+    const uint64_t empty_interior = ~occ & g.interior;
+    const uint64_t landing = empty_interior | (player ? g.goal_bottom : g.goal_top);
+    const uint64_t bounce_on = occ & g.interior;
+    const uint32_t up = player ? 0u : (uint32_t)g.w, down = player ? (uint32_t)g.w : 0u;
+    uint64_t pending = 1ull << src, done = 0, targets = 0;
+    while (pending) {
+        const int c = __ffsll((unsigned long long)pending) - 1;
+        pending &= pending - 1;
+        done |= 1ull << c;
+        const uint64_t land = b_segment(g, b_value_at(b, c), c, empty_interior, up, down);
+        targets |= land & landing;
+        pending |= land & bounce_on & ~done;
+    }
+    return targets;
+}
+
+// the action list of a board: per-column target counts packed a byte each (a source has at most 64 targets), masks in
+// the lane's LDS column ([dword][lane]).  NC words of counts: boards up to 8 * NC columns.
+template <int NC>
+struct BMoves {
+    uint64_t counts[NC];
+    uint32_t n;          // number of actions
+    uint32_t row_base;   // cell index of column 0 of the active row
+};
+
+// K3f's flattened search: one loop a wave, every lane expanding one cell of its own queue per iteration; lanes without
+// `want` idle through it and keep their column and list
+template <class GEO, int NC>
+__device__ __forceinline__ void b_enumerate(const GEO& g, const BBoard& b, uint64_t occ, uint32_t player, bool want,
+                                            uint32_t* column, BMoves<NC>& m) {
+    const uint64_t empty_interior = ~occ & g.interior;
+    const uint64_t landing = empty_interior | (player ? g.goal_bottom : g.goal_top);
+    const uint64_t bounce_on = occ & g.interior;
+    const uint32_t up = player ? 0u : (uint32_t)g.w, down = player ? (uint32_t)g.w : 0u;
+    uint64_t rem = want ? b_movable(g, occ, player) : 0ull;
+    if (want) {
+        const int first = rem ? __ffsll((unsigned long long)rem) - 1 : 0;
+        m.row_base = (uint32_t)((int)(((uint32_t)first * g.inv_w) >> 16) * g.w);
+#pragma unroll
+        for (int k = 0; k < NC; ++k) m.counts[k] = 0;
+        m.n = 0;
+    }
+    uint64_t pending = 0, done = 0, targets = 0;
+    uint32_t x = 0;
+    bool open_source = false;
+    while (__builtin_amdgcn_ballot_w64(rem != 0 || pending != 0 || open_source)) {
+        if (pending == 0) {
+            if (open_source) {   // the source's closure is complete: book it
+                const uint32_t cnt = (uint32_t)__popcll(targets);
+#pragma unroll
+                for (int k = 0; k < NC; ++k) m.counts[k] |= (x >> 3) == (uint32_t)k ? (uint64_t)cnt << (8u * (x & 7u)) : 0ull;
+                m.n += cnt;
+                column[(2u * x) * BGS_BLOCK] = (uint32_t)targets;
+                column[(2u * x + 1u) * BGS_BLOCK] = (uint32_t)(targets >> 32);
+                open_source = false;
+            }
+            if (rem) {
+                const int cell = __ffsll((unsigned long long)rem) - 1;
+                rem &= rem - 1;
+                x = (uint32_t)cell - m.row_base;
+                pending = 1ull << cell;
+                done = 0;
+                targets = 0;
+                open_source = true;
+            }
+        }
+        if (pending) {
+            const int c = __ffsll((unsigned long long)pending) - 1;
+            pending &= pending - 1;
+            done |= 1ull << c;
+            const uint64_t land = b_segment(g, b_value_at(b, c), c, empty_interior, up, down);
+            targets |= land & landing;
+            pending |= land & bounce_on & ~done;
+        }
+    }
+}
+
+// the idx-th action of the canonical list (sources by ascending x, targets by ascending cell)
+template <int NC>
+__device__ __forceinline__ void b_pick(const BMoves<NC>& m, const uint32_t* column, uint32_t idx, int& src_cell, int& dst_cell) {
+    uint32_t col = 0;
+    bool found = false;
+#pragma unroll
+    for (int x = 0; x < 8 * NC; ++x) {
+        const uint32_t cnt = (uint32_t)(m.counts[x >> 3] >> (8 * (x & 7))) & 255u;
+        const bool here = !found && idx < cnt;
+        col = here ? (uint32_t)x : col;
+        idx = (found || here) ? idx : idx - cnt;
+        found = found || here;
+    }
+    const uint64_t chosen = ((uint64_t)column[(2u * col + 1u) * BGS_BLOCK] << 32) | column[(2u * col) * BGS_BLOCK];
+    src_cell = (int)(m.row_base + col);
+    dst_cell = (int)select_bit64(chosen, idx);
+}
+
+__device__ __forceinline__ void b_move(BBoard& b, int src_cell, int dst_cell) {
+    const uint32_t v = b_value_at(b, src_cell);
+    const uint64_t keep = ~(1ull << src_cell);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b.v[j] = (b.v[j] & keep) | ((uint64_t)((v >> j) & 1u) << dst_cell);
+}
+
+__device__ __forceinline__ BBoard b_load(const uint64_t* __restrict__ planes, int64_t n, int64_t i) {
+    BBoard b;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b.v[j] = planes[(int64_t)j * n + i];
+    return b;
+}
+
+// legal moves of a root: 0 when it has ended or holds the most plies a board can (a move could not be stored)
+template <class GEO>
+__device__ __forceinline__ uint32_t b_root_moves(const GEO& g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status,
+                                                 const uint16_t* __restrict__ plies_buf, int64_t n, int64_t i) {
+    if (status[i] != BGS_ST_RUNNING || plies_buf[i] >= kBounceMaxPlies) return 0u;
+    const BBoard b = b_load(planes, n, i);
+    const uint64_t occ = b_occupancy(b);
+    const uint32_t player = plies_buf[i] & 1u;
+    uint64_t src = b_movable(g, occ, player);
+    uint32_t cnt = 0;
+    while (src) {
+        const int s = __ffsll((unsigned long long)src) - 1;
+        src &= src - 1;
+        cnt += (uint32_t)__popcll(b_reach(g, b, occ, player, s));
+    }
+    return cnt;
+}
+
+// ---- the first pass: legal moves a root -> ends[i] (inclusive prefix over the batch), in three small kernels
+// (each workgroup scans its 256 roots; one workgroup scans the workgroups' totals; the totals are added back)
+__device__ __forceinline__ uint64_t block_inclusive_scan(uint64_t v, uint64_t* lds) {
+    lds[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t off = 1; off < BGS_BLOCK; off <<= 1) {
+        const uint64_t add = threadIdx.x >= off ? lds[threadIdx.x - off] : 0ull;
+        __syncthreads();
+        lds[threadIdx.x] += add;
+        __syncthreads();
+    }
+    return lds[threadIdx.x];
+}
+
+template <class GEO>
+__global__ void __launch_bounds__(BGS_BLOCK)
+k_bounce_eval_count(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, const uint16_t* __restrict__ plies_buf,
+                    int64_t n, uint64_t* __restrict__ ends, uint64_t* __restrict__ totals) {
+    __shared__ uint64_t lds[BGS_BLOCK];
+    const int64_t i = (int64_t)blockIdx.x * BGS_BLOCK + threadIdx.x;
+    const uint64_t mine = i < n ? b_root_moves(g, planes, status, plies_buf, n, i) : 0ull;
+    const uint64_t incl = block_inclusive_scan(mine, lds);
+    if (i < n) ends[i] = incl;
+    if (threadIdx.x == BGS_BLOCK - 1) totals[blockIdx.x] = incl;
+}
+
+// totals[0 .. blocks) -> exclusive prefix, in place (one workgroup, a contiguous run of entries a thread)
+__global__ void __launch_bounds__(BGS_BLOCK) k_bounce_eval_scan_totals(uint64_t* __restrict__ totals, int64_t blocks) {
+    __shared__ uint64_t lds[BGS_BLOCK];
+    const int64_t per = (blocks + BGS_BLOCK - 1) / BGS_BLOCK;
+    const int64_t lo = (int64_t)threadIdx.x * per, hi = lo + per < blocks ? lo + per : blocks;
+    uint64_t sum = 0;
+    for (int64_t k = lo; k < hi; ++k) sum += totals[k];
+    uint64_t run = block_inclusive_scan(sum, lds) - sum;
+    for (int64_t k = lo; k < hi; ++k) {
+        const uint64_t t = totals[k];
+        totals[k] = run;
+        run += t;
+    }
+}
+
+__global__ void __launch_bounds__(BGS_BLOCK)
+k_bounce_eval_add_totals(uint64_t* __restrict__ ends, const uint64_t* __restrict__ totals, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * BGS_BLOCK + threadIdx.x;
+    if (i < n && blockIdx.x) ends[i] += totals[blockIdx.x];
+}
+
+template <class GEO, int NC>
+__global__ void __launch_bounds__(BGS_BLOCK)
+k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, const uint16_t* __restrict__ plies_buf,
+                  int64_t n, uint64_t seed, uint64_t game_base, uint32_t playouts, uint32_t max_plies, uint32_t slots,
+                  const uint64_t* __restrict__ ends, unsigned long long* __restrict__ queue, uint32_t chunk,
+                  int32_t* __restrict__ counts, unsigned long long* __restrict__ steps) {
+    extern __shared__ uint32_t target_tile[];   // [2 * 8 * NC dwords][256 lanes]
+    __shared__ uint32_t tally_lds[kEvalWavesPerBlock][kBounceEvalWindow * 3];
+    __shared__ uint64_t where_lds[kEvalWavesPerBlock][kBounceEvalWindow];   // root * S + slot of a window segment
+    uint32_t* const column = target_tile + threadIdx.x;
+    const uint32_t lane = threadIdx.x & (BGS_WAVE - 1);
+    uint32_t* const tally = tally_lds[threadIdx.x >> 6];
+    uint64_t* const where = where_lds[threadIdx.x >> 6];
+    for (uint32_t k = lane; k < kBounceEvalWindow * 3; k += BGS_WAVE) tally[k] = 0;
+
+    const uint64_t total = ends[n - 1] * (uint64_t)playouts;   // playouts of the batch
+    const uint32_t hw = (uint32_t)(g.h * g.w);
+    uint64_t c_next = 0, c_end = 0;   // (wave-uniform) the wave's chunk: playouts [c_next, c_end) still to hand out
+    uint64_t win_base = 0;            // (wave-uniform) first segment of the tally's window
+    bool dry = false;
+
+    BBoard b, cb;                     // the lane's game; the board after its segment's first move
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b.v[j] = cb.v[j] = 0;
+    BMoves<NC> mv;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) mv.counts[k] = 0;
+    mv.n = 0;
+    mv.row_base = 0;
+    uint32_t st = 0, plies = 0, child_st = 0, child_ply = 0, root_mover = 0, stepped = 0;
+    uint32_t wins = 0, draws = 0, losses = 0;
+    uint64_t cur_seg = ~0ull, cur_where = 0, game = 0;
+    bool has = false, search = false, have_block = false;
+    Philox4 blk;
+    blk.v[0] = blk.v[1] = blk.v[2] = blk.v[3] = 0;
+
+    auto count = [&](uint32_t s) {   // s: status of a finished game (0: capped, counted nowhere)
+        wins += (s != 0u && s != BGS_ST_DRAW && s - 1u == root_mover) ? 1u : 0u;
+        losses += (s != 0u && s != BGS_ST_DRAW && s - 1u != root_mover) ? 1u : 0u;
+        draws += s == BGS_ST_DRAW ? 1u : 0u;
+    };
+    auto flush = [&]() {   // this lane's counts of cur_seg -> the window, or global memory
+        if (wins | draws | losses) {
+            const uint64_t k = cur_seg - win_base;
+            if (cur_seg >= win_base && k < kBounceEvalWindow) {
+                where[k] = cur_where;
+                if (wins) atomicAdd(tally + 3 * k + 0, wins);
+                if (draws) atomicAdd(tally + 3 * k + 1, draws);
+                if (losses) atomicAdd(tally + 3 * k + 2, losses);
+            } else {
+                int32_t* c = counts + cur_where * 3;
+                if (wins) atomicAdd(c + 0, (int32_t)wins);
+                if (draws) atomicAdd(c + 1, (int32_t)draws);
+                if (losses) atomicAdd(c + 2, (int32_t)losses);
+            }
+        }
+        wins = draws = losses = 0;
+    };
+    auto drain = [&]() {   // the window -> global memory (every lane has flushed into it)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+        const uint32_t k = lane;   // (kBounceEvalWindow == BGS_WAVE)
+        const uint32_t t0 = tally[3 * k], t1 = tally[3 * k + 1], t2 = tally[3 * k + 2];
+        if (t0 | t1 | t2) {
+            int32_t* c = counts + where[k] * 3;
+            if (t0) atomicAdd(c + 0, (int32_t)t0);
+            if (t1) atomicAdd(c + 1, (int32_t)t1);
+            if (t2) atomicAdd(c + 2, (int32_t)t2);
+            tally[3 * k] = tally[3 * k + 1] = tally[3 * k + 2] = 0;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    };
+
+    for (;;) {
+        // ---- refill: idle lanes take the next playouts of the chunk; a spent chunk is replaced from the queue (the
+        // window moves to the new chunk's segments once every lane's counts of the old one are in it)
+        for (;;) {
+            const uint64_t need = __builtin_amdgcn_ballot_w64(!has);
+            if (!need || dry) break;
+            if (c_next >= c_end) {
+                unsigned long long start = 0;
+                if (lane == 0) start = atomicAdd(queue, (unsigned long long)chunk);
+                start = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(start >> 32)) << 32) |
+                        (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)start);
+                if (start >= total) {
+                    dry = true;
+                    break;
+                }
+                flush();
+                drain();
+                c_next = start;
+                c_end = total - start < chunk ? total : start + chunk;
+                win_base = start / playouts;
+            }
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+            const uint64_t avail = c_end - c_next;
+            if (!has && rank < avail) {
+                const uint64_t t = c_next + rank;
+                const uint64_t seg = t / playouts;
+                const uint32_t p = (uint32_t)(t - seg * playouts);
+                if (seg != cur_seg) {
+                    flush();
+                    cur_seg = seg;
+                    // the root: the first i with ends[i] > seg
+                    int64_t lo = 0, hi = n - 1;
+                    while (lo < hi) {
+                        const int64_t mid = (lo + hi) >> 1;
+                        if (ends[mid] > seg) hi = mid;
+                        else lo = mid + 1;
+                    }
+                    const int64_t i = lo;
+                    uint32_t j = (uint32_t)(seg - (i ? ends[i - 1] : 0ull));   // the root's j-th legal move
+                    const BBoard r = b_load(planes, n, i);
+                    const uint32_t rply = plies_buf[i];
+                    root_mover = rply & 1u;
+                    const uint64_t occ = b_occupancy(r);
+                    uint64_t src = b_movable(g, occ, root_mover);
+                    int s_cell = 0, t_cell = 0;
+                    while (src) {
+                        const int s = __ffsll((unsigned long long)src) - 1;
+                        src &= src - 1;
+                        const uint64_t tm = b_reach(g, r, occ, root_mover, s);
+                        const uint32_t cnt = (uint32_t)__popcll(tm);
+                        if (j < cnt) {
+                            s_cell = s;
+                            t_cell = (int)select_bit64(tm, j);
+                            break;
+                        }
+                        j -= cnt;
+                    }
+                    const uint32_t x = (uint32_t)s_cell - (uint32_t)(((uint32_t)s_cell * g.inv_w) >> 16) * (uint32_t)g.w;
+                    cur_where = (uint64_t)i * slots + (uint64_t)x * hw + (uint32_t)t_cell;
+                    cb = r;
+                    b_move(cb, s_cell, t_cell);
+                    child_ply = rply + 1u;
+                    child_st = ((1ull << t_cell) & (g.goal_top | g.goal_bottom)) ? root_mover + 1u : BGS_ST_RUNNING;
+                }
+                stepped += 1u;   // the first move: a transition of the replicated board
+                game = game_base + cur_where * playouts + p;
+                b = cb;
+                plies = child_ply;
+                st = child_st;
+                has = true;
+                search = st == BGS_ST_RUNNING;   // (a blocked side to move is settled by the search, also at the cap)
+                have_block = false;
+            }
+            const uint32_t wanted = (uint32_t)__popcll(need);
+            c_next = avail < wanted ? c_end : c_next + wanted;
+        }
+        if (!__builtin_amdgcn_ballot_w64(has)) break;
+
+        // ---- the action lists of the boards that have just moved; a side to move without an action settles the game:
+        // the other side wins if IT could move, else a draw
+        if (__builtin_amdgcn_ballot_w64(search)) {
+            const uint64_t occ = b_occupancy(b);
+            b_enumerate<GEO, NC>(g, b, occ, plies & 1u, search, column, mv);
+            const bool blocked = search && mv.n == 0u;
+            if (__builtin_amdgcn_ballot_w64(blocked)) {
+                BMoves<NC> other;
+#pragma unroll
+                for (int k = 0; k < NC; ++k) other.counts[k] = 0;
+                other.n = 0;
+                other.row_base = 0;
+                b_enumerate<GEO, NC>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
+                if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
+            }
+            search = false;
+        }
+        const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
+        if (has && !run) {
+            count(st);
+            has = false;
+        }
+        // ---- one ply on every running board
+        if (run) {
+            if (!have_block || (plies & 3u) == 0u) {
+                blk = philox4x32_10(seed, game, plies >> 2);
+                have_block = true;
+            }
+            const uint32_t mover = plies & 1u;
+            int s, t;
+            b_pick<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, t);
+            b_move(b, s, t);
+            ++plies;
+            stepped += 1u;
+            if ((1ull << t) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
+            else search = true;
+        }
+    }
+    flush();
+    drain();
+    add_steps(steps, stepped);
+}
+
+template <class GEO, int NC>
+void launch_bounce_evaluate(const bgs_batch* b, const GEO& g, uint64_t seed, uint32_t playouts, uint32_t max_plies, int32_t* d_counts,
+                            uint64_t* d_ends, uint64_t* d_totals) {
+    const uint32_t slots = (uint32_t)(b->bg.w * b->bg.h * b->bg.w);
+    const int64_t blocks = (b->n + BGS_BLOCK - 1) / BGS_BLOCK;
+    hipLaunchKernelGGL((k_bounce_eval_count<GEO>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), 0, b->stream, g, (const uint64_t*)b->d_planes,
+                       (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, d_ends, d_totals);
+    if (blocks > 1) {
+        hipLaunchKernelGGL(k_bounce_eval_scan_totals, dim3(1), dim3(BGS_BLOCK), 0, b->stream, d_totals, blocks);
+        hipLaunchKernelGGL(k_bounce_eval_add_totals, dim3((uint32_t)blocks), dim3(BGS_BLOCK), 0, b->stream, d_ends,
+                           (const uint64_t*)d_totals, b->n);
+    }
+    (void)hipMemsetAsync(d_counts, 0, (size_t)b->n * slots * 3 * sizeof(int32_t), b->stream);
+    unsigned long long* queue = reinterpret_cast<unsigned long long*>(b->d_work_count);   // (8-byte aligned: a region start)
+    (void)hipMemsetAsync(queue, 0, sizeof(unsigned long long), b->stream);
+    // a chunk spans at most kBounceEvalWindow segments: chunk / P + 1 <= 64
+    uint64_t chunk = (uint64_t)(kBounceEvalWindow - 1) * playouts;
+    if (chunk > kBounceEvalChunk) chunk = kBounceEvalChunk;
+    // ---- the game ids: ((first_game + i) * S + s) * P + p = first_game * S * P + (i * S + s) * P + p, mod 2^64
+    const uint64_t game_base = b->first_game * (uint64_t)slots * (uint64_t)playouts;
+    const int64_t waves = (int64_t)b->num_cus * 4 * (b->bounce_eval_wps > 0 ? b->bounce_eval_wps : kBounceEvalWps);
+    const size_t tile = sizeof(uint32_t) * 2 * 8 * NC * BGS_BLOCK;
+    hipLaunchKernelGGL((k_bounce_evaluate<GEO, NC>), dim3((uint32_t)((waves + kEvalWavesPerBlock - 1) / kEvalWavesPerBlock)), dim3(BGS_BLOCK),
+                       tile, b->stream, g, (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, seed,
+                       game_base, playouts, max_plies, slots, (const uint64_t*)d_ends, queue, (uint32_t)chunk, d_counts, b->d_steps);
+}
+
 }  // namespace
+
+void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts, uint64_t* d_ends,
+                     uint64_t* d_totals) {
+    uint32_t cap = (uint32_t)max_plies;
+    if (cap > kBounceMaxPlies) cap = kBounceMaxPlies;   // plies are stored as uint16
+    const uint32_t p = (uint32_t)playouts;
+    if (b->bounce_static_geom && bounce_is_default(b->bg))
+        launch_bounce_evaluate<DefaultBounceGeom, 1>(b, DefaultBounceGeom{}, seed, p, cap, d_counts, d_ends, d_totals);
+    else if (b->bg.w <= 8)
+        launch_bounce_evaluate<BounceGeom, 1>(b, b->bg, seed, p, cap, d_counts, d_ends, d_totals);
+    else
+        launch_bounce_evaluate<BounceGeom, 3>(b, b->bg, seed, p, cap, d_counts, d_ends, d_totals);
+}
 
 void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts) {
     EvalGeom g{};

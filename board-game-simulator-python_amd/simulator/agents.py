@@ -1,41 +1,64 @@
 """Agents on top of the batched engine, in the shape of the reference's ``textual/examples/agent.py``:
 ``Agent.predict(state) -> dict[Action, float]``.
 
-``MonteCarloAgent`` is flat Monte-Carlo: every legal column of a position is valued by ``playouts`` uniform random games
-that start with it, ``(wins + draws / 2) / playouts`` for the player to move.  All columns of all positions are played
-and counted in ONE launch (``ConnectBatch.evaluate_actions``).
+``MonteCarloAgent`` is flat Monte-Carlo: every legal action of a position is valued by ``playouts`` uniform random games
+that start with it, ``(wins + draws / 2) / playouts`` for the player to move.  All actions of all positions are played
+and counted in ONE launch: ``ConnectBatch.evaluate_actions`` for Connect states (a column each),
+``BounceBatch.evaluate_moves`` for Bounce states (a (source, target) move each).
 """
 
 from __future__ import annotations
 
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .batch import DEFAULT_SEED, ConnectBatch
-from .game import connect
+from .batch import DEFAULT_SEED, BounceBatch, ConnectBatch
+from .game import bounce, connect
+
+# Bounce playouts stop at this absolute ply count unless the agent is given another cap: random Bounce games are short
+# (28 plies on average), but a few in 2^18 never end, and a capped game counts as neither a win, a draw nor a loss.
+BOUNCE_MAX_PLIES = 1024
 
 
 class MonteCarloAgent:
-    """Flat Monte-Carlo evaluation of Connect positions (``simulator.game.connect.State``).
+    """Flat Monte-Carlo evaluation of Connect positions (``simulator.game.connect.State``) and Bounce positions
+    (``simulator.game.bounce.State``), dispatched on the state's type.
 
     The playouts of the position at index k of a call are games ``((first_game + k) * width + c) * playouts + p`` of
-    ``seed``: ``predict(state, game=k)`` gives what ``predict_many(states)[k]`` gives for the same ``state``.
+    ``seed`` for Connect (c the column) and ``((first_game + k) * S + s) * playouts + p`` for Bounce (S = width * height *
+    width, s = x * height * width + ty * width + tx for the move of the piece in column x of the active row to (tx, ty)):
+    ``predict(state, game=k)`` gives what ``predict_many(states)[k]`` gives for the same ``state``.
+
+    ``max_plies`` caps every playout at that absolute ply count (a capped playout adds nothing to the value).  None: no
+    cap for Connect, whose games end by themselves, and ``BOUNCE_MAX_PLIES`` (1024) for Bounce.
     """
 
-    def __init__(self, playouts: int = 256, seed: int = DEFAULT_SEED, device: int = 0):
+    def __init__(self, playouts: int = 256, seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None):
         if playouts < 1:
             raise ValueError("playouts must be >= 1")
+        if max_plies is not None and max_plies < 1:
+            raise ValueError("max_plies must be >= 1")
         self.playouts = int(playouts)
         self.seed = int(seed)
         self.device = int(device)
-        self._batches: Dict[tuple, ConnectBatch] = {}
+        self.max_plies = None if max_plies is None else int(max_plies)
+        self._batches: Dict[tuple, Union[ConnectBatch, BounceBatch]] = {}
 
     def _batch(self, config: connect.Config, n: int) -> ConnectBatch:
-        key = (config.height, config.width, config.count, n)
+        key = ("connect", config.height, config.width, config.count, n)
         b = self._batches.get(key)
         if b is None:
             b = ConnectBatch(config.height, config.width, config.count, n, device=self.device)
+            self._batches[key] = b
+        return b
+
+    def _bounce_batch(self, config: bounce.Config, n: int) -> BounceBatch:
+        grid = config.grid
+        key = ("bounce", grid.shape, grid.tobytes(), n)
+        b = self._batches.get(key)
+        if b is None:
+            b = BounceBatch(grid, n, device=self.device)
             self._batches[key] = b
         return b
 
@@ -44,18 +67,37 @@ class MonteCarloAgent:
         move, NaN where the column is illegal or the board has ended.  Sets the batch's first_game to `first_game`; the
         boards are not modified."""
         batch.set_first_game(first_game)
-        counts = batch.evaluate_actions(seed=self.seed, playouts=self.playouts).astype(np.float64)
+        cap = 2**31 - 1 if self.max_plies is None else self.max_plies
+        counts = batch.evaluate_actions(seed=self.seed, playouts=self.playouts, max_plies=cap).astype(np.float64)
         v = (counts[..., 0] + 0.5 * counts[..., 1]) / self.playouts
         v[batch.legal == 0] = np.nan
         return v
 
-    def predict_many(self, states: Sequence[connect.State], first_game: int = 0) -> List[Dict[connect.Action, float]]:
-        """`predict` of every state, evaluated in one call (all states must share one Config)."""
+    def bounce_values(self, batch: BounceBatch, first_game: int = 0) -> np.ndarray:
+        """float64[n, width, height * width] for the boards of a BounceBatch: (wins + draws / 2) / playouts of the move of
+        the piece in column x of the active row to cell c, for the player to move; NaN where that move is illegal or the
+        board has ended.  Sets the batch's first_game to `first_game`; the boards are not modified."""
+        batch.set_first_game(first_game)
+        cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
+        counts = batch.evaluate_moves(seed=self.seed, playouts=self.playouts, max_plies=cap).astype(np.float64)
+        v = (counts[..., 0] + 0.5 * counts[..., 1]) / self.playouts
+        t = batch.targets[:, : batch.width]
+        cells = np.arange(batch.height * batch.width, dtype=np.uint64)
+        legal = ((t[..., None] >> cells) & np.uint64(1)) != 0
+        v[~legal] = np.nan
+        return v
+
+    def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict]:
+        """`predict` of every state, evaluated in one call (all states must be of one game and share one Config)."""
         if not states:
             return []
         config = states[0].config
-        if any(s.config != config for s in states):
+        if any(type(s) is not type(states[0]) or s.config != config for s in states):
             raise ValueError("predict_many: the states must share one Config")
+        if isinstance(states[0], bounce.State):
+            return self._predict_bounce(states, first_game)
+        if not isinstance(states[0], connect.State):
+            raise TypeError(f"predict_many: Connect or Bounce states, not {type(states[0]).__name__}")
         b = self._batch(config, len(states))
         grid = np.stack([s.grid for s in states])
         player = np.array([s.player for s in states], dtype=np.int8)
@@ -66,7 +108,24 @@ class MonteCarloAgent:
         v = self.values(b, first_game)
         return [{a: float(v[k, a.column]) for a in s.actions} for k, s in enumerate(states)]
 
-    def predict(self, state: connect.State, game: int = 0) -> Dict[connect.Action, float]:
+    def _predict_bounce(self, states: Sequence[bounce.State], first_game: int) -> List[Dict[bounce.Action, float]]:
+        b = self._bounce_batch(states[0].config, len(states))
+        grid = np.stack([s.grid for s in states])
+        player = np.array([s.player for s in states], dtype=np.int8)
+        winner = np.array([s.to_json()["winner"] for s in states], dtype=np.int8)
+        # the state's own ply count: a playout's draws are keyed by the absolute ply
+        plies = np.array([s._plies for s in states], dtype=np.int32)
+        status = b.write_state(grid, player, winner, plies)
+        if (status != 0).any():
+            raise ValueError("predict_many: a state could not be loaded")
+        v = self.bounce_values(b, first_game)
+        w = b.width
+        out = []
+        for k, s in enumerate(states):
+            out.append({a: float(v[k, a._source[0], a._target[1] * w + a._target[0]]) for a in s.actions})
+        return out
+
+    def predict(self, state, game: int = 0) -> Dict:
         """{action: value} for every action in ``state.actions`` (the keys are those Action objects)."""
         return self.predict_many([state], first_game=game)[0]
 

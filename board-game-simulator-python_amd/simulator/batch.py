@@ -885,10 +885,36 @@ class BounceBatch(_Batch):
         self._after_create()
 
     def evaluate_actions(self, *args, **kwargs):
-        """Not available for Bounce: flat Monte-Carlo evaluation covers bit-packed Connect boards only."""
-        raise ValueError("evaluate_actions: Connect batches only (Bounce boards are not supported yet)")
+        """Not available for Bounce: evaluate_actions covers bit-packed Connect boards; Bounce has `evaluate_moves`."""
+        raise ValueError("evaluate_actions: Connect batches only (Bounce boards: evaluate_moves)")
 
     evaluate_actions_tensor = evaluate_actions
+
+    def evaluate_moves(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1) -> np.ndarray:
+        """Flat Monte-Carlo evaluation of every legal move of every board (bgs_bounce_evaluate_moves), one launch:
+        int32[n, W, H * W, 3]; entry [i, x, c] = (wins, draws, losses) of the player to move over `playouts` games that
+        start with the move of the piece in column x of the active row to cell c = ty * W + tx (bit c of targets[i, x])
+        and continue by the uniform random policy until they end or hold `max_plies` plies (clamped to 65535; a capped game
+        counts in none of the three).  Illegal slots and ended boards give 0, 0, 0.  The boards are not modified.
+        Playout p of slot s = x * H * W + c of board i is game ((first_game + i) * W * H * W + s) * playouts + p."""
+        out = np.empty((self.n, self.width, self.height * self.width, 3), dtype=np.int32)
+        _abi.check(_abi.lib().bgs_bounce_evaluate_moves(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
+                                                        ctypes.c_int32(max_plies), ctypes.c_void_p(out.ctypes.data), 0))
+        return out
+
+    def evaluate_moves_tensor(self, out=None, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1):
+        """`evaluate_moves` into a device tensor int32[n, W, H * W, 3] (allocated when None), enqueued on the batch's stream
+        with no synchronisation.  Every entry is written."""
+        t = self._need_torch("evaluate_moves_tensor")
+        shape = (self.n, self.width, self.height * self.width, 3)
+        if out is None:
+            out = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
+        if not (out.is_cuda and out.dtype == t.int32 and tuple(out.shape) == shape and out.is_contiguous()
+                and out.data_ptr() % 16 == 0):
+            raise TypeError(f"out must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        _abi.check(_abi.lib().bgs_bounce_evaluate_moves(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
+                                                        ctypes.c_int32(max_plies), ctypes.c_void_p(out.data_ptr()), 1))
+        return out
 
     def step_actions(self, moves, want_status: bool = True):
         """moves int32[n, 4] = source x, y, target x, y; a negative first entry skips the board."""

@@ -183,6 +183,23 @@ BGS_API int bgs_rollout(bgs_batch* b, uint64_t seed, int32_t max_plies, uint32_t
  * first_game * width * playouts over the boards replicated width * playouts times and stepped by their column. */
 BGS_API int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies,
                                          int32_t* counts, int counts_on_device);
+/* Flat Monte-Carlo evaluation of every legal move of every board (Bounce, bit-packed boards only: at most 64 cells,
+ * piece values <= 15).  counts int32[n][width][height * width][3]: entry [i][x][c] = (wins, draws, losses) of the
+ * player to move at board i over `playouts` games that start with the move of the piece in column x of the active row
+ * to cell c = ty * width + tx (bit c of targets[i][x], bgs_bounce_read_targets), then continue by the uniform random
+ * policy until they end or hold max_plies plies (clamped to 65535: plies are 16-bit); a capped game is counted in none
+ * of the three.  Illegal slots and ended boards (boards without a legal move among them): 0, 0, 0.  The batch's boards
+ * are not modified; the transitions played, first moves included, are added to bgs_steps.  counts_on_device: as
+ * bgs_connect_evaluate_actions (a 16-byte aligned device pointer, enqueued on the batch's stream, no synchronisation, no
+ * allocation; otherwise a host buffer, filled when the call returns).
+ * RNG: with S = width * height * width, playout p of slot s = x * height * width + c of board i is the game with global
+ * id G = ((first_game + i) * S + s) * playouts + p (mod 2^64), its draws keyed by (seed, G, ply), a philox word per ply,
+ * ply the board's absolute ply count: the playouts of board i in (s, p) order are a bgs_rollout(seed) with first_game =
+ * first_game * S * playouts over the boards replicated S * playouts times and stepped by their slot's move, the
+ * illegal slots dropped.  Refused (BGS_ERR_ARG): Connect and generic batches, playouts < 1, max_plies < 1, a misaligned
+ * device pointer, n * S * playouts beyond int64. */
+BGS_API int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
+                                      int counts_on_device);
 /* env-steps (transitions applied to running boards) since the last bgs_reset / bgs_reset_steps */
 BGS_API int bgs_steps(bgs_batch* b, uint64_t* steps);
 BGS_API int bgs_reset_steps(bgs_batch* b);
