@@ -516,6 +516,27 @@ void sink_publish(bgs_reward_sink* s, int64_t ticket, int64_t n_games, int8_t* h
 // the caller spins a little before it sleeps -- the last deliveries are a few tens of microseconds away and overlap
 // with nothing, while a wake-up out of hipEventSynchronize or a condition variable costs as much again.  In the steady
 // state (waits that only throttle the launching thread) nobody spins.
+bool sink_takes_group(const bgs_reward_sink* s, int count) { return s != nullptr && !s->grids && s->slots >= count; }
+int sink_rollout_group(bgs_reward_sink* s, bgs_batch* const* bs, const uint64_t* seeds, const bool* writes, int count,
+                       hipStream_t stream, int8_t* const* host_rewards, int64_t* tickets) {
+    NEED(count >= 1 && count <= kConnectGroupMax && count <= s->slots, "bad step group");
+    for (int i = 0; i < count; ++i)   // (before any ticket exists: a claimed ticket is always published)
+        NEED(bs[i]->device == s->device && bs[i]->n <= s->max_games, "the batch does not fit the sink");
+    uint32_t* codes[kConnectGroupMax];
+    for (int i = 0; i < count; ++i) {
+        tickets[i] = claim(s);
+        codes[i] = reinterpret_cast<uint32_t*>(s->mapped[tickets[i] % s->slots]);
+    }
+    connect_rollout_steps(bs, seeds, codes, writes, count, stream);
+    hipError_t err = hipGetLastError();
+    // every step's codes are in its slot when the launch completes: the events all follow it
+    for (int i = 0; i < count; ++i) {
+        if (err == hipSuccess) err = hipEventRecord(s->landed[tickets[i] % s->slots], stream);
+        publish(s, tickets[i], bs[i]->n, host_rewards[i], err == hipSuccess);
+    }
+    if (err != hipSuccess) return fail(BGS_ERR_RUNTIME, "grouped rollout could not be enqueued: %s", hipGetErrorString(err));
+    return BGS_OK;
+}
 int sink_wait(bgs_reward_sink* s, int64_t ticket, bool urgent) {
     NEED(s != nullptr, "sink is NULL");
     NEED(ticket >= 0 && ticket < s->a_submitted.load(std::memory_order_acquire), "unknown ticket %lld", (long long)ticket);

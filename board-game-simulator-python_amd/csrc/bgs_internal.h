@@ -125,6 +125,11 @@ void connect_transition(const bgs_batch* b, const int32_t* d_actions, int32_t* d
                         int8_t* d_winner, int32_t* d_plies, uint8_t* d_legal, int8_t* d_reward_out, uint32_t* d_done = nullptr,
                         uint32_t ticket = 0);  // d_done: host word the one-workgroup kernel sets to `ticket` behind its records
 bool connect_rollout(const bgs_batch* b, uint64_t seed, int32_t max_plies, uint32_t flags, uint32_t* codes_out);
+// the multi-step form (bgs_pipeline.hip): may these steps of batch b go to connect_rollout_steps (codes: they hand their
+// outcome codes to a sink's slots), and the launch of `count` of them on `stream` -- see connect_kernels.hip
+bool connect_steps_ok(const bgs_batch* b, int32_t max_plies, uint32_t flags, bool codes);
+void connect_rollout_steps(const bgs_batch* const* bs, const uint64_t* seeds, uint32_t* const* codes, const bool* writes, int count,
+                           hipStream_t stream);
 void connect_unpack_grid(const bgs_batch* b, int8_t* d_grid);
 void connect_cell_planes(const bgs_batch* b, uint64_t* d_dst);  // wire format of the grid hand-over (see the kernel)
 void connect_meta(const bgs_batch* b, int8_t* d_player, uint8_t* d_ended, int8_t* d_winner, int32_t* d_plies);
@@ -191,6 +196,12 @@ hipEvent_t sink_slot_event(bgs_reward_sink* s, int64_t ticket);
 void sink_publish(bgs_reward_sink* s, int64_t ticket, int64_t n_games, int8_t* host_reward, bool ok, int64_t event_ticket = -1,
                   bool all_end = false);
 int sink_wait(bgs_reward_sink* s, int64_t ticket, bool urgent);  // urgent: poll / spin (the end of a run)
+// a reward sink (not a grid sink) with at least `count` slots: bgs_pipeline.hip may hand it grouped steps
+bool sink_takes_group(const bgs_reward_sink* s, int count);
+// bgs_sink_rollout for `count` steps of a multi-step Connect launch on `stream` (connect_rollout_steps): one ticket, slot,
+// host array and `landed` event per step, claimed and published in step order; tickets[i] receives step i's
+int sink_rollout_group(bgs_reward_sink* s, bgs_batch* const* bs, const uint64_t* seeds, const bool* writes, int count,
+                       hipStream_t stream, int8_t* const* host_rewards, int64_t* tickets);
 int gather_wait(bgs_gather* g, int64_t ticket, bool urgent);     // bgs_multi.hip
 
 }  // namespace bgs

@@ -115,7 +115,9 @@ struct bgs_pipeline {
     bool feeding = false;          // the feeder thread exists
     bool stop = false;
     int feed_rc = BGS_OK;          // the first failure of an enqueue made by the feeder ...
-    std::string feed_error;        // ... and its message (reported by the consumer's next call)
+    std::string feed_error;        // ... and its message (reported by the consumer's next call)    // grouped launches (enqueue_steps): events that order them against the batches' own streams
+    std::vector<hipEvent_t> start_ev, end_ev;   // [depth]
+    int64_t launches = 0;          // grouped launches so far (launch g goes to the stream of batches[g % depth])
 };
 
 extern "C" {
@@ -179,6 +181,31 @@ static int consume(bgs_pipeline* p, int64_t j) {
     return bgs_progress_store(p->consumed, j + 1);
 }
 
+// Steps per launch (S) of a call of `count` steps: kConnectGroupSteps when the call has at least kConnectGroupMinCall
+// steps, every batch runs the multi-step kernel (connect_steps_ok) and the hand-over is a reward sink with a slot and a
+// host array for each step of a group, else 1.  Experiment connect_group=N (the test library): N steps per launch in a
+// call of any length instead, 1 = one launch per step.
+static int group_size(const bgs_pipeline* p, int64_t count, int handover, bool from_feeder) {
+    int s = count >= kConnectGroupMinCall ? kConnectGroupSteps : 1;
+    if (const char* e = bgs::experiment("connect_group")) s = atoi(e);
+    if (s > kConnectGroupMax) s = kConnectGroupMax;
+    if (s < 2 || from_feeder || p->rank_words) return 1;
+    if (handover && (p->gather || !bgs::sink_takes_group(p->sink, s) || (int)p->host.size() < s)) return 1;
+    for (const bgs_batch* b : p->batches)
+        if (!bgs::connect_steps_ok(b, p->max_plies, p->flags, handover != 0)) return 1;
+    return s;
+}
+
+// Grouped steps and the batches' arenas.  Step s still plays the boards of batches[s % depth] with seed seed0 + s, but a
+// group of S consecutive steps is ONE launch, on the stream of batches[g % depth] (g counts grouped launches), and with
+// three groups in flight a batch is the batch of several steps in flight.  So only the LAST step of the call on a batch
+// stores its boards, status and rewards -- the last `depth` steps of a call are one-step launches on their own batch's
+// stream -- and a grouped step delivers its outcome codes and env-steps and nothing else (nobody can read its boards:
+// a later step of the call overwrites them before the call returns).  What a
+// caller reads after the call -- host arrays, each batch's boards, status, rewards and env-steps -- is what one launch
+// per step leaves.  A grouped launch waits for what was enqueued on the streams of the batches it plays before the call
+// (start_ev), and at the end of the call every batch's stream waits for the launches that played it (end_ev): work the
+// caller enqueues on a batch's stream afterwards is ordered behind the batch's steps, as before.
 static int enqueue_steps(bgs_pipeline* p, const uint64_t* seeds, int64_t count, int handover, int time_stride, bool from_feeder = false) {
     NEED(p != nullptr && count >= 0, "bad argument");
     NEED(!handover || p->sink || p->gather, "this pipeline has no hand-over");
@@ -191,7 +218,121 @@ static int enqueue_steps(bgs_pipeline* p, const uint64_t* seeds, int64_t count, 
     HIP_TRY(hipSetDevice(p->device));
     const int depth = (int)p->batches.size();
     const int n_host = (int)p->host.size();
-    for (int64_t i = 0; i < count; ++i) {
+    const int group = count >= 2 ? group_size(p, count, handover, from_feeder) : 1;
+    std::vector<uint64_t> waited, played;   // [stream] batches whose start_ev / whose steps a stream's launches waited for / played
+    if (group > 1) {
+        while ((int)p->start_ev.size() < depth) {
+            hipEvent_t a = nullptr, z = nullptr;
+            HIP_TRY(hipEventCreateWithFlags(&a, hipEventDisableTiming));
+            p->start_ev.push_back(a);
+            HIP_TRY(hipEventCreateWithFlags(&z, hipEventDisableTiming));
+            p->end_ev.push_back(z);
+        }
+        waited.assign(depth, 0);
+        played.assign(depth, 0);
+        for (int k = 0; k < depth; ++k) {
+            HIP_TRY(hipEventRecord(p->start_ev[k], p->batches[k]->stream));
+            waited[k] = played[k] = 1ull << (k & 63);
+        }
+    }
+    // (at the end of a grouped call: every batch's stream waits for the other streams' launches that played it)
+    auto join = [&]() -> int {
+        for (int y = 0; y < (int)played.size(); ++y) {
+            if ((played[y] & ~(1ull << (y & 63))) == 0) continue;
+            HIP_TRY(hipEventRecord(p->end_ev[y], p->batches[y]->stream));
+            for (int k = 0; k < depth; ++k)
+                if (k != y && (played[y] >> (k & 63) & 1u)) HIP_TRY(hipStreamWaitEvent(p->batches[k]->stream, p->end_ev[y], 0));
+        }
+        played.clear();
+        return BGS_OK;
+    };
+    for (int64_t i = 0; i < count;) {
+        // (the last `depth` steps of the call -- the last of each batch, the ones that leave its boards -- are one launch
+        // each on their batch's stream: the end of a call, where the launches in flight thin out, stays one step deep)
+        const int64_t left = count - depth - i;
+        const int64_t k_steps = left < group ? left : group;
+        if (k_steps >= 2) {
+            // ---- S steps, one launch
+            const int k = (int)k_steps;
+            const int y = (int)(p->launches % depth);
+            hipStream_t stream = p->batches[y]->stream;
+            bgs_batch* bs[kConnectGroupMax];
+            uint64_t sd[kConnectGroupMax];
+            bool writes[kConnectGroupMax];
+            int8_t* hosts[kConnectGroupMax];
+            int64_t tickets[kConnectGroupMax];
+            bool bracketed = false;
+            for (int q = 0; q < k; ++q) {
+                const int kb = (int)((p->step + q) % depth);
+                bs[q] = p->batches[kb];
+                sd[q] = seeds ? seeds[i + q] : p->seed0 + (uint64_t)(p->step + q);
+                writes[q] = i + q + depth >= count;   // the last step of this call on its batch
+                if (time_stride > 0 && (i + q) % time_stride == 0) bracketed = true;
+                if (!(waited[y] >> (kb & 63) & 1u)) {
+                    HIP_TRY(hipStreamWaitEvent(stream, p->start_ev[kb], 0));
+                    waited[y] |= 1ull << (kb & 63);
+                }
+                played[y] |= 1ull << (kb & 63);
+            }
+            size_t bracket = (size_t)-1;
+            if (bracketed) {
+                if (p->brackets == p->ev0.size()) {
+                    hipEvent_t a = nullptr, z = nullptr;
+                    HIP_TRY(hipEventCreate(&a));
+                    p->ev0.push_back(a);
+                    HIP_TRY(hipEventCreate(&z));
+                    p->ev1.push_back(z);
+                }
+                bracket = p->brackets;
+                HIP_TRY(hipEventRecord(p->ev0[bracket], stream));
+            }
+            int rc;
+            if (handover) {
+                for (int q = 0; q < k; ++q) {
+                    const int h = (int)((p->handed + q) % n_host);
+                    hosts[q] = p->host[h];
+                    lock.lock();
+                    const int64_t before = p->ticket[h];
+                    lock.unlock();
+                    if (before >= 0) {   // the array is about to be overwritten: its previous delivery must be over
+                        if ((rc = wait_ticket(p, before))) { (void)join(); return rc; }
+                        lock.lock();
+                        if (p->ticket[h] == before) p->ticket[h] = -1;
+                        lock.unlock();
+                    }
+                }
+                for (int q = 0; q < k; ++q) tickets[q] = -1;
+                rc = bgs::sink_rollout_group(p->sink, bs, sd, writes, k, stream, hosts, tickets);
+                if (tickets[0] < 0) { (void)join(); return rc; }   // (refused before any ticket was claimed)
+                lock.lock();
+                for (int q = 0; q < k; ++q) {   // (a failed group has published its tickets as failed: they are still the steps')
+                    const int h = (int)(p->handed % n_host);
+                    p->ticket[h] = tickets[q];
+                    p->held[h] = p->handed;
+                    ++p->handed;
+                }
+                p->released = p->handed;
+                lock.unlock();
+                if (rc) { (void)join(); return rc; }
+            } else {
+                bgs::connect_rollout_steps(bs, sd, nullptr, writes, k, stream);
+                const hipError_t e = hipGetLastError();
+                if (e != hipSuccess) {
+                    (void)join();
+                    return fail(BGS_ERR_RUNTIME, "grouped rollout could not be enqueued: %s", hipGetErrorString(e));
+                }
+            }
+            if (bracket != (size_t)-1) {
+                HIP_TRY(hipEventRecord(p->ev1[bracket], stream));
+                ++p->brackets;
+            }
+            ++p->launches;
+            lock.lock();
+            p->step += k;
+            lock.unlock();
+            i += k;
+            continue;
+        }
         bgs_batch* b = p->batches[p->step % depth];
         const uint64_t seed = seeds ? seeds[i] : p->seed0 + (uint64_t)p->step;
         size_t bracket = (size_t)-1;
@@ -250,8 +391,9 @@ static int enqueue_steps(bgs_pipeline* p, const uint64_t* seeds, int64_t count, 
         lock.lock();
         ++p->step;
         lock.unlock();
+        ++i;
     }
-    return BGS_OK;
+    return join();
 }
 
 // the feeder thread: one fed seed at a time, as soon as its host array has been released.  The seed LEAVES the deque under

@@ -1380,6 +1380,324 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
     add_steps(steps, stepped);
 }
 
+// K2o over several pipeline steps in one launch (the executor's grouped form, bgs_pipeline.hip).  A launch's waves are
+// the same as a one-step launch's -- chunk w of every step belongs to wave w -- but when the chunk of step s is handed
+// out, the lanes that would idle until the wave's longest game has ended take the games of step s + 1's chunk instead:
+// the drain is paid once per launch, not once per step.  A game is the same game bit for bit (its draws are keyed by
+// the step's seed, its global id and the block), so is everything it leaves: a step's outcome bytes, reward pairs and
+// codes are flushed, in the one-step layout, when the last game of its chunk has ended.
+//   * At most two steps of a wave are open at a time: the one whose games are handed out (`cur`) and the one before it,
+//     whose last games may still be playing (`old` lanes).  Their outcome bytes live in two LDS slices (by step parity),
+//     their env-steps in two counters per lane.  A wave starts step cur + 1 only once step cur - 1 is flushed; until then
+//     the lanes that find nothing to take sit out (never in practice: a chunk holds eight games a lane).
+//   * The pool and the lane words are K2o's: the pool only ever holds games of `cur` (a chunk's openings are padded to
+//     64 games, so when it is handed out the pool holds no game of it).
+//   * A step whose `planes` is NULL writes nothing but its codes and env-steps: the executor gives the arena of a batch
+//     only to the LAST step of its call on that batch, so launches in flight never store into the same arena.
+// Only the per-block contract (the strict one keeps one-step launches).
+template <class G, int OPEN_BLOCKS, bool CODES>
+__global__ void __launch_bounds__(BGS_BLOCK)
+k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t games_per_wave) {
+    using OW = OpenedWords<G, OPEN_BLOCKS, false>;
+    constexpr int NWORDS = OW::QUADS * 4;
+    using Pool = OpenedPool<OW::QUADS>;
+    extern __shared__ uint32_t code_lds[];  // two outcome slices per wave, games_per_wave bytes each
+    __shared__ Pool pools[BGS_BLOCK / BGS_WAVE];
+    __shared__ uint32_t lane_words[BGS_BLOCK / BGS_WAVE][NWORDS][BGS_WAVE];
+    constexpr uint32_t ONES = 0x11111111u;
+    const uint32_t top = (uint32_t)g.h() + 7u;
+    const uint32_t columns = g.w() >= 8 ? ONES : (ONES & ((1u << (4 * g.w())) - 1u));
+    const uint32_t stride = (uint32_t)g.h() + 1u;
+    const uint32_t column_top = 8u * columns;
+    const uint64_t eights = 0x88888888ull;
+
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (BGS_BLOCK / BGS_WAVE) + (threadIdx.x >> 6));
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t begin = (int64_t)wave * games_per_wave;
+    const int64_t end = begin + games_per_wave < n ? begin + games_per_wave : n;
+    const uint32_t avail = begin < end ? (uint32_t)(end - begin) : 0u;   // the same for every step: the batches are alike
+    const uint32_t nsteps = (uint32_t)tab.count;
+    uint32_t taken = 0, opened = 0;
+    Pool& pool = pools[threadIdx.x >> 6];
+
+    // the step whose games are handed out, and what its games store into (wave-uniform)
+    uint32_t cur = 0;
+    bool pending = false;                // step cur - 1 is not flushed yet
+    uint64_t cur_seed = tab.step[0].seed, cur_first = tab.step[0].first_game;
+    uint64_t* cur_planes = tab.step[0].planes ? tab.step[0].planes + begin : nullptr;
+    uint64_t* prev_planes = nullptr;
+
+    uint64_t p[2] = {0, 0};
+    uint32_t hts = 0, live = 0, game = 0;
+    uint32_t old = 0;                    // 1: this lane's game is of step cur - 1
+    uint32_t stepped0 = 0, stepped1 = 0; // env-steps of the games of even / odd steps
+    bool anywon = false;
+    uint32_t wnext = 0;
+    uint32_t* const my_words = &lane_words[threadIdx.x >> 6][0][lane];
+    uint32_t wrow = 0;
+
+    if (avail == 0u) return;
+    uint8_t* const slices = reinterpret_cast<uint8_t*>(code_lds + (threadIdx.x >> 6) * (games_per_wave >> 1));
+    auto slice_of = [&](uint32_t s) { return slices + (s & 1u) * games_per_wave; };
+    auto zero_slice = [&](uint32_t s) {
+        uint32_t* const w = reinterpret_cast<uint32_t*>(slice_of(s));
+        for (uint32_t i = lane; i < ((avail + 3u) >> 2); i += BGS_WAVE) w[i] = 0u;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    zero_slice(0u);
+
+    // K2o's full ply, opening ply and block (see k_connect_rollout_opened)
+    auto full_ply = [&](auto j_tag, uint32_t draw, uint64_t (&q)[2], uint32_t& h4, uint32_t& op, uint32_t& alive,
+                        bool& won_any) {
+        constexpr uint32_t J = decltype(j_tag)::value;
+        const uint32_t cnt = (uint32_t)__popc(op);
+        const uint32_t idx = sample_index(draw, cnt);
+        uint64_t cmp64;
+        {
+            uint64_t carry;
+            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(cmp64), "=s"(carry) : "v"(idx - op), "s"(ONES), "v"(eights));
+        }
+        const uint32_t cmp = (uint32_t)cmp64;
+        uint32_t col = (uint32_t)__popc(cmp & column_top);
+        if (g.w() >= 8) col &= 7u;
+        const uint32_t sh = col * 4u;
+        const uint32_t v = (h4 >> sh) & 15u;
+        uint32_t base = col * stride + top;
+        asm("" : "+v"(base));
+        uint32_t pos = base - v;
+        if ((uint32_t)g.w() * stride + top > 63u) pos &= 63u;
+        const uint32_t act = alive;
+        uint64_t& mine = q[J & 1u];
+        const uint64_t bit = 1ull << pos;
+        mine = ((uint64_t)and_or((uint32_t)(bit >> 32), act, (uint32_t)(mine >> 32)) << 32) |
+               and_or((uint32_t)bit, act, (uint32_t)mine);
+        h4 += act << sh;
+        op = (h4 >> 3) & ONES;
+        bool won;
+        if (g.k() == 4) {
+            won = four_in_a_row_at(mine, g.h(), pos);
+        } else {
+            Bits<1> b;
+            b.w[0] = mine;
+            won = has_run(g, b);
+        }
+        won_any = won_any || won;
+        alive = (won || op == 0u) ? 0u : alive;
+    };
+    // the outcome of a board that has just ended; its plies go to the counter of its step's parity
+    auto outcome_of = [&](const uint64_t (&q)[2], bool won_any, uint32_t parity) -> uint32_t {
+        const uint32_t stones = (uint32_t)__popcll(q[0]) + (uint32_t)__popcll(q[1]);
+        stepped0 += parity ? 0u : stones;   // (value selects: an if / else here made the two counters a stack array)
+        stepped1 += parity ? stones : 0u;
+        return won_any ? ((stones - 1u) & 1u) + 1u : (uint32_t)BGS_ST_DRAW;
+    };
+    auto cheap_ply = [&](uint32_t j, uint32_t draw, uint64_t (&q)[2], uint32_t& h4) {
+        const uint32_t col = sample_index(draw, (uint32_t)g.w());
+        const uint32_t sh = col * 4u;
+        const uint32_t v = (h4 >> sh) & 15u;
+        const uint32_t pos = col * stride + top - v;
+        q[j & 1u] |= 1ull << pos;
+        h4 -= 1u << sh;
+    };
+    auto play_block = [&]() {
+        const uint32_t was_live = live;
+        const uint32_t word = wnext;
+        wnext = my_words[wrow * BGS_WAVE];
+        wrow = wrow + 1u < (uint32_t)NWORDS - 1u ? wrow + 1u : (uint32_t)NWORDS - 1u;
+        uint32_t open = (hts >> 3) & ONES;
+        full_ply(std::integral_constant<uint32_t, 0>{}, sub_draw<0>(word), p, hts, open, live, anywon);
+        full_ply(std::integral_constant<uint32_t, 1>{}, sub_draw<1>(word), p, hts, open, live, anywon);
+        full_ply(std::integral_constant<uint32_t, 2>{}, sub_draw<2>(word), p, hts, open, live, anywon);
+        full_ply(std::integral_constant<uint32_t, 3>{}, sub_draw<3>(word), p, hts, open, live, anywon);
+        if (was_live != 0 && live == 0) {
+            uint64_t* const planes = old ? prev_planes : cur_planes;
+            if (planes) {
+                *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(planes) + (game * 8u)) = p[0];
+                *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(planes + n) + (game * 8u)) = p[1];
+            }
+            const uint32_t s = cur - old;
+            slice_of(s)[game] = (uint8_t)outcome_of(p, anywon, s & 1u);
+        }
+    };
+    // an idle lane takes game `which` of step cur's chunk out of the pool
+    auto take = [&](uint32_t which) {
+        game = which;
+        old = 0u;
+        const uint32_t slot = which & (Pool::SLOTS - 1u);
+        p[0] = pool.plane[0][slot];
+        p[1] = pool.plane[1][slot];
+        hts = pool.cols[slot];
+#pragma unroll
+        for (int k = 0; k < OW::QUADS; ++k) {
+            const uint4 v = pool.words[k][slot];
+            if (k == 0) wnext = v.x; else my_words[(4 * k) * BGS_WAVE] = v.x;
+            my_words[(4 * k + 1) * BGS_WAVE] = v.y;
+            my_words[(4 * k + 2) * BGS_WAVE] = v.z;
+            my_words[(4 * k + 3) * BGS_WAVE] = v.w;
+        }
+        wrow = 1u;
+        anywon = false;
+        live = hts != 0u ? ~0u : 0u;
+    };
+    // all 64 lanes open step cur's next 64 games and park them with their words
+    auto open_games = [&]() {
+        const uint32_t og = opened + lane;
+        const uint64_t id = cur_first + (uint64_t)(begin + og);
+        uint64_t q[2] = {0, 0};
+        uint32_t h4 = top * columns, alive = ~0u, op = columns;
+        bool won_any = false;
+        uint32_t words[12];
+        const Philox4 own = philox4x32_10(cur_seed, id, 0u);
+        using J2 = std::integral_constant<uint32_t, 2>; using J3 = std::integral_constant<uint32_t, 3>;
+        using J0 = std::integral_constant<uint32_t, 0>; using J1 = std::integral_constant<uint32_t, 1>;
+        words[0] = own.v[0]; words[1] = own.v[1]; words[2] = own.v[2]; words[3] = own.v[3];
+#pragma unroll
+        for (int c = 1; c < 3; ++c) {
+            if (4 * c <= OW::LAST) {
+                const Philox4 d = philox4x32_10(cur_seed, id, (uint32_t)c);
+                words[4 * c] = d.v[0]; words[4 * c + 1] = d.v[1]; words[4 * c + 2] = d.v[2]; words[4 * c + 3] = d.v[3];
+            } else {
+                words[4 * c] = words[4 * c + 1] = words[4 * c + 2] = words[4 * c + 3] = 0u;
+            }
+        }
+        cheap_ply(0u, sub_draw<0>(words[0]), q, h4);
+        cheap_ply(1u, sub_draw<1>(words[0]), q, h4);
+        cheap_ply(2u, sub_draw<2>(words[0]), q, h4);
+        cheap_ply(3u, sub_draw<3>(words[0]), q, h4);
+        if (OPEN_BLOCKS >= 2) {
+            cheap_ply(0u, sub_draw<0>(words[1]), q, h4);
+            cheap_ply(1u, sub_draw<1>(words[1]), q, h4);
+            op = (h4 >> 3) & ONES;
+            full_ply(J2{}, sub_draw<2>(words[1]), q, h4, op, alive, won_any);
+            full_ply(J3{}, sub_draw<3>(words[1]), q, h4, op, alive, won_any);
+        }
+#pragma unroll
+        for (int ob = 2; ob < OPEN_BLOCKS; ++ob) {
+            full_ply(J0{}, sub_draw<0>(words[ob]), q, h4, op, alive, won_any);
+            full_ply(J1{}, sub_draw<1>(words[ob]), q, h4, op, alive, won_any);
+            full_ply(J2{}, sub_draw<2>(words[ob]), q, h4, op, alive, won_any);
+            full_ply(J3{}, sub_draw<3>(words[ob]), q, h4, op, alive, won_any);
+        }
+        if (OPEN_BLOCKS >= 2 && og < avail && alive == 0) {
+            if (cur_planes) {
+                cur_planes[og] = q[0];
+                cur_planes[n + og] = q[1];
+            }
+            slice_of(cur)[og] = (uint8_t)outcome_of(q, won_any, cur & 1u);
+        }
+        const uint32_t slot = og & (Pool::SLOTS - 1u);
+        pool.plane[0][slot] = q[0];
+        pool.plane[1][slot] = q[1];
+        pool.cols[slot] = alive ? h4 : 0u;
+#pragma unroll
+        for (int k = 0; k < OW::QUADS; ++k) {
+            auto at = [&](int i) { return OPEN_BLOCKS + i <= 11 ? words[OPEN_BLOCKS + i <= 11 ? OPEN_BLOCKS + i : 11] : 0u; };
+            pool.words[k][slot] = make_uint4(at(4 * k), at(4 * k + 1), at(4 * k + 2), at(4 * k + 3));
+        }
+        opened += 64u;
+    };
+    // step s's chunk is done: status, reward pairs and codes as the one-step kernel stores them, and its env-steps
+    auto flush = [&](uint32_t s) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const ConnectGroupStep& e = tab.step[s];
+        const uint8_t* const outcome = slice_of(s);
+        if (e.planes) {
+            uint8_t* __restrict__ const status_out = e.status + begin;
+            uint16_t* __restrict__ const reward_out = e.reward + begin;
+            for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
+                const uint32_t four = reinterpret_cast<const uint32_t*>(outcome)[g4 >> 2];
+                if (g4 + 4u <= avail) {
+                    *reinterpret_cast<uint32_t*>(status_out + g4) = four;
+                    uint2 r;
+                    r.x = (uint32_t)reward_pair(four & 255u) | ((uint32_t)reward_pair((four >> 8) & 255u) << 16);
+                    r.y = (uint32_t)reward_pair((four >> 16) & 255u) | ((uint32_t)reward_pair(four >> 24) << 16);
+                    *reinterpret_cast<uint2*>(reward_out + g4) = r;
+                } else {
+                    for (uint32_t k = 0; g4 + k < avail; ++k) {
+                        const uint32_t ck = (four >> (8u * k)) & 255u;
+                        status_out[g4 + k] = (uint8_t)ck;
+                        reward_out[g4 + k] = reward_pair(ck);
+                    }
+                }
+            }
+        }
+        if (CODES) {
+            uint8_t* __restrict__ const packed_out = reinterpret_cast<uint8_t*>(e.codes) + (begin >> 2);
+            for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
+                const uint32_t four = reinterpret_cast<const uint32_t*>(outcome)[g4 >> 2];
+                packed_out[g4 >> 2] = (uint8_t)((four & 3u) | ((four >> 6) & 0xCu) | ((four >> 12) & 0x30u) | ((four >> 18) & 0xC0u));
+            }
+        }
+        const uint32_t odd = s & 1u;
+        add_steps(e.steps, odd ? stepped1 : stepped0);
+        stepped0 = odd ? stepped0 : 0u;
+        stepped1 = odd ? 0u : stepped1;
+    };
+    // step cur - 1 is flushed as soon as none of its games is playing any more
+    auto flush_done = [&]() {
+        if (pending && __builtin_amdgcn_ballot_w64(live != 0 && old != 0) == 0) {
+            flush(cur - 1u);
+            pending = false;
+        }
+    };
+
+    // ---- the chunks: idle lanes take the next opened games, of step cur + 1 once step cur's are handed out
+    while (taken < avail || cur + 1u < nsteps) {
+        const uint64_t need = __builtin_amdgcn_ballot_w64(live == 0);
+        if (need) {
+            const bool needy = live == 0;
+            const uint32_t wanted = (uint32_t)__popcll(need);
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+            const uint32_t have = opened - taken;
+            if (wanted > have && opened < avail) {
+                const bool first = needy && rank < have;
+                const bool second = needy && !first;
+                if (first && taken + rank < avail) take(taken + rank);
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                open_games();
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (second && taken + rank < avail) take(taken + rank);
+            } else if (needy && taken + rank < avail) {
+                take(taken + rank);
+            }
+            const uint32_t served = avail - taken < wanted ? avail - taken : wanted;
+            taken += served;
+            if (served < wanted && cur + 1u < nsteps && !pending) {
+                // ---- step cur is handed out: every game held now is of the step before; the lanes that got nothing
+                // open and take the first games of the next step
+                old = 1u;
+                prev_planes = cur_planes;
+                cur = __builtin_amdgcn_readfirstlane(cur + 1u);
+                pending = true;
+                cur_seed = tab.step[cur].seed;
+                cur_first = tab.step[cur].first_game;
+                cur_planes = tab.step[cur].planes ? tab.step[cur].planes + begin : nullptr;
+                zero_slice(cur);   // (its last reader was the flush of step cur - 2)
+                taken = 0;
+                opened = 0;
+                open_games();
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (needy && rank >= served && rank - served < avail) take(rank - served);
+                taken = avail < wanted - served ? avail : wanted - served;
+            }
+        }
+        play_block();
+        flush_done();
+    }
+    // ---- the drain of the last step
+    while (__builtin_amdgcn_ballot_w64(live != 0)) {
+        play_block();
+        flush_done();
+    }
+    if (pending) flush(cur - 1u);
+    flush(cur);
+}
+
 // K2b: the block-aligned, branch-free rollout for every other geometry (multi-word planes, up to 16 columns, up to 15
 // rows).  Same structure as K2a; column state is a nibble of height per column (64 bits) plus "column open" flags
 // kept nibble-spread in two 32-bit halves (columns 0-7 and 8-15), so the idx-th open column is one SWAR select inside
@@ -2312,6 +2630,55 @@ bool connect_rollout(const bgs_batch* b, uint64_t seed, int32_t max_plies, uint3
         with_game(Tag<GenericGame<G>>{});
     });
     return fused;
+}
+
+// The steps connect_rollout_steps can take: the ones connect_rollout gives to K2o with the default opening on a compile-time
+// one-word geometry (6x7x4) -- from the initial state, no cap, the per-block contract -- delivering their codes to a
+// sink's slot (`codes`) or nothing.
+bool connect_steps_ok(const bgs_batch* b, int32_t max_plies, uint32_t flags, bool codes) {
+    if (b->game != BGS_GAME_CONNECT || b->generic || !(b->cg.h == 6 && b->cg.w == 7 && b->cg.k == 4)) return false;
+    if (!(flags & 1u) || (flags & 4u) || b->rng_per_ply || b->rollout_generic || b->rollout_opening != kRolloutOpeningBlocks) return false;
+    if (max_plies < 0 || (uint32_t)max_plies < (uint32_t)(b->cg.h * b->cg.w)) return false;
+    const int64_t resident = (int64_t)b->num_cus * 4 * b->rollout_wps;
+    int64_t per_wave = b->rollout_chunk > 0 ? b->rollout_chunk : (b->n + resident - 1) / resident;
+    per_wave = (per_wave + BGS_WAVE - 1) / BGS_WAVE * BGS_WAVE;
+    // connect_rollout's own conditions for K2o and for its fused codes, with the group's two outcome slices a wave
+    if ((size_t)8 * per_wave > (32u << 10)) return false;
+    if (codes && (size_t)4 * (per_wave / 16) * sizeof(uint32_t) > (32u << 10)) return false;
+    return true;
+}
+
+// `count` (1 .. kConnectGroupMax) steps in ONE launch on `stream`: step i plays every board of bs[i] (alike batches,
+// each passing connect_steps_ok) with seeds[i]; its codes go to codes[i] when `codes` is given; it leaves its boards,
+// status and rewards in bs[i] only where writes[i]
+void connect_rollout_steps(const bgs_batch* const* bs, const uint64_t* seeds, uint32_t* const* codes, const bool* writes, int count,
+                           hipStream_t stream) {
+    const bgs_batch* b = bs[0];
+    const int64_t resident = (int64_t)b->num_cus * 4 * b->rollout_wps;
+    int64_t per_wave = b->rollout_chunk > 0 ? b->rollout_chunk : (b->n + resident - 1) / resident;
+    per_wave = (per_wave + BGS_WAVE - 1) / BGS_WAVE * BGS_WAVE;
+    const int64_t waves = (b->n + per_wave - 1) / per_wave;
+    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    ConnectGroup tab = {};
+    tab.count = count;
+    for (int i = 0; i < count; ++i) {
+        ConnectGroupStep& e = tab.step[i];
+        e.seed = seeds[i];
+        e.first_game = bs[i]->first_game;
+        e.planes = writes[i] ? bs[i]->d_planes : nullptr;
+        e.status = writes[i] ? bs[i]->d_status : nullptr;
+        e.reward = writes[i] ? reinterpret_cast<uint16_t*>(bs[i]->d_reward) : nullptr;
+        e.codes = codes ? codes[i] : nullptr;
+        e.steps = bs[i]->d_steps;
+    }
+    const size_t outcome_lds = (size_t)4 * 2 * per_wave;   // two slices of one outcome byte per game, four waves
+    using G = Geo<1, 6, 7, 4>;
+    if (codes)
+        hipLaunchKernelGGL((k_connect_rollout_opened_steps<G, kRolloutOpeningBlocks, true>), dim3(blocks), dim3(BGS_BLOCK), outcome_lds,
+                           stream, G{6, 7, 4}, tab, b->n, (uint32_t)per_wave);
+    else
+        hipLaunchKernelGGL((k_connect_rollout_opened_steps<G, kRolloutOpeningBlocks, false>), dim3(blocks), dim3(BGS_BLOCK), outcome_lds,
+                           stream, G{6, 7, 4}, tab, b->n, (uint32_t)per_wave);
 }
 
 void connect_unpack_grid(const bgs_batch* b, int8_t* d_grid) {

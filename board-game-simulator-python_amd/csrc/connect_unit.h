@@ -15,3 +15,29 @@ struct ConnectGeom {
 constexpr int kRolloutOpeningBlocks = 3;    // K2o: 4-ply blocks played in lock step before a board joins the refill loop
 constexpr int kGamesPerLaneOneWord = 8;     // one-word Connect boards: games per lane a launch aims for (512 per wave at 2^20)
 constexpr int kGamesPerLane = 4;            // every other rollout
+
+// Multi-step form of the K2o rollout (k_connect_rollout_opened_steps): one launch plays the batches of up to
+// kConnectGroupMax consecutive pipeline steps, every wave chunk w of each step in turn, its lanes carrying on from one
+// step's chunk into the next instead of idling until the wave's longest game has ended.  The executor hands
+// kConnectGroupSteps steps to a launch (S; bgs_pipeline.hip).
+// Measured on one MI355X (bench.py, 2^20 boards, three batches, docs/EXPERIMENTS.md §17): S = 2 and 3 read the same
+// (+8 % on 200-step regions); a call of 20 steps gains nothing -- its ramp and tail are most of it -- and its first
+// region read 3-5 % lower, so a call groups its steps only from kConnectGroupMinCall steps on.
+constexpr int kConnectGroupSteps = 2;
+constexpr int kConnectGroupMax = 8;
+constexpr int kConnectGroupMinCall = 48;
+
+// one step of a grouped launch, by value in the kernel's arguments
+struct ConnectGroupStep {
+    uint64_t seed;
+    uint64_t first_game;
+    uint64_t* planes;            // the step's arena, or NULL: it leaves no boards, status or rewards (a later step of the same
+    uint8_t* status;             // launch sequence overwrites that batch; its outcome codes and env-steps still go out)
+    uint16_t* reward;
+    uint32_t* codes;             // 2-bit outcome codes, (n + 15) / 16 dwords (the sink's page-locked slot), or NULL
+    unsigned long long* steps;   // the batch's env-step counter
+};
+struct ConnectGroup {
+    ConnectGroupStep step[kConnectGroupMax];
+    int count;
+};

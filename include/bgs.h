@@ -399,7 +399,9 @@ BGS_API int bgs_gather_destroy(bgs_gather* g);
  * bounds how far the launching thread runs ahead).  time_stride > 0 brackets every time_stride-th launch of the call
  * with timing events on the batch's stream; bgs_pipeline_kernel_ms (after bgs_pipeline_drain) returns their mean and
  * resets them.  bgs_pipeline_drain: every enqueued step's rewards are in their host arrays and the streams are idle.
- * The batches, sink, gather and host arrays belong to the caller and must outlive the pipeline. */
+ * The batches, sink, gather and host arrays belong to the caller and must outlive the pipeline.  A long call of Connect
+ * 6x7x4 steps from the initial state may play two steps in one launch on another batch's stream; every batch's stream
+ * waits for the steps that played it before the call returns, and what the steps leave is the same. */
 typedef struct bgs_pipeline bgs_pipeline;
 BGS_API int bgs_pipeline_create(bgs_batch* const* batches, int depth, bgs_reward_sink* sink, bgs_gather* gather,
                         int8_t* const* host_rewards, int n_host, uint64_t seed0, int32_t max_plies, uint32_t flags,
