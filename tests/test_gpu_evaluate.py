@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
+from tests.mc_expected import connect_expected as expected
 
 pytestmark = pytest.mark.gpu
 
@@ -49,27 +50,6 @@ def make_roots(h, w, k, n, seed):
             break
         orc.step_actions(cols)
     return orc.grid.copy(), orc.player.copy(), orc.winner.copy(), orc.plies.copy()
-
-
-def expected(h, w, k, roots, seed, first_game, playouts, max_plies, per_ply):
-    """(counts int32[n, w, 3], env-steps) from the oracle"""
-    grid, player, winner, plies = roots
-    n = grid.shape[0]
-    rep = w * playouts
-    orc = oracle.ConnectOracle(h, w, k, n * rep, per_ply=per_ply)
-    orc.grid[:] = np.repeat(grid, rep, axis=0)
-    orc.player[:] = np.repeat(player, rep)
-    orc.winner[:] = np.repeat(winner, rep)
-    orc.plies[:] = np.repeat(plies, rep)
-    cols = np.tile(np.repeat(np.arange(w, dtype=np.int32), playouts), n)
-    legal = orc.step_actions(cols) == 0
-    orc.winner[~legal] = 2            # an illegal column: the board leaves the count (and the rollout)
-    steps = int(legal.sum()) + orc.rollout(seed, first_game=first_game * rep, max_plies=max_plies)
-    win = orc.winner.reshape(n, w, playouts)
-    ok = legal.reshape(n, w, playouts)
-    mover = player.astype(np.int16)[:, None, None]
-    counts = np.stack([(ok & (win == mover)).sum(-1), (ok & (win == 2)).sum(-1), (ok & (win == 1 - mover)).sum(-1)], -1)
-    return counts.astype(np.int32), steps
 
 
 def load(h, w, k, roots, per_ply=False, first_game=0, use_torch=None):
