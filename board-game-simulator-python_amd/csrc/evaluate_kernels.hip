@@ -1,6 +1,6 @@
 // evaluate_kernels.hip -- flat Monte-Carlo evaluation of every column of a batch of packed Connect boards
-// (bgs_connect_evaluate_actions), and of every move of a batch of packed Bounce boards (bgs_bounce_evaluate_moves, the
-// second half of this file).  Connect: for board i and column c, `playouts` games that start with column c on board i and
+// (bgs_connect_evaluate_actions), of every move of a batch of packed Bounce boards (bgs_bounce_evaluate_moves, the
+// second half of this file), and the exact Connect solver (bgs_connect_solve_actions, between the two).  Connect: for board i and column c, `playouts` games that start with column c on board i and
 // continue by the uniform random policy, reduced on the device to (wins, draws, losses) of the player to move at board i.
 //
 // Game ids (include/bgs.h): playout p of column c of board i is global game
@@ -20,6 +20,7 @@
 // takes.  W/D/L are counted in registers, flushed to the wave's LDS tally when the lane moves to the next segment, and
 // the wave writes its segments once at the end (sliced segments: one integer atomic per wave and counter into counts the
 // launcher zeroed).
+#include "../../include/bgs.h"
 #include "bgs_common.h"
 #include "bgs_internal.h"
 
@@ -890,6 +891,362 @@ void launch_bounce_evaluate(const bgs_batch* b, const GEO& g, uint64_t seed, uin
                        game_base, playouts, max_plies, slots, (const uint64_t*)d_ends, queue, (uint32_t)chunk, d_counts, b->d_steps);
 }
 
+EvalGeom eval_geom(const bgs_batch* b) {
+    EvalGeom g{};
+    g.h = b->cg.h;
+    g.w = b->cg.w;
+    g.k = b->cg.k;
+    g.cells_total = (uint32_t)(g.h * g.w);
+    for (int x = 0; x < g.w; ++x) {
+        const int bit = x * (g.h + 1);
+        g.bottoms[bit >> 6] |= 1ull << (bit & 63);
+        for (int y = 0; y < g.h; ++y) g.cells[(bit + y) >> 6] |= 1ull << ((bit + y) & 63);
+    }
+    return g;
+}
+
+// ================================================================================================================
+// Exact Connect solver (bgs_connect_solve_actions): for board i and column c, a depth-first alpha-beta search of the
+// position after c, with a horizon of `depth` plies counted from board i (column c is ply 1).  Scores are seen from the
+// side to move at a node and are absolute in the ply: a win that ends T plies after board i scores kSolveK - T for the
+// winner and -(kSolveK - T) for the loser, a draw or a line the horizon cuts scores 0 -- so a plain negamax gives the
+// fastest win and the slowest loss, and a window passes from parent to child by negation alone.
+//
+// Shape.  A task is one (board, column); one lane runs one task.  Persistent one-wave workgroups draw tasks from a
+// device-wide counter: the wave's idle lanes take the next ones together (one atomic per refill), and a task that
+// settles without a search (an ended board, a full column, an immediate win or draw, depth 1) frees its lane in the same
+// refill pass.  The search is one uniform loop; in an iteration a lane may return from a child (pop), choose and play
+// its next move (push), and evaluate the node it has just entered -- so most iterations visit one node a lane.
+//
+// Node evaluation, in this order: a full board or an exhausted horizon scores 0; a landing cell that completes k in a
+// row for the mover is an immediate win; with one ply of horizon left nothing else can end inside it (0); two winning
+// landing cells of the opponent lose in two plies; one is the only move searched (any other loses in two plies, and
+// the block never scores below that); otherwise every legal column, centre first.
+//
+// Stack.  Moves are undone by XOR, so a level holds one 32-bit word in LDS, [level][lane] (no bank conflicts):
+// bits 0-7 the cell played (or the forced block), 8-12 the next column index in centre-first order, 13 "forced",
+// 16-31 alpha (int16).  Beta is not stored: a level's beta is minus its parent's alpha.
+// ================================================================================================================
+constexpr int kSolveK = 1024;             // |score| of a win or loss that ends T plies after the root: kSolveK - T
+constexpr int kSolveWavesPerCU = 16;      // persistent waves a CU (fewer when the stack does not fit the LDS)
+constexpr uint32_t kSolveLdsPerCU = 160u * 1024u;
+enum : uint32_t { kSolveIdle = 0, kSolveEnter = 1, kSolveCont = 2, kSolveRet = 3 };
+
+// bit x of the result is bit x - s of `a` (s >= 0; bits below the plane read as 0)
+template <int NW>
+__device__ __forceinline__ Planes<NW> shl(const Planes<NW>& a, int s) {
+    Planes<NW> r;
+    if (NW == 1) {
+        r.w[0] = s < 64 ? a.w[0] << s : 0ull;
+        return r;
+    }
+    const int q = s >> 6, rr = s & 63;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        uint64_t x = 0, y = 0;
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            x = (k == j - q) ? a.w[k] : x;
+            y = (k == j - q - 1) ? a.w[k] : y;
+        }
+        r.w[j] = rr ? (x << rr) | (y >> (64 - rr)) : x;
+    }
+    return r;
+}
+
+template <int NW>
+__device__ __forceinline__ void pand(Planes<NW>& a, const Planes<NW>& b) {
+#pragma unroll
+    for (int j = 0; j < NW; ++j) a.w[j] &= b.w[j];
+}
+
+template <int NW>
+__device__ __forceinline__ void por_into(Planes<NW>& a, const Planes<NW>& b) {
+#pragma unroll
+    for (int j = 0; j < NW; ++j) a.w[j] |= b.w[j];
+}
+
+// the cells where a stone of `me` would complete k in a row (occupied cells and sentinels included: the caller masks).
+// The sentinel row between columns is never a stone, so no run wraps from one column into the next.  k = 4: the runs
+// before (B_m) and after (A_m) a cell are built once per direction and joined, A3 | A2 B1 | A1 B2 | B3; any other k
+// tests every split of the k - 1 other stones.
+template <int NW>
+__device__ __forceinline__ Planes<NW> threats(const EvalGeom& g, const Planes<NW>& me) {
+    const int dirs[3] = {g.h + 1, g.h + 2, g.h};
+    Planes<NW> t;
+    if (g.k == 4) {
+        t = shl(me, 1);
+        pand(t, shl(me, 2));
+        pand(t, shl(me, 3));
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            Planes<NW> a1 = shr(me, dirs[d]), b1 = shl(me, dirs[d]);
+            Planes<NW> a2 = a1, b2 = b1;
+            pand(a2, shr(me, 2 * dirs[d]));
+            pand(b2, shl(me, 2 * dirs[d]));
+            Planes<NW> a3 = a2, b3 = b2;
+            pand(a3, shr(me, 3 * dirs[d]));
+            pand(b3, shl(me, 3 * dirs[d]));
+            pand(a2, b1);
+            pand(a1, b2);
+            por_into(t, a3);
+            por_into(t, b3);
+            por_into(t, a2);
+            por_into(t, a1);
+        }
+        return t;
+    }
+#pragma unroll
+    for (int j = 0; j < NW; ++j) t.w[j] = ~0ull;
+    for (int m = 1; m < g.k; ++m) pand(t, shl(me, m));   // vertical: the k - 1 cells below
+    for (int d = 0; d < 3; ++d) {
+        for (int split = 0; split < g.k; ++split) {       // `split` stones after the cell, k - 1 - split before it
+            Planes<NW> m;
+#pragma unroll
+            for (int j = 0; j < NW; ++j) m.w[j] = ~0ull;
+            for (int i = 1; i <= split; ++i) pand(m, shr(me, i * dirs[d]));
+            for (int i = 1; i < g.k - split; ++i) pand(m, shl(me, i * dirs[d]));
+            por_into(t, m);
+        }
+    }
+    return t;
+}
+
+template <int NW>
+__device__ __forceinline__ void flip(Planes<NW>& a, uint32_t pos) {
+#pragma unroll
+    for (int j = 0; j < NW; ++j) a.w[j] ^= ((uint32_t)j == (pos >> 6)) ? 1ull << (pos & 63u) : 0ull;
+}
+
+template <int NW>
+__device__ __forceinline__ uint32_t popc(const Planes<NW>& a) {
+    uint32_t c = 0;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) c += (uint32_t)__popcll(a.w[j]);
+    return c;
+}
+
+template <int NW>
+__device__ __forceinline__ uint32_t lowest(const Planes<NW>& a) {   // position of the lowest set bit (a != 0)
+    uint32_t pos = 0;
+    bool found = false;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        const bool here = !found && a.w[j] != 0ull;
+        pos = here ? 64u * j + (uint32_t)(__ffsll((unsigned long long)a.w[j]) - 1) : pos;
+        found = found || here;
+    }
+    return pos;
+}
+
+template <int NW>
+__device__ __forceinline__ bool is_zero(const Planes<NW>& a) {
+    uint64_t o = 0;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) o |= a.w[j];
+    return o == 0ull;
+}
+
+template <int NW>
+__global__ void __launch_bounds__(BGS_WAVE)
+k_connect_solve(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n, int32_t depth,
+                uint64_t max_nodes, unsigned long long* __restrict__ queue, int8_t* __restrict__ codes, int16_t* __restrict__ plies_out,
+                unsigned long long* __restrict__ nodes_out) {
+    extern __shared__ uint32_t solve_stack[];   // [levels][64 lanes]
+    uint32_t* const stk = solve_stack + threadIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const uint64_t tasks = (uint64_t)n * (uint64_t)g.w;
+    const uint32_t stride = (uint32_t)g.h + 1u;
+    const uint64_t colmask = (1ull << g.h) - 1ull;
+    const uint32_t half = (uint32_t)g.w >> 1;
+
+    Planes<NW> me, op;   // stones of the side to move at the current node, and of the other side
+#pragma unroll
+    for (int j = 0; j < NW; ++j) me.w[j] = op.w[j] = 0;
+    uint32_t mode = kSolveIdle, empty = 0;
+    int l = 0, val = 0;
+    uint64_t task = 0, visited = 0, total = 0;
+    bool dry = false;
+
+    auto finish = [&](int code, int plies) {
+        codes[task] = (int8_t)code;
+        if (plies_out) plies_out[task] = (int16_t)plies;
+        total += visited;
+        mode = kSolveIdle;
+    };
+
+    for (;;) {
+        // ---- refill: idle lanes take the next tasks; a task settled before any search frees its lane at once
+        for (;;) {
+            const uint64_t need = __builtin_amdgcn_ballot_w64(mode == kSolveIdle);
+            if (!need || dry) break;
+            const uint32_t wanted = (uint32_t)__popcll(need);
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(queue, (unsigned long long)wanted);
+            base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32) |
+                   (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base);
+            if (base + wanted >= tasks) dry = true;
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+            if (mode == kSolveIdle && base + rank < tasks) {
+                task = base + rank;
+                visited = 0;
+                const int64_t i = (int64_t)(task / (uint32_t)g.w);
+                const uint32_t col = (uint32_t)(task - (uint64_t)i * (uint32_t)g.w);
+                Planes<NW> r0, r1;
+#pragma unroll
+                for (int j = 0; j < NW; ++j) {
+                    r0.w[j] = planes[(int64_t)j * n + i];
+                    r1.w[j] = planes[(int64_t)(NW + j) * n + i];
+                }
+                const uint32_t stones = popc(r0) + popc(r1);
+                empty = g.cells_total - stones;
+                const uint32_t mover = stones & 1u;
+                const uint64_t cell = bits_at(landing_of(g, por(r0, r1)), (int)(col * stride)) & colmask;
+                if (status[i] != BGS_ST_RUNNING || cell == 0ull) {
+                    finish(BGS_SOLVE_NONE, 0);
+                } else {
+                    const uint32_t pos = col * stride + (uint32_t)(__ffsll((unsigned long long)cell) - 1);
+                    me = mover ? r1 : r0;   // the root's mover, then the opponent moves at level 0
+                    op = mover ? r0 : r1;
+                    if (drop_and_test(g, me, pos, ~0u)) {
+                        finish(BGS_SOLVE_WIN, 1);
+                    } else if (empty == 1u) {
+                        finish(BGS_SOLVE_DRAW, (int)empty);
+                    } else if (depth == 1) {
+                        finish(BGS_SOLVE_UNKNOWN, 0);
+                    } else {
+                        const Planes<NW> t = me;
+                        me = op;
+                        op = t;
+                        l = 0;
+                        mode = kSolveEnter;
+                    }
+                }
+            }
+        }
+        if (!__builtin_amdgcn_ballot_w64(mode != kSolveIdle)) break;
+
+        // ---- return from a child: undo the parent's move, raise its alpha, cut off at its beta
+        if (mode == kSolveRet) {
+            if (l == 0) {
+                const int s = -val;
+                if (s > 0) finish(BGS_SOLVE_WIN, kSolveK - s);
+                else if (s < 0) finish(BGS_SOLVE_LOSS, kSolveK + s);
+                else if (empty <= (uint32_t)depth) finish(BGS_SOLVE_DRAW, (int)empty);
+                else finish(BGS_SOLVE_UNKNOWN, 0);
+            } else {
+                --l;
+                const uint32_t word = stk[l * BGS_WAVE];
+                const Planes<NW> t = me;
+                me = op;
+                op = t;
+                flip(me, word & 255u);
+                int alpha = (int)(int16_t)(word >> 16);
+                const int beta = l == 0 ? kSolveK : -(int)(int16_t)(stk[(l - 1) * BGS_WAVE] >> 16);
+                alpha = -val > alpha ? -val : alpha;
+                if (alpha >= beta) {
+                    val = alpha;
+                } else {
+                    stk[l * BGS_WAVE] = (word & 0xFFFFu) | ((uint32_t)alpha << 16);
+                    mode = kSolveCont;
+                }
+            }
+        }
+        // ---- the node's next move: push it, or return alpha
+        if (mode == kSolveCont) {
+            const uint32_t word = stk[l * BGS_WAVE];
+            uint32_t next = (word >> 8) & 31u, pos = 0;
+            bool found = false;
+            if (word & (1u << 13)) {
+                found = next == 0u;
+                pos = word & 255u;
+                next = (uint32_t)g.w;
+            } else {
+                const Planes<NW> land = landing_of(g, por(me, op));
+                for (; next < (uint32_t)g.w && !found; ++next) {
+                    const uint32_t col = (next & 1u) ? half - ((next + 1u) >> 1) : half + (next >> 1);
+                    const uint64_t cell = bits_at(land, (int)(col * stride)) & colmask;
+                    found = cell != 0ull;
+                    pos = found ? col * stride + (uint32_t)(__ffsll((unsigned long long)cell) - 1) : pos;
+                }
+            }
+            if (!found) {
+                val = (int)(int16_t)(word >> 16);
+                mode = kSolveRet;
+            } else {
+                stk[l * BGS_WAVE] = (word & 0xFFFF2000u) | (next << 8) | pos;
+                flip(me, pos);
+                const Planes<NW> t = me;
+                me = op;
+                op = t;
+                ++l;
+                mode = kSolveEnter;
+            }
+        }
+        // ---- a node entered: settle it, or open its level
+        if (mode == kSolveEnter) {
+            ++visited;
+            const Planes<NW> land = landing_of(g, por(me, op));
+            const int r = depth - 1 - l;   // plies the horizon leaves from this node
+            if (visited > max_nodes) {
+                finish(BGS_SOLVE_BUDGET, 0);
+            } else if (is_zero(land) || r <= 0) {
+                val = 0;
+                mode = kSolveRet;
+            } else {
+                Planes<NW> wins = threats(g, me);
+                pand(wins, land);
+                if (!is_zero(wins)) {
+                    val = kSolveK - (l + 2);
+                    mode = kSolveRet;
+                } else if (r == 1) {
+                    val = 0;
+                    mode = kSolveRet;
+                } else {
+                    Planes<NW> lose = threats(g, op);
+                    pand(lose, land);
+                    const uint32_t cnt = popc(lose);
+                    if (cnt >= 2u) {
+                        val = -(kSolveK - (l + 3));
+                        mode = kSolveRet;
+                    } else {
+                        const int alpha = l <= 1 ? -kSolveK : (int)(int16_t)(stk[(l - 2) * BGS_WAVE] >> 16);
+                        stk[l * BGS_WAVE] = (cnt ? lowest(lose) | (1u << 13) : 0u) | ((uint32_t)alpha << 16);
+                        mode = kSolveCont;
+                    }
+                }
+            }
+        }
+    }
+    // ---- positions visited: one atomic per wave
+    for (int off = 32; off >= 1; off >>= 1) total += __shfl_xor(total, off);
+    if (lane == 0 && total) atomicAdd(nodes_out, (unsigned long long)total);
+}
+
+template <int NW>
+void launch_solve(const bgs_batch* b, const EvalGeom& g, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,
+                  unsigned long long* d_nodes) {
+    // No line is longer than the board has cells, so a deeper horizon cuts nothing: depth > cells is the same full solve
+    // (and DRAW, empty <= depth, stays exact).  The clamp also bounds the stack.  Level l is opened only by a node with
+    // r = depth - 1 - l >= 2 plies of horizon, so l <= depth - 3 = levels - 1.  Unclamped, a node of an empty root with
+    // one empty cell left (level cells - 2) could open a level past the allocation.
+    if (depth > (int32_t)g.cells_total) depth = (int32_t)g.cells_total;
+    int64_t levels = depth - 2;
+    if (levels < 1) levels = 1;
+    const size_t lds = (size_t)levels * BGS_WAVE * sizeof(uint32_t);
+    int64_t per_cu = (int64_t)(kSolveLdsPerCU / lds);
+    if (per_cu > kSolveWavesPerCU) per_cu = kSolveWavesPerCU;
+    if (per_cu < 1) per_cu = 1;
+    const int64_t tasks = b->n * g.w;
+    int64_t waves = (int64_t)b->num_cus * per_cu;
+    if (waves > (tasks + BGS_WAVE - 1) / BGS_WAVE) waves = (tasks + BGS_WAVE - 1) / BGS_WAVE;
+    unsigned long long* queue = reinterpret_cast<unsigned long long*>(b->d_work_count);   // (8-byte aligned: a region start)
+    (void)hipMemsetAsync(queue, 0, sizeof(unsigned long long), b->stream);
+    (void)hipMemsetAsync(d_nodes, 0, sizeof(unsigned long long), b->stream);
+    hipLaunchKernelGGL((k_connect_solve<NW>), dim3((uint32_t)waves), dim3(BGS_WAVE), lds, b->stream, g, (const uint64_t*)b->d_planes,
+                       (const uint8_t*)b->d_status, b->n, depth, (uint64_t)max_nodes, queue, d_codes, d_plies, d_nodes);
+}
+
 }  // namespace
 
 void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts, uint64_t* d_ends,
@@ -905,17 +1262,18 @@ void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_
         launch_bounce_evaluate<BounceGeom, 3>(b, b->bg, seed, p, cap, d_counts, d_ends, d_totals);
 }
 
-void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts) {
-    EvalGeom g{};
-    g.h = b->cg.h;
-    g.w = b->cg.w;
-    g.k = b->cg.k;
-    g.cells_total = (uint32_t)(g.h * g.w);
-    for (int x = 0; x < g.w; ++x) {
-        const int bit = x * (g.h + 1);
-        g.bottoms[bit >> 6] |= 1ull << (bit & 63);
-        for (int y = 0; y < g.h; ++y) g.cells[(bit + y) >> 6] |= 1ull << ((bit + y) & 63);
+void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,
+                   unsigned long long* d_nodes) {
+    const EvalGeom g = eval_geom(b);
+    switch (b->cg.nw) {
+        case 1: launch_solve<1>(b, g, depth, max_nodes, d_codes, d_plies, d_nodes); break;
+        case 2: launch_solve<2>(b, g, depth, max_nodes, d_codes, d_plies, d_nodes); break;
+        default: launch_solve<3>(b, g, depth, max_nodes, d_codes, d_plies, d_nodes); break;
     }
+}
+
+void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts) {
+    const EvalGeom g = eval_geom(b);
     const uint32_t p = (uint32_t)playouts, cap = (uint32_t)max_plies;
     const bool per_ply = b->rng_per_ply != 0;
     switch (b->cg.nw) {

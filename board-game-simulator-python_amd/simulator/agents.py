@@ -5,6 +5,9 @@
 that start with it, ``(wins + draws / 2) / playouts`` for the player to move.  All actions of all positions are played
 and counted in ONE launch: ``ConnectBatch.evaluate_actions`` for Connect states (a column each),
 ``BounceBatch.evaluate_moves`` for Bounce states (a (source, target) move each).
+
+``SolverAgent`` values Connect positions exactly where it can (``ConnectBatch.solve_actions``): 1.0 for a forced win,
+0.5 for a draw, 0.0 for a forced loss, and a fallback agent's value where the search was cut by its horizon or budget.
 """
 
 from __future__ import annotations
@@ -13,7 +16,8 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .batch import DEFAULT_SEED, BounceBatch, ConnectBatch
+from .batch import (DEFAULT_SEED, DEFAULT_SOLVE_NODES, SOLVE_BUDGET, SOLVE_DRAW, SOLVE_LOSS, SOLVE_UNKNOWN, SOLVE_WIN,
+                    BounceBatch, ConnectBatch)
 from .game import bounce, connect
 
 # Bounce playouts stop at this absolute ply count unless the agent is given another cap: random Bounce games are short
@@ -128,6 +132,99 @@ class MonteCarloAgent:
     def predict(self, state, game: int = 0) -> Dict:
         """{action: value} for every action in ``state.actions`` (the keys are those Action objects)."""
         return self.predict_many([state], first_game=game)[0]
+
+    def close(self) -> None:
+        for b in self._batches.values():
+            b.close()
+        self._batches.clear()
+
+
+class SolverAgent:
+    """Exact values of Connect positions (``simulator.game.connect.State``) by the batched alpha-beta solver.
+
+    ``predict(state)`` maps every action of ``state.actions`` to 1.0 (the mover can force a win after it), 0.5 (a draw
+    with best play) or 0.0 (the opponent can force a win), within lines of at most ``depth`` plies (None: a full solve)
+    and ``max_nodes`` positions a column.  A column the horizon or the budget left open takes the value of ``fallback``
+    (e.g. a ``MonteCarloAgent``), or 0.5 without one.  ``choose(state)`` plays the fastest win, else the best of the
+    draws and open columns, else the slowest loss.
+    """
+
+    def __init__(self, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES, fallback=None, device: int = 0):
+        if depth is not None and depth < 1:
+            raise ValueError("depth must be >= 1")
+        if max_nodes < 1:
+            raise ValueError("max_nodes must be >= 1")
+        self.depth = None if depth is None else int(depth)
+        self.max_nodes = int(max_nodes)
+        self.fallback = fallback
+        self.device = int(device)
+        self._batches: Dict[tuple, ConnectBatch] = {}
+
+    def _batch(self, config: connect.Config, n: int) -> ConnectBatch:
+        key = (config.height, config.width, config.count, n)
+        b = self._batches.get(key)
+        if b is None:
+            b = ConnectBatch(config.height, config.width, config.count, n, device=self.device)
+            self._batches[key] = b
+        return b
+
+    def solve_many(self, states: Sequence):
+        """(codes int8[n, width], plies int16[n, width]) of `states` (Connect states sharing one Config)"""
+        config = states[0].config
+        if any(not isinstance(s, connect.State) or s.config != config for s in states):
+            raise ValueError("SolverAgent: Connect states that share one Config")
+        b = self._batch(config, len(states))
+        grid = np.stack([s.grid for s in states])
+        player = np.array([s.player for s in states], dtype=np.int8)
+        winner = np.array([-1 if not s.has_ended else int(s.to_json()["winner"]) for s in states], dtype=np.int8)
+        if (b.write_state(grid, player, winner) != 0).any():
+            raise ValueError("SolverAgent: a state could not be loaded")
+        return b.solve_actions(depth=self.depth, max_nodes=self.max_nodes)
+
+    def _values(self, states: Sequence, codes: np.ndarray) -> List[Dict]:
+        """{action: value} of every state from its row of solver codes; the fallback (one call for all states) fills the
+        columns the horizon or the budget left open"""
+        open_ = (codes == SOLVE_UNKNOWN) | (codes == SOLVE_BUDGET)
+        fill = None
+        if self.fallback is not None and open_.any():
+            fill = self.fallback.predict_many(list(states))
+        exact = {SOLVE_WIN: 1.0, SOLVE_DRAW: 0.5, SOLVE_LOSS: 0.0}
+        out = []
+        for k, s in enumerate(states):
+            v = {}
+            for a in s.actions:
+                c = int(codes[k, a.column])
+                v[a] = exact[c] if c in exact else (float(fill[k][a]) if fill is not None else 0.5)
+            out.append(v)
+        return out
+
+    def predict_many(self, states: Sequence) -> List[Dict]:
+        """`predict` of every state, solved in one call"""
+        if not states:
+            return []
+        codes, _ = self.solve_many(states)
+        return self._values(states, codes)
+
+    def predict(self, state) -> Dict:
+        """{action: value} for every action in ``state.actions``"""
+        return self.predict_many([state])[0]
+
+    def choose(self, state):
+        """the fastest win, else the best-valued draw or open column, else the slowest loss"""
+        codes, plies = self.solve_many([state])
+        values = self._values([state], codes)[0]
+        best, best_key = None, None
+        for a in state.actions:
+            c, p = int(codes[0, a.column]), int(plies[0, a.column])
+            if c == SOLVE_WIN:
+                key = (2, -p)
+            elif c == SOLVE_LOSS:
+                key = (0, p)
+            else:
+                key = (1, values[a])
+            if best_key is None or key > best_key:
+                best, best_key = a, key
+        return best
 
     def close(self) -> None:
         for b in self._batches.values():

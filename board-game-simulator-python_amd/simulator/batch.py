@@ -23,6 +23,9 @@ import numpy as np
 from .game import _abi
 
 DEFAULT_SEED = 0x0123456789ABCDEF
+# bgs_connect_solve_actions: the codes (include/bgs.h) and the default node budget of one (board, column) search
+SOLVE_NONE, SOLVE_LOSS, SOLVE_DRAW, SOLVE_WIN, SOLVE_UNKNOWN, SOLVE_BUDGET = -2, -1, 0, 1, 2, 3
+DEFAULT_SOLVE_NODES = 1 << 20
 
 
 def _ptr(a: np.ndarray, ctype):
@@ -806,6 +809,41 @@ class ConnectBatch(_Batch):
                                                            ctypes.c_int32(max_plies), ctypes.c_void_p(out.data_ptr()), 1))
         return out
 
+    def solve_actions(self, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
+        """Exact solve of every column of every board (bgs_connect_solve_actions), one launch: (codes int8[n, width],
+        plies int16[n, width] or None).  Seen from the player to move; lines of at most `depth` plies from the board,
+        the column itself counted (None: a full solve).  Codes: SOLVE_WIN 1 / SOLVE_LOSS -1 (plies: to the end, the
+        winner fastest, the loser slowest), SOLVE_DRAW 0 (plies: the board's empty cells), SOLVE_UNKNOWN 2 (the horizon
+        cut some lines), SOLVE_BUDGET 3 (the search of that column visited more than `max_nodes` positions),
+        SOLVE_NONE -2 (an illegal column or an ended board).  The boards and `steps` are not modified."""
+        depth = self.height * self.width if depth is None else int(depth)
+        codes = np.empty((self.n, self.width), dtype=np.int8)
+        plies = np.empty((self.n, self.width), dtype=np.int16) if with_plies else None
+        _abi.check(_abi.lib().bgs_connect_solve_actions(
+            self._handle, ctypes.c_int32(depth), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.ctypes.data),
+            None if plies is None else ctypes.c_void_p(plies.ctypes.data), None, 0))
+        return codes, plies
+
+    def solve_actions_tensor(self, codes=None, plies=None, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES,
+                             with_plies: bool = True):
+        """`solve_actions` into device tensors int8[n, width] and int16[n, width] (allocated when None; plies only
+        `with_plies` or when given), enqueued on the batch's stream with no synchronisation: (codes, plies or None)."""
+        t = self._need_torch("solve_actions_tensor")
+        shape = (self.n, self.width)
+        if codes is None:
+            codes = t.empty(shape, dtype=t.int8, device=f"cuda:{self.device}")
+        if plies is None and with_plies:
+            plies = t.empty(shape, dtype=t.int16, device=f"cuda:{self.device}")
+        for name, x, dt in (("codes", codes, t.int8), ("plies", plies, t.int16)):
+            if x is not None and not (x.is_cuda and x.dtype == dt and tuple(x.shape) == shape and x.is_contiguous()
+                                      and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned {dt} device tensor of shape {shape}")
+        depth = self.height * self.width if depth is None else int(depth)
+        _abi.check(_abi.lib().bgs_connect_solve_actions(
+            self._handle, ctypes.c_int32(depth), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.data_ptr()),
+            None if plies is None else ctypes.c_void_p(plies.data_ptr()), None, 1))
+        return codes, plies
+
     @property
     def legal(self) -> np.ndarray:
         out = np.empty((self.n, self.width), dtype=np.uint8)
@@ -889,6 +927,12 @@ class BounceBatch(_Batch):
         raise ValueError("evaluate_actions: Connect batches only (Bounce boards: evaluate_moves)")
 
     evaluate_actions_tensor = evaluate_actions
+
+    def solve_actions(self, *args, **kwargs):
+        """Not available for Bounce: the exact solver covers bit-packed Connect boards (Bounce games can cycle)."""
+        raise ValueError("solve_actions: Connect batches only")
+
+    solve_actions_tensor = solve_actions
 
     def evaluate_moves(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1) -> np.ndarray:
         """Flat Monte-Carlo evaluation of every legal move of every board (bgs_bounce_evaluate_moves), one launch:

@@ -200,6 +200,32 @@ BGS_API int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t pl
  * device pointer, n * S * playouts beyond int64. */
 BGS_API int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
                                       int counts_on_device);
+/* Exact solve of every column of every board (Connect, bit-packed boards only): a depth-first alpha-beta search a
+ * (board, column), no RNG.  Entry [i][c] is seen from the player to move at board i; the lines searched are at most
+ * `depth` plies long, column c itself counted (depth >= height * width: a full solve).
+ *   codes int8[n][width]   BGS_SOLVE_WIN: after c the mover can force a win that ends at most `depth` plies from board i;
+ *                          BGS_SOLVE_LOSS: after c the opponent can force one within the same horizon;
+ *                          BGS_SOLVE_DRAW: neither, and board i has at most `depth` empty cells (no line was cut: exact);
+ *                          BGS_SOLVE_UNKNOWN: neither, and the horizon cut some lines;
+ *                          BGS_SOLVE_BUDGET: the search of this (board, column) visited more than max_nodes positions;
+ *                          BGS_SOLVE_NONE: an illegal column or an ended board.
+ *   plies int16[n][width]  (may be NULL) WIN / LOSS: plies from board i to the end when the winner wins fastest and the
+ *                          loser loses slowest (1 = c wins at once); DRAW: board i's empty cells; otherwise 0.
+ *   nodes                  (may be NULL) positions the search visited in all; its value is implementation-defined.
+ * A draw needs a full board, and empty cells and horizon fall by one a ply together: either no line is cut (W / D / L
+ * exact) or no draw is reachable (W / L / unknown).  Only BUDGET depends on max_nodes or on the search order.
+ * on_device != 0: device pointers (codes and plies 16-byte aligned, nodes 8-byte aligned), enqueued on the batch's
+ * stream, no synchronisation, no allocation; otherwise host buffers, filled when the call returns.  The boards and
+ * bgs_steps are not modified.  Refused (BGS_ERR_ARG): Bounce and generic batches, depth < 1, max_nodes < 1, NULL codes,
+ * a misaligned device pointer. */
+#define BGS_SOLVE_NONE (-2)
+#define BGS_SOLVE_LOSS (-1)
+#define BGS_SOLVE_DRAW 0
+#define BGS_SOLVE_WIN 1
+#define BGS_SOLVE_UNKNOWN 2
+#define BGS_SOLVE_BUDGET 3
+BGS_API int bgs_connect_solve_actions(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies,
+                                      uint64_t* nodes, int on_device);
 /* env-steps (transitions applied to running boards) since the last bgs_reset / bgs_reset_steps */
 BGS_API int bgs_steps(bgs_batch* b, uint64_t* steps);
 BGS_API int bgs_reset_steps(bgs_batch* b);
