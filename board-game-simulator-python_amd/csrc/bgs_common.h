@@ -146,6 +146,25 @@ __host__ __device__ __forceinline__ uint32_t sample_index(uint32_t draw, uint32_
     return (uint32_t)(((uint64_t)draw * n_actions) >> 32);
 }
 
+// position of the k-th set bit of m (k < popcount(m)) without a loop: a popcount-guided binary search.  The loop form
+// (clear the lowest bit k times) costs a wave the largest k of its 64 lanes.
+__device__ __forceinline__ uint32_t select_bit64(uint64_t m, uint32_t k) {
+    const uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
+    const uint32_t below = (uint32_t)__popc(lo);
+    const bool upper = k >= below;
+    uint32_t word = upper ? hi : lo, pos = upper ? 32u : 0u;
+    k -= upper ? below : 0u;
+#pragma unroll
+    for (uint32_t half = 16u; half >= 1u; half >>= 1) {
+        const uint32_t cnt = (uint32_t)__popc(word & ((1u << half) - 1u));
+        const bool up = k >= cnt;
+        word = up ? word >> half : word;
+        pos += up ? half : 0u;
+        k -= up ? cnt : 0u;
+    }
+    return pos;
+}
+
 // reward pair packed as two int8 in one uint16 (little endian: byte 0 = player 0)
 __host__ __device__ __forceinline__ uint16_t reward_pair(uint32_t status) {
     return status == 1u ? (uint16_t)0xFF01u : status == 2u ? (uint16_t)0x01FFu : (uint16_t)0u;

@@ -26,6 +26,7 @@
 
 #include "bgs_common.h"
 #include "bgs_internal.h"
+#include "bounce_board.h"
 
 // identity of this translation unit as compiled: hash of this file, the kernel headers and the compile flags (csrc/Makefile)
 #ifndef BGS_TU_ID
@@ -36,85 +37,9 @@ extern "C" const char bgs_tu_id_bounce[] = BGS_TU_ID;
 namespace bgs {
 namespace {
 
-struct Board {
-    uint64_t v[4];
-};
-
 // plies are stored as uint16: a board that holds 65535 plies is not stepped any further (no wrap-around, no reuse
 // of philox blocks); bgs_step_actions reports BGS_ERR_ILLEGAL for it
 constexpr uint32_t kMaxPlies = 65535u;
-
-__device__ __forceinline__ uint64_t occupancy(const Board& b) { return b.v[0] | b.v[1] | b.v[2] | b.v[3]; }
-
-__device__ __forceinline__ uint32_t value_at(const Board& b, int c) {
-    return (uint32_t)((b.v[0] >> c) & 1ull) | ((uint32_t)((b.v[1] >> c) & 1ull) << 1) |
-           ((uint32_t)((b.v[2] >> c) & 1ull) << 2) | ((uint32_t)((b.v[3] >> c) & 1ull) << 3);
-}
-
-// position of the k-th set bit of m (k < popcount(m)) without a loop: a popcount-guided binary search.  The loop form
-// (clear the lowest bit k times) costs a wave the largest k of its 64 lanes.
-__device__ __forceinline__ uint32_t select_bit64(uint64_t m, uint32_t k) {
-    const uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
-    const uint32_t below = (uint32_t)__popc(lo);
-    const bool upper = k >= below;
-    uint32_t word = upper ? hi : lo, pos = upper ? 32u : 0u;
-    k -= upper ? below : 0u;
-#pragma unroll
-    for (uint32_t half = 16u; half >= 1u; half >>= 1) {
-        const uint32_t cnt = (uint32_t)__popc(word & ((1u << half) - 1u));
-        const bool up = k >= cnt;
-        word = up ? word >> half : word;
-        pos += up ? half : 0u;
-        k -= up ? cnt : 0u;
-    }
-    return pos;
-}
-
-// every legal landing cell of the piece on cell `src` for `player` (SURVEY Appendix B rules 4-5).
-// Walkers only ever stand on interior cells (the start piece, empty interior cells), so a forward step never leaves
-// the board and needs no mask; forward is "<< w" for player 0 and ">> w" for player 1, written as two shifts one of
-// which is by 0, so there is no per-lane select in the step.
-__device__ __forceinline__ uint64_t reach(const BounceGeom& g, const Board& b, uint64_t occ, uint32_t player, int src) {
-    const uint64_t empty_interior = ~occ & g.interior;
-    const uint64_t landing = empty_interior | (player ? g.goal_bottom : g.goal_top);
-    const uint64_t bounce_on = occ & g.interior;
-    const uint32_t up = player ? 0u : (uint32_t)g.w, down = player ? (uint32_t)g.w : 0u;
-    uint64_t pending = 1ull << src, done = 0, targets = 0;
-    while (pending) {
-        const int c = __ffsll((unsigned long long)pending) - 1;
-        pending &= pending - 1;
-        done |= 1ull << c;
-        const uint32_t v = value_at(b, c);
-        uint64_t a0 = 1ull << c, al = 0, ar = 0, land = 0;
-        for (uint32_t s = 1; s <= v; ++s) {
-            const uint64_t via_left = a0 | al, via_right = a0 | ar;  // who may go on left / right (no reversal)
-            const uint64_t nf = ((via_left | ar) << up) >> down;
-            const uint64_t nl = (via_left & g.not_col0) >> 1;
-            const uint64_t nr = (via_right & g.not_collast) << 1;
-            if (s < v) {
-                a0 = nf & empty_interior;
-                al = nl & empty_interior;
-                ar = nr & empty_interior;
-                if (!(a0 | al | ar)) break;
-            } else {
-                land = nf | nl | nr;
-            }
-        }
-        targets |= land & landing;
-        pending |= land & bounce_on & ~done;
-    }
-    return targets;
-}
-
-// pieces the side to move may pick: those in the occupied non-goal row nearest its own side (Appendix B rule 3)
-template <class GEO>
-__device__ __forceinline__ uint64_t movable(const GEO& g, uint64_t occ, uint32_t player) {
-    const uint64_t oi = occ & g.interior;
-    if (!oi) return 0;
-    const int cell = player ? 63 - __clzll((long long)oi) : __ffsll((unsigned long long)oi) - 1;
-    const int row = (int)(((uint32_t)cell * g.inv_w) >> 16);
-    return oi & (((1ull << g.w) - 1ull) << (row * g.w));
-}
 
 __device__ __forceinline__ uint32_t count_actions(const BounceGeom& g, const Board& b, uint64_t occ, uint32_t player) {
     uint64_t src = movable(g, occ, player);
@@ -147,13 +72,6 @@ __device__ __forceinline__ void pick_action(const BounceGeom& g, const Board& b,
     }
 }
 
-__device__ __forceinline__ void move_piece(Board& b, int src_cell, int dst_cell) {
-    const uint32_t v = value_at(b, src_cell);
-    const uint64_t keep = ~(1ull << src_cell);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) b.v[j] = (b.v[j] & keep) | ((uint64_t)((v >> j) & 1u) << dst_cell);
-}
-
 // terminal test after `mover` moved to dst_cell (Appendix B rule 7); n_next = action count of the next player
 __device__ __forceinline__ uint32_t settle(const BounceGeom& g, const Board& b, uint32_t mover, int dst_cell,
                                            uint32_t& n_next) {
@@ -168,18 +86,6 @@ __device__ __forceinline__ uint32_t settle(const BounceGeom& g, const Board& b, 
 // a board whose side to move has no action although nobody ended the game (start positions, loaded boards)
 __device__ __forceinline__ uint32_t settle_blocked(const BounceGeom& g, const Board& b, uint32_t player) {
     return count_actions(g, b, occupancy(b), 1u - player) ? (1u - player) + 1u : BGS_ST_DRAW;
-}
-
-__device__ __forceinline__ Board load_board(const uint64_t* __restrict__ planes, int64_t n, int64_t i) {
-    Board b;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) b.v[j] = planes[(int64_t)j * n + i];
-    return b;
-}
-
-__device__ __forceinline__ void store_board(uint64_t* __restrict__ planes, int64_t n, int64_t i, const Board& b) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) planes[(int64_t)j * n + i] = b.v[j];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -479,100 +385,11 @@ k_bounce_rollout(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// K3f: the fused rollout, flattened.  One lane per board as in GL = 1 -- but the move search of a ply is not run as
-// nested loops (for every column: while cells are pending: for every step), whose trip counts differ from lane to
-// lane so that a wave executes the SUM over columns of the per-column maxima.  It is ONE loop per wave in which every
-// lane expands one cell of its own work queue per iteration -- the queue runs through the lane's sources one after
-// the other and through each source's pending bounce cells -- so a wave executes the maximum over its lanes of the
-// number of cells, and all lanes run the same instructions on different cells (measured before: 12.7 of 64 lanes
-// active per VALU instruction in lane-group mode, 8.4 with one lane per board).
-// Per-source target masks go to a per-lane dword column of LDS ([dword][lane]: the bank is the lane, dynamic indices
-// never conflict); per-source counts are packed 8 bits each (a source has at most 64 targets: 0..64 needs 7 bits).
+// K3f: the fused rollout, flattened.  One lane per board as in GL = 1, the move search of a ply the flat move list of
+// bounce_board.h (enumerate_flat / pick_flat: one loop a wave, every lane expanding one cell of its own queue per
+// iteration; measured before: 12.7 of 64 lanes active per VALU instruction in lane-group mode, 8.4 with one lane per
+// board).
 // ------------------------------------------------------------------------------------------------
-struct FlatMoves {
-    uint64_t counts;     // byte x = number of targets of the piece in column x of the active row
-    uint32_t n;          // number of actions
-    uint32_t row_base;   // cell index of column 0 of the active row
-};
-
-// the action list of `player` for the lanes with `want` set; the other lanes idle through the loop
-__device__ __forceinline__ void enumerate_flat(const BounceGeom& g, const Board& b, uint64_t occ, uint32_t player, bool want,
-                                               uint32_t* column, FlatMoves& m) {
-    const uint64_t empty_interior = ~occ & g.interior;
-    const uint64_t landing = empty_interior | (player ? g.goal_bottom : g.goal_top);
-    const uint64_t bounce_on = occ & g.interior;
-    const uint32_t up = player ? 0u : (uint32_t)g.w, down = player ? (uint32_t)g.w : 0u;
-    uint64_t rem = want ? movable(g, occ, player) : 0ull;   // sources still to search
-    const int first = rem ? __ffsll((unsigned long long)rem) - 1 : 0;
-    m.row_base = (uint32_t)((int)(((uint32_t)first * g.inv_w) >> 16) * g.w);
-    m.counts = 0;
-    m.n = 0;
-    uint64_t pending = 0, done = 0, targets = 0;
-    uint32_t x = 0;
-    bool open_source = false;  // a source is being searched and has not been booked yet
-    while (__builtin_amdgcn_ballot_w64(rem != 0 || pending != 0 || open_source)) {
-        if (pending == 0) {
-            if (open_source) {  // the source's closure is complete: book it
-                const uint32_t cnt = (uint32_t)__popcll(targets);
-                m.counts |= (uint64_t)cnt << (8u * x);
-                m.n += cnt;
-                column[(2u * x) * BGS_BLOCK] = (uint32_t)targets;
-                column[(2u * x + 1u) * BGS_BLOCK] = (uint32_t)(targets >> 32);
-                open_source = false;
-            }
-            if (rem) {  // next source
-                const int cell = __ffsll((unsigned long long)rem) - 1;
-                rem &= rem - 1;
-                x = (uint32_t)cell - m.row_base;
-                pending = 1ull << cell;
-                done = 0;
-                targets = 0;
-                open_source = true;
-            }
-        }
-        if (pending) {  // expand one cell: a segment of value(cell) steps
-            const int c = __ffsll((unsigned long long)pending) - 1;
-            pending &= pending - 1;
-            done |= 1ull << c;
-            const uint32_t v = value_at(b, c);
-            uint64_t a0 = 1ull << c, al = 0, ar = 0, land = 0;
-            for (uint32_t s = 1; s <= v; ++s) {
-                const uint64_t via_left = a0 | al, via_right = a0 | ar;
-                const uint64_t nf = ((via_left | ar) << up) >> down;
-                const uint64_t nl = (via_left & g.not_col0) >> 1;
-                const uint64_t nr = (via_right & g.not_collast) << 1;
-                if (s < v) {
-                    a0 = nf & empty_interior;
-                    al = nl & empty_interior;
-                    ar = nr & empty_interior;
-                    if (!(a0 | al | ar)) break;
-                } else {
-                    land = nf | nl | nr;
-                }
-            }
-            targets |= land & landing;
-            pending |= land & bounce_on & ~done;
-        }
-    }
-}
-
-// the idx-th action of the canonical list from the packed counts and the LDS column
-__device__ __forceinline__ void pick_flat(const FlatMoves& m, const uint32_t* column, uint32_t idx, int& src_cell, int& dst_cell) {
-    uint32_t col = 0;
-    bool found = false;
-#pragma unroll
-    for (int x = 0; x < kMaxTrackedColumns; ++x) {
-        const uint32_t cnt = (uint32_t)(m.counts >> (8 * x)) & 255u;
-        const bool here = !found && idx < cnt;
-        col = here ? (uint32_t)x : col;
-        idx = (found || here) ? idx : idx - cnt;
-        found = found || here;
-    }
-    const uint64_t chosen = ((uint64_t)column[(2u * col + 1u) * BGS_BLOCK] << 32) | column[(2u * col) * BGS_BLOCK];
-    src_cell = (int)(m.row_base + col);
-    dst_cell = (int)select_bit64(chosen, idx);
-}
-
 // Boards a draining wave has parked for the other waves of its workgroup (see the drain paragraph in the kernel).
 struct ParkedBoards {
     static constexpr uint32_t WAVES = BGS_BLOCK / BGS_WAVE, CAP = 32;
@@ -632,8 +449,8 @@ k_bounce_rollout_flat(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __re
 
     Board b;
     b.v[0] = b.v[1] = b.v[2] = b.v[3] = 0;
-    FlatMoves mv;
-    mv.counts = 0;
+    FlatMoves<1> mv;
+    mv.counts[0] = 0;
     mv.n = 0;
     mv.row_base = 0;
     uint32_t st = 0, plies = 0, first_ply = 0, game = 0, stepped = 0;
@@ -719,13 +536,13 @@ k_bounce_rollout_flat(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __re
         // side to move has no action is settled here, also at the ply cap (the transition that blocked it counts)
         if (__builtin_amdgcn_ballot_w64(search)) {
             const uint64_t occ = occupancy(b);
-            enumerate_flat(g, b, occ, plies & 1u, search, column, mv);
+            enumerate_flat<1, false>(g, b, occ, plies & 1u, search, column, mv);
             const bool blocked = search && mv.n == 0u;
             if (__builtin_amdgcn_ballot_w64(blocked)) {
                 // the other side wins if IT could move, else a draw (Appendix B rule 7; a loaded or start position
                 // without moves is settled the same way)
-                FlatMoves other;
-                enumerate_flat(g, b, occ, 1u - (plies & 1u), blocked, column, other);
+                FlatMoves<1> other;
+                enumerate_flat<1, false>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
                 if (blocked) {
                     st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
                     dirty = true;
@@ -952,7 +769,7 @@ __device__ __forceinline__ void land_all(const GEO& g, const PieceBoard<PMAX>& b
         L.v[k] = 0;
         if (k < (int)g.piece_count) {
             const uint32_t v = g.piece_value[k];  // wave-uniform: the step loop below does not diverge
-            uint64_t a0 = 1ull << cell[k], al = 0, ar = 0, land = 0;
+            uint64_t a0 = 1ull << cell[k], al = 0, ar = 0, land = 0;   // (reach's walk in bounce_board.h, without its early exit)
             for (uint32_t s = 1; s <= v; ++s) {
                 const uint64_t via_left = a0 | al, via_right = a0 | ar;  // who may go on left / right (no reversal)
                 const uint64_t nf = ((via_left | ar) << up) >> down;
@@ -1290,7 +1107,7 @@ __device__ __forceinline__ void enumerate_wave(const GEO& g, const Board& b, uin
     const uint64_t empty_interior = ~occ & g.interior;
     const uint64_t landing = empty_interior | (player ? g.goal_bottom : g.goal_top);
     const uint32_t up = player ? 0u : (uint32_t)g.w, down = player ? (uint32_t)g.w : 0u;
-    // A: the landing cells of this lane's piece
+    // A: the landing cells of this lane's piece (reach's walk in bounce_board.h, a wave-uniform trip count)
     uint64_t a0 = alive ? 1ull << cell : 0ull, al = 0, ar = 0, land = 0;
     for (uint32_t s = 1; __builtin_amdgcn_ballot_w64(s <= value) != 0ull; ++s) {
         if (s <= value) {

@@ -8,10 +8,8 @@
 // ply -- exactly an oracle rollout(seed, first_game * width * playouts) over the boards replicated W * P times, in
 // (i, c, p) order, and stepped by their column.
 //
-// A unit of its own (bgs_kernel_unit_id(3)): the Connect unit and its id stay as they are.  The ply below restates, on
-// the same board packing (connect_kernels.hip: two bit-planes, column-major, a sentinel bit on top of every column), what
-// the Connect unit's `play_plies` / `select_landing` / `select_bit64` (one-word boards), `four_in_a_row_at` and
-// `has_run` / `drop_stone` (any board) do.
+// A unit of its own (bgs_kernel_unit_id(3)).  The boards and their primitives are the Connect and Bounce units' own:
+// connect_board.h and bounce_board.h.
 //
 // Shape.  A wave owns either several whole (board, column) segments -- P <= games per wave -- or one slice of one segment.
 // Its lanes take the chunk's playouts in order (the refill loop of K2a: lanes take new games at 4-ply block boundaries,
@@ -23,6 +21,8 @@
 #include "../../include/bgs.h"
 #include "bgs_common.h"
 #include "bgs_internal.h"
+#include "bounce_board.h"
+#include "connect_board.h"
 
 #ifndef BGS_TU_ID
 #define BGS_TU_ID "unknown"
@@ -39,157 +39,23 @@ constexpr uint32_t kEvalGamesWide = 256;        // multi-word boards: 4 a lane
 constexpr uint32_t kIllegal = 0xFFu;            // child code of an illegal column / an ended board
 
 struct EvalGeom {
-    int h, w, k;
+    int rh, rw, rk;
+    __host__ __device__ __forceinline__ int h() const { return rh; }
+    __host__ __device__ __forceinline__ int w() const { return rw; }
+    __host__ __device__ __forceinline__ int k() const { return rk; }
     uint32_t cells_total;          // h * w: a board with this many stones is full
     uint64_t bottoms[BGS_CONNECT_MAX_WORDS];   // the bottom cell of every column
     uint64_t cells[BGS_CONNECT_MAX_WORDS];     // every real cell (no sentinels)
 };
 
-template <int NW>
-struct Planes {
-    uint64_t w[NW];
-};
-
-template <int NW>
-__device__ __forceinline__ Planes<NW> por(const Planes<NW>& a, const Planes<NW>& b) {
-    Planes<NW> r;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) r.w[j] = a.w[j] | b.w[j];
-    return r;
-}
-
-// 64 bits of `a` starting at bit `s` (>= 0; bits beyond the plane read as 0) -- the Connect unit's word_at / shr
-template <int NW>
-__device__ __forceinline__ uint64_t bits_at(const Planes<NW>& a, int s) {
-    const int q = s >> 6, r = s & 63;
-    uint64_t lo = 0, hi = 0;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-        lo = (j == q) ? a.w[j] : lo;
-        hi = (j == q + 1) ? a.w[j] : hi;
-    }
-    return r ? (lo >> r) | (hi << (64 - r)) : lo;
-}
-
-template <int NW>
-__device__ __forceinline__ Planes<NW> shr(const Planes<NW>& a, int s) {
-    Planes<NW> r;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) r.w[j] = bits_at(a, 64 * j + s);
-    return r;
-}
-
-// k stones in a row anywhere on the plane (the Connect unit's has_run): shift-and-AND with run doubling over the four
-// directions vertical 1, horizontal H+1, rising H+2, falling H
-template <int NW>
-__device__ __forceinline__ bool has_run(const EvalGeom& g, const Planes<NW>& b) {
-    const int dirs[4] = {1, g.h + 1, g.h + 2, g.h};
-    uint64_t hit = 0;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        Planes<NW> m = b;
-        int len = 1;
-        while (2 * len <= g.k) {
-            const Planes<NW> s = shr(m, len * dirs[d]);
-#pragma unroll
-            for (int j = 0; j < NW; ++j) m.w[j] &= s.w[j];
-            len *= 2;
-        }
-        if (len < g.k) {
-            const Planes<NW> s = shr(m, (g.k - len) * dirs[d]);
-#pragma unroll
-            for (int j = 0; j < NW; ++j) m.w[j] &= s.w[j];
-        }
-#pragma unroll
-        for (int j = 0; j < NW; ++j) hit |= m.w[j];
-    }
-    return hit != 0;
-}
-
-// (a & b) | c in one VALU instruction (v_bitop3_b32, truth table 0xEA)
-__device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r;
-    asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xea" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
-
-// four in a row through the stone just dropped on `pos` of a one-word plane (the Connect unit's four_in_a_row_at): the
-// vertical run is the four cells ending at pos, the three other directions are tested on the whole plane
-__device__ __forceinline__ bool four_in_a_row_at(uint64_t b, int h, uint32_t pos) {
-    const int dirs[3] = {h + 1, h + 2, h};
-    uint32_t acc_lo = 0, acc_hi = 0;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const uint64_t s1 = b >> dirs[d];
-        const uint32_t pl = (uint32_t)b & (uint32_t)s1, ph = (uint32_t)(b >> 32) & (uint32_t)(s1 >> 32);
-        const uint64_t pairs = ((uint64_t)ph << 32) | pl;
-        uint64_t s2;
-        asm("v_lshrrev_b64 %0, %1, %2" : "=v"(s2) : "s"(2 * dirs[d]), "v"(pairs));
-        if (d == 0) {
-            acc_lo = pl & (uint32_t)s2;
-            acc_hi = ph & (uint32_t)(s2 >> 32);
-        } else {
-            acc_lo = and_or(pl, (uint32_t)s2, acc_lo);
-            acc_hi = and_or(ph, (uint32_t)(s2 >> 32), acc_hi);
-        }
-    }
-    uint32_t column = (uint32_t)(b >> ((pos - 3u) & 63u));
-    asm("" : "+v"(column));
-    return ((acc_lo | acc_hi) != 0u) | ((column & 15u) == 15u);
-}
-
-// position of the k-th set bit of m (k < popcount(m)): the Connect unit's select_bit64
-__device__ __forceinline__ uint32_t select_bit64(uint64_t m, uint32_t k) {
-    const uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
-    const uint32_t below = (uint32_t)__popc(lo);
-    const bool upper = k >= below;
-    uint32_t word = upper ? hi : lo, pos = upper ? 32u : 0u;
-    k -= upper ? below : 0u;
-#pragma unroll
-    for (uint32_t half = 16u; half >= 1u; half >>= 1) {
-        const uint32_t cnt = (uint32_t)__popc(word & ((1u << half) - 1u));
-        const bool up = k >= cnt;
-        word = up ? word >> half : word;
-        pos += up ? half : 0u;
-        k -= up ? cnt : 0u;
-    }
-    return pos;
-}
-
-// the idx-th set bit of a one-word `landing` (at most one bit per column field, never a field's top bit) by arithmetic
-// on the fields: the Connect unit's select_landing.  Needs w <= 2^h.
-__device__ __forceinline__ uint32_t select_landing(uint64_t landing, uint64_t bottoms, uint64_t tops, uint32_t stride, uint32_t idx) {
-    const uint64_t flags = ((landing + (tops - bottoms)) & tops) >> (stride - 1u);
-    const uint64_t cmp = ((uint64_t)idx - flags) * bottoms + tops;
-    const uint32_t col = (uint32_t)__popcll(cmp & tops);
-    const uint64_t low = (1ull << stride) - 1ull;
-    return (uint32_t)__ffsll((unsigned long long)(landing & (low << (col * stride)))) - 1u;
-}
-
-// the cells the next stone of every open column would take: (stones + column bottoms) carries through each column's
-// stones and stops under its sentinel; a carry may cross a word boundary with the column
-template <int NW>
-__device__ __forceinline__ Planes<NW> landing_of(const EvalGeom& g, const Planes<NW>& occ) {
-    Planes<NW> r;
-    uint64_t carry = 0;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-        const uint64_t s = occ.w[j] + g.bottoms[j];
-        const uint64_t t = s + carry;
-        carry = (uint64_t)(s < occ.w[j]) + (uint64_t)(t < s);
-        r.w[j] = t & g.cells[j];
-    }
-    return r;
-}
-
 // the mover of this ply drops a stone on `pos` (act = all ones) or nothing (act = 0); returns "the mover has won"
 template <int NW>
-__device__ __forceinline__ bool drop_and_test(const EvalGeom& g, Planes<NW>& mine, uint32_t pos, uint32_t act) {
+__device__ __forceinline__ bool drop_and_test(const EvalGeom& g, Bits<NW>& mine, uint32_t pos, uint32_t act) {
     if (NW == 1) {
         const uint64_t bit = 1ull << (pos & 63u);
         mine.w[0] = ((uint64_t)and_or((uint32_t)(bit >> 32), act, (uint32_t)(mine.w[0] >> 32)) << 32) |
                     and_or((uint32_t)bit, act, (uint32_t)mine.w[0]);
-        const bool won = g.k == 4 ? four_in_a_row_at(mine.w[0], g.h, pos) : has_run(g, mine);
+        const bool won = g.k() == 4 ? four_in_a_row_at(mine.w[0], g.h(), pos) : has_run(g, mine);
         return won && act;
     }
 #pragma unroll
@@ -199,12 +65,12 @@ __device__ __forceinline__ bool drop_and_test(const EvalGeom& g, Planes<NW>& min
 
 // one uniformly drawn ply on the board (p0, p1) by the side `mover`: the position of the stone it drops
 template <int NW>
-__device__ __forceinline__ uint32_t draw_position(const EvalGeom& g, const Planes<NW>& occ, uint32_t draw) {
-    const Planes<NW> landing = landing_of(g, occ);
+__device__ __forceinline__ uint32_t draw_position(const EvalGeom& g, const Bits<NW>& occ, uint32_t draw) {
+    const Bits<NW> landing = landing_of(g, occ);
     if (NW == 1) {
         const uint32_t idx = sample_index(draw, (uint32_t)__popcll(landing.w[0]));
-        const bool by_fields = g.h <= 15 && (uint32_t)g.w <= (1u << g.h);   // (uniform)
-        return by_fields ? select_landing(landing.w[0], g.bottoms[0], g.bottoms[0] << g.h, (uint32_t)g.h + 1u, idx)
+        const bool by_fields = g.h() <= 15 && (uint32_t)g.w() <= (1u << g.h());   // (uniform)
+        return by_fields ? select_landing(landing.w[0], g.bottoms[0], g.bottoms[0] << g.h(), (uint32_t)g.h() + 1u, idx)
                          : select_bit64(landing.w[0], idx);
     }
     uint32_t cnt = 0;
@@ -236,7 +102,7 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
     __syncthreads();
 
     // ---- the wave's work: segments [seg0, seg0 + nseg), playouts [pbeg, pbeg + per_seg) of each
-    const int64_t segments = n * g.w;
+    const int64_t segments = n * g.w();
     const int64_t wave = wave_base + (int64_t)__builtin_amdgcn_readfirstlane(blockIdx.x * kEvalWavesPerBlock + (threadIdx.x >> 6));
     int64_t seg0 = 0;
     uint32_t nseg = 0, pbeg = 0, per_seg = playouts;
@@ -255,9 +121,9 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
     const uint32_t avail = nseg * per_seg;
     uint32_t taken = 0;
 
-    const uint32_t stride = (uint32_t)g.h + 1u;
-    Planes<NW> p[2];                 // the lane's game: stones of player 0 / player 1
-    Planes<NW> c0, c1;               // the board after the current segment's first move
+    const uint32_t stride = (uint32_t)g.h() + 1u;
+    Bits<NW> p[2];                 // the lane's game: stones of player 0 / player 1
+    Bits<NW> c0, c1;               // the board after the current segment's first move
     uint32_t child = kIllegal;       // its status (0 running, 1 / 2 winner, 3 draw) or kIllegal
     uint32_t child_ply = 0, root_mover = 0;
     int64_t cur_seg = -1;
@@ -300,9 +166,9 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
                 if (seg != cur_seg) {
                     flush();
                     cur_seg = seg;
-                    const int64_t i = seg / g.w;
-                    const int col = (int)(seg - i * g.w);
-                    Planes<NW> r0, r1;
+                    const int64_t i = seg / g.w();
+                    const int col = (int)(seg - i * g.w());
+                    Bits<NW> r0, r1;
 #pragma unroll
                     for (int j = 0; j < NW; ++j) {
                         r0.w[j] = planes[(int64_t)j * n + i];
@@ -312,10 +178,10 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
 #pragma unroll
                     for (int j = 0; j < NW; ++j) rply += (uint32_t)__popcll(r0.w[j]) + (uint32_t)__popcll(r1.w[j]);
                     root_mover = rply & 1u;
-                    const uint32_t height = (uint32_t)__popcll(bits_at(por(r0, r1), col * (int)stride) & ((1ull << g.h) - 1ull));
+                    const uint32_t height = (uint32_t)__popcll(shr(r0 | r1, col * (int)stride).w[0] & ((1ull << g.h()) - 1ull));
                     child = kIllegal;
-                    if (status[i] == BGS_ST_RUNNING && height < (uint32_t)g.h) {
-                        Planes<NW>& mine = root_mover ? r1 : r0;
+                    if (status[i] == BGS_ST_RUNNING && height < (uint32_t)g.h()) {
+                        Bits<NW>& mine = root_mover ? r1 : r0;
                         const bool won = drop_and_test(g, mine, (uint32_t)col * stride + height, ~0u);
                         child_ply = rply + 1u;
                         child = won ? root_mover + 1u : (child_ply == g.cells_total ? BGS_ST_DRAW : BGS_ST_RUNNING);
@@ -362,7 +228,7 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
             const uint32_t draw = PER_PLY ? ph.v[j] : sub_draw(word, j);
             const uint32_t act = j >= skip ? live : 0u;
             const uint32_t ply = 4u * blk + j;          // stones before this sub-step; its mover is player j & 1
-            const uint32_t pos = draw_position(g, por(p[0], p[1]), draw);
+            const uint32_t pos = draw_position(g, p[0] | p[1], draw);
             const bool won = drop_and_test(g, p[j & 1u], pos, act);
             const bool full = ply + 1u == g.cells_total;
             if (act) {
@@ -392,7 +258,7 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
 template <int NW, bool PER_PLY>
 void launch_evaluate(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t playouts, uint32_t max_plies,
                      int32_t* d_counts) {
-    const int64_t segments = b->n * g.w;
+    const int64_t segments = b->n * g.w();
     const uint32_t per_wave = NW == 1 ? kEvalGamesOneWord : kEvalGamesWide;
     uint32_t segs_per_wave = 1, slices = 1, slice_len = playouts;
     if (playouts <= per_wave) {
@@ -406,7 +272,7 @@ void launch_evaluate(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint3
     }
     const int64_t waves = slices == 1 ? (segments + segs_per_wave - 1) / segs_per_wave : segments * (int64_t)slices;
     // game ids: ((first_game + i) * W + c) * P + p = first_game * W * P + (i * W + c) * P + p, mod 2^64
-    const uint64_t game_base = b->first_game * (uint64_t)g.w * (uint64_t)playouts;
+    const uint64_t game_base = b->first_game * (uint64_t)g.w() * (uint64_t)playouts;
     constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
     for (int64_t w0 = 0; w0 < waves; w0 += kMaxBlocks * kEvalWavesPerBlock) {
         int64_t blocks = (waves - w0 + kEvalWavesPerBlock - 1) / kEvalWavesPerBlock;
@@ -425,10 +291,9 @@ void launch_evaluate(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint3
 // keyed by the board's absolute ply): an oracle rollout(seed, first_game * S * P) over the roots replicated S * P times
 // and stepped by their slot's move, illegal slots dropped.
 //
-// The ply below restates, on the Bounce unit's packing (bounce_kernels.hip: four value bit-planes, cell y * W + x), what
-// its `movable` / `reach` / `enumerate_flat` / `pick_flat` / `move_piece` do -- the one-lane-per-board ply of K3f, whose
-// target masks live in a per-lane dword column of LDS.  It reads boards from memory and never assumes they descend from
-// the configured start position (K3p's piece list does).
+// The ply is K3f's one-lane-per-board ply (bounce_board.h: enumerate_flat / pick_flat, target masks in a per-lane dword
+// column of LDS).  It reads boards from memory and never assumes they descend from the configured start position (K3p's
+// piece list does).
 //
 // Shape.  A first pass counts the legal moves of every root and scans them (uint64 inclusive prefix `ends` in the
 // staging region): the legal (root, slot) segments are numbered 0 .. ends[n-1] - 1 in (root, slot) order, their playouts
@@ -448,174 +313,20 @@ constexpr uint32_t kBounceMaxPlies = 65535u;      // plies are uint16 (the Bounc
 // 256 roots x 256 playouts / 4096 x 64: 1 wave 2.01 / 2.47, 2 waves 2.71 / 4.09, 4 waves 2.88 / 5.13 (docs/EXPERIMENTS.md §16)
 constexpr int kBounceEvalWps = 4;
 
-struct BBoard {
-    uint64_t v[4];
-};
-
-__device__ __forceinline__ uint64_t b_occupancy(const BBoard& b) { return b.v[0] | b.v[1] | b.v[2] | b.v[3]; }
-
-__device__ __forceinline__ uint32_t b_value_at(const BBoard& b, int c) {
-    return (uint32_t)((b.v[0] >> c) & 1ull) | ((uint32_t)((b.v[1] >> c) & 1ull) << 1) |
-           ((uint32_t)((b.v[2] >> c) & 1ull) << 2) | ((uint32_t)((b.v[3] >> c) & 1ull) << 3);
-}
-
-// pieces the side to move may pick: the occupied non-goal row nearest its own side
-template <class GEO>
-__device__ __forceinline__ uint64_t b_movable(const GEO& g, uint64_t occ, uint32_t player) {
-    const uint64_t oi = occ & g.interior;
-    if (!oi) return 0;
-    const int cell = player ? 63 - __clzll((long long)oi) : __ffsll((unsigned long long)oi) - 1;
-    const int row = (int)(((uint32_t)cell * g.inv_w) >> 16);
-    return oi & (((1ull << g.w) - 1ull) << (row * g.w));
-}
-
-// one segment of v steps from cell c (the frontier walk of the Bounce unit's reach): the cells it ends on
-template <class GEO>
-__device__ __forceinline__ uint64_t b_segment(const GEO& g, uint32_t v, int c, uint64_t empty_interior, uint32_t up, uint32_t down) {
-    uint64_t a0 = 1ull << c, al = 0, ar = 0, land = 0;
-    for (uint32_t s = 1; s <= v; ++s) {
-        const uint64_t via_left = a0 | al, via_right = a0 | ar;   // no immediate left <-> right reversal
-        const uint64_t nf = ((via_left | ar) << up) >> down;
-        const uint64_t nl = (via_left & g.not_col0) >> 1;
-        const uint64_t nr = (via_right & g.not_collast) << 1;
-        if (s < v) {
-            a0 = nf & empty_interior;
-            al = nl & empty_interior;
-            ar = nr & empty_interior;
-            if (!(a0 | al | ar)) break;
-        } else {
-            land = nf | nl | nr;
-        }
-    }
-    return land;
-}
-
-// every legal landing cell of the piece on `src` for `player` (a lane's own loop: roots only)
-template <class GEO>
-__device__ __forceinline__ uint64_t b_reach(const GEO& g, const BBoard& b, uint64_t occ, uint32_t player, int src) {
-    const uint64_t empty_interior = ~occ & g.interior;
-    const uint64_t landing = empty_interior | (player ? g.goal_bottom : g.goal_top);
-    const uint64_t bounce_on = occ & g.interior;
-    const uint32_t up = player ? 0u : (uint32_t)g.w, down = player ? (uint32_t)g.w : 0u;
-    uint64_t pending = 1ull << src, done = 0, targets = 0;
-    while (pending) {
-        const int c = __ffsll((unsigned long long)pending) - 1;
-        pending &= pending - 1;
-        done |= 1ull << c;
-        const uint64_t land = b_segment(g, b_value_at(b, c), c, empty_interior, up, down);
-        targets |= land & landing;
-        pending |= land & bounce_on & ~done;
-    }
-    return targets;
-}
-
-// the action list of a board: per-column target counts packed a byte each (a source has at most 64 targets), masks in
-// the lane's LDS column ([dword][lane]).  NC words of counts: boards up to 8 * NC columns.
-template <int NC>
-struct BMoves {
-    uint64_t counts[NC];
-    uint32_t n;          // number of actions
-    uint32_t row_base;   // cell index of column 0 of the active row
-};
-
-// K3f's flattened search: one loop a wave, every lane expanding one cell of its own queue per iteration; lanes without
-// `want` idle through it and keep their column and list
-template <class GEO, int NC>
-__device__ __forceinline__ void b_enumerate(const GEO& g, const BBoard& b, uint64_t occ, uint32_t player, bool want,
-                                            uint32_t* column, BMoves<NC>& m) {
-    const uint64_t empty_interior = ~occ & g.interior;
-    const uint64_t landing = empty_interior | (player ? g.goal_bottom : g.goal_top);
-    const uint64_t bounce_on = occ & g.interior;
-    const uint32_t up = player ? 0u : (uint32_t)g.w, down = player ? (uint32_t)g.w : 0u;
-    uint64_t rem = want ? b_movable(g, occ, player) : 0ull;
-    if (want) {
-        const int first = rem ? __ffsll((unsigned long long)rem) - 1 : 0;
-        m.row_base = (uint32_t)((int)(((uint32_t)first * g.inv_w) >> 16) * g.w);
-#pragma unroll
-        for (int k = 0; k < NC; ++k) m.counts[k] = 0;
-        m.n = 0;
-    }
-    uint64_t pending = 0, done = 0, targets = 0;
-    uint32_t x = 0;
-    bool open_source = false;
-    while (__builtin_amdgcn_ballot_w64(rem != 0 || pending != 0 || open_source)) {
-        if (pending == 0) {
-            if (open_source) {   // the source's closure is complete: book it
-                const uint32_t cnt = (uint32_t)__popcll(targets);
-#pragma unroll
-                for (int k = 0; k < NC; ++k) m.counts[k] |= (x >> 3) == (uint32_t)k ? (uint64_t)cnt << (8u * (x & 7u)) : 0ull;
-                m.n += cnt;
-                column[(2u * x) * BGS_BLOCK] = (uint32_t)targets;
-                column[(2u * x + 1u) * BGS_BLOCK] = (uint32_t)(targets >> 32);
-                open_source = false;
-            }
-            if (rem) {
-                const int cell = __ffsll((unsigned long long)rem) - 1;
-                rem &= rem - 1;
-                x = (uint32_t)cell - m.row_base;
-                pending = 1ull << cell;
-                done = 0;
-                targets = 0;
-                open_source = true;
-            }
-        }
-        if (pending) {
-            const int c = __ffsll((unsigned long long)pending) - 1;
-            pending &= pending - 1;
-            done |= 1ull << c;
-            const uint64_t land = b_segment(g, b_value_at(b, c), c, empty_interior, up, down);
-            targets |= land & landing;
-            pending |= land & bounce_on & ~done;
-        }
-    }
-}
-
-// the idx-th action of the canonical list (sources by ascending x, targets by ascending cell)
-template <int NC>
-__device__ __forceinline__ void b_pick(const BMoves<NC>& m, const uint32_t* column, uint32_t idx, int& src_cell, int& dst_cell) {
-    uint32_t col = 0;
-    bool found = false;
-#pragma unroll
-    for (int x = 0; x < 8 * NC; ++x) {
-        const uint32_t cnt = (uint32_t)(m.counts[x >> 3] >> (8 * (x & 7))) & 255u;
-        const bool here = !found && idx < cnt;
-        col = here ? (uint32_t)x : col;
-        idx = (found || here) ? idx : idx - cnt;
-        found = found || here;
-    }
-    const uint64_t chosen = ((uint64_t)column[(2u * col + 1u) * BGS_BLOCK] << 32) | column[(2u * col) * BGS_BLOCK];
-    src_cell = (int)(m.row_base + col);
-    dst_cell = (int)select_bit64(chosen, idx);
-}
-
-__device__ __forceinline__ void b_move(BBoard& b, int src_cell, int dst_cell) {
-    const uint32_t v = b_value_at(b, src_cell);
-    const uint64_t keep = ~(1ull << src_cell);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) b.v[j] = (b.v[j] & keep) | ((uint64_t)((v >> j) & 1u) << dst_cell);
-}
-
-__device__ __forceinline__ BBoard b_load(const uint64_t* __restrict__ planes, int64_t n, int64_t i) {
-    BBoard b;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) b.v[j] = planes[(int64_t)j * n + i];
-    return b;
-}
-
 // legal moves of a root: 0 when it has ended or holds the most plies a board can (a move could not be stored)
 template <class GEO>
 __device__ __forceinline__ uint32_t b_root_moves(const GEO& g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status,
                                                  const uint16_t* __restrict__ plies_buf, int64_t n, int64_t i) {
     if (status[i] != BGS_ST_RUNNING || plies_buf[i] >= kBounceMaxPlies) return 0u;
-    const BBoard b = b_load(planes, n, i);
-    const uint64_t occ = b_occupancy(b);
+    const Board b = load_board(planes, n, i);
+    const uint64_t occ = occupancy(b);
     const uint32_t player = plies_buf[i] & 1u;
-    uint64_t src = b_movable(g, occ, player);
+    uint64_t src = movable(g, occ, player);
     uint32_t cnt = 0;
     while (src) {
         const int s = __ffsll((unsigned long long)src) - 1;
         src &= src - 1;
-        cnt += (uint32_t)__popcll(b_reach(g, b, occ, player, s));
+        cnt += (uint32_t)__popcll(reach(g, b, occ, player, s));
     }
     return cnt;
 }
@@ -688,10 +399,10 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
     uint64_t win_base = 0;            // (wave-uniform) first segment of the tally's window
     bool dry = false;
 
-    BBoard b, cb;                     // the lane's game; the board after its segment's first move
+    Board b, cb;                     // the lane's game; the board after its segment's first move
 #pragma unroll
     for (int j = 0; j < 4; ++j) b.v[j] = cb.v[j] = 0;
-    BMoves<NC> mv;
+    FlatMoves<NC> mv;
 #pragma unroll
     for (int k = 0; k < NC; ++k) mv.counts[k] = 0;
     mv.n = 0;
@@ -782,16 +493,16 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
                     }
                     const int64_t i = lo;
                     uint32_t j = (uint32_t)(seg - (i ? ends[i - 1] : 0ull));   // the root's j-th legal move
-                    const BBoard r = b_load(planes, n, i);
+                    const Board r = load_board(planes, n, i);
                     const uint32_t rply = plies_buf[i];
                     root_mover = rply & 1u;
-                    const uint64_t occ = b_occupancy(r);
-                    uint64_t src = b_movable(g, occ, root_mover);
+                    const uint64_t occ = occupancy(r);
+                    uint64_t src = movable(g, occ, root_mover);
                     int s_cell = 0, t_cell = 0;
                     while (src) {
                         const int s = __ffsll((unsigned long long)src) - 1;
                         src &= src - 1;
-                        const uint64_t tm = b_reach(g, r, occ, root_mover, s);
+                        const uint64_t tm = reach(g, r, occ, root_mover, s);
                         const uint32_t cnt = (uint32_t)__popcll(tm);
                         if (j < cnt) {
                             s_cell = s;
@@ -803,7 +514,7 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
                     const uint32_t x = (uint32_t)s_cell - (uint32_t)(((uint32_t)s_cell * g.inv_w) >> 16) * (uint32_t)g.w;
                     cur_where = (uint64_t)i * slots + (uint64_t)x * hw + (uint32_t)t_cell;
                     cb = r;
-                    b_move(cb, s_cell, t_cell);
+                    move_piece(cb, s_cell, t_cell);
                     child_ply = rply + 1u;
                     child_st = ((1ull << t_cell) & (g.goal_top | g.goal_bottom)) ? root_mover + 1u : BGS_ST_RUNNING;
                 }
@@ -824,16 +535,16 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
         // ---- the action lists of the boards that have just moved; a side to move without an action settles the game:
         // the other side wins if IT could move, else a draw
         if (__builtin_amdgcn_ballot_w64(search)) {
-            const uint64_t occ = b_occupancy(b);
-            b_enumerate<GEO, NC>(g, b, occ, plies & 1u, search, column, mv);
+            const uint64_t occ = occupancy(b);
+            enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
             const bool blocked = search && mv.n == 0u;
             if (__builtin_amdgcn_ballot_w64(blocked)) {
-                BMoves<NC> other;
+                FlatMoves<NC> other;
 #pragma unroll
                 for (int k = 0; k < NC; ++k) other.counts[k] = 0;
                 other.n = 0;
                 other.row_base = 0;
-                b_enumerate<GEO, NC>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
+                enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
                 if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
             }
             search = false;
@@ -851,8 +562,8 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
             }
             const uint32_t mover = plies & 1u;
             int s, t;
-            b_pick<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, t);
-            b_move(b, s, t);
+            pick_flat<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, t);
+            move_piece(b, s, t);
             ++plies;
             stepped += 1u;
             if ((1ull << t) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
@@ -893,14 +604,14 @@ void launch_bounce_evaluate(const bgs_batch* b, const GEO& g, uint64_t seed, uin
 
 EvalGeom eval_geom(const bgs_batch* b) {
     EvalGeom g{};
-    g.h = b->cg.h;
-    g.w = b->cg.w;
-    g.k = b->cg.k;
-    g.cells_total = (uint32_t)(g.h * g.w);
-    for (int x = 0; x < g.w; ++x) {
-        const int bit = x * (g.h + 1);
+    g.rh = b->cg.h;
+    g.rw = b->cg.w;
+    g.rk = b->cg.k;
+    g.cells_total = (uint32_t)(g.h() * g.w());
+    for (int x = 0; x < g.w(); ++x) {
+        const int bit = x * (g.h() + 1);
         g.bottoms[bit >> 6] |= 1ull << (bit & 63);
-        for (int y = 0; y < g.h; ++y) g.cells[(bit + y) >> 6] |= 1ull << ((bit + y) & 63);
+        for (int y = 0; y < g.h(); ++y) g.cells[(bit + y) >> 6] |= 1ull << ((bit + y) & 63);
     }
     return g;
 }
@@ -932,119 +643,50 @@ constexpr int kSolveWavesPerCU = 16;      // persistent waves a CU (fewer when t
 constexpr uint32_t kSolveLdsPerCU = 160u * 1024u;
 enum : uint32_t { kSolveIdle = 0, kSolveEnter = 1, kSolveCont = 2, kSolveRet = 3 };
 
-// bit x of the result is bit x - s of `a` (s >= 0; bits below the plane read as 0)
-template <int NW>
-__device__ __forceinline__ Planes<NW> shl(const Planes<NW>& a, int s) {
-    Planes<NW> r;
-    if (NW == 1) {
-        r.w[0] = s < 64 ? a.w[0] << s : 0ull;
-        return r;
-    }
-    const int q = s >> 6, rr = s & 63;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-        uint64_t x = 0, y = 0;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) {
-            x = (k == j - q) ? a.w[k] : x;
-            y = (k == j - q - 1) ? a.w[k] : y;
-        }
-        r.w[j] = rr ? (x << rr) | (y >> (64 - rr)) : x;
-    }
-    return r;
-}
-
-template <int NW>
-__device__ __forceinline__ void pand(Planes<NW>& a, const Planes<NW>& b) {
-#pragma unroll
-    for (int j = 0; j < NW; ++j) a.w[j] &= b.w[j];
-}
-
-template <int NW>
-__device__ __forceinline__ void por_into(Planes<NW>& a, const Planes<NW>& b) {
-#pragma unroll
-    for (int j = 0; j < NW; ++j) a.w[j] |= b.w[j];
-}
-
 // the cells where a stone of `me` would complete k in a row (occupied cells and sentinels included: the caller masks).
 // The sentinel row between columns is never a stone, so no run wraps from one column into the next.  k = 4: the runs
 // before (B_m) and after (A_m) a cell are built once per direction and joined, A3 | A2 B1 | A1 B2 | B3; any other k
 // tests every split of the k - 1 other stones.
 template <int NW>
-__device__ __forceinline__ Planes<NW> threats(const EvalGeom& g, const Planes<NW>& me) {
-    const int dirs[3] = {g.h + 1, g.h + 2, g.h};
-    Planes<NW> t;
-    if (g.k == 4) {
+__device__ __forceinline__ Bits<NW> threats(const EvalGeom& g, const Bits<NW>& me) {
+    const int dirs[3] = {g.h() + 1, g.h() + 2, g.h()};
+    Bits<NW> t;
+    if (g.k() == 4) {
         t = shl(me, 1);
-        pand(t, shl(me, 2));
-        pand(t, shl(me, 3));
+        t = t & shl(me, 2);
+        t = t & shl(me, 3);
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            Planes<NW> a1 = shr(me, dirs[d]), b1 = shl(me, dirs[d]);
-            Planes<NW> a2 = a1, b2 = b1;
-            pand(a2, shr(me, 2 * dirs[d]));
-            pand(b2, shl(me, 2 * dirs[d]));
-            Planes<NW> a3 = a2, b3 = b2;
-            pand(a3, shr(me, 3 * dirs[d]));
-            pand(b3, shl(me, 3 * dirs[d]));
-            pand(a2, b1);
-            pand(a1, b2);
-            por_into(t, a3);
-            por_into(t, b3);
-            por_into(t, a2);
-            por_into(t, a1);
+            Bits<NW> a1 = shr(me, dirs[d]), b1 = shl(me, dirs[d]);
+            Bits<NW> a2 = a1, b2 = b1;
+            a2 = a2 & shr(me, 2 * dirs[d]);
+            b2 = b2 & shl(me, 2 * dirs[d]);
+            Bits<NW> a3 = a2, b3 = b2;
+            a3 = a3 & shr(me, 3 * dirs[d]);
+            b3 = b3 & shl(me, 3 * dirs[d]);
+            a2 = a2 & b1;
+            a1 = a1 & b2;
+            t = t | a3;
+            t = t | b3;
+            t = t | a2;
+            t = t | a1;
         }
         return t;
     }
 #pragma unroll
     for (int j = 0; j < NW; ++j) t.w[j] = ~0ull;
-    for (int m = 1; m < g.k; ++m) pand(t, shl(me, m));   // vertical: the k - 1 cells below
+    for (int m = 1; m < g.k(); ++m) t = t & shl(me, m);   // vertical: the k - 1 cells below
     for (int d = 0; d < 3; ++d) {
-        for (int split = 0; split < g.k; ++split) {       // `split` stones after the cell, k - 1 - split before it
-            Planes<NW> m;
+        for (int split = 0; split < g.k(); ++split) {       // `split` stones after the cell, k - 1 - split before it
+            Bits<NW> m;
 #pragma unroll
             for (int j = 0; j < NW; ++j) m.w[j] = ~0ull;
-            for (int i = 1; i <= split; ++i) pand(m, shr(me, i * dirs[d]));
-            for (int i = 1; i < g.k - split; ++i) pand(m, shl(me, i * dirs[d]));
-            por_into(t, m);
+            for (int i = 1; i <= split; ++i) m = m & shr(me, i * dirs[d]);
+            for (int i = 1; i < g.k() - split; ++i) m = m & shl(me, i * dirs[d]);
+            t = t | m;
         }
     }
     return t;
-}
-
-template <int NW>
-__device__ __forceinline__ void flip(Planes<NW>& a, uint32_t pos) {
-#pragma unroll
-    for (int j = 0; j < NW; ++j) a.w[j] ^= ((uint32_t)j == (pos >> 6)) ? 1ull << (pos & 63u) : 0ull;
-}
-
-template <int NW>
-__device__ __forceinline__ uint32_t popc(const Planes<NW>& a) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) c += (uint32_t)__popcll(a.w[j]);
-    return c;
-}
-
-template <int NW>
-__device__ __forceinline__ uint32_t lowest(const Planes<NW>& a) {   // position of the lowest set bit (a != 0)
-    uint32_t pos = 0;
-    bool found = false;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-        const bool here = !found && a.w[j] != 0ull;
-        pos = here ? 64u * j + (uint32_t)(__ffsll((unsigned long long)a.w[j]) - 1) : pos;
-        found = found || here;
-    }
-    return pos;
-}
-
-template <int NW>
-__device__ __forceinline__ bool is_zero(const Planes<NW>& a) {
-    uint64_t o = 0;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) o |= a.w[j];
-    return o == 0ull;
 }
 
 template <int NW>
@@ -1055,12 +697,12 @@ k_connect_solve(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* 
     extern __shared__ uint32_t solve_stack[];   // [levels][64 lanes]
     uint32_t* const stk = solve_stack + threadIdx.x;
     const uint32_t lane = threadIdx.x;
-    const uint64_t tasks = (uint64_t)n * (uint64_t)g.w;
-    const uint32_t stride = (uint32_t)g.h + 1u;
-    const uint64_t colmask = (1ull << g.h) - 1ull;
-    const uint32_t half = (uint32_t)g.w >> 1;
+    const uint64_t tasks = (uint64_t)n * (uint64_t)g.w();
+    const uint32_t stride = (uint32_t)g.h() + 1u;
+    const uint64_t colmask = (1ull << g.h()) - 1ull;
+    const uint32_t half = (uint32_t)g.w() >> 1;
 
-    Planes<NW> me, op;   // stones of the side to move at the current node, and of the other side
+    Bits<NW> me, op;   // stones of the side to move at the current node, and of the other side
 #pragma unroll
     for (int j = 0; j < NW; ++j) me.w[j] = op.w[j] = 0;
     uint32_t mode = kSolveIdle, empty = 0;
@@ -1090,18 +732,18 @@ k_connect_solve(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* 
             if (mode == kSolveIdle && base + rank < tasks) {
                 task = base + rank;
                 visited = 0;
-                const int64_t i = (int64_t)(task / (uint32_t)g.w);
-                const uint32_t col = (uint32_t)(task - (uint64_t)i * (uint32_t)g.w);
-                Planes<NW> r0, r1;
+                const int64_t i = (int64_t)(task / (uint32_t)g.w());
+                const uint32_t col = (uint32_t)(task - (uint64_t)i * (uint32_t)g.w());
+                Bits<NW> r0, r1;
 #pragma unroll
                 for (int j = 0; j < NW; ++j) {
                     r0.w[j] = planes[(int64_t)j * n + i];
                     r1.w[j] = planes[(int64_t)(NW + j) * n + i];
                 }
-                const uint32_t stones = popc(r0) + popc(r1);
+                const uint32_t stones = popcount(r0) + popcount(r1);
                 empty = g.cells_total - stones;
                 const uint32_t mover = stones & 1u;
-                const uint64_t cell = bits_at(landing_of(g, por(r0, r1)), (int)(col * stride)) & colmask;
+                const uint64_t cell = shr(landing_of(g, r0 | r1), (int)(col * stride)).w[0] & colmask;
                 if (status[i] != BGS_ST_RUNNING || cell == 0ull) {
                     finish(BGS_SOLVE_NONE, 0);
                 } else {
@@ -1115,7 +757,7 @@ k_connect_solve(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* 
                     } else if (depth == 1) {
                         finish(BGS_SOLVE_UNKNOWN, 0);
                     } else {
-                        const Planes<NW> t = me;
+                        const Bits<NW> t = me;
                         me = op;
                         op = t;
                         l = 0;
@@ -1137,7 +779,7 @@ k_connect_solve(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* 
             } else {
                 --l;
                 const uint32_t word = stk[l * BGS_WAVE];
-                const Planes<NW> t = me;
+                const Bits<NW> t = me;
                 me = op;
                 op = t;
                 flip(me, word & 255u);
@@ -1160,12 +802,12 @@ k_connect_solve(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* 
             if (word & (1u << 13)) {
                 found = next == 0u;
                 pos = word & 255u;
-                next = (uint32_t)g.w;
+                next = (uint32_t)g.w();
             } else {
-                const Planes<NW> land = landing_of(g, por(me, op));
-                for (; next < (uint32_t)g.w && !found; ++next) {
+                const Bits<NW> land = landing_of(g, me | op);
+                for (; next < (uint32_t)g.w() && !found; ++next) {
                     const uint32_t col = (next & 1u) ? half - ((next + 1u) >> 1) : half + (next >> 1);
-                    const uint64_t cell = bits_at(land, (int)(col * stride)) & colmask;
+                    const uint64_t cell = shr(land, (int)(col * stride)).w[0] & colmask;
                     found = cell != 0ull;
                     pos = found ? col * stride + (uint32_t)(__ffsll((unsigned long long)cell) - 1) : pos;
                 }
@@ -1176,7 +818,7 @@ k_connect_solve(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* 
             } else {
                 stk[l * BGS_WAVE] = (word & 0xFFFF2000u) | (next << 8) | pos;
                 flip(me, pos);
-                const Planes<NW> t = me;
+                const Bits<NW> t = me;
                 me = op;
                 op = t;
                 ++l;
@@ -1186,26 +828,26 @@ k_connect_solve(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* 
         // ---- a node entered: settle it, or open its level
         if (mode == kSolveEnter) {
             ++visited;
-            const Planes<NW> land = landing_of(g, por(me, op));
+            const Bits<NW> land = landing_of(g, me | op);
             const int r = depth - 1 - l;   // plies the horizon leaves from this node
             if (visited > max_nodes) {
                 finish(BGS_SOLVE_BUDGET, 0);
-            } else if (is_zero(land) || r <= 0) {
+            } else if (!any(land) || r <= 0) {
                 val = 0;
                 mode = kSolveRet;
             } else {
-                Planes<NW> wins = threats(g, me);
-                pand(wins, land);
-                if (!is_zero(wins)) {
+                Bits<NW> wins = threats(g, me);
+                wins = wins & land;
+                if (any(wins)) {
                     val = kSolveK - (l + 2);
                     mode = kSolveRet;
                 } else if (r == 1) {
                     val = 0;
                     mode = kSolveRet;
                 } else {
-                    Planes<NW> lose = threats(g, op);
-                    pand(lose, land);
-                    const uint32_t cnt = popc(lose);
+                    Bits<NW> lose = threats(g, op);
+                    lose = lose & land;
+                    const uint32_t cnt = popcount(lose);
                     if (cnt >= 2u) {
                         val = -(kSolveK - (l + 3));
                         mode = kSolveRet;
@@ -1237,7 +879,7 @@ void launch_solve(const bgs_batch* b, const EvalGeom& g, int32_t depth, int64_t 
     int64_t per_cu = (int64_t)(kSolveLdsPerCU / lds);
     if (per_cu > kSolveWavesPerCU) per_cu = kSolveWavesPerCU;
     if (per_cu < 1) per_cu = 1;
-    const int64_t tasks = b->n * g.w;
+    const int64_t tasks = b->n * g.w();
     int64_t waves = (int64_t)b->num_cus * per_cu;
     if (waves > (tasks + BGS_WAVE - 1) / BGS_WAVE) waves = (tasks + BGS_WAVE - 1) / BGS_WAVE;
     unsigned long long* queue = reinterpret_cast<unsigned long long*>(b->d_work_count);   // (8-byte aligned: a region start)

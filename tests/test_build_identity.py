@@ -1,6 +1,6 @@
 """The build identity (bgs_build_id) belongs to what was COMPILED: a changed compile flag rebuilds every object without a
 `make clean`, and the id the library reports is folded from the ids its kernel objects were compiled with.  CPU only
-(hipcc cross-compiles gfx950); three full builds and a partial one of the library in a scratch copy of csrc/, about 80 s on 8 cores."""
+(hipcc cross-compiles gfx950); three full builds and a few partial ones of the library in a scratch copy of csrc/, about 80 s on 8 cores."""
 
 import ctypes
 import os
@@ -11,15 +11,16 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "board-game-simulator-python_amd")
 
-OBJECTS = ["bgs_capi", "bgs_host", "bgs_multi", "bgs_pipeline", "connect_kernels", "bounce_kernels", "generic_kernels"]
+OBJECTS = ["bgs_capi", "bgs_host", "bgs_multi", "bgs_pipeline", "connect_kernels", "bounce_kernels", "generic_kernels",
+           "evaluate_kernels"]
 
 
 def _ids(lib_path):
-    """(build id, the three kernel units' ids) of a library file, read in a child process."""
+    """(build id, the four kernel units' ids: connect, bounce, generic, evaluate) of a library file, read in a child process."""
     code = (
         "import ctypes, sys; l = ctypes.CDLL(sys.argv[1]); l.bgs_build_id.restype = ctypes.c_char_p; "
         "l.bgs_kernel_unit_id.restype = ctypes.c_char_p; l.bgs_kernel_unit_id.argtypes = [ctypes.c_int]; "
-        "print(l.bgs_build_id().decode(), *[l.bgs_kernel_unit_id(i).decode() for i in range(3)])"
+        "print(l.bgs_build_id().decode(), *[l.bgs_kernel_unit_id(i).decode() for i in range(4)])"
     )
     out = subprocess.check_output([sys.executable, "-c", code, lib_path], text=True).split()
     return out[0], out[1:]
@@ -43,7 +44,7 @@ def test_a_changed_flag_rebuilds_every_object_and_changes_the_id(tmp_path):
     _make(csrc)
     first, first_units = _ids(lib)
     assert len(first) == 16 and first != "unknown" and first == _print_id(csrc)
-    assert len(set(first_units)) == 3 and all(len(u) == 16 for u in first_units)
+    assert len(set(first_units)) == 4 and all(len(u) == 16 for u in first_units)
     stamps = {o: os.stat(os.path.join(csrc, o + ".o")).st_mtime_ns for o in OBJECTS}
 
     # nothing changed: nothing is compiled
@@ -84,7 +85,25 @@ def test_a_changed_flag_rebuilds_every_object_and_changes_the_id(tmp_path):
     assert fourth_units[1] not in (first_units[1], third_units[1])
     units = dict(line.split() for line in subprocess.check_output(
         ["make", "-s", "--no-print-directory", "-C", csrc, "print-unit-ids"], text=True).splitlines())
-    assert [units["connect"], units["bounce"], units["generic"]] == fourth_units
+    assert [units["connect"], units["bounce"], units["generic"], units["evaluate"]] == fourth_units
+
+    # the board headers two units share (connect_board.h: the Connect unit and the evaluation unit; bounce_board.h: the
+    # Bounce unit and the evaluation unit) move the ids of the units that include them, and no other
+    with open(os.path.join(csrc, "connect_board.h"), "a") as fh:
+        fh.write("\n// build identity test\n")
+    _make(csrc)
+    fifth, fifth_units = _ids(lib)
+    assert fifth not in (first, second, third, fourth) and fifth == _print_id(csrc)
+    assert fifth_units[0] != fourth_units[0] and fifth_units[3] != fourth_units[3]
+    assert fifth_units[1] == fourth_units[1] and fifth_units[2] == fourth_units[2]
+
+    with open(os.path.join(csrc, "bounce_board.h"), "a") as fh:
+        fh.write("\n// build identity test\n")
+    _make(csrc)
+    sixth, sixth_units = _ids(lib)
+    assert sixth not in (first, second, third, fourth, fifth) and sixth == _print_id(csrc)
+    assert sixth_units[1] != fifth_units[1] and sixth_units[3] != fifth_units[3]
+    assert sixth_units[0] == fifth_units[0] and sixth_units[2] == fifth_units[2]
 
 
 def test_the_library_in_the_tree_is_the_one_its_sources_give():
