@@ -1132,6 +1132,52 @@ int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int
     return BGS_OK;
 }
 
+int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
+                           int on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(codes != nullptr, "codes is NULL");
+    NEED(b->game == BGS_GAME_BOUNCE, "solve_moves: Bounce batches only (Connect boards: bgs_connect_solve_actions)");
+    NEED(!b->generic, "solve_moves: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
+         BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
+    NEED(depth >= 1, "depth must be >= 1 (got %d)", depth);
+    NEED(depth <= BGS_BOUNCE_SOLVE_MAX_DEPTH, "depth %d is beyond the maximum of %d plies the search stack is sized for", depth,
+         BGS_BOUNCE_SOLVE_MAX_DEPTH);
+    NEED(max_nodes >= 1, "max_nodes must be >= 1 (got %lld)", (long long)max_nodes);
+    const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;
+    // scratch: the boards' legal-move prefix and the workgroups' totals, in the staging region (ordered on the stream)
+    Stage st(b);
+    uint64_t* d_ends = st.take<uint64_t>((size_t)b->n);
+    uint64_t* d_totals = st.take<uint64_t>((size_t)(b->n + BGS_BLOCK - 1) / BGS_BLOCK);
+    NEED(d_ends && d_totals, "staging region too small");
+    if (on_device) {
+        NEED((reinterpret_cast<uintptr_t>(codes) & 15u) == 0, "device codes must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(plies) & 15u) == 0, "device plies must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(nodes) & 7u) == 0, "device nodes must be 8-byte aligned");
+        // without a caller's counter the total goes to the batch's own scratch word (behind the work-queue head)
+        unsigned long long* d_nodes = nodes ? reinterpret_cast<unsigned long long*>(nodes)
+                                            : reinterpret_cast<unsigned long long*>(b->d_work_count) + 1;
+        bgs::bounce_solve(b, depth, max_nodes, codes, plies, d_nodes, d_ends, d_totals);
+        return finish_launch();
+    }
+    // one device buffer: nodes (8 bytes), codes, plies -- each 16-byte aligned
+    const size_t codes_off = 16, plies_off = codes_off + ((cells + 15) & ~(size_t)15);
+    const size_t bytes = plies_off + cells * sizeof(int16_t);
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
+    bgs::bounce_solve(b, depth, max_nodes, reinterpret_cast<int8_t*>(d + codes_off),
+                      plies ? reinterpret_cast<int16_t*>(d + plies_off) : nullptr, reinterpret_cast<unsigned long long*>(d), d_ends,
+                      d_totals);
+    rc = finish_launch();
+    if (rc == BGS_OK) rc = copy_to_host(b, codes, d + codes_off, cells);
+    if (rc == BGS_OK && plies) rc = copy_to_host(b, plies, d + plies_off, cells * sizeof(int16_t));
+    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d, sizeof(uint64_t));
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
 int bgs_steps(bgs_batch* b, uint64_t* steps) {
     int rc = enter(b);
     if (rc) return rc;

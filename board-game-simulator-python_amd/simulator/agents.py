@@ -8,6 +8,7 @@ and counted in ONE launch: ``ConnectBatch.evaluate_actions`` for Connect states 
 
 ``SolverAgent`` values Connect positions exactly where it can (``ConnectBatch.solve_actions``): 1.0 for a forced win,
 0.5 for a draw, 0.0 for a forced loss, and a fallback agent's value where the search was cut by its horizon or budget.
+Bounce positions go to the horizon search ``BounceBatch.solve_moves`` in the same way (dispatched on the state's type).
 """
 
 from __future__ import annotations
@@ -16,8 +17,8 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .batch import (DEFAULT_SEED, DEFAULT_SOLVE_NODES, SOLVE_BUDGET, SOLVE_DRAW, SOLVE_LOSS, SOLVE_UNKNOWN, SOLVE_WIN,
-                    BounceBatch, ConnectBatch)
+from .batch import (DEFAULT_BOUNCE_SOLVE_DEPTH, DEFAULT_SEED, DEFAULT_SOLVE_NODES, SOLVE_BUDGET, SOLVE_DRAW, SOLVE_LOSS,
+                    SOLVE_UNKNOWN, SOLVE_WIN, BounceBatch, ConnectBatch)
 from .game import bounce, connect
 
 # Bounce playouts stop at this absolute ply count unless the agent is given another cap: random Bounce games are short
@@ -140,13 +141,18 @@ class MonteCarloAgent:
 
 
 class SolverAgent:
-    """Exact values of Connect positions (``simulator.game.connect.State``) by the batched alpha-beta solver.
+    """Exact values of Connect positions (``simulator.game.connect.State``) and Bounce positions
+    (``simulator.game.bounce.State``) by the batched alpha-beta solvers, dispatched on the state's type.
 
     ``predict(state)`` maps every action of ``state.actions`` to 1.0 (the mover can force a win after it), 0.5 (a draw
-    with best play) or 0.0 (the opponent can force a win), within lines of at most ``depth`` plies (None: a full solve)
-    and ``max_nodes`` positions a column.  A column the horizon or the budget left open takes the value of ``fallback``
-    (e.g. a ``MonteCarloAgent``), or 0.5 without one.  ``choose(state)`` plays the fastest win, else the best of the
-    draws and open columns, else the slowest loss.
+    with best play) or 0.0 (the opponent can force a win), within lines of at most ``depth`` plies (None: a full solve
+    for Connect; for Bounce, whose games can cycle, the default horizon of ``BounceBatch.solve_moves``) and ``max_nodes``
+    positions an action.  An action the horizon or the budget left open takes the value of ``fallback`` (e.g. a
+    ``MonteCarloAgent``), or 0.5 without one.  ``choose(state)`` plays the fastest win, else the best of the draws and
+    open actions, else the slowest loss.
+
+    ``solve_many`` returns the solver's own arrays: ``[n, width]`` for Connect (indexed by column), ``[n, width, height *
+    width]`` for Bounce (indexed by the source's column and the target cell ``ty * width + tx``).
     """
 
     def __init__(self, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES, fallback=None, device: int = 0):
@@ -158,7 +164,7 @@ class SolverAgent:
         self.max_nodes = int(max_nodes)
         self.fallback = fallback
         self.device = int(device)
-        self._batches: Dict[tuple, ConnectBatch] = {}
+        self._batches: Dict[tuple, Union[ConnectBatch, BounceBatch]] = {}
 
     def _batch(self, config: connect.Config, n: int) -> ConnectBatch:
         key = (config.height, config.width, config.count, n)
@@ -168,9 +174,39 @@ class SolverAgent:
             self._batches[key] = b
         return b
 
+    def _bounce_batch(self, config: bounce.Config, n: int) -> BounceBatch:
+        grid = config.grid
+        key = ("bounce", grid.shape, grid.tobytes(), n)
+        b = self._batches.get(key)
+        if b is None:
+            b = BounceBatch(grid, n, device=self.device)
+            self._batches[key] = b
+        return b
+
+    @staticmethod
+    def _slot(state, action) -> tuple:
+        """the index of `action` in a row of solver codes"""
+        if isinstance(state, bounce.State):
+            (sx, _), (tx, ty) = action.source.tolist(), action.target.tolist()
+            return (sx, ty * state.grid.shape[1] + tx)
+        return (action.column,)
+
     def solve_many(self, states: Sequence):
-        """(codes int8[n, width], plies int16[n, width]) of `states` (Connect states sharing one Config)"""
+        """(codes, plies) of `states` (states of one game sharing one Config): int8 / int16 [n, width] for Connect,
+        [n, width, height * width] for Bounce"""
         config = states[0].config
+        if isinstance(states[0], bounce.State):
+            if any(not isinstance(s, bounce.State) or s.config != config for s in states):
+                raise ValueError("SolverAgent: Bounce states that share one Config")
+            b = self._bounce_batch(config, len(states))
+            grid = np.stack([s.grid for s in states])
+            player = np.array([s.player for s in states], dtype=np.int8)
+            winner = np.array([s.to_json()["winner"] for s in states], dtype=np.int8)
+            plies = np.array([s._plies for s in states], dtype=np.int32)
+            if (b.write_state(grid, player, winner, plies) != 0).any():
+                raise ValueError("SolverAgent: a state could not be loaded")
+            depth = DEFAULT_BOUNCE_SOLVE_DEPTH if self.depth is None else self.depth
+            return b.solve_moves(depth=depth, max_nodes=self.max_nodes)
         if any(not isinstance(s, connect.State) or s.config != config for s in states):
             raise ValueError("SolverAgent: Connect states that share one Config")
         b = self._batch(config, len(states))
@@ -183,7 +219,7 @@ class SolverAgent:
 
     def _values(self, states: Sequence, codes: np.ndarray) -> List[Dict]:
         """{action: value} of every state from its row of solver codes; the fallback (one call for all states) fills the
-        columns the horizon or the budget left open"""
+        actions the horizon or the budget left open"""
         open_ = (codes == SOLVE_UNKNOWN) | (codes == SOLVE_BUDGET)
         fill = None
         if self.fallback is not None and open_.any():
@@ -193,7 +229,7 @@ class SolverAgent:
         for k, s in enumerate(states):
             v = {}
             for a in s.actions:
-                c = int(codes[k, a.column])
+                c = int(codes[(k,) + self._slot(s, a)])
                 v[a] = exact[c] if c in exact else (float(fill[k][a]) if fill is not None else 0.5)
             out.append(v)
         return out
@@ -210,12 +246,13 @@ class SolverAgent:
         return self.predict_many([state])[0]
 
     def choose(self, state):
-        """the fastest win, else the best-valued draw or open column, else the slowest loss"""
+        """the fastest win, else the best-valued draw or open action, else the slowest loss"""
         codes, plies = self.solve_many([state])
         values = self._values([state], codes)[0]
         best, best_key = None, None
         for a in state.actions:
-            c, p = int(codes[0, a.column]), int(plies[0, a.column])
+            at = (0,) + self._slot(state, a)
+            c, p = int(codes[at]), int(plies[at])
             if c == SOLVE_WIN:
                 key = (2, -p)
             elif c == SOLVE_LOSS:

@@ -26,6 +26,9 @@ DEFAULT_SEED = 0x0123456789ABCDEF
 # bgs_connect_solve_actions: the codes (include/bgs.h) and the default node budget of one (board, column) search
 SOLVE_NONE, SOLVE_LOSS, SOLVE_DRAW, SOLVE_WIN, SOLVE_UNKNOWN, SOLVE_BUDGET = -2, -1, 0, 1, 2, 3
 DEFAULT_SOLVE_NODES = 1 << 20
+# bgs_bounce_solve_moves: the deepest horizon (BGS_BOUNCE_SOLVE_MAX_DEPTH) and the default one
+BOUNCE_SOLVE_MAX_DEPTH = 16
+DEFAULT_BOUNCE_SOLVE_DEPTH = 3
 
 
 def _ptr(a: np.ndarray, ctype):
@@ -844,6 +847,12 @@ class ConnectBatch(_Batch):
             None if plies is None else ctypes.c_void_p(plies.data_ptr()), None, 1))
         return codes, plies
 
+    def solve_moves(self, *args, **kwargs):
+        """Not available for Connect: solve_moves is the Bounce horizon search; Connect has `solve_actions`."""
+        raise ValueError("solve_moves: Bounce batches only (Connect boards: solve_actions)")
+
+    solve_moves_tensor = solve_moves
+
     @property
     def legal(self) -> np.ndarray:
         out = np.empty((self.n, self.width), dtype=np.uint8)
@@ -959,6 +968,42 @@ class BounceBatch(_Batch):
         _abi.check(_abi.lib().bgs_bounce_evaluate_moves(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
                                                         ctypes.c_int32(max_plies), ctypes.c_void_p(out.data_ptr()), 1))
         return out
+
+    def solve_moves(self, depth: int = DEFAULT_BOUNCE_SOLVE_DEPTH, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
+        """Exact horizon search of every legal move of every board (bgs_bounce_solve_moves), one launch: (codes int8[n, W,
+        H * W], plies int16[n, W, H * W] or None); entry [i, x, c] is the move of the piece in column x of the active row
+        to cell c = ty * W + tx, seen from the player to move, over lines of at most `depth` plies from the board (the
+        move itself counted; 1 .. BOUNCE_SOLVE_MAX_DEPTH -- Bounce games can cycle, there is no full solve).  Codes:
+        SOLVE_WIN 1 / SOLVE_LOSS -1 (plies: to the end, the winner fastest, the loser slowest), SOLVE_DRAW 0 (the move
+        itself ends the game as a draw; plies 1), SOLVE_UNKNOWN 2 (neither side can force a win within the horizon),
+        SOLVE_BUDGET 3 (the search of that move visited more than `max_nodes` positions), SOLVE_NONE -2 (an illegal slot,
+        an ended board).  The boards and `steps` are not modified."""
+        shape = (self.n, self.width, self.height * self.width)
+        codes = np.empty(shape, dtype=np.int8)
+        plies = np.empty(shape, dtype=np.int16) if with_plies else None
+        _abi.check(_abi.lib().bgs_bounce_solve_moves(
+            self._handle, ctypes.c_int32(int(depth)), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.ctypes.data),
+            None if plies is None else ctypes.c_void_p(plies.ctypes.data), None, 0))
+        return codes, plies
+
+    def solve_moves_tensor(self, codes=None, plies=None, depth: int = DEFAULT_BOUNCE_SOLVE_DEPTH,
+                           max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
+        """`solve_moves` into device tensors int8[n, W, H * W] and int16[n, W, H * W] (allocated when None; plies only
+        `with_plies` or when given), enqueued on the batch's stream with no synchronisation: (codes, plies or None)."""
+        t = self._need_torch("solve_moves_tensor")
+        shape = (self.n, self.width, self.height * self.width)
+        if codes is None:
+            codes = t.empty(shape, dtype=t.int8, device=f"cuda:{self.device}")
+        if plies is None and with_plies:
+            plies = t.empty(shape, dtype=t.int16, device=f"cuda:{self.device}")
+        for name, x, dt in (("codes", codes, t.int8), ("plies", plies, t.int16)):
+            if x is not None and not (x.is_cuda and x.dtype == dt and tuple(x.shape) == shape and x.is_contiguous()
+                                      and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned {dt} device tensor of shape {shape}")
+        _abi.check(_abi.lib().bgs_bounce_solve_moves(
+            self._handle, ctypes.c_int32(int(depth)), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.data_ptr()),
+            None if plies is None else ctypes.c_void_p(plies.data_ptr()), None, 1))
+        return codes, plies
 
     def step_actions(self, moves, want_status: bool = True):
         """moves int32[n, 4] = source x, y, target x, y; a negative first entry skips the board."""

@@ -81,6 +81,9 @@ SIGNATURES = {
     "bgs_bounce_evaluate_moves": (
         ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int]
     ),
+    "bgs_bounce_solve_moves": (
+        ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    ),
     "bgs_steps": (ctypes.c_int, [c_handle, _u64p]),
     "bgs_reset_steps": (ctypes.c_int, [c_handle]),
     "bgs_read_grid": (ctypes.c_int, [c_handle, _i8p]),

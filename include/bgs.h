@@ -226,6 +226,37 @@ BGS_API int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playo
 #define BGS_SOLVE_BUDGET 3
 BGS_API int bgs_connect_solve_actions(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies,
                                       uint64_t* nodes, int on_device);
+/* Exact horizon search of every legal move of every board (Bounce, bit-packed boards only: at most 64 cells, piece
+ * values <= 15): a depth-first alpha-beta search a legal (board, move), no RNG.  Bounce games can cycle and have no
+ * bound on their length, so there is no full solve: for board i (running, player P to move) and the move m of the piece
+ * in column x of the active row to cell c = ty * width + tx (the slots of bgs_bounce_evaluate_moves), the lines searched
+ * are at most `depth` plies long, counted from board i (m itself is ply 1), and a game ends exactly as the rules say: a
+ * landing in the mover's goal row wins; a move after which the opponent has no legal move wins for the mover if the
+ * mover itself could still move, and is a draw if neither can.
+ *   codes int8[n][width][height * width]
+ *       BGS_SOLVE_WIN      after m, P can force the game to end with P as winner at most `depth` plies from board i;
+ *       BGS_SOLVE_LOSS     after m, the opponent can force its own win within the same horizon;
+ *       BGS_SOLVE_DRAW     m itself ends the game as a draw (ply 1).  Deeper draws are not reported: a drawn end inside a
+ *                          line scores like a cut line (neither side has won), so it can only turn a would-be WIN / LOSS
+ *                          into UNKNOWN, never the reverse;
+ *       BGS_SOLVE_UNKNOWN  none of the above: within the horizon neither side can force a win;
+ *       BGS_SOLVE_BUDGET   the search of this (board, move) visited more than max_nodes positions;
+ *       BGS_SOLVE_NONE     an illegal slot, an ended board, a board without a legal move.
+ *   plies int16[n][width][height * width]  (may be NULL) WIN / LOSS: plies from board i to the end when the winner wins
+ *       as fast as it can and the loser loses as slowly as it can (1 = m wins at once); DRAW: 1; otherwise 0.
+ *   nodes  (may be NULL) positions the search visited in all; its value is implementation-defined.
+ * Only BUDGET depends on max_nodes or on the order in which moves are searched; everything else is a function of (grid,
+ * player, depth) -- the board's ply counter beyond its parity (the player) plays no part, nor do first_game, the way a
+ * batch is split or the launch geometry.  A deeper horizon never changes a WIN or LOSS or its plies.  The boards,
+ * bgs_steps and the RNG are not touched.
+ * on_device: as bgs_connect_solve_actions (codes and plies 16-byte aligned, nodes 8-byte aligned device pointers,
+ * enqueued on the batch's stream, no synchronisation, no allocation: scratch comes out of the batch's staging region;
+ * otherwise host buffers, filled when the call returns).  Refused (BGS_ERR_ARG): Connect and generic batches, depth < 1,
+ * depth > BGS_BOUNCE_SOLVE_MAX_DEPTH (what the search stack is sized for; never clamped: a deeper Bounce horizon is a
+ * different question), max_nodes < 1, NULL codes, a misaligned device pointer. */
+#define BGS_BOUNCE_SOLVE_MAX_DEPTH 16
+BGS_API int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies,
+                                   uint64_t* nodes, int on_device);
 /* env-steps (transitions applied to running boards) since the last bgs_reset / bgs_reset_steps */
 BGS_API int bgs_steps(bgs_batch* b, uint64_t* steps);
 BGS_API int bgs_reset_steps(bgs_batch* b);
