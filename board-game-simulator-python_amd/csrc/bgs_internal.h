@@ -31,9 +31,7 @@ struct bgs_batch {
     int rollout_wps;         // waves per SIMD the fused rollout is sized for
     int bounce_group;        // lanes per board of a single-launch Bounce rollout: 8 (small batches) or 1 (experiment bounce_group)
     int bounce_group_auto;   // 1: not set from the environment (bounce_rollout may still choose by the launches in flight)
-    int bounce_flat;         // 1: one-lane-per-board Bounce rollouts use the flattened search (experiment bounce_flat=0: nested loops)
     int bounce_pieces;       // 1: from-initial flat rollouts run on the piece list (K3p; experiment bounce_pieces=0: K3f)
-    int bounce_block;        // K3p: threads per workgroup, 256 / 512 / 1024 (experiment bounce_block): the waves of a workgroup share their drain
     int bounce_flat_wps;     // waves per SIMD of a flat Bounce rollout launch (experiment bounce_flat_wps)
     int bounce_eval_wps;     // waves per SIMD of bgs_bounce_evaluate_moves (0: the evaluate unit's default; experiment bounce_eval_wps)
     int bounce_flat_waves;   // > 0: that many waves per launch instead (experiment bounce_flat_waves)
@@ -52,15 +50,6 @@ struct bgs_batch {
     int bounce_wave_grid;    // > 0: one-wave workgroups of a K3w launch (experiment bounce_wave_grid; 0: 8192)
     int transition_wave;     // 1: the object API's one-board transition runs on one wave, a piece per lane (experiment transition_wave=0: thread per board)
     int bounce_static_geom;  // 1: the default board is played by the kernels instantiated on its compile-time geometry (experiment bounce_static_geom=0: the run-time record)
-    int bounce_tail;         // 1: the games beyond K3p's ply cap are finished by a tail kernel that runs BESIDE it (experiment bounce_tail=0: a pass behind it); -1: by the launch shape
-    int bounce_tail_handoff; // >= 0: a workgroup's last wave hands its boards to the tail queue at this many or fewer (experiment; -1: bounce_shape())
-    int bounce_tail_prio;    // s_setprio of the tail kernel's waves (experiment bounce_tail_prio, 0..3)
-    int bounce_tail_limit;   // > 0: tail waves that may wait for entries at a time (experiment; 0: bounce_shape())
-    enum { kTailStages = 4 };
-    mutable hipStream_t tail_stream[kTailStages];   // the streams of the staged tail launches beside the bulk kernel (created at the first such rollout)
-    mutable hipEvent_t tail_fork, tail_bulk_done, tail_join[kTailStages];
-    mutable uint32_t tail_serial;     // the "entry complete" word of the last fused launch (the region of d_worklist holds such words)
-    mutable int tail_flags_dirty;     // 1: d_worklist holds something else (game indices of a compaction pass, nothing yet)
     int rollout_generic;     // 1: never take the block-aligned from-initial kernel (A/B timing, experiment rollout_generic)
     int rollout_chunk;       // games per wave of the fused rollout, 0 = derived from rollout_wps (experiment rollout_chunk)
     int rollout_opening;     // opening blocks of the from-initial one-word rollout: 0 = K2a, 1..4, default 3 (experiment rollout_opening)

@@ -172,29 +172,7 @@ k_bounce_play(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __restrict__
 // ------------------------------------------------------------------------------------------------
 constexpr int kMaxTrackedColumns = 8;
 
-struct Moves {
-    uint64_t t[kMaxTrackedColumns];  // legal landing cells of the piece in column x of the active row (0 if none)
-    uint32_t row_base;               // cell index of column 0 of the active row
-    uint32_t n;                      // number of actions
-};
-
-__device__ __forceinline__ void enumerate(const BounceGeom& g, const Board& b, uint64_t occ, uint32_t player, Moves& m) {
-    const uint64_t src = movable(g, occ, player);
-    const int first = src ? __ffsll((unsigned long long)src) - 1 : 0;
-    const int row = (int)(((uint32_t)first * g.inv_w) >> 16);
-    m.row_base = (uint32_t)(row * g.w);
-    m.n = 0;
-#pragma unroll
-    for (int x = 0; x < kMaxTrackedColumns; ++x) {
-        const int c = (int)m.row_base + x;
-        uint64_t t = 0;
-        if (x < g.w && ((src >> (c & 63)) & 1ull)) t = reach(g, b, occ, player, c);
-        m.t[x] = t;
-        m.n += (uint32_t)__popcll(t);
-    }
-}
-
-// The same list computed by the 8 lanes that share one board (lane-group mode): lane `sub` of the group searches the
+// The action list as the 8 lanes that share one board compute it: lane `sub` of the group searches the
 // piece in column `sub` of the active row and KEEPS its mask; the group only exchanges counts (an 8-lane prefix sum)
 // and, when a move is picked, the one (source, target) pair.  The move search of a board is a handful of independent
 // walks; one lane runs them one after the other, eight lanes run them side by side -- a ply then costs one walk, which
@@ -239,30 +217,13 @@ __device__ __forceinline__ void pick_group(const GroupMoves& m, uint32_t idx, in
     dst_cell = (int)(pair >> 8);
 }
 
-// the idx-th action of the canonical list (sources by ascending x, targets by ascending cell index)
-__device__ __forceinline__ void pick_from(const Moves& m, uint32_t idx, int& src_cell, int& dst_cell) {
-    uint64_t chosen = 0;
-    uint32_t column = 0;
-    bool found = false;
-#pragma unroll
-    for (int x = 0; x < kMaxTrackedColumns; ++x) {
-        const uint32_t cnt = (uint32_t)__popcll(m.t[x]);
-        const bool here = !found && idx < cnt;
-        chosen = here ? m.t[x] : chosen;
-        column = here ? (uint32_t)x : column;
-        idx = (found || here) ? idx : idx - cnt;
-        found = found || here;
-    }
-    src_cell = (int)(m.row_base + column);
-    dst_cell = (int)select_bit64(chosen, idx);
-}
-
-// GL = lanes per board: 1 (a lane owns a board) or 8 (a lane group shares a board; all eight lanes hold the same
-// state and take the same decisions, lane 0 of the group stores)
+// 8 lanes per board: a lane group shares a board; all eight lanes hold the same state and take the same decisions,
+// lane 0 of the group stores.
 // worklist != nullptr: the launch plays the boards worklist[0 .. *work_count) (indices into the batch, any order)
 // instead of boards 0 .. n-1 -- the later passes of the multi-pass rollout, see bounce_rollout().  Results do not
 // depend on which wave or lane plays a board: RNG streams are keyed by the board's global game id.
-template <bool FROM_INITIAL, int GL>
+constexpr uint32_t kGroupLanes = 8;
+template <bool FROM_INITIAL>
 __global__ void __launch_bounds__(BGS_BLOCK)
 k_bounce_rollout(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __restrict__ status, uint16_t* __restrict__ plies_buf,
                  uint16_t* __restrict__ reward, int64_t n, uint64_t seed, uint64_t first_game, uint32_t max_plies,
@@ -288,12 +249,12 @@ k_bounce_rollout(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __restric
     }
     uint32_t taken = 0;
     const uint32_t lane = threadIdx.x & 63u;
-    const bool stores = GL == 1 || (lane & (GL - 1)) == 0;           // the lane that owns the board in memory
-    const uint64_t below_group = (1ull << (lane & ~(uint32_t)(GL - 1))) - 1ull;  // lanes below this lane's group
+    const bool stores = (lane & (kGroupLanes - 1u)) == 0u;                       // the lane that owns the board in memory
+    const uint64_t below_group = (1ull << (lane & ~(kGroupLanes - 1u))) - 1ull;  // lanes below this lane's group
 
     Board b;
     b.v[0] = b.v[1] = b.v[2] = b.v[3] = 0;
-    typename std::conditional<GL == 1, Moves, GroupMoves>::type mv;
+    GroupMoves mv;
     uint32_t st = 0, plies = 0, first_ply = 0, game = 0, stepped = 0;
     bool live = false, dirty = false;
     Philox4 blk;
@@ -330,8 +291,7 @@ k_bounce_rollout(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __restric
                 dirty = FROM_INITIAL;
                 have_block = false;
                 if (st == BGS_ST_RUNNING) {
-                    if constexpr (GL == 1) enumerate(g, b, occupancy(b), plies & 1u, mv);
-                    else enumerate_group(g, b, occupancy(b), plies & 1u, mv);
+                    enumerate_group(g, b, occupancy(b), plies & 1u, mv);
                     if (mv.n == 0) {  // a running board whose side to move is blocked: settle it now
                         st = settle_blocked(g, b, plies & 1u);
                         dirty = true;
@@ -351,8 +311,7 @@ k_bounce_rollout(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __restric
             }
             const uint32_t mover = plies & 1u;
             int s, t;
-            if constexpr (GL == 1) pick_from(mv, sample_index(philox_word(blk, plies), mv.n), s, t);
-            else pick_group(mv, sample_index(philox_word(blk, plies), mv.n), s, t);
+            pick_group(mv, sample_index(philox_word(blk, plies), mv.n), s, t);
             move_piece(b, s, t);
             ++plies;
             dirty = true;
@@ -360,8 +319,7 @@ k_bounce_rollout(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __restric
                 st = mover + 1u;
             } else {
                 const uint64_t occ = occupancy(b);
-                if constexpr (GL == 1) enumerate(g, b, occ, 1u - mover, mv);
-                else enumerate_group(g, b, occ, 1u - mover, mv);
+                enumerate_group(g, b, occ, 1u - mover, mv);
                 if (mv.n == 0) st = count_actions(g, b, occ, mover) ? mover + 1u : BGS_ST_DRAW;
             }
             live = st == BGS_ST_RUNNING && plies < max_plies;
@@ -385,7 +343,7 @@ k_bounce_rollout(BounceGeom g, uint64_t* __restrict__ planes, uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
-// K3f: the fused rollout, flattened.  One lane per board as in GL = 1, the move search of a ply the flat move list of
+// K3f: the fused rollout, flattened.  One lane per board, the move search of a ply the flat move list of
 // bounce_board.h (enumerate_flat / pick_flat: one loop a wave, every lane expanding one cell of its own queue per
 // iteration; measured before: 12.7 of 64 lanes active per VALU instruction in lane-group mode, 8.4 with one lane per
 // board).
@@ -1182,9 +1140,7 @@ struct WaveMemo {
     uint32_t link[kWaveMemoSlots][kWaveLinks + 1u];
 };
 
-// orders the LDS accesses of ONE wave's lanes (the memo is wave-private: no other wave ever touches it).  The stand-alone
-// K3w kernel has one-wave workgroups; the tail role of the bulk kernel (round 6) runs this code on waves of a four-wave
-// workgroup, where a workgroup barrier would wait for waves that are somewhere else entirely.
+// orders the LDS accesses of ONE wave's lanes (the memo is wave-private: no other wave ever touches it)
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup", "local");
     __builtin_amdgcn_wave_barrier();
@@ -1398,89 +1354,12 @@ __device__ __forceinline__ void wave_play_game(const GEO& g, WaveMemo<PMAX>& mem
     }
 }
 
-
-// ---- the TAIL QUEUE (round 6): the games that outlive the bulk pass, finished WHILE the bulk pass runs -- an experiment
-// (bounce_tail=1, test build), measured slower than the pass behind the bulk kernel in each of its three forms; no automatic
-// plan takes it.
-// Until round 5 a rollout was K3p to a ply cap -> positions to planes -> a compaction of the boards still running -> K3w,
-// one after the other on the batch's stream: a lone launch spends a third of its time in a nearly empty K3w, which can
-// only start when K3p's last wave has left -- although the games it waits for (the one that never ends: 4 000 plies along the
-// memo's links; the longest that wanders) mostly crossed the bulk cap in K3p's first third.  With the queue K3p hands a game
-// that reaches the bulk cap over at once (and, `handoff_at`, the last boards of a workgroup's last wave): an entry of
-// positions / game / plies, then its "complete" word (the launch's serial, release at agent scope).
-//   Form 1: K3p's own waves turn into K3w waves when they leave the bulk loop.  No wave leaves before the queue is dry, i.e.
-//     when the tail's games have long been waiting; the merged kernel needs 129 VGPRs and 50 KB LDS.  1.79-2.03 ms a lone
-//     launch against 1.61 (compile-time geometry, before the shape was retuned).  Removed.
-//   Form 2: a second kernel (K3w's code on 256-2048 one-wave workgroups) on a stream of the batch's own, its waves WAITING for
-//     tickets' entries while the bulk kernel runs.  1.72 ms at its best against 1.44: the waiting waves' polls (agent-scope
-//     loads, a million a millisecond) and their plies compete with the bulk waves.  Removed.
-//   Form 3 (what is here): STAGED launches of that kernel, nobody waits on the device: stage k owns the entries [lo, hi) and
-//     sits on a stream of its own behind a hipStreamWaitValue32 on the queue's progress word -- the command processor holds
-//     the launch back until K3p has allocated `hi` entries (or has finished: its last wave stores the largest value) -- and the
-//     last stage, behind K3p itself, owns the rest.  1.51-1.56 ms against 1.44 (256-2048 waves a stage, hand-over at 0 / 16 / 32,
-//     wave priority 0 / 1 / 3 all within 5 %).  What the overlap saves -- the long games start at 0.35 ms instead of 0.9 -- the
-//     four cross-stream joins, the bulk waves' lost issue slots and the last stage (a long game that crossed the cap late is
-//     still the launch's end) take back.
-//   counters  tq[0] entries allocated   tq[2] bulk waves that have left   tq[3] the progress word the streams wait on
-//   ready[e]  = the launch's serial once entry e is complete
-//   entry e   = 8 dwords: positions (4), game, plies, -, -
-constexpr uint32_t kTailEntryWords = 8;
-
-// value planes (wave-uniform, scalar registers) from the piece list of a queue entry
-template <int PMAX, class GEO>
-__device__ __forceinline__ Board planes_from_positions(const GEO& g, const uint32_t (&pos)[4]) {
-    Board out;
-    out.v[0] = out.v[1] = out.v[2] = out.v[3] = 0;
-#pragma unroll
-    for (int k = 0; k < PMAX; ++k)
-        if (k < (int)g.piece_count) {
-            const uint64_t bit = 1ull << ((pos[k >> 2] >> (8 * (k & 3))) & 63u);
-            const uint32_t v = g.piece_value[k];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if ((v >> q) & 1u) out.v[q] |= bit;
-        }
-    return out;
-}
-
-// ... and back, where a tail wave's game has ended: the board goes to memory in K3p's format (k_bounce_positions_to_planes
-// runs behind the kernel for every board).  Pieces are numbered by ascending (value, cell) at the start and keep their
-// values, so ANY numbering that is ascending in the value reproduces the planes: rank = pieces of smaller value + pieces of
-// the same value on lower cells.  Lane k holds the k-th occupied cell (as in enumerate_wave).
-template <int PMAX>
-__device__ __forceinline__ void wave_store_positions(const Board& b, uint64_t* __restrict__ planes, int64_t n, int64_t i) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t occ = occupancy(b);
-    const uint32_t pieces = (uint32_t)__popcll(occ);
-    const bool alive = lane < pieces;
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(occ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)occ, 0u));
-    const bool occupied = ((occ >> lane) & 1ull) != 0ull;
-    const uint32_t told = (uint32_t)__builtin_amdgcn_ds_permute((int)((occupied ? below : 63u) << 2), (int)lane);
-    const uint32_t cell = alive ? told : 0u;
-    const uint32_t value = alive ? value_at(b, (int)cell) : 0xFFu;
-    uint32_t rank = 0;
-#pragma unroll
-    for (int j = 0; j < PMAX; ++j) {
-        const uint32_t vj = (uint32_t)__builtin_amdgcn_readlane((int)value, j);
-        rank += (vj < value || (vj == value && (uint32_t)j < lane)) ? 1u : 0u;
-    }
-    const uint32_t got = (uint32_t)__builtin_amdgcn_ds_permute((int)((alive ? rank : 63u) << 2), (int)cell);
-    const uint32_t part = alive ? (got & 63u) << (8u * (lane & 3u)) : 0u;
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < PMAX; ++k) w[k >> 2] |= (uint32_t)__builtin_amdgcn_readlane((int)part, k);
-    if (lane == 0u) {
-        planes[i] = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-        if (PMAX > 8) planes[n + i] = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
-    }
-}
-
 // the device-wide pool of parked boards (see the kernel): boards a workgroup parks, dwords per entry (positions, game, plies)
 constexpr uint32_t kPoolCap = 64, kPoolWords = 6;
 
-template <int PMAX, int BLOCK>
+template <int PMAX>
 struct ParkedPieces {
-    static constexpr uint32_t WAVES = BLOCK / BGS_WAVE, CAP = 64;   // (a wave parks at most 63 boards: park_at <= 63)
+    static constexpr uint32_t WAVES = kBounceBlock / BGS_WAVE, CAP = 64;   // (a wave parks at most 63 boards: park_at <= 63)
     uint32_t pos[PMAX / 4][WAVES][CAP];
     uint32_t game[WAVES][CAP];
     uint32_t plies[WAVES][CAP];
@@ -1489,8 +1368,6 @@ struct ParkedPieces {
     uint32_t active;             // waves still in their loop
 };
 
-// BLOCK threads per workgroup (256, 512 or 1024): the waves of a workgroup share their drain through LDS, so a larger
-// workgroup ends with fewer half-empty waves (one per workgroup carries the workgroup's longest games to their end)
 // Waves per SIMD: with the opening book's loads the kernel needs 98 VGPRs -- two more than five waves a SIMD allow.  Held to
 // 96 (amdgpu_waves_per_eu) the 8- and 12-piece instantiations fit without a spill (the 16-piece one spills 44 bytes), and a
 // fifth wave a SIMD hides more of a ply's 17 us of dependent instructions: tools/k3p_waves_ab.sh has the A/B.
@@ -1502,39 +1379,35 @@ struct ParkedPieces {
 #else
 #define BGS_K3P_OCCUPANCY
 #endif
-// what the tail role of a launch needs (TAIL; see "the TAIL QUEUE" above)
-struct TailArgs {
-    uint32_t* counters;       // tq[0..3]
-    uint32_t* ready;          // [capacity]
-    uint32_t* entries;        // [capacity][kTailEntryWords]
-    uint32_t capacity;
-    uint32_t serial;          // this launch's "entry complete" word
-    uint32_t final_cap;       // the rollout's ply cap (the bulk loop stops at max_plies)
-    uint32_t handoff_at;      // a workgroup's last wave hands its boards over at this many or fewer (0: plays them to the bulk cap)
-    uint32_t limit;           // tail waves that may wait for entries at a time (the last bulk wave always stays)
-    uint32_t epoch_limit, cold_limit, bypass_plies;   // K3w's memo policy
-    uint32_t prio;            // s_setprio of the tail kernel's waves
+// where a bulk pass leaves the work list of the pass behind it: the games still running at its own cap (max_plies), below the
+// rollout's.  list == nullptr: there is no pass behind it.
+// (The two pointers are kept apart on purpose: side by side the compiler fetches them with one four-dword scalar load, and
+// K3p, which has no scalar register to spare, comes out with a different register allocation and block layout throughout.)
+struct NextPass {
+    uint32_t* count;          // entries written so far (zeroed before the launch)
+    uint32_t final_cap;       // the rollout's ply cap
+    uint32_t* list;           // board indices, any order
 };
 
-template <int PMAX, int BLOCK, bool TAIL, class GEO>
-__global__ void __launch_bounds__(BLOCK) BGS_K3P_OCCUPANCY
+template <int PMAX, class GEO>
+__global__ void __launch_bounds__(kBounceBlock) BGS_K3P_OCCUPANCY
 k_bounce_rollout_pieces(GEO g, uint64_t* __restrict__ planes, uint8_t* __restrict__ status, uint16_t* __restrict__ plies_buf,
                         uint16_t* __restrict__ reward, int64_t n, uint64_t seed, uint64_t first_game, uint32_t max_plies,
                         unsigned long long* __restrict__ steps, uint32_t chunk, uint32_t* __restrict__ queue, uint32_t park_at,
                         uint32_t* gpool, const uint32_t* __restrict__ book_links, const BookEntry* __restrict__ book_table,
-                        uint32_t book_depth, uint32_t book_n0, TailArgs tail) {
-    __shared__ ParkedPieces<PMAX, BLOCK> parked;
+                        uint32_t book_depth, uint32_t book_n0, NextPass next) {
+    __shared__ ParkedPieces<PMAX> parked;
     __shared__ uint32_t book_lds[kBookLdsLinks];   // the opening book's links of levels 1 and 2 (4.25 KB)
     // ... and the boards of the wave's current chunk as the book hands them out: a chunk (at most 64 games) is walked through
     // the book by ALL lanes at once when it is drawn from the queue -- one philox call and one walk per lane, every lane busy
     // -- and parked here, a 64-byte line a game; a lane that takes a game reads its line.  (Walked where the lane takes the
     // game, the walk ran in almost every iteration -- some lane of 64 always finishes -- for two or three lanes: ~100 VALU
     // an iteration, 4 % of a ply.)
-    __shared__ uint4 opened_lds[BLOCK / BGS_WAVE][4][BGS_WAVE];
+    __shared__ uint4 opened_lds[kBounceBlock / BGS_WAVE][4][BGS_WAVE];
     if (book_depth >= 2u)
-        for (uint32_t i = threadIdx.x; i < kBookLdsLinks; i += BLOCK) book_lds[i] = book_links[i];
+        for (uint32_t i = threadIdx.x; i < kBookLdsLinks; i += kBounceBlock) book_lds[i] = book_links[i];
     Lands<PMAX> lands;   // (registers; valid from a ply's search to its move)
-    constexpr uint32_t WAVES = ParkedPieces<PMAX, BLOCK>::WAVES;
+    constexpr uint32_t WAVES = ParkedPieces<PMAX>::WAVES;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63u;
     if (threadIdx.x < WAVES) {
@@ -1580,25 +1453,6 @@ k_bounce_rollout_pieces(GEO g, uint64_t* __restrict__ planes, uint8_t* __restric
             old = acq_rel ? __hip_atomic_fetch_add(word, by, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT)
                           : __hip_atomic_fetch_add(word, by, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return (uint32_t)__builtin_amdgcn_readfirstlane(old);
-    };
-
-    // the lanes with `mine` set hand their boards (positions, game, plies) to the tail queue: one allocation a wave
-    auto push_tail = [&](bool mine, const PieceBoard<PMAX>& board, uint32_t the_game, uint32_t the_plies) {
-        const uint64_t who = __builtin_amdgcn_ballot_w64(mine);
-        if (!who) return;
-        const uint32_t base = gbump(tail.counters, (uint32_t)__popcll(who), false);
-        if (mine) {
-            const uint32_t e = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(who >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)who, 0u));
-            uint32_t* slot = tail.entries + (size_t)e * kTailEntryWords;   // (e < capacity: a game is handed over at most once)
-            *reinterpret_cast<uint4*>(slot) = make_uint4(board.pos[0], PMAX > 4 ? board.pos[PMAX > 4 ? 1 : 0] : 0u,
-                                                         PMAX > 8 ? board.pos[PMAX > 8 ? 2 : 0] : 0u, PMAX > 12 ? board.pos[PMAX > 12 ? 3 : 0] : 0u);
-            *reinterpret_cast<uint2*>(slot + 4) = make_uint2(the_game, the_plies);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            __hip_atomic_store(tail.ready + e, tail.serial, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        // the word the STREAMS of the staged tail launches wait on (hipStreamWaitValue32: the command processor watches it, no
-        // wave does): entries allocated so far
-        if (lane == 0u) (void)__hip_atomic_fetch_max(tail.counters + 3, base + (uint32_t)__popcll(who), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     };
 
     PieceBoard<PMAX> b;
@@ -1820,24 +1674,14 @@ k_bounce_rollout_pieces(GEO g, uint64_t* __restrict__ planes, uint8_t* __restric
         const bool run = has && !pending && st == BGS_ST_RUNNING && plies < max_plies;
 
         // ---- boards that stopped go to memory and free their lane (from the start position: every board is written)
-        if (TAIL) {
-            // a game that goes on beyond the bulk cap: to the tail queue (its action list, if one was just counted, is left behind)
-            const bool over = has && !run && !pending && st == BGS_ST_RUNNING && plies < tail.final_cap;
-            push_tail(over, b, game, plies);
-            if (over) {
-                stepped += plies - first_ply;
-                has = false;
-                search = false;
-            }
-        }
-        if (!TAIL && tail.entries) {
+        if (next.list) {
             // the games the NEXT pass has to finish -- still running at this pass's cap, below the rollout's -- go on its work
             // list here (round 6; until then a compaction kernel read every board's status behind this one: 44 us for a lone launch)
-            const bool more = has && !run && !pending && st == BGS_ST_RUNNING && plies < tail.final_cap;
+            const bool more = has && !run && !pending && st == BGS_ST_RUNNING && plies < next.final_cap;
             const uint64_t who = __builtin_amdgcn_ballot_w64(more);
             if (who) {
-                const uint32_t base = gbump(tail.counters, (uint32_t)__popcll(who), false);
-                if (more) tail.entries[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(who >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)who, 0u))] = game;
+                const uint32_t base = gbump(next.count, (uint32_t)__popcll(who), false);
+                if (more) next.list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(who >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)who, 0u))] = game;
             }
         }
         if (has && !run && !pending) {
@@ -1866,17 +1710,6 @@ k_bounce_rollout_pieces(GEO g, uint64_t* __restrict__ planes, uint8_t* __restric
             if (leave() > 1u) break;    // others are still running: whatever gets parked later is theirs
             last = true;                // everybody else has left: sweep up what they parked
             continue;
-        }
-        if (TAIL && draining && last && tail.handoff_at && lds_exhausted) {
-            // ---- the workgroup's last wave hands its last boards to the tail queue and follows them (same condition as the
-            // device-wide pool's below: only in an iteration whose adoption attempt has emptied the workgroup's LDS pool)
-            const uint32_t left = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(has));
-            if (left <= tail.handoff_at) {
-                push_tail(has, b, game, plies);
-                if (has) stepped += plies - first_ply;
-                has = false;
-                break;
-            }
         }
         if (draining && last && !glast && gpool && park_at && lds_exhausted) {
             // ---- the workgroup's last wave parks its last boards for the other workgroups' last waves -- but only in an
@@ -1969,14 +1802,6 @@ k_bounce_rollout_pieces(GEO g, uint64_t* __restrict__ planes, uint8_t* __restric
             }
         }
     }
-    if (TAIL) {
-        // this wave's part is over: its entries, then its departure (the tail kernel's end signal is the last one's)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        const uint32_t gone = gbump(tail.counters + 2, 1u, true) + 1u;
-        // the launch's last bulk wave releases every staged tail launch that is still waiting for its threshold
-        if (gone == gridDim.x * (BLOCK / BGS_WAVE) && lane == 0u)
-            __hip_atomic_store(tail.counters + 3, 0x7FFFFFFFu, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
 #ifdef BGS_BOUNCE_STATS
     if (lane == 0) {  // words 1..4 of shard 0's cache line are free
         atomicAdd(steps + 1, (unsigned long long)stat_iters);
@@ -1984,71 +1809,6 @@ k_bounce_rollout_pieces(GEO g, uint64_t* __restrict__ planes, uint8_t* __restric
         atomicAdd(steps + 3, (unsigned long long)stat_drain_iters);
     }
 #endif
-    add_steps(steps, stepped);
-}
-
-// the tail kernel (see "the TAIL QUEUE"): K3w's code on one-wave workgroups.  Nobody waits for K3p: the launches of this
-// kernel are STAGED -- stage k owns the queue's entries [lo, hi) and sits on a stream of its own behind a
-// hipStreamWaitValue32 on the queue's progress word, i.e. the command processor holds the launch back until K3p has allocated
-// `hi` entries (or has finished: its last wave stores the largest value); the last stage, behind K3p itself, owns everything
-// from its `lo` on.  So when a stage runs, every entry of its range exists (or never will): its waves draw tickets from the
-// stage's own counter and leave when the range is used up -- no wave ever holds a ticket for an entry that is still to come,
-// and no two waves meet on a compare-and-swap (a first version claimed the queue's head that way: 2048 waves, 5000 entries,
-// 200 ms a launch).
-template <int PMAX, class GEO>
-__global__ void __launch_bounds__(BGS_WAVE)
-k_bounce_tail(GEO g, uint64_t* __restrict__ planes, uint8_t* __restrict__ status, uint16_t* __restrict__ plies_buf,
-              uint16_t* __restrict__ reward, int64_t n, uint64_t seed, uint64_t first_game, unsigned long long* __restrict__ steps,
-              TailArgs tail, uint32_t lo, uint32_t hi, uint32_t* __restrict__ stage_counter) {
-    // (K3w raises its waves' priority: they are its launch's critical path.  Beside the bulk kernel that is a choice: tail.prio)
-    if (tail.prio == 3u) __builtin_amdgcn_s_setprio(3);
-    else if (tail.prio == 2u) __builtin_amdgcn_s_setprio(2);
-    else if (tail.prio == 1u) __builtin_amdgcn_s_setprio(1);
-    const uint32_t lane = threadIdx.x & 63u;
-    __shared__ WaveMemo<PMAX> memo;
-    uint32_t epoch = 1, stepped = 0;
-    bool memo_ready = false;
-    // (the stage was released because `hi` entries exist, or because the bulk kernel is over: either way what is allocated now
-    // is all this stage will ever own)
-    uint32_t allocated = 0;
-    if (lane == 0u) allocated = __hip_atomic_load(tail.counters, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-    allocated = (uint32_t)__builtin_amdgcn_readfirstlane((int)allocated);
-    const uint32_t end = hi < allocated ? hi : allocated;
-    for (;;) {
-        uint32_t t = 0;
-        if (lane == 0u) t = __hip_atomic_fetch_add(stage_counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = lo + (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-        if (t >= end) break;
-        if (!memo_ready) {
-            wave_memo_reset(memo, lane);
-            memo_ready = true;
-        }
-        for (;;) {   // (the entry's last word is written a few instructions after its allocation)
-            uint32_t flag = 0;
-            if (lane == 0u) flag = __hip_atomic_load(tail.ready + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((uint32_t)__builtin_amdgcn_readfirstlane((int)flag) == tail.serial) break;
-            __builtin_amdgcn_s_sleep(2);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        const uint32_t* e = tail.entries + (size_t)t * kTailEntryWords;
-        uint32_t where[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) where[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[j]);
-        const uint32_t game = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[4]);
-        uint32_t plies = (uint32_t)__builtin_amdgcn_readfirstlane((int)e[5]);
-        const uint32_t came_with = plies;
-        Board b = planes_from_positions<PMAX>(g, where);
-        uint32_t st = BGS_ST_RUNNING;
-        wave_play_game<PMAX>(g, memo, epoch, b, st, plies, seed, first_game + (uint64_t)game, tail.final_cap, tail.epoch_limit,
-                             tail.cold_limit, tail.bypass_plies);
-        wave_store_positions<PMAX>(b, planes, n, (int64_t)game);
-        if (lane == 0u) {
-            status[game] = (uint8_t)st;
-            plies_buf[game] = (uint16_t)plies;
-            reward[game] = reward_pair(st);
-            stepped += plies - came_with;
-        }
-    }
     add_steps(steps, stepped);
 }
 
@@ -2280,8 +2040,7 @@ k_bounce_compact(const uint8_t* __restrict__ status, const uint16_t* __restrict_
         worklist[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u))] = (uint32_t)i;
 }
 
-// (K3w's enumeration, memo and ply loop -- enumerate_wave, WaveMemo, wave_play_game -- are defined in front of K3p, whose waves
-// run them too when they have left the bulk loop: see there)
+// (K3w's enumeration, memo and ply loop -- enumerate_wave, WaveMemo, wave_play_game -- are defined in front of K3p)
 template <int PMAX, class GEO>
 __global__ void __launch_bounds__(BGS_WAVE)
 k_bounce_rollout_wave(GEO g, uint64_t* __restrict__ planes, uint8_t* __restrict__ status, uint16_t* __restrict__ plies_buf,
@@ -2468,12 +2227,10 @@ void bounce_step_random(const bgs_batch* b, uint64_t seed, uint32_t count) {
 }
 
 // One launch of the fused rollout: over the whole batch (worklist == nullptr) or over a work list.
-// group = lanes per board (1 or 8), wps = waves per SIMD the grid is sized for.
-// final_cap > cap: the bulk pass of a plan whose tail is K3w's code INSIDE the same launch (K3p only; see "the TAIL QUEUE")
-// next_list / next_count (K3p without the tail inside): where the bulk pass leaves the work list of the pass behind it
+// group = lanes per board (1, 8 or 64: K3w), wps = waves per SIMD the grid is sized for.
+// next (K3p only): where the bulk pass leaves the work list of the pass behind it
 static void launch_rollout(const bgs_batch* b, uint64_t seed, uint32_t cap, bool from_initial, int group, int wps,
-                           const uint32_t* worklist, const uint32_t* work_count, uint32_t* queue, uint32_t final_cap = 0,
-                           uint32_t* next_list = nullptr, uint32_t* next_count = nullptr) {
+                           const uint32_t* worklist, const uint32_t* work_count, uint32_t* queue, NextPass next = NextPass{}) {
     if (group == 64) {   // K3w: a work list of a few very long games, one wave each (a wave strides over the list)
         auto launch_wave = [&](auto pmax_tag) {
             constexpr int PMAX = decltype(pmax_tag)::value;
@@ -2514,10 +2271,9 @@ static void launch_rollout(const bgs_batch* b, uint64_t seed, uint32_t cap, bool
         waves = (b->n + per_wave - 1) / per_wave;
     }
     const unsigned blocks = (unsigned)((waves + 3) / 4);
-    auto launch = [&](auto initial_tag, auto group_tag) {
+    auto launch = [&](auto initial_tag) {
         constexpr bool INITIAL = decltype(initial_tag)::value;
-        constexpr int GL = decltype(group_tag)::value;
-        hipLaunchKernelGGL((k_bounce_rollout<INITIAL, GL>), dim3(blocks), dim3(BGS_BLOCK), 0, b->stream, b->bg, b->d_planes,
+        hipLaunchKernelGGL((k_bounce_rollout<INITIAL>), dim3(blocks), dim3(BGS_BLOCK), 0, b->stream, b->bg, b->d_planes,
                            b->d_status, b->d_plies, reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed, b->first_game, cap,
                            b->d_steps, (uint32_t)per_wave, worklist, work_count, queue);
     };
@@ -2534,10 +2290,8 @@ static void launch_rollout(const bgs_batch* b, uint64_t seed, uint32_t cap, bool
                            b->stream, b->bg, b->d_planes, b->d_status, b->d_plies, reinterpret_cast<uint16_t*>(b->d_reward), b->n,
                            seed, b->first_game, cap, b->d_steps, chunk, worklist, work_count, queue, (uint32_t)b->bounce_park);
     };
-    auto launch_pieces = [&](auto pmax_tag, auto block_tag, auto tail_tag) {
+    auto launch_pieces = [&](auto pmax_tag) {
         constexpr int PMAX = decltype(pmax_tag)::value;
-        constexpr int BLOCK = decltype(block_tag)::value;
-        constexpr bool TAIL = decltype(tail_tag)::value;
         const size_t tile = 0;  // (the landing masks live in registers; LDS only holds the parked boards)
         const uint32_t chunk0 = (uint32_t)b->bounce_flat_chunk;
         // Every ply costs a wave the same whatever the number of its lanes that still hold a game, so what counts is how
@@ -2550,15 +2304,7 @@ static void launch_rollout(const bgs_batch* b, uint64_t seed, uint32_t cap, bool
         else if (b->n / per_wave < flat_waves) flat_waves = b->n / per_wave > 256 ? b->n / per_wave : 256;
         const int64_t most = (b->n + 63) / 64;    // (never more waves than 64-board loads)
         if (flat_waves > most) flat_waves = most;
-        constexpr int per_block = BLOCK / BGS_WAVE;
-        if (tile > 48 * 1024) {  // beyond the default dynamic-LDS limit (gfx950 has 160 KB per CU)
-            static bool raised = false;  // (per instantiation; the attribute belongs to the function, not the launch)
-            if (!raised) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bounce_rollout_pieces<PMAX, BLOCK, TAIL, BounceGeom>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile);
-                raised = true;
-            }
-        }
+        constexpr int per_block = kBounceBlock / BGS_WAVE;
         const unsigned groups = (unsigned)((flat_waves + per_block - 1) / per_block);
         // the opening book of the start position (bounce_book_acquire): games start `depth` plies in -- unless the cap is shorter
         const uint32_t book_depth = b->book_table && b->book_depth > 0 && cap >= (uint32_t)b->book_depth ? (uint32_t)b->book_depth : 0u;
@@ -2568,100 +2314,18 @@ static void launch_rollout(const bgs_batch* b, uint64_t seed, uint32_t cap, bool
         const int park_at = b->bounce_pieces_park >= 0 ? b->bounce_pieces_park : bounce_shape(b->launches_in_flight).park;
         uint32_t* pool = b->bounce_pool && park_at > 0 && groups >= 2 && groups <= (unsigned)BGS_BOUNCE_POOL_GROUPS ? b->d_pool : nullptr;
         if (pool) (void)hipMemsetAsync(pool, 0, sizeof(uint32_t) * (4 + 2 * (size_t)groups), b->stream);
-        TailArgs tail{};
-        if (TAIL) {
-            // the tail queue: counters among the rollout's list counters (cleared at its start: words 4 .. 7, the lengths of passes
-            // no automatic plan has), "entry complete" words in the work list's region (one per game; they hold launch serials, so
-            // they are cleared only when something else has written there), the entries in the staging region (32 bytes a game;
-            // nothing else of this batch runs beside its rollout)
-            const BounceShape shape = bounce_shape(b->launches_in_flight);
-            if (b->tail_flags_dirty || b->tail_serial == 0xFFFFFFFFu) {
-                (void)hipMemsetAsync(b->d_worklist, 0, sizeof(uint32_t) * (size_t)b->n, b->stream);
-                b->tail_flags_dirty = 0;
-                b->tail_serial = 0;
-            }
-            tail.counters = b->d_work_count + 4;
-            tail.ready = b->d_worklist;
-            tail.entries = reinterpret_cast<uint32_t*>(b->d_staging);
-            tail.capacity = (uint32_t)b->n;
-            tail.serial = ++b->tail_serial;
-            tail.final_cap = final_cap;
-            tail.handoff_at = b->bounce_tail_handoff >= 0 ? (uint32_t)b->bounce_tail_handoff : (uint32_t)shape.handoff_at;
-            tail.limit = b->bounce_tail_limit > 0 ? (uint32_t)b->bounce_tail_limit : (uint32_t)shape.tail_waves;
-            tail.epoch_limit = b->bounce_epoch_limit >= 2 && b->bounce_epoch_limit < (int)kWaveEpochLimit ? (uint32_t)b->bounce_epoch_limit : kWaveEpochLimit;
-            tail.cold_limit = (uint32_t)b->bounce_memo_cold;
-            tail.bypass_plies = (uint32_t)b->bounce_memo_bypass;
-            tail.prio = (uint32_t)b->bounce_tail_prio;
-        } else if (next_list && next_count && final_cap > cap) {
-            tail.entries = next_list;
-            tail.counters = next_count;
-            tail.final_cap = final_cap;
-        }
         // (Tried, round 4: a kernel specialised on "exactly PMAX pieces" -- every "is there a piece k" test decided at compile
         // time.  18 % fewer static instructions, one basic block a phase, and 174 VGPRs; held to 128 it spills 43 and reads
         // 1.14 against 1.26 x 10^10 with 20 launches in flight.)
-        // TAIL: the staged launches of the tail kernel, each on a stream of the batch's own behind (1) everything the batch's
-        // stream holds so far (the fork event) and (2) a wait for the queue's progress word to reach the stage's threshold; the
-        // last one behind the bulk kernel itself.  The batch's stream goes on behind them all (the join events).  The bulk kernel
-        // is enqueued FIRST: on whatever hardware queue a stage's wait ends up, the kernel that satisfies it is ahead of it.
-        constexpr int kStages = bgs_batch::kTailStages;   // (the last stage is the one behind the bulk kernel)
-        bool forked = false;
-        if (TAIL) {
-            if (!b->tail_stream[0]) {
-                bool ok = true;
-                for (int k = 0; k < kStages && ok; ++k) {
-                    ok = hipStreamCreateWithFlags(&b->tail_stream[k], hipStreamNonBlocking) == hipSuccess &&
-                         hipEventCreateWithFlags(&b->tail_join[k], hipEventDisableTiming) == hipSuccess;
-                }
-                ok = ok && hipEventCreateWithFlags(&b->tail_fork, hipEventDisableTiming) == hipSuccess &&
-                     hipEventCreateWithFlags(&b->tail_bulk_done, hipEventDisableTiming) == hipSuccess;
-                if (!ok) b->tail_stream[0] = nullptr;   // (no staged launches: one tail launch behind the bulk kernel, on its stream)
-            }
-            forked = b->tail_stream[0] && hipEventRecord(b->tail_fork, b->stream) == hipSuccess;
-            for (int k = 0; k < kStages && forked; ++k) forked = hipStreamWaitEvent(b->tail_stream[k], b->tail_fork, 0) == hipSuccess;
-        }
         auto go = [&](auto geo) {
-            hipLaunchKernelGGL((k_bounce_rollout_pieces<PMAX, BLOCK, TAIL, decltype(geo)>), dim3(groups),
-                               dim3(BLOCK), tile, b->stream, geo, b->d_planes, b->d_status, b->d_plies,
+            hipLaunchKernelGGL((k_bounce_rollout_pieces<PMAX, decltype(geo)>), dim3(groups),
+                               dim3(kBounceBlock), tile, b->stream, geo, b->d_planes, b->d_status, b->d_plies,
                                reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed, b->first_game, cap, b->d_steps, chunk, queue,
                                (uint32_t)park_at, pool, b->book_links,
-                               reinterpret_cast<const BookEntry*>(b->book_table), book_depth, b->book_n0, tail);
-            if (TAIL) {
-                // (a stage's ticket counter: words 12 .. 15 of the rollout's counters, cleared with them; the sweep-up launch of a
-                // failed enqueue shares the last stage's)
-                auto tail_launch = [&](hipStream_t on, unsigned waves, uint32_t lo, uint32_t hi, int stage) {
-                    hipLaunchKernelGGL((k_bounce_tail<PMAX, decltype(geo)>), dim3(waves), dim3(BGS_WAVE), 0, on, geo, b->d_planes,
-                                       b->d_status, b->d_plies, reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed, b->first_game,
-                                       b->d_steps, tail, lo, hi, b->d_work_count + 12 + stage);
-                };
-                if (!forked) {
-                    tail_launch(b->stream, 8192u, 0u, 0xFFFFFFFFu, kStages - 1);
-                } else {
-                    // stage k is released when the bulk kernel has handed over threshold[k] games (2 % of a batch outlive an
-                    // 80-ply bulk pass: ~5 000 of 2^18)
-                    const uint32_t expected = (uint32_t)(b->n / 50) + 1u;
-                    bool ok = hipEventRecord(b->tail_bulk_done, b->stream) == hipSuccess;
-                    uint32_t lo = 0;
-                    int k = 0;
-                    for (; k < kStages && ok; ++k) {
-                        // stage k owns [lo, hi): released at `hi` entries; the last stage owns the rest and follows the bulk kernel
-                        const uint32_t hi = k + 1 < kStages ? (k == 0 ? 32u : expected * (uint32_t)k / (uint32_t)(kStages - 1)) : 0xFFFFFFFFu;
-                        if (k + 1 < kStages) ok = hipStreamWaitValue32(b->tail_stream[k], tail.counters + 3, hi, hipStreamWaitValueGte, 0xFFFFFFFFu) == hipSuccess;
-                        else ok = hipStreamWaitEvent(b->tail_stream[k], b->tail_bulk_done, 0) == hipSuccess;
-                        if (!ok) break;
-                        tail_launch(b->tail_stream[k], k + 1 < kStages ? tail.limit : 8192u, lo, hi, k);
-                        ok = hipEventRecord(b->tail_join[k], b->tail_stream[k]) == hipSuccess && hipStreamWaitEvent(b->stream, b->tail_join[k], 0) == hipSuccess;
-                        lo = hi;
-                    }
-                    if (!ok) {   // (something could not be enqueued: wait for what was, then the rest on the batch's stream)
-                        for (int j = 0; j < kStages; ++j) (void)hipStreamSynchronize(b->tail_stream[j]);
-                        tail_launch(b->stream, 8192u, lo, 0xFFFFFFFFu, kStages - 1);
-                    }
-                }
-            }
+                               reinterpret_cast<const BookEntry*>(b->book_table), book_depth, b->book_n0, next);
         };
-        // (the default board: the compile-time geometry, see bounce_unit.h -- 256-thread workgroups only, the shape every plan uses)
-        if constexpr (PMAX == 12 && BLOCK == 256) {
+        // (the default board: the compile-time geometry, see bounce_unit.h)
+        if constexpr (PMAX == 12) {
             if (b->bounce_static_geom && bounce_is_default(b->bg)) go(DefaultBounceGeom{});
             else go(b->bg);
         } else {
@@ -2670,24 +2334,17 @@ static void launch_rollout(const bgs_batch* b, uint64_t seed, uint32_t cap, bool
         // every board was written as the positions of its pieces: the value planes for all of them, at full lanes
         hipLaunchKernelGGL(k_bounce_positions_to_planes, dim3(grid_for(b->n)), dim3(BGS_BLOCK), 0, b->stream, b->bg, b->d_planes, b->n);
     };
-    auto with_block = [&](auto pmax_tag) {
-        if (final_cap > cap && !next_list) launch_pieces(pmax_tag, std::integral_constant<int, 256>{}, std::true_type{});
-        else if (b->bounce_block >= 1024) launch_pieces(pmax_tag, std::integral_constant<int, 1024>{}, std::false_type{});
-        else if (b->bounce_block >= 512) launch_pieces(pmax_tag, std::integral_constant<int, 512>{}, std::false_type{});
-        else launch_pieces(pmax_tag, std::integral_constant<int, 256>{}, std::false_type{});
-    };
     // K3p: from the start position, no work list, at most 16 pieces
-    if (group == 1 && b->bounce_flat && b->bounce_pieces && from_initial && !worklist && b->bg.piece_count >= 1 &&
+    if (group == 1 && b->bounce_pieces && from_initial && !worklist && b->bg.piece_count >= 1 &&
         b->n < (int64_t)0xFFFFFFFFu) {
-        if (b->bg.piece_count <= 8) with_block(std::integral_constant<int, 8>{});
-        else if (b->bg.piece_count <= 12) with_block(std::integral_constant<int, 12>{});
-        else with_block(std::integral_constant<int, 16>{});
+        if (b->bg.piece_count <= 8) launch_pieces(std::integral_constant<int, 8>{});
+        else if (b->bg.piece_count <= 12) launch_pieces(std::integral_constant<int, 12>{});
+        else launch_pieces(std::integral_constant<int, 16>{});
         return;
     }
     auto with_group = [&](auto initial_tag) {
-        if (group == 1 && b->bounce_flat) launch_flat(initial_tag);   // one lane per board, flattened search
-        else if (group == 1) launch(initial_tag, std::integral_constant<int, 1>{});
-        else launch(initial_tag, std::integral_constant<int, 8>{});
+        if (group == 1) launch_flat(initial_tag);   // one lane per board, flattened search
+        else launch(initial_tag);                   // 8 lanes per board
     };
     if (from_initial) with_group(std::true_type{});
     else with_group(std::false_type{});
@@ -2731,7 +2388,7 @@ void bounce_rollout(const bgs_batch* b, uint64_t seed, int32_t max_plies, uint32
         // time it only wins from 2^17 boards (2^16: 2.05 ms against 1.75 with 8 lanes + K3w; 2^17: 2.46 against 2.62), with
         // four and more launches in flight from 2^15 as before
         const BounceShape shape = bounce_shape(b->launches_in_flight);
-        const bool piece_list = b->bounce_flat && b->bounce_pieces && from_initial && b->bg.piece_count >= 1;
+        const bool piece_list = b->bounce_pieces && from_initial && b->bg.piece_count >= 1;
         int lanes = b->bounce_group;
         if (b->bounce_group_auto && piece_list && b->launches_in_flight < 4) lanes = b->n >= 131072 ? 1 : 8;
         // K3w as the last pass: any batch whose configured start position has at most 16 pieces (piece_count = 0: more)
@@ -2774,23 +2431,12 @@ void bounce_rollout(const bgs_batch* b, uint64_t seed, int32_t max_plies, uint32
             const uint32_t pass_cap = (last || pass_cap_of[pass] > cap) ? cap : pass_cap_of[pass];
             const int group = pass_group_of[pass];
             if (pass == 0) {
-                // K3p with K3w as the second and last pass; experiment bounce_tail=1: the tail kernel BESIDE the bulk kernel ("the
-                // TAIL QUEUE" -- measured slower than the pass behind it, so no automatic plan takes it)
-                const bool fused = b->bounce_tail > 0 && passes == 2 && group == 1 && pass_group_of[1] == 64 && piece_list && from_initial &&
-                                   b->bounce_block < 512 && b->bg.piece_count <= BGS_BOUNCE_MAX_PIECES && b->d_pool != nullptr &&
-                                   b->n < (int64_t)0xFFFFFFFFu && b->staging_bytes >= (size_t)b->n * kTailEntryWords * sizeof(uint32_t);
-                if (fused) {
-                    launch_rollout(b, seed, pass_cap, from_initial, group, b->rollout_wps, nullptr, nullptr, queues, cap);
-                    return;
-                }
                 // (K3p writes the next pass's work list itself: no compaction kernel behind it)
                 listed = group == 1 && piece_list && from_initial && b->bg.piece_count <= BGS_BOUNCE_MAX_PIECES && b->n < (int64_t)0xFFFFFFFFu &&
                          pass_cap < cap;
-                if (listed) b->tail_flags_dirty = 1;
                 launch_rollout(b, seed, pass_cap, from_initial, group, group == 1 ? b->rollout_wps : 8, nullptr, nullptr, queues,
-                               listed ? cap : 0u, listed ? list : nullptr, listed ? counts + 1 : nullptr);
+                               listed ? NextPass{counts + 1, cap, list} : NextPass{});
             } else {
-                b->tail_flags_dirty = 1;   // (the work list's region is about to hold game indices)
                 // boards still running below the final cap after the previous pass -> this pass's list
                 if (!(pass == 1 && listed))
                 hipLaunchKernelGGL(k_bounce_compact, dim3(grid_for(b->n)), dim3(BGS_BLOCK), 0, b->stream, b->d_status, b->d_plies,

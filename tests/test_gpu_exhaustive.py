@@ -55,7 +55,7 @@ BOUNCE_WALKS = {"narrow": (None, 2), "blocked_start": (None, 1), "three_next_to_
 # forced families that accept loaded boards ({} = the default plan); "per_ply" = the strict RNG contract
 CONNECT_FAMILIES = {"default": {}, "rollout_generic": {"rollout_generic": "1"}, "force_generic": {"force_generic": "1"},
                     "per_ply": {}}
-BOUNCE_FAMILIES = {"default": {}, "flat": {"bounce_group": "1", "bounce_pieces": "0"}, "nested": {"bounce_group": "1", "bounce_flat": "0"},
+BOUNCE_FAMILIES = {"default": {}, "flat": {"bounce_group": "1", "bounce_pieces": "0"},
                    "group8": {"bounce_group": "8"}, "no_wave_pass": {"bounce_wave_pass": "0"}, "force_generic": {"force_generic": "1"}}
 BOUNCE_CAP = 4096   # Bounce has games that never end
 

@@ -352,16 +352,15 @@ def test_connect_rollout_kernel_families_agree_with_the_oracle(batch_mod, mode):
                 knobs[k] = v
 
 
-@pytest.mark.parametrize("mode", ["1", "1:flat", "8", "1:nested", "passes"])
+@pytest.mark.parametrize("mode", ["1", "1:flat", "8", "passes"])
 def test_bounce_rollout_kernel_families_agree_with_the_oracle(batch_mod, mode):
     """Every fused Bounce rollout kernel on the same mid-size batch: one lane per board on the piece list (K3p, default for
     large batches from the start position) or with the flattened cell search (K3f: boards loaded from memory), both with
-    the work queue; 8 lanes per board (default for small batches), the nested-loop kernel and the multi-pass plan (flat
+    the work queue; 8 lanes per board (default for small batches) and the multi-pass plan (flat
     passes, then a lane-group pass over the compacted work list)."""
     import os
 
     env = {"1": {"bounce_group": "1"}, "1:flat": {"bounce_group": "1", "bounce_pieces": "0"}, "8": {"bounce_group": "8"},
-           "1:nested": {"bounce_group": "1", "bounce_flat": "0"},
            "passes": {"bounce_plan": "16:1,64:1,0:8", "bounce_chunk": "8"}}[mode]
     old = {k: knobs.get(k) for k in env}
     knobs.update(env)
@@ -1123,27 +1122,6 @@ def test_connect_strict_contract_through_the_reward_sink(batch_mod):
     sink.close()
     with pytest.raises(ValueError):
         dev.set_rng_contract("per-game")
-
-
-def test_bounce_tail_kernel_beside_the_bulk_kernel(batch_mod, monkeypatch):
-    """Experiment bounce_tail=1 (round 6; measured slower, no automatic plan takes it): K3p hands the games that reach its ply cap
-    -- and the last boards of a workgroup's last wave -- to a device-wide queue, a second kernel on a stream of the batch's own
-    finishes them while the bulk kernel runs.  Same boards as the oracle's, whatever the hand-over threshold and the number
-    of tail waves; twice on the same batch (the queue's "entry complete" words are launch serials)."""
-    n = 1 << 17
-    orc = oracle.BounceOracle(DEFAULT_BOUNCE, n)
-    total = orc.rollout(SEED + 41, max_plies=4096)
-    for handoff, limit in (("0", "64"), ("16", "512"), ("32", "1024")):
-        monkeypatch.setitem(knobs, "bounce_tail", "1")
-        monkeypatch.setitem(knobs, "bounce_tail_handoff", handoff)
-        monkeypatch.setitem(knobs, "bounce_tail_limit", limit)
-        dev = batch_mod.BounceBatch(DEFAULT_BOUNCE, n)
-        for _ in range(2):
-            dev.reset_steps()
-            dev.rollout(SEED + 41, max_plies=4096, from_initial=True)
-            assert_same(dev, orc, f"handoff {handoff}, {limit} tail waves")
-            assert dev.steps == total
-        dev.close()
 
 
 @pytest.mark.parametrize("hint,n", [(1, 1 << 17), (8, 1 << 16), (20, 1 << 16)])

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Parametrised sweeps on the GPU box (round 4: one script instead of a directory of one-off shell loops).
 
-    python3 tools/sweep.py bounce-block   [--reps N]     K3p workgroup size (bounce_block) x parking threshold, 20 in flight
     python3 tools/sweep.py bounce-park    [--reps N]     K3p parking threshold (bounce_pieces_park) with / without the device-wide pool
     python3 tools/sweep.py bounce-tail    [--reps N]     ply cap of the bulk pass (bounce_plan) x parking threshold, 20 in flight
     python3 tools/sweep.py bounce-depth   [--reps N]     Bounce batches in flight (8 .. 28) with the default launch shape
@@ -59,7 +58,7 @@ def main():
     ap.add_argument("--env", default="", help="bench sweep: NAME=v1,v2,...")
     ap.add_argument("--args", default="", help="bench sweep: further bench.py arguments")
     ap.add_argument("--repeat", type=int, default=1)
-    ap.add_argument("what", choices=("bench", "bounce-block", "bounce-park", "bounce-tail", "bounce-depth", "k2c-shape", "k2c-depth", "headline-depth"))
+    ap.add_argument("what", choices=("bench", "bounce-park", "bounce-tail", "bounce-depth", "k2c-shape", "k2c-depth", "headline-depth"))
     ap.add_argument("--reps", type=int, default=0)
     args = ap.parse_args()
     rows = []
@@ -72,12 +71,6 @@ def main():
                 extra = args.args.split()
                 r = bench_point({}, extra + [name, v]) if name.startswith("--") else bench_point({name: v}, extra)
                 rows.append(dict({name: v}, **r))
-                print(rows[-1], flush=True)
-    elif args.what == "bounce-block":
-        for block in (256, 512, 1024):
-            for park in (16, 32):
-                r = point("bounce", 20, args.reps or 120, {"bounce_block": block, "bounce_park": park})
-                rows.append(dict({"block": block, "park": park}, **r))
                 print(rows[-1], flush=True)
     elif args.what == "bounce-park":
         for pool in (1, 0):
