@@ -1,20 +1,25 @@
 """Differential fuzzing of the HIP path against the CPU oracle: random geometries, random start grids, random mixes of
-sampled plies, caller-chosen moves, loads and rollouts.  Seeds are fixed; everything is bit-exact or it fails."""
+sampled plies, caller-chosen moves, loads and rollouts; and the evaluation and solver launches (evaluate_actions,
+evaluate_moves, solve_actions, solve_moves) over the random and hand-picked cases of tests/fuzz_cases.py against the
+oracle's expected counts and the retrograde references.  Seeds are fixed; everything is bit-exact or it fails."""
 
 import numpy as np
 import pytest
 
+from tests import fuzz_cases as fc
+from tests import game_trees as gt
+from tests import solve_reference as ref
+from tests.fuzz_cases import EXTRA, random_bounce_grid, random_connect_geometries, random_piece_list_grid
 from tests.knobs import knobs
 
 from oracle import oracle
 
 pytestmark = pytest.mark.gpu
 
-import os
-
 SEED = 0x0123456789ABCDEF
-# BGS_FUZZ_CASES=N widens the sweep (default: 24 Connect + 32 Bounce cases)
-EXTRA = int(os.environ.get("BGS_FUZZ_CASES", "0"))
+# BGS_FUZZ_CASES=N widens the sweeps (default: 24 Connect + 32 Bounce + 24 piece-list cases of steps and rollouts; 24
+# Connect + 16 Bounce cases, and the corner tables, of every evaluation and solver launch)
+SOLVE_NODES = 1 << 22    # the depths of fuzz_cases keep every search far below it: no BUDGET code may appear
 
 
 def same(dev, orc, what):
@@ -22,16 +27,6 @@ def same(dev, orc, what):
     np.testing.assert_array_equal(dev.winner, orc.winner, err_msg=f"winner {what}")
     np.testing.assert_array_equal(dev.plies, orc.plies, err_msg=f"plies {what}")
     np.testing.assert_array_equal(dev.reward, orc.reward, err_msg=f"reward {what}")
-
-
-def random_connect_geometries(rng, count):
-    out = []
-    while len(out) < count:
-        h, w = int(rng.integers(1, 16)), int(rng.integers(1, 17))
-        if w * (h + 1) > 192:
-            continue
-        out.append((h, w, int(rng.integers(1, 8))))
-    return out
 
 
 @pytest.mark.parametrize("case", range(max(24, EXTRA)))
@@ -73,21 +68,6 @@ def test_connect_random_geometry(case):
     again = ConnectBatch(h, w, k, n)
     assert (again.write_state(orc.grid) == 0).all()
     same(again, orc, what + " reloaded")
-
-
-def random_bounce_grid(rng):
-    while True:
-        h, w = int(rng.integers(3, 12)), int(rng.integers(1, 13))
-        if h * w <= 64:
-            break
-    grid = np.zeros((h, w), dtype=np.int8)
-    density = rng.uniform(0.05, 0.7)
-    max_value = int(rng.choice([1, 2, 3, 3, 3, 5, 9, 15]))
-    for y in range(1, h - 1):
-        for x in range(w):
-            if rng.random() < density:
-                grid[y, x] = int(rng.integers(1, max_value + 1))
-    return grid
 
 
 @pytest.mark.parametrize("case", range(max(32, EXTRA)))
@@ -148,22 +128,6 @@ def test_bounce_random_grid(case):
     same(again, orc, what + " reloaded")
 
 
-def random_piece_list_grid(rng):
-    """A start grid the piece-list kernel takes: at most 8 columns and 16 pieces (values 1..15, a few cells each)."""
-    while True:
-        h, w = int(rng.integers(3, 12)), int(rng.integers(1, 9))
-        if h * w <= 64:
-            break
-    grid = np.zeros((h, w), dtype=np.int8)
-    cells = [(y, x) for y in range(1, h - 1) for x in range(w)]
-    pieces = int(rng.integers(1, min(16, len(cells)) + 1))
-    max_value = int(rng.choice([1, 2, 3, 3, 3, 4, 6, 15]))
-    for k in rng.choice(len(cells), size=pieces, replace=False):
-        y, x = cells[int(k)]
-        grid[y, x] = int(rng.integers(1, max_value + 1))
-    return grid
-
-
 @pytest.mark.parametrize("case", range(max(24, EXTRA)))
 def test_bounce_piece_list_random_grid(case):
     """K3p (one lane per board on the piece list; the 8-, 12- and 16-piece instantiations, the bulk + tail plan for caps
@@ -193,3 +157,146 @@ def test_bounce_piece_list_random_grid(case):
             del knobs["bounce_group"]
         else:
             knobs["bounce_group"] = old
+
+
+# ---- the evaluation and solver launches over the case table of tests/fuzz_cases.py
+def snapshot(b):
+    return b.grid.tobytes(), b.player.tobytes(), b.winner.tobytes(), b.plies.tobytes()
+
+
+def load_connect(case, roots, evaluate=False):
+    from simulator.batch import ConnectBatch
+
+    b = ConnectBatch(case.h, case.w, case.k, roots[0].shape[0])
+    assert (b.write_state(*roots) == 0).all(), fc.describe(case)
+    if evaluate:
+        if case.per_ply:
+            b.set_rng_contract("per-ply")
+        b.set_first_game(case.first_game)
+    b.reset_steps()
+    return b
+
+
+def load_bounce(case, roots):
+    from simulator.batch import BounceBatch
+
+    b = BounceBatch(case.grid, roots[0].shape[0])
+    assert (b.write_state(*roots) == 0).all(), fc.describe(case)
+    b.set_first_game(case.first_game)
+    b.reset_steps()
+    return b
+
+
+def assert_rows_equal(got, want, rows, what, names):
+    """got, want: tuples of arrays [n, ...]; names the first differing root (its row in the case's roots) and entries"""
+    n = got[0].shape[0]
+    bad = np.zeros(n, dtype=bool)
+    for g, w in zip(got, want):
+        assert g.shape == w.shape, (what, g.shape, w.shape)
+        bad |= (g != w).reshape(n, -1).any(axis=1)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        at = np.argwhere(np.logical_or.reduce([g[i] != w[i] for g, w in zip(got, want)]))[:6]
+        detail = [(tuple(int(v) for v in a),) + tuple(x for g, w in zip(got, want) for x in (g[i][tuple(a)].tolist(), w[i][tuple(a)].tolist()))
+                  for a in at]
+        raise AssertionError(f"{what}: {int(bad.sum())} of {n} roots differ, first root {int(rows[i])} of the case "
+                             f"(entry, {', '.join(f'{m}, want' for m in names)}) {detail}")
+
+
+@pytest.mark.parametrize("key", fc.connect_keys(), ids=str)
+def test_connect_solve_random_geometry(key):
+    case = fc.connect_case(key)
+    for depth, rows in fc.connect_solves(case):
+        roots = fc.take(case.roots, rows)
+        what = f"{fc.describe(case)} solve_actions depth {depth}"
+        b = load_connect(case, roots)
+        before = snapshot(b)
+        codes, plies = b.solve_actions(depth=depth, max_nodes=SOLVE_NODES)
+        assert not (codes == ref.BUDGET).any(), what
+        assert_rows_equal((codes, plies), ref.solve(case.h, case.w, case.k, roots, depth), rows, what, ("code", "plies"))
+        assert snapshot(b) == before and b.steps == 0, what
+        b.close()
+
+
+@pytest.mark.parametrize("key", fc.bounce_keys(), ids=str)
+def test_bounce_solve_random_grid(key):
+    case = fc.bounce_case(key)
+    h, w = case.grid.shape
+    rows = np.arange(case.roots[0].shape[0])
+    legal = np.zeros((rows.size, w, h * w), dtype=bool)
+    for i, acts in enumerate(gt.bounce_actions(case.grid, case.roots)):
+        for (sx, _), (tx, ty) in acts:
+            legal[i, sx, ty * w + tx] = True
+    b = load_bounce(case, case.roots)
+    before = snapshot(b)
+    for depth in fc.bounce_depths(key):
+        what = f"{fc.describe(case)} solve_moves depth {depth}"
+        codes, plies = b.solve_moves(depth=depth, max_nodes=SOLVE_NODES)
+        assert not (codes == ref.BUDGET).any(), what
+        assert_rows_equal((codes, plies), fc.bounce_reference(key, depth)[:2], rows, what, ("code", "plies"))
+        assert_rows_equal((codes != ref.NONE,), (legal,), rows, what + " legal slots", ("legal",))
+        assert snapshot(b) == before and b.steps == 0, what
+    b.close()
+
+
+@pytest.mark.parametrize("key", fc.connect_keys(), ids=str)
+def test_connect_evaluate_random_geometry(key):
+    case = fc.connect_case(key)
+    for j, playouts in enumerate(case.playouts):
+        roots, want, steps = fc.connect_eval_expected(case, j)
+        what = (f"{fc.describe(case)} evaluate_actions playouts {playouts} max_plies {case.max_plies} per_ply {case.per_ply} "
+                f"first_game {case.first_game}")
+        b = load_connect(case, roots, evaluate=True)
+        before = snapshot(b)
+        got = b.evaluate_actions(seed=fc.EVAL_SEED, playouts=playouts, max_plies=case.max_plies)
+        assert_rows_equal((got,), (want,), case.eval_rows[j], what, ("count",))
+        assert b.steps == steps, what
+        assert snapshot(b) == before, what
+        b.close()
+
+
+@pytest.mark.parametrize("key", fc.bounce_keys(), ids=str)
+def test_bounce_evaluate_random_grid(key):
+    case = fc.bounce_case(key)
+    for max_plies in case.max_plies:
+        roots, want, steps = fc.bounce_eval_expected(case, max_plies)
+        what = f"{fc.describe(case)} evaluate_moves playouts {case.playouts} max_plies {max_plies} first_game {case.first_game}"
+        b = load_bounce(case, roots)
+        before = snapshot(b)
+        got = b.evaluate_moves(seed=fc.EVAL_SEED, playouts=case.playouts, max_plies=max_plies)
+        assert_rows_equal((got,), (want,), case.eval_rows, what, ("count",))
+        assert b.steps == steps, what
+        assert snapshot(b) == before, what
+        b.close()
+
+
+def test_default_board_static_and_run_time_geometry_agree_in_evaluate_and_solve(monkeypatch):
+    """the 9x6 default grid through the compile-time geometry (the product's choice) and, under the test-build knob
+    bounce_static_geom=0, through the run-time record every other grid takes: the same counts, codes and plies, the
+    references' ones.  The knob is read when a batch is created."""
+    case = fc.bounce_case("default")
+    max_plies = case.max_plies[0]
+    roots, want, steps = fc.bounce_eval_expected(case, max_plies)
+    results = []
+    for static in (True, False):
+        if not static:
+            monkeypatch.setitem(knobs, "bounce_static_geom", "0")
+        else:
+            assert "bounce_static_geom" not in knobs
+        what = f"{fc.describe(case)} static geometry {static}"
+        b = load_bounce(case, roots)            # created after the knob is set
+        counts = b.evaluate_moves(seed=fc.EVAL_SEED, playouts=case.playouts, max_plies=max_plies)
+        assert_rows_equal((counts,), (want,), case.eval_rows, what + f" evaluate_moves playouts {case.playouts} max_plies {max_plies}", ("count",))
+        assert b.steps == steps, what
+        b.close()
+        b = load_bounce(case, case.roots)
+        solved = []
+        for depth in fc.bounce_depths("default"):
+            codes, plies = b.solve_moves(depth=depth, max_nodes=SOLVE_NODES)
+            assert_rows_equal((codes, plies), fc.bounce_reference("default", depth)[:2], np.arange(codes.shape[0]),
+                              what + f" solve_moves depth {depth}", ("code", "plies"))
+            solved += [codes, plies]
+        b.close()
+        results.append([counts] + solved)
+    for a, c in zip(*results):
+        np.testing.assert_array_equal(a, c)
