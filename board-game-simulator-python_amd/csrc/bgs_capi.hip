@@ -1002,10 +1002,9 @@ int bgs_rollout(bgs_batch* b, uint64_t seed, int32_t max_plies, uint32_t flags) 
     return finish_launch();
 }
 
-int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
-                                 int counts_on_device) {
-    int rc = enter(b);
-    if (rc) return rc;
+// the body of both evaluate_actions entry points (the caller has entered the batch's device)
+static int connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy, int32_t* counts,
+                                    int counts_on_device) {
     NEED(counts != nullptr, "counts is NULL");
     NEED(b->game == BGS_GAME_CONNECT, "evaluate_actions: Connect batches only (Bounce boards are not supported yet)");
     NEED(!b->generic, "evaluate_actions: bit-packed Connect boards only (up to %d bits a plane); %dx%d boards are generic",
@@ -1017,18 +1016,35 @@ int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, 
          b->cg.w, playouts);
     const size_t bytes = (size_t)b->n * b->cg.w * 3 * sizeof(int32_t);
     if (counts_on_device) {
-        bgs::connect_evaluate(b, seed, playouts, max_plies, counts);
+        bgs::connect_evaluate(b, seed, playouts, max_plies, counts, policy);
         return finish_launch();
     }
     int32_t* d = nullptr;
     HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
-    bgs::connect_evaluate(b, seed, playouts, max_plies, d);
-    rc = finish_launch();
+    bgs::connect_evaluate(b, seed, playouts, max_plies, d, policy);
+    int rc = finish_launch();
     if (rc == BGS_OK) rc = copy_to_host(b, counts, d, bytes);
     const hipError_t e = hipFreeAsync(d, b->stream);
     if (rc) return rc;
     HIP_TRY(e);
     return BGS_OK;
+}
+
+int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
+                                 int counts_on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    return connect_evaluate_actions(b, seed, playouts, max_plies, BGS_POLICY_UNIFORM, counts, counts_on_device);
+}
+
+int bgs_connect_evaluate_actions_policy(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy, int32_t* counts,
+                                        int counts_on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "evaluate_actions: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    return connect_evaluate_actions(b, seed, playouts, max_plies, policy, counts, counts_on_device);
 }
 
 int bgs_connect_solve_actions(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,

@@ -3,6 +3,8 @@
 // second half of this file), the exact Connect solver (bgs_connect_solve_actions, between the two) and the exact Bounce
 // solver (bgs_bounce_solve_moves, at the end).  Connect: for board i and column c, `playouts` games that start with column c on board i and
 // continue by the uniform random policy, reduced on the device to (wins, draws, losses) of the player to move at board i.
+// bgs_connect_evaluate_actions_policy plays the same games by a playout policy (include/bgs.h: BGS_POLICY_DECISIVE takes a
+// winning cell, else blocks the opponent's, else plays uniformly); the policy is a template parameter of the same kernel.
 //
 // Game ids (include/bgs.h): playout p of column c of board i is global game
 // G = ((first_game + i) * width + c) * playouts + p (mod 2^64), drawn under the batch's RNG contract at the board's absolute
@@ -49,48 +51,85 @@ struct EvalGeom {
     uint64_t cells[BGS_CONNECT_MAX_WORDS];     // every real cell (no sentinels)
 };
 
-// the mover of this ply drops a stone on `pos` (act = all ones) or nothing (act = 0); returns "the mover has won"
+// the mover drops a stone on `pos` (act = all ones) or nothing (act = 0), untested
 template <int NW>
-__device__ __forceinline__ bool drop_and_test(const EvalGeom& g, Bits<NW>& mine, uint32_t pos, uint32_t act) {
+__device__ __forceinline__ void drop(Bits<NW>& mine, uint32_t pos, uint32_t act) {
     if (NW == 1) {
         const uint64_t bit = 1ull << (pos & 63u);
         mine.w[0] = ((uint64_t)and_or((uint32_t)(bit >> 32), act, (uint32_t)(mine.w[0] >> 32)) << 32) |
                     and_or((uint32_t)bit, act, (uint32_t)mine.w[0]);
-        const bool won = g.k() == 4 ? four_in_a_row_at(mine.w[0], g.h(), pos) : has_run(g, mine);
-        return won && act;
+        return;
     }
 #pragma unroll
     for (int j = 0; j < NW; ++j) mine.w[j] |= ((uint32_t)j == (pos >> 6) && act) ? 1ull << (pos & 63u) : 0ull;
+}
+
+// the mover of this ply drops a stone on `pos` (act = all ones) or nothing (act = 0); returns "the mover has won"
+template <int NW>
+__device__ __forceinline__ bool drop_and_test(const EvalGeom& g, Bits<NW>& mine, uint32_t pos, uint32_t act) {
+    drop(mine, pos, act);
+    if (NW == 1) {
+        const bool won = g.k() == 4 ? four_in_a_row_at(mine.w[0], g.h(), pos) : has_run(g, mine);
+        return won && act;
+    }
     return act && has_run(g, mine);
 }
 
-// one uniformly drawn ply on the board (p0, p1) by the side `mover`: the position of the stone it drops
+// the idx-th cell of `set` in ascending order, idx drawn from `draw` over its cells.  `set` is a subset of the landing
+// cells: at most one cell a column and never a sentinel, so ascending cells are ascending columns and the one-word
+// field search (select_landing) serves any such subset
 template <int NW>
-__device__ __forceinline__ uint32_t draw_position(const EvalGeom& g, const Bits<NW>& occ, uint32_t draw) {
-    const Bits<NW> landing = landing_of(g, occ);
+__device__ __forceinline__ uint32_t draw_from_cells(const EvalGeom& g, const Bits<NW>& set, uint32_t draw) {
     if (NW == 1) {
-        const uint32_t idx = sample_index(draw, (uint32_t)__popcll(landing.w[0]));
+        const uint32_t idx = sample_index(draw, (uint32_t)__popcll(set.w[0]));
         const bool by_fields = g.h() <= 15 && (uint32_t)g.w() <= (1u << g.h());   // (uniform)
-        return by_fields ? select_landing(landing.w[0], g.bottoms[0], g.bottoms[0] << g.h(), (uint32_t)g.h() + 1u, idx)
-                         : select_bit64(landing.w[0], idx);
+        return by_fields ? select_landing(set.w[0], g.bottoms[0], g.bottoms[0] << g.h(), (uint32_t)g.h() + 1u, idx)
+                         : select_bit64(set.w[0], idx);
     }
     uint32_t cnt = 0;
 #pragma unroll
-    for (int j = 0; j < NW; ++j) cnt += (uint32_t)__popcll(landing.w[j]);
+    for (int j = 0; j < NW; ++j) cnt += (uint32_t)__popcll(set.w[j]);
     uint32_t idx = sample_index(draw, cnt), pos = 0;
     bool found = false;
 #pragma unroll
     for (int j = 0; j < NW; ++j) {
-        const uint32_t c = (uint32_t)__popcll(landing.w[j]);
+        const uint32_t c = (uint32_t)__popcll(set.w[j]);
         const bool here = !found && idx < c;
-        pos = here ? 64u * j + select_bit64(landing.w[j], idx) : pos;
+        pos = here ? 64u * j + select_bit64(set.w[j], idx) : pos;
         idx -= (!found && !here) ? c : 0u;
         found = found || here;
     }
     return pos;
 }
 
-template <int NW, bool PER_PLY>
+// one uniformly drawn ply on a board with the stones `occ`: the position of the stone it drops
+template <int NW>
+__device__ __forceinline__ uint32_t draw_position(const EvalGeom& g, const Bits<NW>& occ, uint32_t draw) {
+    return draw_from_cells(g, landing_of(g, occ), draw);
+}
+
+template <int NW>
+__device__ __forceinline__ Bits<NW> threats(const EvalGeom& g, const Bits<NW>& me);   // (with the solver, below)
+
+// one ply of BGS_POLICY_DECISIVE by the side with the stones `me` against `op`: the candidate cells are the landing
+// cells that complete a run of `me` (W), else those that would complete one of `op` (B), else every landing cell; the
+// ply's draw indexes them in ascending column order.  `wins`: the cell came from W -- the stone dropped there wins, and
+// no other cell of this ply could, so the caller needs no win test of its own.
+template <int NW>
+__device__ __forceinline__ uint32_t decisive_position(const EvalGeom& g, const Bits<NW>& me, const Bits<NW>& op, uint32_t draw,
+                                                      bool& wins) {
+    const Bits<NW> landing = landing_of(g, me | op);
+    const Bits<NW> w = threats(g, me) & landing;
+    const Bits<NW> b = threats(g, op) & landing;
+    wins = any(w);
+    const bool block = any(b);
+    Bits<NW> set;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) set.w[j] = wins ? w.w[j] : (block ? b.w[j] : landing.w[j]);
+    return draw_from_cells(g, set, draw);
+}
+
+template <int NW, bool PER_PLY, int POLICY = BGS_POLICY_UNIFORM>
 __global__ void __launch_bounds__(BGS_BLOCK)
 k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n,
                    uint64_t seed, uint64_t game_base, uint32_t playouts, uint32_t max_plies, uint32_t segs_per_wave,
@@ -229,8 +268,15 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
             const uint32_t draw = PER_PLY ? ph.v[j] : sub_draw(word, j);
             const uint32_t act = j >= skip ? live : 0u;
             const uint32_t ply = 4u * blk + j;          // stones before this sub-step; its mover is player j & 1
-            const uint32_t pos = draw_position(g, p[0] | p[1], draw);
-            const bool won = drop_and_test(g, p[j & 1u], pos, act);
+            bool won;
+            if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                const uint32_t pos = decisive_position(g, p[j & 1u], p[(j & 1u) ^ 1u], draw, won);
+                drop(p[j & 1u], pos, act);
+                won = won && act;
+            } else {
+                const uint32_t pos = draw_position(g, p[0] | p[1], draw);
+                won = drop_and_test(g, p[j & 1u], pos, act);
+            }
             const bool full = ply + 1u == g.cells_total;
             if (act) {
                 st = won ? (j & 1u) + 1u : (full ? BGS_ST_DRAW : BGS_ST_RUNNING);
@@ -256,7 +302,7 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
     add_steps(steps, stepped);
 }
 
-template <int NW, bool PER_PLY>
+template <int NW, bool PER_PLY, int POLICY = BGS_POLICY_UNIFORM>
 void launch_evaluate(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t playouts, uint32_t max_plies,
                      int32_t* d_counts) {
     const int64_t segments = b->n * g.w();
@@ -278,7 +324,7 @@ void launch_evaluate(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint3
     for (int64_t w0 = 0; w0 < waves; w0 += kMaxBlocks * kEvalWavesPerBlock) {
         int64_t blocks = (waves - w0 + kEvalWavesPerBlock - 1) / kEvalWavesPerBlock;
         if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-        hipLaunchKernelGGL((k_connect_evaluate<NW, PER_PLY>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), 0, b->stream, g,
+        hipLaunchKernelGGL((k_connect_evaluate<NW, PER_PLY, POLICY>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), 0, b->stream, g,
                            (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, seed, game_base, playouts, max_plies,
                            segs_per_wave, slices, slice_len, w0, waves, d_counts, b->d_steps);
     }
@@ -1317,10 +1363,19 @@ void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t*
     }
 }
 
-void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts) {
+void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts, int policy) {
     const EvalGeom g = eval_geom(b);
     const uint32_t p = (uint32_t)playouts, cap = (uint32_t)max_plies;
     const bool per_ply = b->rng_per_ply != 0;
+    if (policy == BGS_POLICY_DECISIVE) {
+        constexpr int D = BGS_POLICY_DECISIVE;
+        switch (b->cg.nw) {
+            case 1: per_ply ? launch_evaluate<1, true, D>(b, g, seed, p, cap, d_counts) : launch_evaluate<1, false, D>(b, g, seed, p, cap, d_counts); break;
+            case 2: per_ply ? launch_evaluate<2, true, D>(b, g, seed, p, cap, d_counts) : launch_evaluate<2, false, D>(b, g, seed, p, cap, d_counts); break;
+            default: per_ply ? launch_evaluate<3, true, D>(b, g, seed, p, cap, d_counts) : launch_evaluate<3, false, D>(b, g, seed, p, cap, d_counts); break;
+        }
+        return;
+    }
     switch (b->cg.nw) {
         case 1: per_ply ? launch_evaluate<1, true>(b, g, seed, p, cap, d_counts) : launch_evaluate<1, false>(b, g, seed, p, cap, d_counts); break;
         case 2: per_ply ? launch_evaluate<2, true>(b, g, seed, p, cap, d_counts) : launch_evaluate<2, false>(b, g, seed, p, cap, d_counts); break;

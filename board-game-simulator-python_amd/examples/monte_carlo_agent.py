@@ -5,7 +5,7 @@ The games live in one ConnectBatch.  Each ply, the side to move of every running
 (all its games are evaluated in ONE launch: every legal column, `playouts` random games each) or the random agent (a
 uniform legal column).  The agent plays first in half of the games and second in the other half.
 
-    python board-game-simulator-python_amd/examples/monte_carlo_agent.py [--games 400] [--playouts 64]
+    python board-game-simulator-python_amd/examples/monte_carlo_agent.py [--games 400] [--playouts 64] [--policy decisive]
 """
 
 import argparse
@@ -25,10 +25,11 @@ def main() -> None:
     ap.add_argument("--games", type=int, default=400)
     ap.add_argument("--playouts", type=int, default=64)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--policy", choices=("uniform", "decisive"), default="uniform", help="the playout policy")
     args = ap.parse_args()
     n = args.games
     games = ConnectBatch(6, 7, 4, n)
-    agent = MonteCarloAgent(playouts=args.playouts, seed=args.seed)
+    agent = MonteCarloAgent(playouts=args.playouts, seed=args.seed, policy=args.policy)
     rng = np.random.default_rng(args.seed)
     agent_player = (np.arange(n) % 2).astype(np.int8)   # the agent is player 0 in even games, player 1 in odd ones
     ply = 0
@@ -45,7 +46,7 @@ def main() -> None:
         ply += 1
     winner = games.winner
     won, drawn = (winner == agent_player).sum(), (winner == 2).sum()
-    print(f"MonteCarloAgent ({args.playouts} playouts a column) against uniform random, {n} games of Connect4: "
+    print(f"MonteCarloAgent ({args.playouts} {args.policy} playouts a column) against uniform random, {n} games of Connect4: "
           f"won {won} ({won / n:.1%}), drew {drawn}, lost {n - won - drawn}")
     agent.close()
 

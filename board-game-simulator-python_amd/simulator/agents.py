@@ -1,8 +1,8 @@
 """Agents on top of the batched engine, in the shape of the reference's ``textual/examples/agent.py``:
 ``Agent.predict(state) -> dict[Action, float]``.
 
-``MonteCarloAgent`` is flat Monte-Carlo: every legal action of a position is valued by ``playouts`` uniform random games
-that start with it, ``(wins + draws / 2) / playouts`` for the player to move.  All actions of all positions are played
+``MonteCarloAgent`` is flat Monte-Carlo: every legal action of a position is valued by ``playouts`` random games (uniform,
+or for Connect by the decisive-move playout policy) that start with it, ``(wins + draws / 2) / playouts`` for the player to move.  All actions of all positions are played
 and counted in ONE launch: ``ConnectBatch.evaluate_actions`` for Connect states (a column each),
 ``BounceBatch.evaluate_moves`` for Bounce states (a (source, target) move each).
 
@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from .batch import (DEFAULT_BOUNCE_SOLVE_DEPTH, DEFAULT_SEED, DEFAULT_SOLVE_NODES, SOLVE_BUDGET, SOLVE_DRAW, SOLVE_LOSS,
-                    SOLVE_UNKNOWN, SOLVE_WIN, BounceBatch, ConnectBatch)
+                    SOLVE_UNKNOWN, SOLVE_WIN, BounceBatch, ConnectBatch, playout_policy)
 from .game import bounce, connect
 
 # Bounce playouts stop at this absolute ply count unless the agent is given another cap: random Bounce games are short
@@ -37,9 +37,15 @@ class MonteCarloAgent:
 
     ``max_plies`` caps every playout at that absolute ply count (a capped playout adds nothing to the value).  None: no
     cap for Connect, whose games end by themselves, and ``BOUNCE_MAX_PLIES`` (1024) for Bounce.
+
+    ``policy`` is the playout policy of Connect states: "uniform", or "decisive" (a playout takes a winning column, else
+    blocks the opponent's, else plays uniformly: ``ConnectBatch.evaluate_actions(policy=...)``).  Bounce has the uniform
+    policy alone: a Bounce state with any other policy raises ValueError.
     """
 
-    def __init__(self, playouts: int = 256, seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None):
+    def __init__(self, playouts: int = 256, seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None,
+                 policy: str = "uniform"):
+        playout_policy(policy)
         if playouts < 1:
             raise ValueError("playouts must be >= 1")
         if max_plies is not None and max_plies < 1:
@@ -48,6 +54,7 @@ class MonteCarloAgent:
         self.seed = int(seed)
         self.device = int(device)
         self.max_plies = None if max_plies is None else int(max_plies)
+        self.policy = policy
         self._batches: Dict[tuple, Union[ConnectBatch, BounceBatch]] = {}
 
     def _batch(self, config: connect.Config, n: int) -> ConnectBatch:
@@ -73,7 +80,7 @@ class MonteCarloAgent:
         boards are not modified."""
         batch.set_first_game(first_game)
         cap = 2**31 - 1 if self.max_plies is None else self.max_plies
-        counts = batch.evaluate_actions(seed=self.seed, playouts=self.playouts, max_plies=cap).astype(np.float64)
+        counts = batch.evaluate_actions(seed=self.seed, playouts=self.playouts, max_plies=cap, policy=self.policy).astype(np.float64)
         v = (counts[..., 0] + 0.5 * counts[..., 1]) / self.playouts
         v[batch.legal == 0] = np.nan
         return v
@@ -100,6 +107,8 @@ class MonteCarloAgent:
         if any(type(s) is not type(states[0]) or s.config != config for s in states):
             raise ValueError("predict_many: the states must share one Config")
         if isinstance(states[0], bounce.State):
+            if self.policy != "uniform":
+                raise ValueError(f"MonteCarloAgent: Bounce playouts are uniform, there is no {self.policy!r} policy for Bounce states")
             return self._predict_bounce(states, first_game)
         if not isinstance(states[0], connect.State):
             raise TypeError(f"predict_many: Connect or Bounce states, not {type(states[0]).__name__}")

@@ -31,6 +31,16 @@ BOUNCE_SOLVE_MAX_DEPTH = 16
 DEFAULT_BOUNCE_SOLVE_DEPTH = 3
 
 
+PLAYOUT_POLICIES = {"uniform": _abi.POLICY_UNIFORM, "decisive": _abi.POLICY_DECISIVE}
+
+
+def playout_policy(name) -> int:
+    """the BGS_POLICY_* code of a playout policy's name ("uniform", "decisive"); ValueError for anything else"""
+    if not isinstance(name, str) or name not in PLAYOUT_POLICIES:
+        raise ValueError(f"unknown playout policy {name!r}: one of {sorted(PLAYOUT_POLICIES)}")
+    return PLAYOUT_POLICIES[name]
+
+
 def _ptr(a: np.ndarray, ctype):
     return a.ctypes.data_as(ctypes.POINTER(ctype))
 
@@ -787,20 +797,36 @@ class ConnectBatch(_Batch):
         """columns int32[n]; a negative entry skips the board.  Returns per-board status (0 / -2 illegal)."""
         return self._step_actions(columns, 1, want_status)
 
-    def evaluate_actions(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1) -> np.ndarray:
+    def _evaluate(self, seed: int, playouts: int, max_plies: int, policy: str, pointer: int, on_device: int) -> None:
+        """the evaluation call of `policy`: "uniform" is bgs_connect_evaluate_actions itself, any other policy goes through
+        bgs_connect_evaluate_actions_policy"""
+        code = playout_policy(policy)
+        args = (self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts), ctypes.c_int32(max_plies))
+        if code == _abi.POLICY_UNIFORM:
+            _abi.check(_abi.lib().bgs_connect_evaluate_actions(*args, ctypes.c_void_p(pointer), on_device))
+        else:
+            _abi.check(_abi.lib().bgs_connect_evaluate_actions_policy(*args, code, ctypes.c_void_p(pointer), on_device))
+
+    def evaluate_actions(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1,
+                         policy: str = "uniform") -> np.ndarray:
         """Flat Monte-Carlo evaluation of every column of every board (bgs_connect_evaluate_actions), one launch:
         int32[n, width, 3] = (wins, draws, losses) of the player to move, over `playouts` games that start with that
         column and continue by the uniform random policy until they end or hold `max_plies` plies (a capped game counts in
         none of the three).  Illegal columns and ended boards give 0, 0, 0.  The boards are not modified.  Playout p of
-        column c of board i is game ((first_game + i) * width + c) * playouts + p of the batch's RNG contract."""
+        column c of board i is game ((first_game + i) * width + c) * playouts + p of the batch's RNG contract.
+        policy="decisive" (bgs_connect_evaluate_actions_policy): the same games and draws, but a ply takes a winning
+        column when there is one, else blocks the opponent's winning column when there is one, else plays uniformly --
+        the ply's draw indexes the winning, else the blocking, else the legal columns."""
+        playout_policy(policy)   # (an unknown name: before anything is allocated)
         out = np.empty((self.n, self.width, 3), dtype=np.int32)
-        _abi.check(_abi.lib().bgs_connect_evaluate_actions(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
-                                                           ctypes.c_int32(max_plies), ctypes.c_void_p(out.ctypes.data), 0))
+        self._evaluate(seed, playouts, max_plies, policy, out.ctypes.data, 0)
         return out
 
-    def evaluate_actions_tensor(self, out=None, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1):
+    def evaluate_actions_tensor(self, out=None, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1,
+                                policy: str = "uniform"):
         """`evaluate_actions` into a device tensor int32[n, width, 3] (allocated when None), enqueued on the batch's stream
         with no synchronisation.  Every entry is written."""
+        playout_policy(policy)
         t = self._need_torch("evaluate_actions_tensor")
         shape = (self.n, self.width, 3)
         if out is None:
@@ -808,8 +834,7 @@ class ConnectBatch(_Batch):
         if not (out.is_cuda and out.dtype == t.int32 and tuple(out.shape) == shape and out.is_contiguous()
                 and out.data_ptr() % 16 == 0):
             raise TypeError(f"out must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
-        _abi.check(_abi.lib().bgs_connect_evaluate_actions(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
-                                                           ctypes.c_int32(max_plies), ctypes.c_void_p(out.data_ptr()), 1))
+        self._evaluate(seed, playouts, max_plies, policy, out.data_ptr(), 1)
         return out
 
     def solve_actions(self, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):

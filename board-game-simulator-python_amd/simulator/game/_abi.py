@@ -26,6 +26,7 @@ ROLLOUT_FROM_INITIAL = 1
 ROLLOUT_DRAW_PER_PLY = 4   # Connect: this rollout call draws under the strict contract
 RNG_PER_BLOCK, RNG_PER_PLY = 0, 1   # bgs_set_rng_contract
 ENV_AUTO_RESET = 1
+POLICY_UNIFORM, POLICY_DECISIVE = 0, 1   # bgs_connect_evaluate_actions_policy
 
 GAME_CONNECT = 1
 GAME_BOUNCE = 2
@@ -74,6 +75,9 @@ SIGNATURES = {
     "bgs_rollout": (ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32]),
     "bgs_connect_evaluate_actions": (
         ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int]
+    ),
+    "bgs_connect_evaluate_actions_policy": (
+        ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     ),
     "bgs_connect_solve_actions": (
         ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]

@@ -183,6 +183,26 @@ BGS_API int bgs_rollout(bgs_batch* b, uint64_t seed, int32_t max_plies, uint32_t
  * first_game * width * playouts over the boards replicated width * playouts times and stepped by their column. */
 BGS_API int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies,
                                          int32_t* counts, int counts_on_device);
+/* bgs_connect_evaluate_actions with a playout policy.  Game ids, the first column, the cap, the bgs_steps accounting,
+ * the counts layout and the refusals are those of bgs_connect_evaluate_actions; the batch is not modified.
+ *   BGS_POLICY_UNIFORM   bgs_connect_evaluate_actions itself: the same launch, byte-identical counts and steps.
+ *   BGS_POLICY_DECISIVE  decisive and anti-decisive moves.  The policy is defined by the build, as the RNG contract is.
+ *                        At every ply of a playout after its forced first column:
+ *                          1. L = the legal columns, ascending;
+ *                          2. W = the columns of L whose landing cell completes `count` in a row for the side to move;
+ *                          3. B = the columns of L whose landing cell would complete `count` in a row for the opponent,
+ *                             if the opponent dropped there now;
+ *                          4. the candidate list S = W if W is not empty, else B if B is not empty, else L;
+ *                          5. the ply draws exactly the word it draws under BGS_POLICY_UNIFORM: the batch's contract
+ *                             (per-block sub-draw or per-ply), keyed by (seed, G, absolute ply);
+ *                          6. it plays element (draw * |S|) >> 32 of S.
+ *                        No ply draws an extra or a different word: only the list the index is taken from changes.
+ * Refused (BGS_ERR_ARG, with a message that says why): an unknown policy, a Bounce batch, a generic batch, and what
+ * bgs_connect_evaluate_actions refuses. */
+#define BGS_POLICY_UNIFORM 0
+#define BGS_POLICY_DECISIVE 1
+BGS_API int bgs_connect_evaluate_actions_policy(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy,
+                                                int32_t* counts, int counts_on_device);
 /* Flat Monte-Carlo evaluation of every legal move of every board (Bounce, bit-packed boards only: at most 64 cells,
  * piece values <= 15).  counts int32[n][width][height * width][3]: entry [i][x][c] = (wins, draws, losses) of the
  * player to move at board i over `playouts` games that start with the move of the piece in column x of the active row
