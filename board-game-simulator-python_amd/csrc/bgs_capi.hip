@@ -1047,6 +1047,48 @@ int bgs_connect_evaluate_actions_policy(bgs_batch* b, uint64_t seed, int32_t pla
     return connect_evaluate_actions(b, seed, playouts, max_plies, policy, counts, counts_on_device);
 }
 
+int bgs_connect_evaluate_actions_halving(bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* counts,
+                                         int32_t* given, int32_t* best, int on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(counts != nullptr, "counts is NULL");
+    NEED(b->game == BGS_GAME_CONNECT, "evaluate_actions_halving: Connect batches only");
+    NEED(!b->generic, "evaluate_actions_halving: bit-packed Connect boards only (up to %d bits a plane); %dx%d boards are generic",
+         64 * BGS_CONNECT_MAX_WORDS, b->cg.h, b->cg.w);
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "evaluate_actions_halving: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    NEED(budget >= bgs::connect_halving_min_budget(b->cg.w),
+         "budget must be >= width * max(1, ceil(log2 width)) = %d, the least that gives every round a playout a column (got %d)",
+         bgs::connect_halving_min_budget(b->cg.w), budget);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    NEED(b->n <= INT64_MAX / b->cg.w / budget, "n * width * budget overflows int64 (%lld x %d x %d)", (long long)b->n, b->cg.w, budget);
+    const size_t cells = (size_t)b->n * b->cg.w;
+    if (on_device) {
+        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(given) & 15u) == 0, "device given must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
+        bgs::connect_evaluate_halving(b, seed, budget, max_plies, policy, counts, given, best);
+        return finish_launch();
+    }
+    // one device buffer: counts, given, best -- each 16-byte aligned
+    const size_t counts_bytes = cells * 3 * sizeof(int32_t), given_bytes = cells * sizeof(int32_t), best_bytes = (size_t)b->n * sizeof(int32_t);
+    const size_t given_off = (counts_bytes + 15) & ~(size_t)15, best_off = given_off + ((given_bytes + 15) & ~(size_t)15);
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), best_off + best_bytes, b->stream));
+    bgs::connect_evaluate_halving(b, seed, budget, max_plies, policy, reinterpret_cast<int32_t*>(d),
+                                  given ? reinterpret_cast<int32_t*>(d + given_off) : nullptr,
+                                  best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr);
+    rc = finish_launch();
+    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
+    if (rc == BGS_OK && given) rc = copy_to_host(b, given, d + given_off, given_bytes);
+    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, best_bytes);
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
 int bgs_connect_solve_actions(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
                               int on_device) {
     int rc = enter(b);

@@ -129,6 +129,12 @@ void connect_pack(const bgs_batch* b, const int8_t* d_grid, const int8_t* d_play
 // ---- flat Monte-Carlo evaluation of packed Connect boards (evaluate_kernels.hip): counts int32[n][w][3] on the device,
 // 16-byte aligned; enqueued on the batch's stream ----
 void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts, int policy);
+// sequential halving over the columns of packed Connect boards (bgs_connect_evaluate_actions_halving): counts
+// int32[n][w][3], given int32[n][w] and best int32[n] (the last two may be NULL) on the device; every entry is written;
+// budget >= connect_halving_min_budget(w) = w * max(1, ceil(log2 w)); enqueued on the batch's stream
+int32_t connect_halving_min_budget(int width);
+void connect_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* d_counts,
+                              int32_t* d_given, int32_t* d_best);
 // exact alpha-beta solve of every column of packed Connect boards (bgs_connect_solve_actions): codes int8[n][w], plies
 // int16[n][w] (may be NULL), *d_nodes = positions visited; device pointers, enqueued on the batch's stream
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,

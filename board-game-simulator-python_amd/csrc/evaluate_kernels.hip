@@ -331,6 +331,223 @@ void launch_evaluate(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint3
 }
 
 // ================================================================================================================
+// Sequential halving (bgs_connect_evaluate_actions_halving, include/bgs.h): a budget of playouts a root, spent in
+// R = max(1, ceil(log2 A)) rounds over the A legal columns; after every round the worse half of the columns leaves.
+//
+// Shape.  One team of lanes -- a workgroup of one wave (64 lanes) or of four (256), the launcher's choice by the
+// playouts of a round -- owns one root for the whole launch.  Lane c < W builds the board after column c and its status
+// once, into LDS.  A round's items are |S_r| * q_r playouts in (column ascending, p) order: the waves of the team draw
+// them from a counter in LDS and refill their idle lanes at 4-ply block boundaries (the refill loop and the block of
+// k_connect_evaluate), so the result does not depend on the team's size.  A finished playout goes into the LDS tally
+// [16][3] by one LDS atomic.  A barrier ends the round; lane c of every wave then ranks column c among the survivors
+// (the count of survivors that beat it on (score descending, column ascending): no sort), the wave's ballot of "rank
+// below ceil(|S_r| / 2)" is the next survivor mask, and a second barrier keeps the next round's tally updates behind
+// every wave's selection.  Global memory is touched for the root, the three outputs and the step counter only.
+//
+// Known limit: a root has one team, so a launch of few roots and a large budget leaves most of the CUs idle.
+// ================================================================================================================
+constexpr uint32_t kHalvingMaxCols = 16;          // the widest packed board (the survivor mask is 16 bits)
+constexpr uint32_t kHalvingWaveItems = 512;       // playouts of a round up to which the team is one wave (8 a lane)
+
+// R(x) = max(1, ceil(log2 x))
+__host__ __device__ __forceinline__ uint32_t halving_rounds(uint32_t x) {
+    uint32_t r = 1;
+    while ((1u << r) < x) ++r;
+    return r;
+}
+
+template <int NW, bool PER_PLY, int POLICY>
+__global__ void __launch_bounds__(BGS_BLOCK)
+k_connect_evaluate_halving(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n,
+                           uint64_t seed, uint64_t game_base, uint32_t budget, uint32_t max_plies, int64_t root_base,
+                           int32_t* __restrict__ counts, int32_t* __restrict__ given, int32_t* __restrict__ best,
+                           unsigned long long* __restrict__ steps) {
+    __shared__ uint64_t child_lds[kHalvingMaxCols][2 * NW];   // the board after column c
+    __shared__ uint32_t child_st[kHalvingMaxCols];            // its status (0 running, 1 / 2 winner, 3 draw) or kIllegal
+    __shared__ uint32_t tally[kHalvingMaxCols * 3];           // cumulative W/D/L of column c
+    __shared__ uint32_t next_item;                            // the round's next playout
+    const uint32_t lane = threadIdx.x & (BGS_WAVE - 1);
+    const uint32_t width = (uint32_t)g.w();
+    const uint32_t stride = (uint32_t)g.h() + 1u;
+    const int64_t i = root_base + (int64_t)blockIdx.x;        // (the grid holds exactly the roots of this launch)
+
+    // ---- the root, once: every lane takes its ply count, lane c builds the board after column c
+    if (threadIdx.x < kHalvingMaxCols * 3) tally[threadIdx.x] = 0;
+    if (threadIdx.x == 0) next_item = 0;
+    Bits<NW> r0, r1;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        r0.w[j] = planes[(int64_t)j * n + i];
+        r1.w[j] = planes[(int64_t)(NW + j) * n + i];
+    }
+    const uint32_t rply = popcount(r0) + popcount(r1);
+    const uint32_t root_mover = rply & 1u, child_ply = rply + 1u;
+    if (threadIdx.x < width) {
+        const uint32_t col = threadIdx.x;
+        const uint32_t height = (uint32_t)__popcll(shr(r0 | r1, (int)(col * stride)).w[0] & ((1ull << g.h()) - 1ull));
+        uint32_t cst = kIllegal;
+        if (status[i] == BGS_ST_RUNNING && height < (uint32_t)g.h()) {
+            Bits<NW>& mine = root_mover ? r1 : r0;
+            const bool won = drop_and_test(g, mine, col * stride + height, ~0u);
+            cst = won ? root_mover + 1u : (child_ply == g.cells_total ? BGS_ST_DRAW : BGS_ST_RUNNING);
+        }
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            child_lds[col][j] = r0.w[j];
+            child_lds[col][NW + j] = r1.w[j];
+        }
+        child_st[col] = cst;
+    }
+    __syncthreads();
+    uint32_t alive = 0;             // (team-uniform) the survivors S_r, bit c = column c
+    for (uint32_t c = 0; c < width; ++c) alive |= (child_st[c] != kIllegal ? 1u : 0u) << c;
+    alive = (uint32_t)__builtin_amdgcn_readfirstlane((int)alive);
+    const uint32_t rounds = alive ? halving_rounds((uint32_t)__popc(alive)) : 0u;
+
+    Bits<NW> p[2];                  // the lane's game: stones of player 0 / player 1
+#pragma unroll
+    for (int j = 0; j < NW; ++j) p[0].w[j] = p[1].w[j] = 0;
+    uint64_t game = 0;
+    uint32_t blk = 0, skip = 0, live = 0, st = 0, fresh = 0, cur_col = 0, stepped = 0;
+    uint32_t first_p = 0;           // (team-uniform) P_r
+    uint32_t my_given = 0;          // lane c of the team's first wave: playouts column c has been given
+    Philox4 ph;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ph.v[j] = 0;
+
+    auto count = [&](uint32_t col, uint32_t s) {   // s: status of a finished game (0: capped, counted nowhere)
+        if (s != 0u) atomicAdd(tally + col * 3u + (s == BGS_ST_DRAW ? 1u : (s - 1u == root_mover ? 0u : 2u)), 1u);
+    };
+
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint32_t m = (uint32_t)__popc(alive);
+        const uint32_t q = budget / (m * rounds);
+        const uint32_t total = m * q;
+        bool dry = false;           // (wave-uniform) the round's counter has nothing left for this wave
+        while (!dry || __builtin_amdgcn_ballot_w64(live != 0)) {
+            // ---- refill: the wave's idle lanes take the round's next playouts.  A playout whose game is decided by the
+            // first move (or capped at once) is counted here and its lane takes another one in the same pass.
+            for (;;) {
+                const uint64_t need = __builtin_amdgcn_ballot_w64(live == 0);
+                if (need == 0 || dry) break;
+                const uint32_t wanted = (uint32_t)__popcll(need);
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(&next_item, wanted);
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                if (base + wanted >= total) dry = true;
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                if (live == 0 && base + rank < total) {
+                    const uint32_t item = base + rank;
+                    const uint32_t k = item / q;
+                    const uint32_t po = first_p + (item - k * q);
+                    const uint32_t col = select_bit64((uint64_t)alive, k);   // the k-th survivor, ascending
+                    const uint32_t cst = child_st[col];
+                    stepped += 1u;   // the first move: a transition of the replicated board
+                    if (cst != BGS_ST_RUNNING) {
+                        count(col, cst);
+                    } else if (child_ply < max_plies) {
+#pragma unroll
+                        for (int j = 0; j < NW; ++j) {
+                            p[0].w[j] = child_lds[col][j];
+                            p[1].w[j] = child_lds[col][NW + j];
+                        }
+                        game = game_base + (uint64_t)((i * (int64_t)width + col) * (int64_t)budget + po);
+                        blk = child_ply >> 2;
+                        skip = child_ply & 3u;
+                        live = ~0u;
+                        fresh = 1u;
+                        st = 0;
+                        cur_col = col;
+                    }
+                }
+            }
+            if (!__builtin_amdgcn_ballot_w64(live != 0)) continue;
+
+            // ---- the 4-ply block of k_connect_evaluate: the same draws, the same ply code
+            if (PER_PLY) {
+                ph = philox4x32_10(seed, game, blk);
+            } else {
+                const bool want = live && (fresh || (blk & 3u) == 0u);
+                if (__builtin_amdgcn_ballot_w64(want)) {
+                    if (want) ph = philox4x32_10(seed, game, blk >> 2);
+                }
+            }
+            fresh = 0;
+            const uint32_t word = PER_PLY ? 0u : philox_word(ph, blk);
+            const uint32_t was_live = live;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t draw = PER_PLY ? ph.v[j] : sub_draw(word, j);
+                const uint32_t act = j >= skip ? live : 0u;
+                const uint32_t ply = 4u * blk + j;          // stones before this sub-step; its mover is player j & 1
+                bool won;
+                if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                    const uint32_t pos = decisive_position(g, p[j & 1u], p[(j & 1u) ^ 1u], draw, won);
+                    drop(p[j & 1u], pos, act);
+                    won = won && act;
+                } else {
+                    const uint32_t pos = draw_position(g, p[0] | p[1], draw);
+                    won = drop_and_test(g, p[j & 1u], pos, act);
+                }
+                const bool full = ply + 1u == g.cells_total;
+                if (act) {
+                    st = won ? (j & 1u) + 1u : (full ? BGS_ST_DRAW : BGS_ST_RUNNING);
+                    live = (won || full || ply + 1u >= max_plies) ? 0u : live;
+                    stepped += 1u;
+                }
+            }
+            blk += 1u;
+            skip = 0;
+            if (was_live && !live) count(cur_col, st);
+        }
+        __syncthreads();   // the round's tally is complete
+
+        // ---- selection: lane c ranks column c among the survivors
+        bool keep = false;
+        if (lane < width && ((alive >> lane) & 1u)) {
+            const uint32_t mine = 2u * tally[lane * 3u] + tally[lane * 3u + 1u];
+            uint32_t rank = 0;
+            for (uint32_t c = 0; c < width; ++c) {
+                const uint32_t other = 2u * tally[c * 3u] + tally[c * 3u + 1u];
+                rank += (((alive >> c) & 1u) && (other > mine || (other == mine && c < lane))) ? 1u : 0u;
+            }
+            keep = rank < (m + 1u) / 2u;
+            my_given += q;
+        }
+        alive = (uint32_t)__builtin_amdgcn_ballot_w64(keep) & 0xFFFFu;
+        first_p += q;
+        if (threadIdx.x == 0) next_item = 0;
+        __syncthreads();   // every wave has read the tally; the counter is back at 0
+    }
+
+    // ---- the outputs of the root (the tally of an illegal column and of an ended board is zero)
+    if (threadIdx.x < width) {
+        const uint32_t c = threadIdx.x;
+#pragma unroll
+        for (uint32_t k = 0; k < 3; ++k) counts[(i * (int64_t)width + c) * 3 + k] = (int32_t)tally[c * 3u + k];
+        if (given) given[i * (int64_t)width + c] = (int32_t)my_given;
+    }
+    if (threadIdx.x == 0 && best) best[i] = rounds ? (int32_t)__builtin_ctz(alive) : -1;
+    add_steps(steps, stepped);
+}
+
+template <int NW, bool PER_PLY, int POLICY>
+void launch_evaluate_halving(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t budget, uint32_t max_plies,
+                             int32_t* d_counts, int32_t* d_given, int32_t* d_best) {
+    // the team: by the playouts of a round of a root with every column legal (about budget / R, whatever the round)
+    const uint32_t team = budget / halving_rounds((uint32_t)g.w()) <= kHalvingWaveItems ? BGS_WAVE : BGS_BLOCK;
+    // game ids: ((first_game + i) * W + c) * B + p = first_game * W * B + (i * W + c) * B + p, mod 2^64
+    const uint64_t game_base = b->first_game * (uint64_t)g.w() * (uint64_t)budget;
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL((k_connect_evaluate_halving<NW, PER_PLY, POLICY>), dim3((uint32_t)blocks), dim3(team), 0, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, seed, game_base, budget, max_plies, i0,
+                           d_counts, d_given, d_best, b->d_steps);
+    }
+}
+
+// ================================================================================================================
 // Bounce (bgs_bounce_evaluate_moves): for root i and slot s = x * H * W + c -- the move of the piece in column x of the
 // active row to cell c, bit c of the root's targets[x] -- `playouts` games that start with that move and continue by the
 // uniform random policy, reduced to (wins, draws, losses) of the player to move at root i.  Playout p of slot s of root i
@@ -1380,6 +1597,33 @@ void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32
         case 1: per_ply ? launch_evaluate<1, true>(b, g, seed, p, cap, d_counts) : launch_evaluate<1, false>(b, g, seed, p, cap, d_counts); break;
         case 2: per_ply ? launch_evaluate<2, true>(b, g, seed, p, cap, d_counts) : launch_evaluate<2, false>(b, g, seed, p, cap, d_counts); break;
         default: per_ply ? launch_evaluate<3, true>(b, g, seed, p, cap, d_counts) : launch_evaluate<3, false>(b, g, seed, p, cap, d_counts); break;
+    }
+}
+
+int32_t connect_halving_min_budget(int width) { return (int32_t)((uint32_t)width * halving_rounds((uint32_t)width)); }
+
+template <int NW>
+static void evaluate_halving_nw(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t budget, uint32_t cap, int policy,
+                                int32_t* d_counts, int32_t* d_given, int32_t* d_best) {
+    constexpr int U = BGS_POLICY_UNIFORM, D = BGS_POLICY_DECISIVE;
+    const bool per_ply = b->rng_per_ply != 0;
+    if (policy == D) {
+        per_ply ? launch_evaluate_halving<NW, true, D>(b, g, seed, budget, cap, d_counts, d_given, d_best)
+                : launch_evaluate_halving<NW, false, D>(b, g, seed, budget, cap, d_counts, d_given, d_best);
+    } else {
+        per_ply ? launch_evaluate_halving<NW, true, U>(b, g, seed, budget, cap, d_counts, d_given, d_best)
+                : launch_evaluate_halving<NW, false, U>(b, g, seed, budget, cap, d_counts, d_given, d_best);
+    }
+}
+
+void connect_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* d_counts,
+                              int32_t* d_given, int32_t* d_best) {
+    const EvalGeom g = eval_geom(b);
+    const uint32_t p = (uint32_t)budget, cap = (uint32_t)max_plies;
+    switch (b->cg.nw) {
+        case 1: evaluate_halving_nw<1>(b, g, seed, p, cap, policy, d_counts, d_given, d_best); break;
+        case 2: evaluate_halving_nw<2>(b, g, seed, p, cap, policy, d_counts, d_given, d_best); break;
+        default: evaluate_halving_nw<3>(b, g, seed, p, cap, policy, d_counts, d_given, d_best); break;
     }
 }
 

@@ -41,11 +41,24 @@ class MonteCarloAgent:
     ``policy`` is the playout policy of Connect states: "uniform", or "decisive" (a playout takes a winning column, else
     blocks the opponent's, else plays uniformly: ``ConnectBatch.evaluate_actions(policy=...)``).  Bounce has the uniform
     policy alone: a Bounce state with any other policy raises ValueError.
+
+    ``allocation`` says how a Connect position's playouts are spread over its columns.  "flat": ``playouts`` a column.
+    "halving": sequential halving (``ConnectBatch.evaluate_actions_halving``) with ``budget`` playouts a position,
+    ``playouts * width`` unless ``budget`` is given -- the same total, moved round by round to the columns still in
+    doubt; a column's value is ``(wins + draws / 2) / given`` over the playouts it was given.  Bounce has the flat
+    allocation alone: a Bounce state with ``allocation="halving"`` raises ValueError.
+
+    ``choose(state)`` / ``choose_many(states)`` return the action to play: flat, the best-valued action (the first in
+    ``state.actions`` order on ties); halving, the last surviving column.
     """
 
     def __init__(self, playouts: int = 256, seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None,
-                 policy: str = "uniform"):
+                 policy: str = "uniform", allocation: str = "flat", budget: Optional[int] = None):
         playout_policy(policy)
+        if allocation not in ("flat", "halving"):
+            raise ValueError(f"unknown allocation {allocation!r}: 'flat' or 'halving'")
+        if budget is not None and (allocation != "halving" or budget < 1):
+            raise ValueError("budget: a positive number of playouts a position, with allocation='halving' only")
         if playouts < 1:
             raise ValueError("playouts must be >= 1")
         if max_plies is not None and max_plies < 1:
@@ -55,6 +68,8 @@ class MonteCarloAgent:
         self.device = int(device)
         self.max_plies = None if max_plies is None else int(max_plies)
         self.policy = policy
+        self.allocation = allocation
+        self.budget = None if budget is None else int(budget)
         self._batches: Dict[tuple, Union[ConnectBatch, BounceBatch]] = {}
 
     def _batch(self, config: connect.Config, n: int) -> ConnectBatch:
@@ -78,12 +93,27 @@ class MonteCarloAgent:
         """float64[n, width] for the boards of `batch`: (wins + draws / 2) / playouts of every column for the player to
         move, NaN where the column is illegal or the board has ended.  Sets the batch's first_game to `first_game`; the
         boards are not modified."""
+        if self.allocation == "halving":
+            return self.halving_values(batch, first_game)[0]
         batch.set_first_game(first_game)
         cap = 2**31 - 1 if self.max_plies is None else self.max_plies
         counts = batch.evaluate_actions(seed=self.seed, playouts=self.playouts, max_plies=cap, policy=self.policy).astype(np.float64)
         v = (counts[..., 0] + 0.5 * counts[..., 1]) / self.playouts
         v[batch.legal == 0] = np.nan
         return v
+
+    def halving_values(self, batch: ConnectBatch, first_game: int = 0):
+        """(float64[n, width], int32[n]) for the boards of `batch` under sequential halving: (wins + draws / 2) / given of
+        every column (NaN where the column is illegal or the board has ended; a legal column is never given zero
+        playouts) and the last surviving column (-1: an ended board).  Sets the batch's first_game to `first_game`."""
+        batch.set_first_game(first_game)
+        cap = 2**31 - 1 if self.max_plies is None else self.max_plies
+        budget = self.playouts * batch.width if self.budget is None else self.budget
+        counts, given, best = batch.evaluate_actions_halving(seed=self.seed, budget=budget, max_plies=cap, policy=self.policy)
+        v = np.full(given.shape, np.nan)
+        played = given > 0
+        v[played] = (counts[..., 0][played] + 0.5 * counts[..., 1][played]) / given[played]
+        return v, best
 
     def bounce_values(self, batch: BounceBatch, first_game: int = 0) -> np.ndarray:
         """float64[n, width, height * width] for the boards of a BounceBatch: (wins + draws / 2) / playouts of the move of
@@ -107,20 +137,30 @@ class MonteCarloAgent:
         if any(type(s) is not type(states[0]) or s.config != config for s in states):
             raise ValueError("predict_many: the states must share one Config")
         if isinstance(states[0], bounce.State):
-            if self.policy != "uniform":
-                raise ValueError(f"MonteCarloAgent: Bounce playouts are uniform, there is no {self.policy!r} policy for Bounce states")
+            self._check_bounce()
             return self._predict_bounce(states, first_game)
+        b = self._load_connect(states)
+        v = self.values(b, first_game)
+        return [{a: float(v[k, a.column]) for a in s.actions} for k, s in enumerate(states)]
+
+    def _check_bounce(self) -> None:
+        if self.policy != "uniform":
+            raise ValueError(f"MonteCarloAgent: Bounce playouts are uniform, there is no {self.policy!r} policy for Bounce states")
+        if self.allocation != "flat":
+            raise ValueError("MonteCarloAgent: Bounce moves are evaluated flat, there is no halving allocation for Bounce states")
+
+    def _load_connect(self, states: Sequence) -> ConnectBatch:
+        """the agent's batch of len(states) boards, holding `states`"""
         if not isinstance(states[0], connect.State):
             raise TypeError(f"predict_many: Connect or Bounce states, not {type(states[0]).__name__}")
-        b = self._batch(config, len(states))
+        b = self._batch(states[0].config, len(states))
         grid = np.stack([s.grid for s in states])
         player = np.array([s.player for s in states], dtype=np.int8)
         winner = np.array([-1 if not s.has_ended else int(s.to_json()["winner"]) for s in states], dtype=np.int8)
         status = b.write_state(grid, player, winner)
         if (status != 0).any():
             raise ValueError("predict_many: a state could not be loaded")
-        v = self.values(b, first_game)
-        return [{a: float(v[k, a.column]) for a in s.actions} for k, s in enumerate(states)]
+        return b
 
     def _predict_bounce(self, states: Sequence[bounce.State], first_game: int) -> List[Dict[bounce.Action, float]]:
         b = self._bounce_batch(states[0].config, len(states))
@@ -142,6 +182,26 @@ class MonteCarloAgent:
     def predict(self, state, game: int = 0) -> Dict:
         """{action: value} for every action in ``state.actions`` (the keys are those Action objects)."""
         return self.predict_many([state], first_game=game)[0]
+
+    def choose_many(self, states: Sequence, first_game: int = 0) -> List:
+        """the action to play in every state (None where it has no action): flat, the best-valued action, the first in
+        ``state.actions`` order on ties; halving, the last surviving column of the same launch `predict_many` makes"""
+        if not states:
+            return []
+        if self.allocation == "halving" and not isinstance(states[0], bounce.State):
+            config = states[0].config
+            if any(type(s) is not type(states[0]) or s.config != config for s in states):
+                raise ValueError("choose_many: the states must share one Config")
+            best = self.halving_values(self._load_connect(states), first_game)[1]
+            return [s.action_at(int(c)) if c >= 0 else None for s, c in zip(states, best)]
+        out = []
+        for s, values in zip(states, self.predict_many(states, first_game)):
+            out.append(max(s.actions, key=values.get) if s.actions else None)   # (max keeps the first of equal values)
+        return out
+
+    def choose(self, state, game: int = 0):
+        """`choose_many` of one state"""
+        return self.choose_many([state], first_game=game)[0]
 
     def close(self) -> None:
         for b in self._batches.values():

@@ -837,6 +837,50 @@ class ConnectBatch(_Batch):
         self._evaluate(seed, playouts, max_plies, policy, out.data_ptr(), 1)
         return out
 
+    def halving_min_budget(self) -> int:
+        """the least budget of `evaluate_actions_halving`: width * max(1, ceil(log2 width)), a playout a column a round"""
+        return self.width * max(1, (self.width - 1).bit_length())
+
+    def evaluate_actions_halving(self, seed: int = DEFAULT_SEED, budget: int = 1024, max_plies: int = 2**31 - 1,
+                                 policy: str = "uniform"):
+        """Sequential-halving Monte-Carlo evaluation of every board (bgs_connect_evaluate_actions_halving), one launch:
+        (counts int32[n, width, 3], given int32[n, width], best int32[n]).  `budget` playouts a board are spent in
+        R = max(1, ceil(log2 A)) rounds over its A legal columns: in round r every surviving column plays
+        floor(budget / (survivors * R)) further playouts, then the better half (rounded up) survives, ranked by
+        2 * wins + draws over all rounds so far, ties to the lower column.  `best` is the last survivor (-1 for an ended
+        board), `given` the playouts a column was given, `counts` its cumulative (wins, draws, losses) for the player to
+        move.  Playout p of column c of board i is game ((first_game + i) * width + c) * budget + p, played as
+        `evaluate_actions(playouts=budget, policy=policy)` plays it: a column's counts are those of its first `given`
+        playouts there.  The boards are not modified."""
+        code = playout_policy(policy)
+        counts = np.empty((self.n, self.width, 3), dtype=np.int32)
+        given = np.empty((self.n, self.width), dtype=np.int32)
+        best = np.empty(self.n, dtype=np.int32)
+        _abi.check(_abi.lib().bgs_connect_evaluate_actions_halving(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
+            ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(given.ctypes.data), ctypes.c_void_p(best.ctypes.data), 0))
+        return counts, given, best
+
+    def evaluate_actions_halving_tensor(self, counts=None, given=None, best=None, seed: int = DEFAULT_SEED, budget: int = 1024,
+                                        max_plies: int = 2**31 - 1, policy: str = "uniform"):
+        """`evaluate_actions_halving` into device tensors int32[n, width, 3], int32[n, width] and int32[n] (allocated when
+        None), enqueued on the batch's stream with no synchronisation: (counts, given, best).  Every entry is written."""
+        code = playout_policy(policy)
+        t = self._need_torch("evaluate_actions_halving_tensor")
+        shapes = {"counts": (self.n, self.width, 3), "given": (self.n, self.width), "best": (self.n,)}
+        outs = {"counts": counts, "given": given, "best": best}
+        for name, shape in shapes.items():
+            x = outs[name]
+            if x is None:
+                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
+            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        _abi.check(_abi.lib().bgs_connect_evaluate_actions_halving(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
+            ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["given"].data_ptr()),
+            ctypes.c_void_p(outs["best"].data_ptr()), 1))
+        return outs["counts"], outs["given"], outs["best"]
+
     def solve_actions(self, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """Exact solve of every column of every board (bgs_connect_solve_actions), one launch: (codes int8[n, width],
         plies int16[n, width] or None).  Seen from the player to move; lines of at most `depth` plies from the board,
@@ -961,6 +1005,12 @@ class BounceBatch(_Batch):
         raise ValueError("evaluate_actions: Connect batches only (Bounce boards: evaluate_moves)")
 
     evaluate_actions_tensor = evaluate_actions
+
+    def evaluate_actions_halving(self, *args, **kwargs):
+        """Not available for Bounce: sequential halving covers bit-packed Connect boards; Bounce has `evaluate_moves`."""
+        raise ValueError("evaluate_actions_halving: Connect batches only (Bounce boards: evaluate_moves)")
+
+    evaluate_actions_halving_tensor = evaluate_actions_halving
 
     def solve_actions(self, *args, **kwargs):
         """Not available for Bounce: the exact solver covers bit-packed Connect boards (Bounce games can cycle)."""

@@ -79,6 +79,11 @@ SIGNATURES = {
     "bgs_connect_evaluate_actions_policy": (
         ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     ),
+    "bgs_connect_evaluate_actions_halving": (
+        ctypes.c_int,
+        [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_int],
+    ),
     "bgs_connect_solve_actions": (
         ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
     ),

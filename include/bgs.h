@@ -203,6 +203,29 @@ BGS_API int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t pl
 #define BGS_POLICY_DECISIVE 1
 BGS_API int bgs_connect_evaluate_actions_policy(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy,
                                                 int32_t* counts, int counts_on_device);
+/* Sequential-halving Monte-Carlo evaluation of every board (Karnin, Koren and Somekh 2013; Connect, bit-packed boards
+ * only), one launch: a fixed `budget` of playouts a board is spent in rounds, and the worse half of the columns leaves
+ * after every round.  For a running board i with A legal columns, R(x) = max(1, ceil(log2 x)):
+ *   start      S_0 = the legal columns, R = R(A), P_0 = 0;
+ *   round r    (r = 0 .. R-1) every column of S_r plays q_r = floor(budget / (|S_r| * R)) further playouts, those with
+ *              the playout indices [P_r, P_r + q_r); P_{r+1} = P_r + q_r;
+ *   selection  a column's score is 2 * wins + draws over all rounds so far (a capped playout scores 0); S_{r+1} = the
+ *              ceil(|S_r| / 2) columns of S_r ranked highest, by score descending, then by column ascending.
+ * best int32[n] = the one column of S_R; given int32[n][width] = the playouts a column was given; counts
+ * int32[n][width][3] = its cumulative (wins, draws, losses) for the player to move at board i.  Illegal columns: all
+ * zeros.  An ended board: all zeros and best = -1.
+ * Playout p of column c of board i is the game G = ((first_game + i) * width + c) * budget + p (mod 2^64), played exactly
+ * as bgs_connect_evaluate_actions_policy plays it (forced first column, policy, the batch's RNG contract keyed by the
+ * absolute ply, the cap): a column's counts are those of the first given[i][c] playouts of the flat evaluation with
+ * playouts = budget, so sharding by first_game holds.  The q_r of a board sum to at most `budget`.
+ * The transitions of the playouts played are added to bgs_steps, first moves included; the boards are not modified.
+ * given and best may be NULL.  on_device != 0: device pointers (16-byte aligned), enqueued on the batch's stream, no
+ * synchronisation, no allocation; otherwise host buffers, filled when the call returns.
+ * Refused (BGS_ERR_ARG, with a message that says why): budget < width * R(width) (the least budget that keeps every
+ * q_r >= 1), max_plies < 1, an unknown policy, a Bounce batch, a generic batch, NULL counts, a misaligned device pointer,
+ * n * width * budget beyond int64. */
+BGS_API int bgs_connect_evaluate_actions_halving(bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy,
+                                                 int32_t* counts, int32_t* given, int32_t* best, int on_device);
 /* Flat Monte-Carlo evaluation of every legal move of every board (Bounce, bit-packed boards only: at most 64 cells,
  * piece values <= 15).  counts int32[n][width][height * width][3]: entry [i][x][c] = (wins, draws, losses) of the
  * player to move at board i over `playouts` games that start with the move of the piece in column x of the active row
