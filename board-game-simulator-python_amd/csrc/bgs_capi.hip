@@ -1127,10 +1127,9 @@ int bgs_connect_solve_actions(bgs_batch* b, int32_t depth, int64_t max_nodes, in
     return BGS_OK;
 }
 
-int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
-                              int counts_on_device) {
-    int rc = enter(b);
-    if (rc) return rc;
+// bgs_bounce_evaluate_moves and bgs_bounce_evaluate_moves_policy behind their entry checks (enter(b), the policy's range)
+static int bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy, int32_t* counts,
+                                 int counts_on_device) {
     NEED(counts != nullptr, "counts is NULL");
     NEED(b->game == BGS_GAME_BOUNCE, "evaluate_moves: Bounce batches only (Connect boards: bgs_connect_evaluate_actions)");
     NEED(!b->generic, "evaluate_moves: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
@@ -1148,18 +1147,35 @@ int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int
     NEED(d_ends && d_totals, "staging region too small");
     const size_t bytes = (size_t)b->n * (size_t)slots * 3 * sizeof(int32_t);
     if (counts_on_device) {
-        bgs::bounce_evaluate(b, seed, playouts, max_plies, counts, d_ends, d_totals);
+        bgs::bounce_evaluate(b, seed, playouts, max_plies, counts, d_ends, d_totals, policy);
         return finish_launch();
     }
     int32_t* d = nullptr;
     HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
-    bgs::bounce_evaluate(b, seed, playouts, max_plies, d, d_ends, d_totals);
-    rc = finish_launch();
+    bgs::bounce_evaluate(b, seed, playouts, max_plies, d, d_ends, d_totals, policy);
+    int rc = finish_launch();
     if (rc == BGS_OK) rc = copy_to_host(b, counts, d, bytes);
     const hipError_t e = hipFreeAsync(d, b->stream);
     if (rc) return rc;
     HIP_TRY(e);
     return BGS_OK;
+}
+
+int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
+                              int counts_on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    return bounce_evaluate_moves(b, seed, playouts, max_plies, BGS_POLICY_UNIFORM, counts, counts_on_device);
+}
+
+int bgs_bounce_evaluate_moves_policy(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy, int32_t* counts,
+                                     int counts_on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "evaluate_moves: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    return bounce_evaluate_moves(b, seed, playouts, max_plies, policy, counts, counts_on_device);
 }
 
 int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,

@@ -140,9 +140,10 @@ void connect_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget,
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,
                    unsigned long long* d_nodes);
 // ... of packed Bounce boards: counts int32[n][w][h * w][3] on the device (zeroed and filled here, 16-byte aligned);
-// d_ends uint64[n] and d_totals uint64[(n + 255) / 256] are scratch (the batch's staging region); enqueued on the stream
+// d_ends uint64[n] and d_totals uint64[(n + 255) / 256] are scratch (the batch's staging region); enqueued on the stream;
+// policy: BGS_POLICY_UNIFORM / BGS_POLICY_DECISIVE (checked by the caller)
 void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts, uint64_t* d_ends,
-                     uint64_t* d_totals);
+                     uint64_t* d_totals, int policy);
 // exact horizon search of every legal move of packed Bounce boards (bgs_bounce_solve_moves): codes int8[n][w][h * w] and
 // plies int16[n][w][h * w] (may be NULL) are filled here (illegal slots NONE / 0), *d_nodes = positions visited; scratch
 // as bounce_evaluate; depth 1 .. BGS_BOUNCE_SOLVE_MAX_DEPTH; device pointers, enqueued on the batch's stream

@@ -643,7 +643,25 @@ k_bounce_eval_add_totals(uint64_t* __restrict__ ends, const uint64_t* __restrict
     if (i < n && blockIdx.x) ends[i] += totals[blockIdx.x];
 }
 
-template <class GEO, int NC>
+// BGS_POLICY_DECISIVE for Bounce (include/bgs.h): the candidate list of a ply is W, the actions whose target lies in the
+// mover's goal row, when W is not empty.  Every element of W ends the game for the mover and the outputs are counts and
+// steps alone, so such a ply neither draws nor moves: the lanes that have just searched fold their sources' LDS masks
+// with the goal row into a flag, and a flagged lane's ply is one transition and the mover's win.  Narrower than Connect's
+// policy (no blocking step): the moves that leave the opponent without a win in one need a move search per candidate.
+template <int NC>
+__device__ __forceinline__ bool b_can_win(const FlatMoves<NC>& m, const uint32_t* column, uint64_t goal) {
+    const uint32_t glo = (uint32_t)goal, ghi = (uint32_t)(goal >> 32);
+    uint32_t hit = 0;
+#pragma unroll
+    for (int x = 0; x < 8 * NC; ++x) {   // (a column without targets was not written by this search: its dwords are stale)
+        const uint32_t cnt = (uint32_t)(m.counts[x >> 3] >> (8 * (x & 7))) & 255u;
+        const uint32_t lo = column[(2u * x) * BGS_BLOCK] & glo, hi = column[(2u * x + 1u) * BGS_BLOCK] & ghi;
+        hit |= cnt ? (lo | hi) : 0u;
+    }
+    return hit != 0u;
+}
+
+template <class GEO, int NC, int POLICY = BGS_POLICY_UNIFORM>
 __global__ void __launch_bounds__(BGS_BLOCK)
 k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, const uint16_t* __restrict__ plies_buf,
                   int64_t n, uint64_t seed, uint64_t game_base, uint32_t playouts, uint32_t max_plies, uint32_t slots,
@@ -718,6 +736,8 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
     };
+
+    [[maybe_unused]] bool can_win = false;   // (BGS_POLICY_DECISIVE) the list the lane holds has a target in the mover's goal row
 
     for (;;) {
         // ---- refill: idle lanes take the next playouts of the chunk; a spent chunk is replaced from the queue (the
@@ -812,6 +832,9 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
                 enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
                 if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
             }
+            if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                if (search) can_win = st == BGS_ST_RUNNING && b_can_win<NC>(mv, column, (plies & 1u) ? g.goal_bottom : g.goal_top);
+            }
             search = false;
         }
         const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
@@ -820,7 +843,14 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
             has = false;
         }
         // ---- one ply on every running board
-        if (run) {
+        if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+            if (run && can_win) {   // every candidate ends the game for the mover: one transition, nothing drawn or moved
+                st = (plies & 1u) + 1u;
+                ++plies;
+                stepped += 1u;
+            }
+        }
+        if (POLICY == BGS_POLICY_DECISIVE ? run && !can_win : run) {
             if (!have_block || (plies & 3u) == 0u) {
                 blk = philox4x32_10(seed, game, plies >> 2);
                 have_block = true;
@@ -840,7 +870,7 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
     add_steps(steps, stepped);
 }
 
-template <class GEO, int NC>
+template <class GEO, int NC, int POLICY = BGS_POLICY_UNIFORM>
 void launch_bounce_evaluate(const bgs_batch* b, const GEO& g, uint64_t seed, uint32_t playouts, uint32_t max_plies, int32_t* d_counts,
                             uint64_t* d_ends, uint64_t* d_totals) {
     const uint32_t slots = (uint32_t)(b->bg.w * b->bg.h * b->bg.w);
@@ -862,7 +892,7 @@ void launch_bounce_evaluate(const bgs_batch* b, const GEO& g, uint64_t seed, uin
     const uint64_t game_base = b->first_game * (uint64_t)slots * (uint64_t)playouts;
     const int64_t waves = (int64_t)b->num_cus * 4 * (b->bounce_eval_wps > 0 ? b->bounce_eval_wps : kBounceEvalWps);
     const size_t tile = sizeof(uint32_t) * 2 * 8 * NC * BGS_BLOCK;
-    hipLaunchKernelGGL((k_bounce_evaluate<GEO, NC>), dim3((uint32_t)((waves + kEvalWavesPerBlock - 1) / kEvalWavesPerBlock)), dim3(BGS_BLOCK),
+    hipLaunchKernelGGL((k_bounce_evaluate<GEO, NC, POLICY>), dim3((uint32_t)((waves + kEvalWavesPerBlock - 1) / kEvalWavesPerBlock)), dim3(BGS_BLOCK),
                        tile, b->stream, g, (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, seed,
                        game_base, playouts, max_plies, slots, (const uint64_t*)d_ends, queue, (uint32_t)chunk, d_counts, b->d_steps);
 }
@@ -1558,10 +1588,20 @@ void bounce_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* 
 }
 
 void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts, uint64_t* d_ends,
-                     uint64_t* d_totals) {
+                     uint64_t* d_totals, int policy) {
     uint32_t cap = (uint32_t)max_plies;
     if (cap > kBounceMaxPlies) cap = kBounceMaxPlies;   // plies are stored as uint16
     const uint32_t p = (uint32_t)playouts;
+    if (policy == BGS_POLICY_DECISIVE) {
+        constexpr int D = BGS_POLICY_DECISIVE;
+        if (b->bounce_static_geom && bounce_is_default(b->bg))
+            launch_bounce_evaluate<DefaultBounceGeom, 1, D>(b, DefaultBounceGeom{}, seed, p, cap, d_counts, d_ends, d_totals);
+        else if (b->bg.w <= 8)
+            launch_bounce_evaluate<BounceGeom, 1, D>(b, b->bg, seed, p, cap, d_counts, d_ends, d_totals);
+        else
+            launch_bounce_evaluate<BounceGeom, 3, D>(b, b->bg, seed, p, cap, d_counts, d_ends, d_totals);
+        return;
+    }
     if (b->bounce_static_geom && bounce_is_default(b->bg))
         launch_bounce_evaluate<DefaultBounceGeom, 1>(b, DefaultBounceGeom{}, seed, p, cap, d_counts, d_ends, d_totals);
     else if (b->bg.w <= 8)

@@ -2,7 +2,7 @@
 ``Agent.predict(state) -> dict[Action, float]``.
 
 ``MonteCarloAgent`` is flat Monte-Carlo: every legal action of a position is valued by ``playouts`` random games (uniform,
-or for Connect by the decisive-move playout policy) that start with it, ``(wins + draws / 2) / playouts`` for the player to move.  All actions of all positions are played
+or by the game's decisive-move playout policy) that start with it, ``(wins + draws / 2) / playouts`` for the player to move.  All actions of all positions are played
 and counted in ONE launch: ``ConnectBatch.evaluate_actions`` for Connect states (a column each),
 ``BounceBatch.evaluate_moves`` for Bounce states (a (source, target) move each).
 
@@ -38,9 +38,12 @@ class MonteCarloAgent:
     ``max_plies`` caps every playout at that absolute ply count (a capped playout adds nothing to the value).  None: no
     cap for Connect, whose games end by themselves, and ``BOUNCE_MAX_PLIES`` (1024) for Bounce.
 
-    ``policy`` is the playout policy of Connect states: "uniform", or "decisive" (a playout takes a winning column, else
-    blocks the opponent's, else plays uniformly: ``ConnectBatch.evaluate_actions(policy=...)``).  Bounce has the uniform
-    policy alone: a Bounce state with any other policy raises ValueError.
+    ``policy`` is the playout policy: "uniform", or "decisive".  For Connect states a decisive playout takes a winning
+    column, else blocks the opponent's, else plays uniformly (``ConnectBatch.evaluate_actions(policy=...)``).  For Bounce
+    states it lands in the mover's goal row when it can, else plays uniformly; there is no blocking step
+    (``BounceBatch.evaluate_moves(policy=...)``).  The two games' "decisive" are different policies under one name, so an
+    agent with a policy other than "uniform" stays with the game of the first states it evaluates: a state of the other
+    game raises ValueError (make an agent a game).  A uniform agent takes states of either game, as before.
 
     ``allocation`` says how a Connect position's playouts are spread over its columns.  "flat": ``playouts`` a column.
     "halving": sequential halving (``ConnectBatch.evaluate_actions_halving``) with ``budget`` playouts a position,
@@ -71,6 +74,17 @@ class MonteCarloAgent:
         self.allocation = allocation
         self.budget = None if budget is None else int(budget)
         self._batches: Dict[tuple, Union[ConnectBatch, BounceBatch]] = {}
+        self._policy_game: Optional[str] = None   # the game whose `policy` this agent plays (set by its first states)
+
+    def _bind(self, game: str) -> None:
+        """a policy other than "uniform" is one game's: the first states evaluated say which"""
+        if self.policy == "uniform":
+            return
+        if self._policy_game is None:
+            self._policy_game = game
+        elif self._policy_game != game:
+            raise ValueError(f"MonteCarloAgent: this agent plays {self._policy_game}'s {self.policy!r} playout policy, which is not "
+                             f"{game}'s policy of that name: make an agent of its own for {game} states")
 
     def _batch(self, config: connect.Config, n: int) -> ConnectBatch:
         key = ("connect", config.height, config.width, config.count, n)
@@ -121,7 +135,7 @@ class MonteCarloAgent:
         board has ended.  Sets the batch's first_game to `first_game`; the boards are not modified."""
         batch.set_first_game(first_game)
         cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
-        counts = batch.evaluate_moves(seed=self.seed, playouts=self.playouts, max_plies=cap).astype(np.float64)
+        counts = batch.evaluate_moves(seed=self.seed, playouts=self.playouts, max_plies=cap, policy=self.policy).astype(np.float64)
         v = (counts[..., 0] + 0.5 * counts[..., 1]) / self.playouts
         t = batch.targets[:, : batch.width]
         cells = np.arange(batch.height * batch.width, dtype=np.uint64)
@@ -144,8 +158,6 @@ class MonteCarloAgent:
         return [{a: float(v[k, a.column]) for a in s.actions} for k, s in enumerate(states)]
 
     def _check_bounce(self) -> None:
-        if self.policy != "uniform":
-            raise ValueError(f"MonteCarloAgent: Bounce playouts are uniform, there is no {self.policy!r} policy for Bounce states")
         if self.allocation != "flat":
             raise ValueError("MonteCarloAgent: Bounce moves are evaluated flat, there is no halving allocation for Bounce states")
 
@@ -153,6 +165,7 @@ class MonteCarloAgent:
         """the agent's batch of len(states) boards, holding `states`"""
         if not isinstance(states[0], connect.State):
             raise TypeError(f"predict_many: Connect or Bounce states, not {type(states[0]).__name__}")
+        self._bind("Connect")
         b = self._batch(states[0].config, len(states))
         grid = np.stack([s.grid for s in states])
         player = np.array([s.player for s in states], dtype=np.int8)
@@ -163,6 +176,7 @@ class MonteCarloAgent:
         return b
 
     def _predict_bounce(self, states: Sequence[bounce.State], first_game: int) -> List[Dict[bounce.Action, float]]:
+        self._bind("Bounce")
         b = self._bounce_batch(states[0].config, len(states))
         grid = np.stack([s.grid for s in states])
         player = np.array([s.player for s in states], dtype=np.int8)

@@ -1018,21 +1018,37 @@ class BounceBatch(_Batch):
 
     solve_actions_tensor = solve_actions
 
-    def evaluate_moves(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1) -> np.ndarray:
+    def _evaluate_moves(self, seed: int, playouts: int, max_plies: int, policy: str, pointer: int, on_device: int) -> None:
+        """the evaluation call of `policy`: "uniform" is bgs_bounce_evaluate_moves itself, any other policy goes through
+        bgs_bounce_evaluate_moves_policy"""
+        code = playout_policy(policy)
+        args = (self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts), ctypes.c_int32(max_plies))
+        if code == _abi.POLICY_UNIFORM:
+            _abi.check(_abi.lib().bgs_bounce_evaluate_moves(*args, ctypes.c_void_p(pointer), on_device))
+        else:
+            _abi.check(_abi.lib().bgs_bounce_evaluate_moves_policy(*args, code, ctypes.c_void_p(pointer), on_device))
+
+    def evaluate_moves(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1,
+                       policy: str = "uniform") -> np.ndarray:
         """Flat Monte-Carlo evaluation of every legal move of every board (bgs_bounce_evaluate_moves), one launch:
         int32[n, W, H * W, 3]; entry [i, x, c] = (wins, draws, losses) of the player to move over `playouts` games that
         start with the move of the piece in column x of the active row to cell c = ty * W + tx (bit c of targets[i, x])
         and continue by the uniform random policy until they end or hold `max_plies` plies (clamped to 65535; a capped game
         counts in none of the three).  Illegal slots and ended boards give 0, 0, 0.  The boards are not modified.
-        Playout p of slot s = x * H * W + c of board i is game ((first_game + i) * W * H * W + s) * playouts + p."""
+        Playout p of slot s = x * H * W + c of board i is game ((first_game + i) * W * H * W + s) * playouts + p.
+        policy="decisive" (bgs_bounce_evaluate_moves_policy): the same games and draws, but a ply whose side to move can
+        land in its goal row does so -- the ply's draw indexes the winning moves, else all moves.  There is no blocking
+        step."""
+        playout_policy(policy)   # (an unknown name: before anything is allocated)
         out = np.empty((self.n, self.width, self.height * self.width, 3), dtype=np.int32)
-        _abi.check(_abi.lib().bgs_bounce_evaluate_moves(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
-                                                        ctypes.c_int32(max_plies), ctypes.c_void_p(out.ctypes.data), 0))
+        self._evaluate_moves(seed, playouts, max_plies, policy, out.ctypes.data, 0)
         return out
 
-    def evaluate_moves_tensor(self, out=None, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1):
+    def evaluate_moves_tensor(self, out=None, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1,
+                              policy: str = "uniform"):
         """`evaluate_moves` into a device tensor int32[n, W, H * W, 3] (allocated when None), enqueued on the batch's stream
         with no synchronisation.  Every entry is written."""
+        playout_policy(policy)
         t = self._need_torch("evaluate_moves_tensor")
         shape = (self.n, self.width, self.height * self.width, 3)
         if out is None:
@@ -1040,8 +1056,7 @@ class BounceBatch(_Batch):
         if not (out.is_cuda and out.dtype == t.int32 and tuple(out.shape) == shape and out.is_contiguous()
                 and out.data_ptr() % 16 == 0):
             raise TypeError(f"out must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
-        _abi.check(_abi.lib().bgs_bounce_evaluate_moves(self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts),
-                                                        ctypes.c_int32(max_plies), ctypes.c_void_p(out.data_ptr()), 1))
+        self._evaluate_moves(seed, playouts, max_plies, policy, out.data_ptr(), 1)
         return out
 
     def solve_moves(self, depth: int = DEFAULT_BOUNCE_SOLVE_DEPTH, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):

@@ -26,7 +26,7 @@ ROLLOUT_FROM_INITIAL = 1
 ROLLOUT_DRAW_PER_PLY = 4   # Connect: this rollout call draws under the strict contract
 RNG_PER_BLOCK, RNG_PER_PLY = 0, 1   # bgs_set_rng_contract
 ENV_AUTO_RESET = 1
-POLICY_UNIFORM, POLICY_DECISIVE = 0, 1   # bgs_connect_evaluate_actions_policy
+POLICY_UNIFORM, POLICY_DECISIVE = 0, 1   # bgs_connect_evaluate_actions_policy, bgs_bounce_evaluate_moves_policy
 
 GAME_CONNECT = 1
 GAME_BOUNCE = 2
@@ -89,6 +89,9 @@ SIGNATURES = {
     ),
     "bgs_bounce_evaluate_moves": (
         ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int]
+    ),
+    "bgs_bounce_evaluate_moves_policy": (
+        ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     ),
     "bgs_bounce_solve_moves": (
         ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]

@@ -243,6 +243,33 @@ BGS_API int bgs_connect_evaluate_actions_halving(bgs_batch* b, uint64_t seed, in
  * device pointer, n * S * playouts beyond int64. */
 BGS_API int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
                                       int counts_on_device);
+/* bgs_bounce_evaluate_moves with a playout policy (BGS_POLICY_*, above).  Game ids, slots, the counts layout, the cap
+ * (clamped to 65535), the bgs_steps accounting (first moves included), the device and host variants and the refusals are
+ * those of bgs_bounce_evaluate_moves; the batch is not modified.
+ *   BGS_POLICY_UNIFORM   bgs_bounce_evaluate_moves itself: the same launch, byte-identical counts and steps.
+ *   BGS_POLICY_DECISIVE  a win in one is taken.  The policy is defined by the build, as the RNG contract is.  At every
+ *                        ply of a playout after its forced first move (a ply is played only if the game is running and
+ *                        holds fewer than max_plies plies):
+ *                          1. L = the canonical action list of the side to move: sources by ascending x, targets by
+ *                             ascending (y, x).  An empty L is settled as under the uniform policy, before the policy
+ *                             and also at the cap: the other side wins if it could move, else a draw;
+ *                          2. W = the actions of L whose target lies in the mover's goal row (the top row for player 0,
+ *                             the bottom row for player 1);
+ *                          3. the candidate list S = W if W is not empty, else L;
+ *                          4. the ply draws exactly the word it draws under BGS_POLICY_UNIFORM: philox keyed by
+ *                             (seed, G, absolute ply), a word per ply;
+ *                          5. it plays element (draw * |S|) >> 32 of S, in L's order.
+ *                        No ply draws an extra or a different word.  Every element of W ends the game for the mover, and
+ *                        counts and bgs_steps, the only outputs, do not depend on which one is played: the kernel ends
+ *                        the game at such a ply without picking or moving (one transition, the mover wins).  Step 5
+ *                        stays in the definition so that a later observer of the final board has one answer.
+ *                        There is no blocking step, which makes this policy narrower than Connect's: finding the moves
+ *                        that leave the opponent without a win in one needs a move search per candidate, about 12
+ *                        searches a ply on the default board.
+ * Refused (BGS_ERR_ARG, with a message that says why): an unknown policy, a Connect batch, a generic batch, and what
+ * bgs_bounce_evaluate_moves refuses. */
+BGS_API int bgs_bounce_evaluate_moves_policy(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy,
+                                             int32_t* counts, int counts_on_device);
 /* Exact solve of every column of every board (Connect, bit-packed boards only): a depth-first alpha-beta search a
  * (board, column), no RNG.  Entry [i][c] is seen from the player to move at board i; the lines searched are at most
  * `depth` plies long, column c itself counted (depth >= height * width: a full solve).
