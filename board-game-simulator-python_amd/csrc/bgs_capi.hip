@@ -1178,6 +1178,49 @@ int bgs_bounce_evaluate_moves_policy(bgs_batch* b, uint64_t seed, int32_t playou
     return bounce_evaluate_moves(b, seed, playouts, max_plies, policy, counts, counts_on_device);
 }
 
+int bgs_bounce_evaluate_moves_halving(bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* counts,
+                                      int32_t* given, int32_t* best, int on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(counts != nullptr, "counts is NULL");
+    NEED(b->game == BGS_GAME_BOUNCE, "evaluate_moves_halving: Bounce batches only (Connect boards: bgs_connect_evaluate_actions_halving)");
+    NEED(!b->generic,
+         "evaluate_moves_halving: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
+         BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "evaluate_moves_halving: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    NEED(budget >= 1, "budget must be >= 1 (got %d)", budget);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    const int64_t slots = (int64_t)b->bg.w * b->bg.h * b->bg.w;
+    NEED(b->n <= INT64_MAX / slots / budget, "n * width * height * width * budget overflows int64 (%lld x %lld x %d)", (long long)b->n,
+         (long long)slots, budget);
+    const size_t cells = (size_t)b->n * (size_t)slots;
+    if (on_device) {
+        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(given) & 15u) == 0, "device given must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
+        bgs::bounce_evaluate_halving(b, seed, budget, max_plies, policy, counts, given, best);
+        return finish_launch();
+    }
+    // one device buffer: counts, given, best -- each 16-byte aligned
+    const size_t counts_bytes = cells * 3 * sizeof(int32_t), given_bytes = cells * sizeof(int32_t), best_bytes = (size_t)b->n * sizeof(int32_t);
+    const size_t given_off = (counts_bytes + 15) & ~(size_t)15, best_off = given_off + ((given_bytes + 15) & ~(size_t)15);
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), best_off + best_bytes, b->stream));
+    bgs::bounce_evaluate_halving(b, seed, budget, max_plies, policy, reinterpret_cast<int32_t*>(d),
+                                 given ? reinterpret_cast<int32_t*>(d + given_off) : nullptr,
+                                 best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr);
+    rc = finish_launch();
+    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
+    if (rc == BGS_OK && given) rc = copy_to_host(b, given, d + given_off, given_bytes);
+    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, best_bytes);
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
 int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
                            int on_device) {
     int rc = enter(b);

@@ -144,6 +144,11 @@ void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t*
 // policy: BGS_POLICY_UNIFORM / BGS_POLICY_DECISIVE (checked by the caller)
 void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* d_counts, uint64_t* d_ends,
                      uint64_t* d_totals, int policy);
+// sequential halving over the legal moves of packed Bounce boards (bgs_bounce_evaluate_moves_halving): counts
+// int32[n][w][h * w][3], given int32[n][w][h * w] and best int32[n] (the last two may be NULL) on the device; counts and
+// given are zeroed here, best is written for every board; no scratch; enqueued on the batch's stream
+void bounce_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* d_counts,
+                             int32_t* d_given, int32_t* d_best);
 // exact horizon search of every legal move of packed Bounce boards (bgs_bounce_solve_moves): codes int8[n][w][h * w] and
 // plies int16[n][w][h * w] (may be NULL) are filled here (illegal slots NONE / 0), *d_nodes = positions visited; scratch
 // as bounce_evaluate; depth 1 .. BGS_BOUNCE_SOLVE_MAX_DEPTH; device pointers, enqueued on the batch's stream

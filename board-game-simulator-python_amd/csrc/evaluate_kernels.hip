@@ -897,6 +897,258 @@ void launch_bounce_evaluate(const bgs_batch* b, const GEO& g, uint64_t seed, uin
                        game_base, playouts, max_plies, slots, (const uint64_t*)d_ends, queue, (uint32_t)chunk, d_counts, b->d_steps);
 }
 
+// ================================================================================================================
+// Sequential halving for Bounce (bgs_bounce_evaluate_moves_halving, include/bgs.h): the schedule of
+// k_connect_evaluate_halving with "column" read as "arm", an arm being one of the root's A legal moves in canonical order
+// (sources by ascending x, targets by ascending cell: ascending slot).
+//
+// Shape.  One workgroup of BGS_BLOCK lanes owns one root for the whole launch.  The piece in column x of the active row is
+// searched by lane x (reach), the masks go to LDS, and every lane of the team fills its share of the arm table (source
+// cell, target cell).  The root board stays in registers: a lane that takes a playout applies its arm's move to it.  A
+// round's items are |S_r| * q_r playouts in (arm ascending, p) order; the waves draw them from a counter in LDS and refill
+// their idle lanes at ply boundaries; the ply is k_bounce_evaluate's (the search into the lane's LDS column, the
+// blocked-side settlement, the decisive short-cut, a philox call per four plies).  A finished playout is one LDS atomic
+// into the tally [arm][3], so the result does not depend on which lane played what.  A barrier ends the round.  Selection
+// is by rank: lanes take the survivors tid, tid + BGS_BLOCK, ... and count those that beat each one on (score descending,
+// arm ascending); an arm that leaves -- in the last round every arm -- stores its counts and its playouts.  The kept arms
+// are compacted in order into the other survivor list behind a second barrier, and a third one keeps the next round's
+// tally updates behind the selection.  Global memory: the root, the three outputs (zeroed by the launcher: illegal slots
+// are never stored) and the step counter.
+//
+// The team is always BGS_BLOCK lanes: the move tile's stride is BGS_BLOCK dwords whatever the team (bounce_board.h), so a
+// smaller team would pay the whole tile for a fraction of its lanes.
+//
+// Known limit: a root has one team, so a launch of few roots and a large budget leaves most of the CUs idle.
+// ================================================================================================================
+// The most arms of a packed root.  The sources are the k <= W pieces of one interior row; a target is an empty interior
+// cell or a cell of the mover's goal row: at most (H - 2) * W - k + W of them whatever else the board holds.  So
+// A <= k * ((H - 1) * W - k), greatest over H * W <= 64 at 16 x 4 with k = 16 (boards of fewer than 3 rows have no
+// interior and no move).
+constexpr uint32_t bounce_most_arms() {
+    uint32_t most = 0;
+    for (uint32_t h = 3; h <= BGS_BOUNCE_MAX_CELLS; ++h)
+        for (uint32_t w = 1; h * w <= BGS_BOUNCE_MAX_CELLS; ++w)
+            for (uint32_t k = 1; k <= w; ++k) most = k * ((h - 1) * w - k) > most ? k * ((h - 1) * w - k) : most;
+    return most;
+}
+constexpr uint32_t kBounceHalvingMaxArms = 512;
+static_assert(bounce_most_arms() == kBounceHalvingMaxArms, "the arm table, the survivor lists and the tally hold every legal move of a root");
+static_assert(kBounceHalvingMaxArms * 10u < (1u << 16), "arm indices and A * R(A) fit the tables' 16 bits and a uint32 with room");
+
+template <class GEO, int NC, int POLICY>
+__global__ void __launch_bounds__(BGS_BLOCK)
+k_bounce_evaluate_halving(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status,
+                          const uint16_t* __restrict__ plies_buf, int64_t n, uint64_t seed, uint64_t game_base, uint32_t budget,
+                          uint32_t max_plies, uint32_t slots, int64_t root_base, int32_t* __restrict__ counts,
+                          int32_t* __restrict__ given, int32_t* __restrict__ best, unsigned long long* __restrict__ steps) {
+    extern __shared__ uint32_t target_tile[];                      // [2 * 8 * NC dwords][256 lanes]
+    __shared__ uint32_t tally[kBounceHalvingMaxArms * 3];          // cumulative W/D/L of an arm
+    __shared__ uint16_t arm_move[kBounceHalvingMaxArms];           // source cell << 8 | target cell
+    __shared__ uint16_t survivors[2][kBounceHalvingMaxArms];       // S_r in [r & 1], ascending
+    __shared__ uint8_t kept[kBounceHalvingMaxArms];                // survivor k stays in S_{r+1}
+    __shared__ uint64_t root_targets[8 * NC];                      // targets of the piece in column x of the active row
+    __shared__ uint32_t next_item;                                 // the round's next playout
+    uint32_t* const column = target_tile + threadIdx.x;
+    const uint32_t tid = threadIdx.x, lane = threadIdx.x & (BGS_WAVE - 1);
+    const uint32_t hw = (uint32_t)(g.h * g.w);
+    const int64_t i = root_base + (int64_t)blockIdx.x;             // (the grid holds exactly the roots of this launch)
+
+    // ---- the root, once: its legal moves, the arm table, S_0
+    for (uint32_t k = tid; k < kBounceHalvingMaxArms * 3; k += BGS_BLOCK) tally[k] = 0;
+    if (tid == 0) next_item = 0;
+    const Board root = load_board(planes, n, i);
+    const uint32_t rply = plies_buf[i];
+    const uint32_t root_mover = rply & 1u, child_ply = rply + 1u;
+    const uint64_t root_occ = occupancy(root);
+    // (an ended root and one that holds the most plies a board can have no arms, as in k_bounce_eval_count)
+    const uint64_t sources = status[i] == BGS_ST_RUNNING && rply < kBounceMaxPlies ? movable(g, root_occ, root_mover) : 0ull;
+    const uint32_t first_source = sources ? (uint32_t)(__ffsll((unsigned long long)sources) - 1) : 0u;
+    const uint32_t row_base = ((first_source * g.inv_w) >> 16) * (uint32_t)g.w;
+    if (tid < 8 * NC) {
+        const bool piece = tid < (uint32_t)g.w && ((sources >> ((row_base + tid) & 63u)) & 1ull);
+        root_targets[tid] = piece ? reach(g, root, root_occ, root_mover, (int)(row_base + tid)) : 0ull;
+    }
+    __syncthreads();
+    uint32_t arms = 0;
+    for (uint32_t x = 0; x < 8 * NC; ++x) arms += (uint32_t)__popcll(root_targets[x]);
+    arms = (uint32_t)__builtin_amdgcn_readfirstlane((int)arms);
+    const uint32_t rounds = arms ? halving_rounds(arms) : 0u;
+    if (arms == 0u || budget < arms * rounds) {   // nothing to play, or some q_r would be 0: the outputs stay zero
+        if (tid == 0 && best) best[i] = arms ? BGS_HALVING_SHORT : -1;
+        return;
+    }
+    for (uint32_t a = tid; a < arms; a += BGS_BLOCK) {
+        uint32_t j = a, x = 0;
+        for (; x < 8 * NC - 1; ++x) {
+            const uint32_t cnt = (uint32_t)__popcll(root_targets[x]);
+            if (j < cnt) break;
+            j -= cnt;
+        }
+        arm_move[a] = (uint16_t)(((row_base + x) << 8) | select_bit64(root_targets[x], j));
+        survivors[0][a] = (uint16_t)a;
+    }
+    __syncthreads();
+    auto slot_of = [&](uint32_t arm) {            // x * H * W + target cell
+        const uint32_t packed = arm_move[arm];
+        return ((packed >> 8) - row_base) * hw + (packed & 255u);
+    };
+
+    Board b;                         // the lane's game
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b.v[j] = 0;
+    FlatMoves<NC> mv;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) mv.counts[k] = 0;
+    mv.n = 0;
+    mv.row_base = 0;
+    uint32_t st = 0, plies = 0, cur_arm = 0, stepped = 0;
+    uint64_t game = 0;
+    bool has = false, search = false, have_block = false;
+    [[maybe_unused]] bool can_win = false;   // (BGS_POLICY_DECISIVE) the list the lane holds has a target in the mover's goal row
+    Philox4 blk;
+    blk.v[0] = blk.v[1] = blk.v[2] = blk.v[3] = 0;
+    uint32_t m = arms;               // (team-uniform) |S_r|
+    uint32_t first_p = 0;            // (team-uniform) P_r
+
+    for (uint32_t r = 0; r < rounds; ++r) {
+        const uint16_t* const cur = survivors[r & 1u];
+        uint16_t* const nxt = survivors[(r & 1u) ^ 1u];
+        const uint32_t q = budget / (m * rounds);
+        const uint32_t total = m * q;
+        bool dry = false;            // (wave-uniform) the round's counter has nothing left for this wave
+        while (!dry || __builtin_amdgcn_ballot_w64(has)) {
+            // ---- refill: the wave's idle lanes take the round's next playouts
+            const uint64_t need = __builtin_amdgcn_ballot_w64(!has);
+            if (need && !dry) {
+                const uint32_t wanted = (uint32_t)__popcll(need);
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(&next_item, wanted);
+                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+                if (base + wanted >= total) dry = true;
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                if (!has && base + rank < total) {
+                    const uint32_t item = base + rank;
+                    const uint32_t k = item / q;
+                    const uint32_t po = first_p + (item - k * q);
+                    cur_arm = cur[k];
+                    const uint32_t move = arm_move[cur_arm];
+                    const int s_cell = (int)(move >> 8), t_cell = (int)(move & 255u);
+                    stepped += 1u;   // the first move: a transition of the replicated board
+                    game = game_base + ((uint64_t)i * slots + slot_of(cur_arm)) * budget + po;
+                    b = root;
+                    move_piece(b, s_cell, t_cell);
+                    plies = child_ply;
+                    st = ((1ull << t_cell) & (g.goal_top | g.goal_bottom)) ? root_mover + 1u : BGS_ST_RUNNING;
+                    has = true;
+                    search = st == BGS_ST_RUNNING;   // (a blocked side to move is settled by the search, also at the cap)
+                    have_block = false;
+                }
+            }
+            if (!__builtin_amdgcn_ballot_w64(has)) continue;
+
+            // ---- the ply of k_bounce_evaluate: the action lists of the boards that have just moved (a side to move
+            // without an action settles the game), the cap, one move
+            if (__builtin_amdgcn_ballot_w64(search)) {
+                const uint64_t occ = occupancy(b);
+                enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
+                const bool blocked = search && mv.n == 0u;
+                if (__builtin_amdgcn_ballot_w64(blocked)) {
+                    FlatMoves<NC> other;
+#pragma unroll
+                    for (int k = 0; k < NC; ++k) other.counts[k] = 0;
+                    other.n = 0;
+                    other.row_base = 0;
+                    enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
+                    if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
+                }
+                if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                    if (search) can_win = st == BGS_ST_RUNNING && b_can_win<NC>(mv, column, (plies & 1u) ? g.goal_bottom : g.goal_top);
+                }
+                search = false;
+            }
+            const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
+            if (has && !run) {       // finished: one LDS atomic (a capped game, st 0, is counted nowhere)
+                if (st != 0u) atomicAdd(tally + cur_arm * 3u + (st == BGS_ST_DRAW ? 1u : (st - 1u == root_mover ? 0u : 2u)), 1u);
+                has = false;
+            }
+            if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                if (run && can_win) {   // every candidate ends the game for the mover: one transition, nothing drawn or moved
+                    st = (plies & 1u) + 1u;
+                    ++plies;
+                    stepped += 1u;
+                }
+            }
+            if (POLICY == BGS_POLICY_DECISIVE ? run && !can_win : run) {
+                if (!have_block || (plies & 3u) == 0u) {
+                    blk = philox4x32_10(seed, game, plies >> 2);
+                    have_block = true;
+                }
+                const uint32_t mover = plies & 1u;
+                int s, t;
+                pick_flat<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, t);
+                move_piece(b, s, t);
+                ++plies;
+                stepped += 1u;
+                if ((1ull << t) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
+                else search = true;
+            }
+        }
+        __syncthreads();   // the round's tally is complete
+
+        // ---- selection: survivor k is ranked among the m survivors; the arms that leave store their outputs
+        const uint32_t keep = (m + 1u) / 2u;
+        const bool last = r + 1u == rounds;
+        for (uint32_t k = tid; k < m; k += BGS_BLOCK) {
+            const uint32_t arm = cur[k];
+            const uint32_t mine = 2u * tally[arm * 3u] + tally[arm * 3u + 1u];
+            uint32_t rank = 0;
+            for (uint32_t j = 0; j < m; ++j) {   // (cur is ascending: survivor j is the lower arm when j < k)
+                const uint32_t other = 2u * tally[cur[j] * 3u] + tally[cur[j] * 3u + 1u];
+                rank += (other > mine || (other == mine && j < k)) ? 1u : 0u;
+            }
+            kept[k] = rank < keep ? 1u : 0u;
+            if (rank >= keep || last) {
+                const int64_t at = i * (int64_t)slots + slot_of(arm);
+#pragma unroll
+                for (uint32_t c = 0; c < 3; ++c) counts[at * 3 + c] = (int32_t)tally[arm * 3u + c];
+                if (given) given[at] = (int32_t)(first_p + q);
+            }
+        }
+        __syncthreads();   // every survivor's flag is written
+        for (uint32_t k = tid; k < m; k += BGS_BLOCK) {
+            if (kept[k]) {
+                uint32_t pos = 0;
+                for (uint32_t j = 0; j < k; ++j) pos += kept[j];
+                nxt[pos] = cur[k];
+            }
+        }
+        m = keep;
+        first_p += q;
+        if (tid == 0) next_item = 0;
+        __syncthreads();   // S_{r+1} is complete, every wave has read the tally, the counter is back at 0
+    }
+    if (tid == 0 && best) best[i] = (int32_t)slot_of(survivors[rounds & 1u][0]);
+    add_steps(steps, stepped);
+}
+
+template <class GEO, int NC, int POLICY>
+void launch_bounce_evaluate_halving(const bgs_batch* b, const GEO& g, uint64_t seed, uint32_t budget, uint32_t max_plies,
+                                    int32_t* d_counts, int32_t* d_given, int32_t* d_best) {
+    const uint32_t slots = (uint32_t)(b->bg.w * b->bg.h * b->bg.w);
+    (void)hipMemsetAsync(d_counts, 0, (size_t)b->n * slots * 3 * sizeof(int32_t), b->stream);
+    if (d_given) (void)hipMemsetAsync(d_given, 0, (size_t)b->n * slots * sizeof(int32_t), b->stream);
+    // game ids: ((first_game + i) * S + s) * B + p = first_game * S * B + (i * S + s) * B + p, mod 2^64
+    const uint64_t game_base = b->first_game * (uint64_t)slots * (uint64_t)budget;
+    const size_t tile = sizeof(uint32_t) * 2 * 8 * NC * BGS_BLOCK;
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL((k_bounce_evaluate_halving<GEO, NC, POLICY>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), tile, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, seed, game_base,
+                           budget, max_plies, slots, i0, d_counts, d_given, d_best, b->d_steps);
+    }
+}
+
 EvalGeom eval_geom(const bgs_batch* b) {
     EvalGeom g{};
     g.rh = b->cg.h;
@@ -1608,6 +1860,27 @@ void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_
         launch_bounce_evaluate<BounceGeom, 1>(b, b->bg, seed, p, cap, d_counts, d_ends, d_totals);
     else
         launch_bounce_evaluate<BounceGeom, 3>(b, b->bg, seed, p, cap, d_counts, d_ends, d_totals);
+}
+
+template <int POLICY>
+static void bounce_evaluate_halving_policy(const bgs_batch* b, uint64_t seed, uint32_t budget, uint32_t cap, int32_t* d_counts,
+                                           int32_t* d_given, int32_t* d_best) {
+    if (b->bounce_static_geom && bounce_is_default(b->bg))
+        launch_bounce_evaluate_halving<DefaultBounceGeom, 1, POLICY>(b, DefaultBounceGeom{}, seed, budget, cap, d_counts, d_given, d_best);
+    else if (b->bg.w <= 8)
+        launch_bounce_evaluate_halving<BounceGeom, 1, POLICY>(b, b->bg, seed, budget, cap, d_counts, d_given, d_best);
+    else
+        launch_bounce_evaluate_halving<BounceGeom, 3, POLICY>(b, b->bg, seed, budget, cap, d_counts, d_given, d_best);
+}
+
+void bounce_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* d_counts,
+                             int32_t* d_given, int32_t* d_best) {
+    uint32_t cap = (uint32_t)max_plies;
+    if (cap > kBounceMaxPlies) cap = kBounceMaxPlies;   // plies are stored as uint16
+    if (policy == BGS_POLICY_DECISIVE)
+        bounce_evaluate_halving_policy<BGS_POLICY_DECISIVE>(b, seed, (uint32_t)budget, cap, d_counts, d_given, d_best);
+    else
+        bounce_evaluate_halving_policy<BGS_POLICY_UNIFORM>(b, seed, (uint32_t)budget, cap, d_counts, d_given, d_best);
 }
 
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,

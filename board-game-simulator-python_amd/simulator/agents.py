@@ -9,6 +9,9 @@ and counted in ONE launch: ``ConnectBatch.evaluate_actions`` for Connect states 
 ``SolverAgent`` values Connect positions exactly where it can (``ConnectBatch.solve_actions``): 1.0 for a forced win,
 0.5 for a draw, 0.0 for a forced loss, and a fallback agent's value where the search was cut by its horizon or budget.
 Bounce positions go to the horizon search ``BounceBatch.solve_moves`` in the same way (dispatched on the state's type).
+
+``BounceHalvingAgent`` spends a fixed budget of playouts a Bounce position by sequential halving
+(``BounceBatch.evaluate_moves_halving``) and plays the last surviving move.
 """
 
 from __future__ import annotations
@@ -18,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import numpy as np
 
 from .batch import (DEFAULT_BOUNCE_SOLVE_DEPTH, DEFAULT_SEED, DEFAULT_SOLVE_NODES, SOLVE_BUDGET, SOLVE_DRAW, SOLVE_LOSS,
-                    SOLVE_UNKNOWN, SOLVE_WIN, BounceBatch, ConnectBatch, playout_policy)
+                    SOLVE_UNKNOWN, SOLVE_WIN, HALVING_SHORT, BounceBatch, ConnectBatch, playout_policy)
 from .game import bounce, connect
 
 # Bounce playouts stop at this absolute ply count unless the agent is given another cap: random Bounce games are short
@@ -211,6 +214,104 @@ class MonteCarloAgent:
         out = []
         for s, values in zip(states, self.predict_many(states, first_game)):
             out.append(max(s.actions, key=values.get) if s.actions else None)   # (max keeps the first of equal values)
+        return out
+
+    def choose(self, state, game: int = 0):
+        """`choose_many` of one state"""
+        return self.choose_many([state], first_game=game)[0]
+
+    def close(self) -> None:
+        for b in self._batches.values():
+            b.close()
+        self._batches.clear()
+
+
+class BounceHalvingAgent:
+    """Sequential halving over the moves of Bounce positions (``simulator.game.bounce.State``):
+    ``BounceBatch.evaluate_moves_halving`` with ``budget`` playouts a position, one launch for all positions of a call.
+
+    ``predict`` / ``predict_many`` map every action of ``state.actions`` to ``(wins + draws / 2) / given`` over the
+    playouts the move was given (0.0 where it was given none); ``choose`` / ``choose_many`` return the last surviving move
+    (None for a state without an action).  The playouts of the position at index k of a call are the games
+    ``((first_game + k) * S + s) * budget + p`` of ``seed``, as for ``MonteCarloAgent`` with ``playouts = budget``.
+    ``max_plies`` caps every playout at that absolute ply count; None: ``BOUNCE_MAX_PLIES`` (1024).  ``policy``:
+    "uniform" or "decisive" (``BounceBatch.evaluate_moves(policy=...)``).
+
+    A position with A legal moves needs ``budget >= BounceBatch.halving_min_budget(A)``; one that needs more raises
+    ValueError.  Connect states raise ValueError: they are ``MonteCarloAgent(allocation="halving")``'s.  (A class of its
+    own because ``MonteCarloAgent(allocation="halving")`` refuses Bounce states; folding the two is a later change.)"""
+
+    def __init__(self, budget: int = 1024, seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None,
+                 policy: str = "uniform"):
+        playout_policy(policy)
+        if budget < 1:
+            raise ValueError("budget must be >= 1")
+        if max_plies is not None and max_plies < 1:
+            raise ValueError("max_plies must be >= 1")
+        self.budget = int(budget)
+        self.seed = int(seed)
+        self.device = int(device)
+        self.max_plies = None if max_plies is None else int(max_plies)
+        self.policy = policy
+        self._batches: Dict[tuple, BounceBatch] = {}
+
+    def _evaluate(self, states: Sequence, first_game: int):
+        """(counts, given, best, width) of the launch over `states`"""
+        if isinstance(states[0], connect.State):
+            raise ValueError('BounceHalvingAgent: Bounce states only; Connect states: MonteCarloAgent(allocation="halving")')
+        if not isinstance(states[0], bounce.State):
+            raise TypeError(f"BounceHalvingAgent: Bounce states, not {type(states[0]).__name__}")
+        config = states[0].config
+        if any(type(s) is not type(states[0]) or s.config != config for s in states):
+            raise ValueError("BounceHalvingAgent: the states must share one Config")
+        grid = config.grid
+        key = (grid.shape, grid.tobytes(), len(states))
+        b = self._batches.get(key)
+        if b is None:
+            b = self._batches[key] = BounceBatch(grid, len(states), device=self.device)
+        boards = np.stack([s.grid for s in states])
+        player = np.array([s.player for s in states], dtype=np.int8)
+        winner = np.array([s.to_json()["winner"] for s in states], dtype=np.int8)
+        plies = np.array([s._plies for s in states], dtype=np.int32)   # a playout's draws are keyed by the absolute ply
+        if (b.write_state(boards, player, winner, plies) != 0).any():
+            raise ValueError("BounceHalvingAgent: a state could not be loaded")
+        b.set_first_game(first_game)
+        cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
+        counts, given, best = b.evaluate_moves_halving(seed=self.seed, budget=self.budget, max_plies=cap, policy=self.policy)
+        for k in np.flatnonzero(best == HALVING_SHORT):
+            moves = len(states[k].actions)
+            raise ValueError(f"BounceHalvingAgent: state {k} has {moves} legal moves and needs a budget of "
+                             f"{BounceBatch.halving_min_budget(moves)} playouts, this agent's is {self.budget}")
+        return counts, given, best, b.width
+
+    def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict[bounce.Action, float]]:
+        """`predict` of every state, evaluated in one launch (the states must share one Config)"""
+        if not states:
+            return []
+        counts, given, _, w = self._evaluate(states, first_game)
+        out = []
+        for k, s in enumerate(states):
+            values = {}
+            for a in s.actions:
+                at = (k, a._source[0], a._target[1] * w + a._target[0])
+                values[a] = float((counts[at][0] + 0.5 * counts[at][1]) / given[at]) if given[at] else 0.0
+            out.append(values)
+        return out
+
+    def predict(self, state, game: int = 0) -> Dict[bounce.Action, float]:
+        """{action: value} for every action in ``state.actions`` (the keys are those Action objects)"""
+        return self.predict_many([state], first_game=game)[0]
+
+    def choose_many(self, states: Sequence, first_game: int = 0) -> List:
+        """the last surviving move of every state, of the same launch `predict_many` makes (None: no action)"""
+        if not states:
+            return []
+        _, _, best, w = self._evaluate(states, first_game)
+        out = []
+        for s, slot in zip(states, best):
+            hw = s.grid.shape[0] * w
+            by_slot = {a._source[0] * hw + a._target[1] * w + a._target[0]: a for a in s.actions}
+            out.append(by_slot[int(slot)] if slot >= 0 else None)
         return out
 
     def choose(self, state, game: int = 0):

@@ -29,6 +29,8 @@ DEFAULT_SOLVE_NODES = 1 << 20
 # bgs_bounce_solve_moves: the deepest horizon (BGS_BOUNCE_SOLVE_MAX_DEPTH) and the default one
 BOUNCE_SOLVE_MAX_DEPTH = 16
 DEFAULT_BOUNCE_SOLVE_DEPTH = 3
+# bgs_bounce_evaluate_moves_halving: `best` of a running board whose legal moves need a larger budget (BGS_HALVING_SHORT)
+HALVING_SHORT = _abi.HALVING_SHORT
 
 
 PLAYOUT_POLICIES = {"uniform": _abi.POLICY_UNIFORM, "decisive": _abi.POLICY_DECISIVE}
@@ -922,6 +924,12 @@ class ConnectBatch(_Batch):
 
     solve_moves_tensor = solve_moves
 
+    def evaluate_moves_halving(self, *args, **kwargs):
+        """Not available for Connect: evaluate_moves_halving covers Bounce boards; Connect has `evaluate_actions_halving`."""
+        raise ValueError("evaluate_moves_halving: Bounce batches only (Connect boards: evaluate_actions_halving)")
+
+    evaluate_moves_halving_tensor = evaluate_moves_halving
+
     @property
     def legal(self) -> np.ndarray:
         out = np.empty((self.n, self.width), dtype=np.uint8)
@@ -1058,6 +1066,58 @@ class BounceBatch(_Batch):
             raise TypeError(f"out must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
         self._evaluate_moves(seed, playouts, max_plies, policy, out.data_ptr(), 1)
         return out
+
+    @staticmethod
+    def halving_min_budget(moves: int) -> int:
+        """the least budget of `evaluate_moves_halving` for a board with `moves` legal moves: moves * max(1, ceil(log2
+        moves)), a playout a move a round"""
+        return int(moves) * max(1, (int(moves) - 1).bit_length())
+
+    def evaluate_moves_halving(self, seed: int = DEFAULT_SEED, budget: int = 1024, max_plies: int = 2**31 - 1,
+                               policy: str = "uniform"):
+        """Sequential-halving Monte-Carlo evaluation of every board (bgs_bounce_evaluate_moves_halving), one launch:
+        (counts int32[n, W, H * W, 3], given int32[n, W, H * W], best int32[n]); entry [i, x, c] is the move of the piece
+        in column x of the active row to cell c = ty * W + tx, as in `evaluate_moves`.  `budget` playouts a board are
+        spent in R = max(1, ceil(log2 A)) rounds over its A legal moves: in round r every surviving move plays
+        floor(budget / (survivors * R)) further playouts, then the better half (rounded up) survives, ranked by
+        2 * wins + draws over all rounds so far, ties to the lower slot x * H * W + c.  `best` is the slot of the last
+        survivor, `given` the playouts a move was given, `counts` its cumulative (wins, draws, losses) for the player to
+        move.  A board that has ended or has no legal move: all zeros and best = -1.  A running board with
+        budget < `halving_min_budget(A)`: all zeros and best = HALVING_SHORT; the other boards are evaluated as usual.
+        Playout p of slot s of board i is game ((first_game + i) * W * H * W + s) * budget + p, played as
+        `evaluate_moves(playouts=budget, policy=policy)` plays it: a move's counts are those of its first `given`
+        playouts there.  The boards are not modified."""
+        code = playout_policy(policy)
+        shape = (self.n, self.width, self.height * self.width)
+        counts = np.empty(shape + (3,), dtype=np.int32)
+        given = np.empty(shape, dtype=np.int32)
+        best = np.empty(self.n, dtype=np.int32)
+        _abi.check(_abi.lib().bgs_bounce_evaluate_moves_halving(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
+            ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(given.ctypes.data), ctypes.c_void_p(best.ctypes.data), 0))
+        return counts, given, best
+
+    def evaluate_moves_halving_tensor(self, counts=None, given=None, best=None, seed: int = DEFAULT_SEED, budget: int = 1024,
+                                      max_plies: int = 2**31 - 1, policy: str = "uniform"):
+        """`evaluate_moves_halving` into device tensors int32[n, W, H * W, 3], int32[n, W, H * W] and int32[n] (allocated
+        when None), enqueued on the batch's stream with no synchronisation: (counts, given, best).  Every entry is
+        written."""
+        code = playout_policy(policy)
+        t = self._need_torch("evaluate_moves_halving_tensor")
+        slots = (self.n, self.width, self.height * self.width)
+        shapes = {"counts": slots + (3,), "given": slots, "best": (self.n,)}
+        outs = {"counts": counts, "given": given, "best": best}
+        for name, shape in shapes.items():
+            x = outs[name]
+            if x is None:
+                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
+            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        _abi.check(_abi.lib().bgs_bounce_evaluate_moves_halving(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
+            ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["given"].data_ptr()),
+            ctypes.c_void_p(outs["best"].data_ptr()), 1))
+        return outs["counts"], outs["given"], outs["best"]
 
     def solve_moves(self, depth: int = DEFAULT_BOUNCE_SOLVE_DEPTH, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """Exact horizon search of every legal move of every board (bgs_bounce_solve_moves), one launch: (codes int8[n, W,

@@ -270,6 +270,35 @@ BGS_API int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playo
  * bgs_bounce_evaluate_moves refuses. */
 BGS_API int bgs_bounce_evaluate_moves_policy(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy,
                                              int32_t* counts, int counts_on_device);
+/* Sequential-halving Monte-Carlo evaluation of every board (Bounce, bit-packed boards only), one launch: the schedule of
+ * bgs_connect_evaluate_actions_halving with "column" read as "arm".  Slots are those of bgs_bounce_evaluate_moves:
+ * S = width * height * width, slot s = x * height * width + c is the move of the piece in column x of the active row to
+ * cell c.  The arms of a running board i are its A legal moves in canonical order (sources by ascending x, targets by
+ * ascending (y, x)): ascending slot order.  With R(x) = max(1, ceil(log2 x)):
+ *   start      S_0 = the legal moves, R = R(A), P_0 = 0;
+ *   round r    (r = 0 .. R-1) every arm of S_r plays q_r = floor(budget / (|S_r| * R)) further playouts, those with the
+ *              playout indices [P_r, P_r + q_r); P_{r+1} = P_r + q_r;
+ *   selection  an arm's score is 2 * wins + draws over all rounds so far (a capped playout scores 0); S_{r+1} = the
+ *              ceil(|S_r| / 2) arms of S_r ranked highest, by score descending, then by slot ascending.
+ * best int32[n] = the slot of the one arm of S_R; given int32[n][width][height * width] = the playouts a slot was given;
+ * counts int32[n][width][height * width][3] = its cumulative (wins, draws, losses) for the player to move at board i.
+ * An illegal slot: all zeros.  A board that has ended, has no legal move or holds 65535 plies (the boards
+ * bgs_bounce_evaluate_moves gives no playouts): all zeros and best = -1.
+ * Playout p of slot s of board i is the game G = ((first_game + i) * S + s) * budget + p (mod 2^64), played exactly as
+ * bgs_bounce_evaluate_moves_policy plays it (forced first move, policy, a philox word per absolute ply, the cap clamped
+ * to 65535, the settlement of a side without a move): an arm's counts are those of the first given[i][s] playouts of the
+ * flat evaluation with playouts = budget, so sharding by first_game holds.  The q_r of a board sum to at most `budget`.
+ * A budget too small for a board: the number of arms differs from board to board, so the least budget is a matter of the
+ * board and not of the call.  A running board with budget < A * R(A) -- some q_r would be 0 -- is not evaluated: its
+ * counts and given are all zeros and best = BGS_HALVING_SHORT; every other board of the batch is evaluated as usual.
+ * The transitions of the playouts played are added to bgs_steps, first moves included; the boards are not modified.
+ * given and best may be NULL.  on_device != 0: device pointers (16-byte aligned), enqueued on the batch's stream, no
+ * synchronisation, no allocation; otherwise host buffers, filled when the call returns.
+ * Refused (BGS_ERR_ARG, with a message that says why): a Connect batch, a generic batch, budget < 1, max_plies < 1, an
+ * unknown policy, NULL counts, a misaligned device pointer, n * S * budget beyond int64. */
+#define BGS_HALVING_SHORT (-2)
+BGS_API int bgs_bounce_evaluate_moves_halving(bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy,
+                                              int32_t* counts, int32_t* given, int32_t* best, int on_device);
 /* Exact solve of every column of every board (Connect, bit-packed boards only): a depth-first alpha-beta search a
  * (board, column), no RNG.  Entry [i][c] is seen from the player to move at board i; the lines searched are at most
  * `depth` plies long, column c itself counted (depth >= height * width: a full solve).
