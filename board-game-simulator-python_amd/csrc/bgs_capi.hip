@@ -1089,6 +1089,84 @@ int bgs_connect_evaluate_actions_halving(bgs_batch* b, uint64_t seed, int32_t bu
     return BGS_OK;
 }
 
+// the checks of both search entry points that need no device; *bytes: the workspace of the batch
+static int connect_search_check(const bgs_batch* b, int32_t iterations, size_t* bytes) {
+    NEED(b->game == BGS_GAME_CONNECT, "search_actions: Connect batches only");
+    NEED(!b->generic, "search_actions: bit-packed Connect boards only (up to %d bits a plane); %dx%d boards are generic",
+         64 * BGS_CONNECT_MAX_WORDS, b->cg.h, b->cg.w);
+    NEED(iterations >= 1, "iterations must be >= 1 (got %d)", iterations);
+    const uint64_t root = bgs::connect_search_root_bytes(b->cg.w, iterations);
+    NEED((uint64_t)b->n <= (uint64_t)(SIZE_MAX / 2) / root, "the workspace of %lld boards x %d iterations overflows size_t",
+         (long long)b->n, iterations);
+    *bytes = (size_t)((uint64_t)b->n * root);
+    return BGS_OK;
+}
+
+int bgs_connect_search_workspace_bytes(const bgs_batch* b, int32_t iterations, size_t* bytes) {
+    NEED(b != nullptr, "batch is NULL");
+    NEED(bytes != nullptr, "bytes is NULL");
+    return connect_search_check(b, iterations, bytes);
+}
+
+int bgs_connect_search_actions(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                               int32_t max_plies, int policy, int32_t* counts, int32_t* visits, int32_t* best, int32_t* nodes,
+                               void* workspace, size_t workspace_bytes, int on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(counts != nullptr, "counts is NULL");
+    size_t need = 0;
+    rc = connect_search_check(b, iterations, &need);
+    if (rc) return rc;
+    NEED(leaf_playouts >= 1, "leaf_playouts must be >= 1 (got %d)", leaf_playouts);
+    NEED((int64_t)iterations * leaf_playouts <= ((int64_t)1 << 29),
+         "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
+    NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "search_actions: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
+         (long long)b->n, iterations, leaf_playouts);
+    const size_t cells = (size_t)b->n * b->cg.w;
+    if (on_device) {
+        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(visits) & 15u) == 0, "device visits must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(nodes) & 15u) == 0, "device nodes must be 16-byte aligned");
+        NEED(workspace != nullptr, "workspace is NULL (on_device: the caller owns it; bgs_connect_search_workspace_bytes says how large)");
+        NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
+        NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
+        bgs::connect_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, counts, visits, best, nodes, workspace);
+        return finish_launch();
+    }
+    if (workspace != nullptr) {
+        NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
+        NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
+    }
+    // one device buffer: counts, visits, best, nodes -- each 16-byte aligned -- and the workspace when the caller gave none
+    const auto up = [](size_t x, size_t a) { return (x + a - 1) & ~(a - 1); };
+    const size_t counts_bytes = cells * 3 * sizeof(int32_t), visits_bytes = cells * sizeof(int32_t), board_bytes = (size_t)b->n * sizeof(int32_t);
+    const size_t visits_off = up(counts_bytes, 16), best_off = visits_off + up(visits_bytes, 16), nodes_off = best_off + up(board_bytes, 16);
+    // the library's own workspace starts at the first 256-byte boundary behind the outputs, wherever the pool put `d`
+    const size_t tree_room = workspace ? 0 : need + 256;
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), nodes_off + board_bytes + tree_room, b->stream));
+    uint8_t* const own = reinterpret_cast<uint8_t*>(up(reinterpret_cast<uintptr_t>(d + nodes_off + board_bytes), 256));
+    bgs::connect_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, reinterpret_cast<int32_t*>(d),
+                        visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
+                        best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr,
+                        nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr, workspace ? workspace : own);
+    rc = finish_launch();
+    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
+    if (rc == BGS_OK && visits) rc = copy_to_host(b, visits, d + visits_off, visits_bytes);
+    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, board_bytes);
+    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d + nodes_off, board_bytes);
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
 int bgs_connect_solve_actions(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
                               int on_device) {
     int rc = enter(b);

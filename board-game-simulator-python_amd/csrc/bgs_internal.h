@@ -135,6 +135,12 @@ void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32
 int32_t connect_halving_min_budget(int width);
 void connect_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* d_counts,
                               int32_t* d_given, int32_t* d_best);
+// UCT tree search over packed Connect boards (bgs_connect_search_actions): counts int32[n][w][3], visits int32[n][w],
+// best int32[n] and nodes int32[n] (the last three may be NULL) on the device, every entry written; d_workspace: n *
+// connect_search_root_bytes(w, iterations) bytes, 256-byte aligned, no preparation needed; enqueued on the batch's stream
+uint64_t connect_search_root_bytes(int width, int32_t iterations);
+void connect_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
+                    int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace);
 // exact alpha-beta solve of every column of packed Connect boards (bgs_connect_solve_actions): codes int8[n][w], plies
 // int16[n][w] (may be NULL), *d_nodes = positions visited; device pointers, enqueued on the batch's stream
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,

@@ -548,6 +548,300 @@ void launch_evaluate_halving(const bgs_batch* b, const EvalGeom& g, uint64_t see
 }
 
 // ================================================================================================================
+// UCT tree search (bgs_connect_search_actions, include/bgs.h): `iterations` iterations of UCT a root, `leaf_playouts`
+// playouts a leaf, integer arithmetic throughout.
+//
+// Shape: leaf-parallel MCTS.  One wave (a 64-lane workgroup) owns one root for the whole launch.  The descent is
+// wave-uniform: the position is rebuilt from the root as the descent goes (nodes hold no boards), lane c holds n, s and
+// the child of column c of the node at hand and computes U(c), and the arg-max is taken over the lanes.  The path goes
+// into LDS as (node, column) pairs.  The 64 lanes then play the leaf's playouts (the refill loop and the 4-ply block of
+// k_connect_evaluate: idle lanes take the leaf's next playouts at block boundaries), W/D/L are reduced by LDS atomics,
+// and lane k updates edge k of the path.
+//
+// The tree lives in the caller's workspace, (iterations + 1) nodes a root; a node is 3 * width words: n[c], s[c],
+// child[c].  A node is zeroed when it is made (the root at the start), so a workspace needs no preparation.  The tree is
+// written by some lanes (lane k of the back-propagation, the lanes that zero a new node) and read by others (lane c of
+// the next descent): a __syncthreads() of the one-wave workgroup stands between every such pair.
+//
+// Known limit: a root has one wave, so a launch of few roots uses few CUs, and leaf_playouts < 64 leaves lanes idle
+// (DESIGN.md §9).
+// ================================================================================================================
+constexpr uint32_t kSearchMaxPath = 64 * BGS_CONNECT_MAX_WORDS;   // a descent drops at most h * w stones
+
+// words of a root's tree in the workspace: iterations + 1 nodes, rounded up to 256 bytes
+__host__ __device__ __forceinline__ uint64_t search_root_words(uint32_t width, uint32_t iterations) {
+    return (((uint64_t)iterations + 1u) * width * 3u + 63u) & ~(uint64_t)63u;
+}
+
+// floor(sqrt(x)), exact
+__device__ __forceinline__ uint32_t search_isqrt(uint32_t x) {
+    uint32_t r = (uint32_t)sqrtf((float)x);
+    while ((uint64_t)r * r > x) --r;
+    while ((uint64_t)(r + 1u) * (r + 1u) <= x) ++r;
+    return r;
+}
+
+// Q = floor(s * 2048 / n), n >= 1, s <= 2 n < 2^31: the double quotient of two integers below 2^42 is within one of it
+__device__ __forceinline__ uint32_t search_q(uint32_t s, uint32_t n) {
+    const uint64_t num = (uint64_t)s << 11;
+    uint32_t q = (uint32_t)((double)num / (double)n);
+    while ((uint64_t)q * n > num) --q;
+    while ((uint64_t)(q + 1u) * n <= num) ++q;
+    return q;
+}
+
+// lg(N) = 256 e + ((256 N) >> e) - 256, e = floor(log2 N): a piecewise-linear log2 in Q8 (N >= 1)
+__host__ __device__ __forceinline__ uint32_t search_lg(uint32_t total) {
+    const uint32_t e = 31u - (uint32_t)__builtin_clz(total);
+    return 256u * e + (uint32_t)(((uint64_t)total << 8) >> e) - 256u;
+}
+
+template <int NW, bool PER_PLY, int POLICY>
+__global__ void __launch_bounds__(BGS_WAVE)
+k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n, uint64_t seed,
+                 uint64_t game_base, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore, uint32_t max_plies,
+                 int64_t root_base, uint32_t* workspace, int32_t* __restrict__ counts, int32_t* __restrict__ visits,
+                 int32_t* __restrict__ best, int32_t* __restrict__ nodes, unsigned long long* __restrict__ steps) {
+    __shared__ uint32_t path_node[kSearchMaxPath];   // the descent: edge k leaves node path_node[k] by column path_col[k]
+    __shared__ uint32_t path_col[kSearchMaxPath];
+    __shared__ uint32_t tally[3];                    // W/D/L of the iteration's playouts, for the root's mover
+    __shared__ unsigned long long step_sum;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t width = (uint32_t)g.w();
+    const uint32_t stride = (uint32_t)g.h() + 1u;
+    const uint32_t node_words = width * 3u;
+    const int64_t i = root_base + (int64_t)blockIdx.x;       // (the grid holds exactly the roots of this launch)
+    uint32_t* const tree = workspace + (uint64_t)i * search_root_words(width, iterations);
+
+    Bits<NW> r0, r1;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        r0.w[j] = planes[(int64_t)j * n + i];
+        r1.w[j] = planes[(int64_t)(NW + j) * n + i];
+    }
+    const uint32_t rply = popcount(r0) + popcount(r1);
+    const uint32_t root_mover = rply & 1u;
+    const bool running = status[i] == BGS_ST_RUNNING;
+    uint32_t cw = 0, cd = 0, cl = 0;    // lane c: W/D/L of the playouts through root column c
+    uint32_t made = 0;                  // (uniform) nodes made, the root not counted
+    uint64_t stepped = 0;
+    if (lane == 0) step_sum = 0;
+    if (running && lane < node_words) tree[lane] = 0;         // the root is node 0 (3 * width <= 48 words)
+    __syncthreads();
+
+    Bits<NW> q[2];                      // the lane's playout: stones of player 0 / player 1
+#pragma unroll
+    for (int j = 0; j < NW; ++j) q[0].w[j] = q[1].w[j] = 0;
+    Philox4 ph;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ph.v[j] = 0;
+
+    for (uint32_t t = 0; running && t < iterations; ++t) {
+        // ---- descent (wave-uniform): p is the position at node v
+        Bits<NW> p[2] = {r0, r1};
+        uint32_t ply = rply, v = 0, depth = 0, leaf = BGS_ST_RUNNING, col0 = 0;
+        for (;;) {
+            const Bits<NW> occ = p[0] | p[1];
+            uint32_t height = (uint32_t)g.h();
+            if (lane < width) height = (uint32_t)__popcll(shr(occ, (int)(lane * stride)).w[0] & ((1ull << g.h()) - 1ull));
+            const bool legal = height < (uint32_t)g.h();
+            uint32_t* const node = tree + (uint64_t)v * node_words;
+            uint32_t nc = 0, sc = 0, ch = 0;
+            if (legal) {
+                nc = node[lane];
+                sc = node[width + lane];
+                ch = node[2u * width + lane];
+            }
+            const uint64_t unvisited = __builtin_amdgcn_ballot_w64(legal && nc == 0u);
+            uint32_t col;
+            if (unvisited) {
+                col = (uint32_t)__builtin_ctzll(unvisited);            // the expansion: the lowest column never played
+            } else {
+                uint32_t total = 0;
+                for (uint32_t c = 0; c < width; ++c) total += (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)c);
+                uint32_t key = 0;                                      // (U(c) << 4 | 15 - c) + 1: the largest U, then the lowest column
+                if (legal) {
+                    const uint32_t u = search_q(sc, nc) + search_isqrt(explore * search_lg(total) / nc);
+                    key = ((u << 4) | (15u - lane)) + 1u;
+                }
+                uint32_t top = 0;
+                for (uint32_t c = 0; c < width; ++c) {
+                    const uint32_t other = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)c);
+                    top = other > top ? other : top;
+                }
+                col = 15u - ((top - 1u) & 15u);
+            }
+            col = (uint32_t)__builtin_amdgcn_readfirstlane((int)col);
+            const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)height, (int)col);
+            const uint32_t before = (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)col);
+            const uint32_t child = (uint32_t)__builtin_amdgcn_readlane((int)ch, (int)col);
+            if (lane == 0) {
+                path_node[depth] = v;
+                path_col[depth] = col;
+            }
+            col0 = depth == 0u ? col : col0;
+            const uint32_t mover = ply & 1u;
+            Bits<NW>& mine = mover ? p[1] : p[0];
+            const bool won = drop_and_test(g, mine, col * stride + at, ~0u);
+            ply += 1u;
+            depth += 1u;
+            leaf = won ? mover + 1u : (ply == g.cells_total ? (uint32_t)BGS_ST_DRAW : (uint32_t)BGS_ST_RUNNING);
+            leaf = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf);
+            if (leaf != BGS_ST_RUNNING) break;                         // a terminal edge: no node, no game
+            if (before == 0u) {                                        // a new node for p'
+                made += 1u;
+                if (lane < node_words) tree[(uint64_t)made * node_words + lane] = 0;
+                if (lane == col) node[2u * width + lane] = made;
+                break;
+            }
+            v = child;
+        }
+
+        // ---- the leaf's playouts: the lanes take them in order, idle lanes refill at 4-ply block boundaries
+        uint32_t wins = 0, draws = 0, losses = 0, played = 0;
+        if (lane < 3u) tally[lane] = 0;
+        if (leaf != BGS_ST_RUNNING) {
+            if (lane == 0) {       // all playouts of the iteration have the edge's outcome
+                wins = (leaf != BGS_ST_DRAW && leaf - 1u == root_mover) ? leaf_playouts : 0u;
+                losses = (leaf != BGS_ST_DRAW && leaf - 1u != root_mover) ? leaf_playouts : 0u;
+                draws = leaf == BGS_ST_DRAW ? leaf_playouts : 0u;
+            }
+        } else if (ply < max_plies) {
+            // G = ((first_game + i) * T + t) * P + j
+            const uint64_t game0 = game_base + ((uint64_t)i * iterations + t) * (uint64_t)leaf_playouts;
+            uint64_t game = 0;
+            uint32_t taken = 0, blk = 0, skip = 0, live = 0, st = 0, fresh = 0;
+            while (taken < leaf_playouts || __builtin_amdgcn_ballot_w64(live != 0)) {
+                const uint64_t need = __builtin_amdgcn_ballot_w64(live == 0);
+                if (need != 0 && taken < leaf_playouts) {
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                    if (live == 0 && rank < leaf_playouts - taken) {
+                        q[0] = p[0];
+                        q[1] = p[1];
+                        game = game0 + (uint64_t)(taken + rank);
+                        blk = ply >> 2;
+                        skip = ply & 3u;
+                        live = ~0u;
+                        fresh = 1u;
+                        st = 0;
+                    }
+                    const uint32_t wanted = (uint32_t)__popcll(need);
+                    taken = leaf_playouts - taken < wanted ? leaf_playouts : taken + wanted;
+                }
+
+                // ---- the 4-ply block of k_connect_evaluate: the same draws, the same ply code
+                if (PER_PLY) {
+                    ph = philox4x32_10(seed, game, blk);
+                } else {
+                    const bool want = live && (fresh || (blk & 3u) == 0u);
+                    if (__builtin_amdgcn_ballot_w64(want)) {
+                        if (want) ph = philox4x32_10(seed, game, blk >> 2);
+                    }
+                }
+                fresh = 0;
+                const uint32_t word = PER_PLY ? 0u : philox_word(ph, blk);
+                const uint32_t was_live = live;
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint32_t draw = PER_PLY ? ph.v[j] : sub_draw(word, j);
+                    const uint32_t act = j >= skip ? live : 0u;
+                    const uint32_t at = 4u * blk + j;          // stones before this sub-step; its mover is player j & 1
+                    bool won;
+                    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                        const uint32_t pos = decisive_position(g, q[j & 1u], q[(j & 1u) ^ 1u], draw, won);
+                        drop(q[j & 1u], pos, act);
+                        won = won && act;
+                    } else {
+                        const uint32_t pos = draw_position(g, q[0] | q[1], draw);
+                        won = drop_and_test(g, q[j & 1u], pos, act);
+                    }
+                    const bool full = at + 1u == g.cells_total;
+                    if (act) {
+                        st = won ? (j & 1u) + 1u : (full ? BGS_ST_DRAW : BGS_ST_RUNNING);
+                        live = (won || full || at + 1u >= max_plies) ? 0u : live;
+                        played += 1u;
+                    }
+                }
+                blk += 1u;
+                skip = 0;
+                if (was_live && !live) {      // (st == 0: capped, counted nowhere)
+                    wins += (st != 0u && st != BGS_ST_DRAW && st - 1u == root_mover) ? 1u : 0u;
+                    losses += (st != 0u && st != BGS_ST_DRAW && st - 1u != root_mover) ? 1u : 0u;
+                    draws += st == BGS_ST_DRAW ? 1u : 0u;
+                }
+            }
+        }
+        stepped += played;
+        __syncthreads();            // the tally is zero, the path and the new node are written
+        if (wins) atomicAdd(tally + 0, wins);
+        if (draws) atomicAdd(tally + 1, draws);
+        if (losses) atomicAdd(tally + 2, losses);
+        __syncthreads();
+        const uint32_t tw = tally[0], td = tally[1], tl = tally[2];
+
+        // ---- back-propagation: lane k takes edge k of the path; its mover is the root's at even k
+        for (uint32_t k = lane; k < depth; k += BGS_WAVE) {
+            uint32_t* const node = tree + (uint64_t)path_node[k] * node_words;
+            const uint32_t c = path_col[k];
+            node[c] += leaf_playouts;
+            node[width + c] += td + 2u * ((k & 1u) ? tl : tw);
+        }
+        if (lane == col0) {
+            cw += tw;
+            cd += td;
+            cl += tl;
+        }
+        __syncthreads();            // the tree is whole again before the next descent reads it; tally and path are free
+    }
+
+    // ---- the outputs of the root (an illegal column was never played: its words of the root are zero)
+    uint32_t nv = 0, sv = 0;
+    if (running && lane < width) {
+        nv = tree[lane];
+        sv = tree[width + lane];
+    }
+    if (lane < width) {
+        counts[(i * (int64_t)width + lane) * 3 + 0] = (int32_t)cw;
+        counts[(i * (int64_t)width + lane) * 3 + 1] = (int32_t)cd;
+        counts[(i * (int64_t)width + lane) * 3 + 2] = (int32_t)cl;
+        if (visits) visits[i * (int64_t)width + lane] = (int32_t)nv;
+    }
+    if (best) {
+        // the most visits, then the larger 2 * wins + draws, then the lower column; an illegal column has no visits
+        int32_t top = -1;
+        uint32_t top_n = 0, top_s = 0;
+        for (uint32_t c = 0; running && c < width; ++c) {
+            const uint32_t cn = (uint32_t)__builtin_amdgcn_readlane((int)nv, (int)c);
+            const uint32_t cs = (uint32_t)__builtin_amdgcn_readlane((int)sv, (int)c);
+            if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
+                top = (int32_t)c;
+                top_n = cn;
+                top_s = cs;
+            }
+        }
+        if (lane == 0) best[i] = top;
+    }
+    if (nodes && lane == 0) nodes[i] = (int32_t)made;
+    if (stepped) atomicAdd(&step_sum, (unsigned long long)stepped);
+    __syncthreads();
+    if (lane == 0 && step_sum) atomicAdd(steps + (size_t)(blockIdx.x % BGS_STEP_SHARDS) * BGS_STEP_STRIDE, step_sum);
+}
+
+template <int NW, bool PER_PLY, int POLICY>
+void launch_search(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
+                   uint32_t max_plies, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace) {
+    // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
+    const uint64_t game_base = b->first_game * (uint64_t)iterations * (uint64_t)leaf_playouts;
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL((k_connect_search<NW, PER_PLY, POLICY>), dim3((uint32_t)blocks), dim3(BGS_WAVE), 0, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, seed, game_base, iterations, leaf_playouts,
+                           explore, max_plies, i0, static_cast<uint32_t*>(d_workspace), d_counts, d_visits, d_best, d_nodes, b->d_steps);
+    }
+}
+
+// ================================================================================================================
 // Bounce (bgs_bounce_evaluate_moves): for root i and slot s = x * H * W + c -- the move of the piece in column x of the
 // active row to cell c, bit c of the root's targets[x] -- `playouts` games that start with that move and continue by the
 // uniform random policy, reduced to (wins, draws, losses) of the player to move at root i.  Playout p of slot s of root i
@@ -1937,6 +2231,35 @@ void connect_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget,
         case 1: evaluate_halving_nw<1>(b, g, seed, p, cap, policy, d_counts, d_given, d_best); break;
         case 2: evaluate_halving_nw<2>(b, g, seed, p, cap, policy, d_counts, d_given, d_best); break;
         default: evaluate_halving_nw<3>(b, g, seed, p, cap, policy, d_counts, d_given, d_best); break;
+    }
+}
+
+uint64_t connect_search_root_bytes(int width, int32_t iterations) {
+    return search_root_words((uint32_t)width, (uint32_t)iterations) * sizeof(uint32_t);
+}
+
+template <int NW>
+static void search_nw(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
+                      uint32_t cap, int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace) {
+    constexpr int U = BGS_POLICY_UNIFORM, D = BGS_POLICY_DECISIVE;
+    const bool per_ply = b->rng_per_ply != 0;
+    if (policy == D) {
+        per_ply ? launch_search<NW, true, D>(b, g, seed, iterations, leaf_playouts, explore, cap, d_counts, d_visits, d_best, d_nodes, d_workspace)
+                : launch_search<NW, false, D>(b, g, seed, iterations, leaf_playouts, explore, cap, d_counts, d_visits, d_best, d_nodes, d_workspace);
+    } else {
+        per_ply ? launch_search<NW, true, U>(b, g, seed, iterations, leaf_playouts, explore, cap, d_counts, d_visits, d_best, d_nodes, d_workspace)
+                : launch_search<NW, false, U>(b, g, seed, iterations, leaf_playouts, explore, cap, d_counts, d_visits, d_best, d_nodes, d_workspace);
+    }
+}
+
+void connect_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
+                    int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace) {
+    const EvalGeom g = eval_geom(b);
+    const uint32_t t = (uint32_t)iterations, p = (uint32_t)leaf_playouts, e = (uint32_t)explore, cap = (uint32_t)max_plies;
+    switch (b->cg.nw) {
+        case 1: search_nw<1>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
+        case 2: search_nw<2>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
+        default: search_nw<3>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
     }
 }
 

@@ -10,6 +10,9 @@ and counted in ONE launch: ``ConnectBatch.evaluate_actions`` for Connect states 
 0.5 for a draw, 0.0 for a forced loss, and a fallback agent's value where the search was cut by its horizon or budget.
 Bounce positions go to the horizon search ``BounceBatch.solve_moves`` in the same way (dispatched on the state's type).
 
+``TreeSearchAgent`` grows a UCT tree a Connect position (``ConnectBatch.search_actions``: all positions of a call in one
+launch) and plays the column with the most visits.
+
 ``BounceHalvingAgent`` spends a fixed budget of playouts a Bounce position by sequential halving
 (``BounceBatch.evaluate_moves_halving``) and plays the last surviving move.
 """
@@ -20,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from .batch import (DEFAULT_BOUNCE_SOLVE_DEPTH, DEFAULT_SEED, DEFAULT_SOLVE_NODES, SOLVE_BUDGET, SOLVE_DRAW, SOLVE_LOSS,
+from .batch import (DEFAULT_BOUNCE_SOLVE_DEPTH, DEFAULT_EXPLORE, DEFAULT_SEED, DEFAULT_SOLVE_NODES, SOLVE_BUDGET, SOLVE_DRAW, SOLVE_LOSS,
                     SOLVE_UNKNOWN, SOLVE_WIN, HALVING_SHORT, BounceBatch, ConnectBatch, playout_policy)
 from .game import bounce, connect
 
@@ -215,6 +218,88 @@ class MonteCarloAgent:
         for s, values in zip(states, self.predict_many(states, first_game)):
             out.append(max(s.actions, key=values.get) if s.actions else None)   # (max keeps the first of equal values)
         return out
+
+    def choose(self, state, game: int = 0):
+        """`choose_many` of one state"""
+        return self.choose_many([state], first_game=game)[0]
+
+    def close(self) -> None:
+        for b in self._batches.values():
+            b.close()
+        self._batches.clear()
+
+
+class TreeSearchAgent:
+    """UCT tree search over Connect positions (``simulator.game.connect.State``): ``ConnectBatch.search_actions`` with
+    ``iterations`` iterations and ``leaf_playouts`` playouts a leaf, ``iterations * leaf_playouts`` playouts a position,
+    one launch for all positions of a call.
+
+    ``predict`` / ``predict_many`` map every action of ``state.actions`` to its share of the root's visits (the shares of
+    a state sum to 1); ``choose`` / ``choose_many`` return the column with the most visits (ties: the larger 2 * wins +
+    draws, then the lower column; None for a state without an action).  The playouts of the position at index k of a call
+    are the games ``((first_game + k) * iterations + t) * leaf_playouts + j`` of ``seed``.  ``explore`` is about 45426 *
+    C * C for a UCB1 constant C; ``policy`` is the playout policy, "uniform" or "decisive"; ``max_plies`` caps every
+    playout at that absolute ply count (None: no cap).  Bounce states raise ValueError: the search covers Connect."""
+
+    def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
+                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None):
+        playout_policy(policy)
+        if iterations < 1 or leaf_playouts < 1:
+            raise ValueError("iterations and leaf_playouts must be >= 1")
+        if not 0 <= explore <= 1 << 18:
+            raise ValueError("explore must be 0 .. 2**18")
+        if max_plies is not None and max_plies < 1:
+            raise ValueError("max_plies must be >= 1")
+        self.iterations = int(iterations)
+        self.leaf_playouts = int(leaf_playouts)
+        self.explore = int(explore)
+        self.policy = policy
+        self.seed = int(seed)
+        self.device = int(device)
+        self.max_plies = None if max_plies is None else int(max_plies)
+        self._batches: Dict[tuple, ConnectBatch] = {}
+
+    def search(self, states: Sequence, first_game: int = 0):
+        """(counts, visits, best, nodes) of the launch over `states` (Connect states that share one Config)"""
+        if isinstance(states[0], bounce.State):
+            raise ValueError("TreeSearchAgent: Connect states only; the tree search does not cover Bounce")
+        if not isinstance(states[0], connect.State):
+            raise TypeError(f"TreeSearchAgent: Connect states, not {type(states[0]).__name__}")
+        config = states[0].config
+        if any(type(s) is not type(states[0]) or s.config != config for s in states):
+            raise ValueError("TreeSearchAgent: the states must share one Config")
+        key = (config.height, config.width, config.count, len(states))
+        b = self._batches.get(key)
+        if b is None:
+            b = self._batches[key] = ConnectBatch(config.height, config.width, config.count, len(states), device=self.device)
+        grid = np.stack([s.grid for s in states])
+        player = np.array([s.player for s in states], dtype=np.int8)
+        winner = np.array([-1 if not s.has_ended else int(s.to_json()["winner"]) for s in states], dtype=np.int8)
+        if (b.write_state(grid, player, winner) != 0).any():
+            raise ValueError("TreeSearchAgent: a state could not be loaded")
+        b.set_first_game(first_game)
+        cap = 2**31 - 1 if self.max_plies is None else self.max_plies
+        return b.search_actions(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore,
+                                max_plies=cap, policy=self.policy)
+
+    def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict]:
+        """`predict` of every state, searched in one launch"""
+        if not states:
+            return []
+        visits = self.search(states, first_game)[1]
+        total = self.iterations * self.leaf_playouts
+        return [{a: float(visits[k, a.column]) / total for a in s.actions} for k, s in enumerate(states)]
+
+    def predict(self, state, game: int = 0) -> Dict:
+        """{action: share of the visits} for every action in ``state.actions`` (the keys are those Action objects)"""
+        return self.predict_many([state], first_game=game)[0]
+
+    def choose_many(self, states: Sequence, first_game: int = 0) -> List:
+        """the column with the most visits of every state, of the same launch `predict_many` makes (None: no action)"""
+        if not states:
+            return []
+        best = self.search(states, first_game)[2]
+        return [s.action_at(int(c)) if c >= 0 else None for s, c in zip(states, best)]
 
     def choose(self, state, game: int = 0):
         """`choose_many` of one state"""

@@ -26,6 +26,8 @@ DEFAULT_SEED = 0x0123456789ABCDEF
 # bgs_connect_solve_actions: the codes (include/bgs.h) and the default node budget of one (board, column) search
 SOLVE_NONE, SOLVE_LOSS, SOLVE_DRAW, SOLVE_WIN, SOLVE_UNKNOWN, SOLVE_BUDGET = -2, -1, 0, 1, 2, 3
 DEFAULT_SOLVE_NODES = 1 << 20
+# bgs_connect_search_actions: `explore` for a UCB1 constant of about 1.2 on rewards in [0, 1] (45426 * C * C)
+DEFAULT_EXPLORE = 65536
 # bgs_bounce_solve_moves: the deepest horizon (BGS_BOUNCE_SOLVE_MAX_DEPTH) and the default one
 BOUNCE_SOLVE_MAX_DEPTH = 16
 DEFAULT_BOUNCE_SOLVE_DEPTH = 3
@@ -785,6 +787,7 @@ class ConnectBatch(_Batch):
     def __init__(self, height: int, width: int, count: int, n: int, device: int = 0, use_torch: Optional[bool] = None):
         super().__init__(n, height, width, device, use_torch)
         self.count = int(count)
+        self._search_workspaces = {}   # iterations -> the uint8 device tensor search_actions_tensor allocated
         nbytes = ctypes.c_size_t()
         _abi.check(_abi.lib().bgs_connect_arena_bytes(self.height, self.width, self.count, self.n, ctypes.byref(nbytes)))
         arena, arena_bytes = self._make_arena(nbytes.value)
@@ -882,6 +885,66 @@ class ConnectBatch(_Batch):
             ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["given"].data_ptr()),
             ctypes.c_void_p(outs["best"].data_ptr()), 1))
         return outs["counts"], outs["given"], outs["best"]
+
+    def search_workspace_bytes(self, iterations: int = 256) -> int:
+        """bytes of device memory `search_actions` needs for its trees at `iterations` (bgs_connect_search_workspace_bytes)"""
+        nbytes = ctypes.c_size_t()
+        _abi.check(_abi.lib().bgs_connect_search_workspace_bytes(self._handle, ctypes.c_int32(iterations), ctypes.byref(nbytes)))
+        return nbytes.value
+
+    def search_actions(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE,
+                       max_plies: int = 2**31 - 1, policy: str = "uniform"):
+        """Batched UCT tree search of every board (bgs_connect_search_actions), one launch: (counts int32[n, width, 3],
+        visits int32[n, width], best int32[n], nodes int32[n]).  Every running board is the root of a tree of its own,
+        grown by `iterations` iterations: descend by UCB (integer arithmetic, include/bgs.h) to an edge never played,
+        make its node, play `leaf_playouts` playouts from there by `policy`, and add them to every edge of the path.
+        `explore` is about 45426 * C * C for a UCB1 constant C on rewards in [0, 1] (0: pure exploitation; at most
+        2**18).  `visits` are the playouts through every root column, `counts` their (wins, draws, losses) for the player
+        to move, `best` the column with the most visits (-1 for an ended board), `nodes` the nodes made.  Playout j of
+        iteration t of board i is game ((first_game + i) * iterations + t) * leaf_playouts + j of the batch's RNG contract.
+        The boards are not modified; the library allocates the trees' memory around the call."""
+        code = playout_policy(policy)
+        counts = np.empty((self.n, self.width, 3), dtype=np.int32)
+        visits = np.empty((self.n, self.width), dtype=np.int32)
+        best = np.empty(self.n, dtype=np.int32)
+        nodes = np.empty(self.n, dtype=np.int32)
+        _abi.check(_abi.lib().bgs_connect_search_actions(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
+            ctypes.c_int32(max_plies), code, ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(visits.ctypes.data),
+            ctypes.c_void_p(best.ctypes.data), ctypes.c_void_p(nodes.ctypes.data), None, 0, 0))
+        return counts, visits, best, nodes
+
+    def search_actions_tensor(self, counts=None, visits=None, best=None, nodes=None, seed: int = DEFAULT_SEED, iterations: int = 256,
+                              leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1,
+                              policy: str = "uniform", workspace=None):
+        """`search_actions` into device tensors int32[n, width, 3], int32[n, width], int32[n] and int32[n] (allocated when
+        None), enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes).  Every entry is
+        written.  `workspace`: a contiguous, 256-byte aligned uint8 device tensor of at least
+        `search_workspace_bytes(iterations)` bytes; None: a tensor of the batch's own, allocated on first use and kept per
+        `iterations`.  The workspace needs no preparation, and calls on one stream may share it."""
+        code = playout_policy(policy)
+        t = self._need_torch("search_actions_tensor")
+        shapes = {"counts": (self.n, self.width, 3), "visits": (self.n, self.width), "best": (self.n,), "nodes": (self.n,)}
+        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes}
+        for name, shape in shapes.items():
+            x = outs[name]
+            if x is None:
+                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
+            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        if workspace is None:
+            need = self.search_workspace_bytes(iterations)     # (refuses iterations < 1 before anything is allocated)
+            workspace = self._search_workspaces.get(int(iterations))
+            if workspace is None:
+                workspace = self._search_workspaces[int(iterations)] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
+        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        _abi.check(_abi.lib().bgs_connect_search_actions(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
+            ctypes.c_int32(max_plies), code, ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["visits"].data_ptr()),
+            ctypes.c_void_p(outs["best"].data_ptr()), ctypes.c_void_p(outs["nodes"].data_ptr()),
+            ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
+        return outs["counts"], outs["visits"], outs["best"], outs["nodes"]
 
     def solve_actions(self, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """Exact solve of every column of every board (bgs_connect_solve_actions), one launch: (codes int8[n, width],
@@ -1019,6 +1082,12 @@ class BounceBatch(_Batch):
         raise ValueError("evaluate_actions_halving: Connect batches only (Bounce boards: evaluate_moves)")
 
     evaluate_actions_halving_tensor = evaluate_actions_halving
+
+    def search_actions(self, *args, **kwargs):
+        """Not available for Bounce: the tree search covers bit-packed Connect boards; Bounce has `evaluate_moves_halving`."""
+        raise ValueError("search_actions: Connect batches only (Bounce boards: evaluate_moves_halving)")
+
+    search_actions_tensor = search_workspace_bytes = search_actions
 
     def solve_actions(self, *args, **kwargs):
         """Not available for Bounce: the exact solver covers bit-packed Connect boards (Bounce games can cycle)."""

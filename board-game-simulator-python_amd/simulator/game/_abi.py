@@ -209,6 +209,12 @@ SIGNATURES = {
     "bgs_multi_rollout": (ctypes.c_int, [c_handle, ctypes.c_uint64, ctypes.c_void_p, _u64p]),
     "bgs_multi_destroy": (ctypes.c_int, [c_handle]),
     "bgs_write_state": (ctypes.c_int, [c_handle, _i8p, _i8p, _i8p, _i32p, _i32p]),
+    "bgs_connect_search_workspace_bytes": (ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]),
+    "bgs_connect_search_actions": (
+        ctypes.c_int,
+        [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int],
+    ),
 }
 
 _lib = None

@@ -226,6 +226,51 @@ BGS_API int bgs_connect_evaluate_actions_policy(bgs_batch* b, uint64_t seed, int
  * n * width * budget beyond int64. */
 BGS_API int bgs_connect_evaluate_actions_halving(bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy,
                                                  int32_t* counts, int32_t* given, int32_t* best, int on_device);
+/* Batched UCT tree search (Connect, bit-packed boards only), one launch: for every running board i (the root),
+ * `iterations` (T) iterations of UCT with `leaf_playouts` (P) playouts a leaf.  Everything is integer arithmetic: the
+ * result is defined bit for bit.  The batch's boards are not modified.
+ * Tree.  A node is a position; for every column c it holds n[c] (the playouts that went through edge c), s[c] (the sum of
+ * 2 * wins + draws of those playouts, seen from the player to move at the node) and the child node, if any.  The root is
+ * node 0.
+ * Iteration t (t = 0 .. T-1), from the root, at node v with position p:
+ *   1. L = the legal columns of p, ascending;
+ *   2. if some column of L has n[c] = 0, take the lowest such column (the expansion);
+ *   3. otherwise take the column of L with the largest U(c) = Q(c) + E(c), ties to the lowest column, where
+ *        N    = the sum of n[c] over L,
+ *        Q(c) = floor(s[c] * 2048 / n[c])                     (0 .. 4096; a 64-bit intermediate),
+ *        E(c) = isqrt(floor(explore * lg(N) / n[c]))          (isqrt: the exact floor square root),
+ *        lg(N) = 256 * e + ((N * 256) >> e) - 256, e = floor(log2 N)   (a piecewise-linear log2 in Q8);
+ *      with explore <= 2^18 and N < 2^31, explore * lg(N) fits 32 bits.  explore is about 45426 * C * C for a UCB1
+ *      constant C on rewards in [0, 1];
+ *   4. play c, giving p'.  p' has ended (c won, or filled the board): no node is made and no game is played, all P
+ *      playouts of the iteration have that outcome.  p' is running and n[c] was 0: a new node is made for p' and the
+ *      iteration's playouts start from p'.  p' is running and n[c] > 0: v becomes child[c], back to step 1;
+ *   5. playout j (0 <= j < P) of iteration t of board i is the game G = ((first_game + i) * T + t) * P + j (mod 2^64),
+ *      played from p' exactly as bgs_connect_evaluate_actions_policy plays a game after its forced first column: the
+ *      policy, the batch's RNG contract keyed by (seed, G, absolute ply), the cap max_plies.  If p' already holds
+ *      >= max_plies plies the P playouts are capped at once.  A capped playout scores 0 but counts in n;
+ *   6. every edge (v, c) of the path gets n[c] += P and s[c] += 2 * (playouts won by the player to move at v) + draws.
+ * Outputs.  visits int32[n][width] (may be NULL) = the root's n[c]; counts int32[n][width][3] = (wins, draws, losses) of
+ * the root's mover over the playouts through root column c, capped playouts in none of the three; best int32[n] (may be
+ * NULL) = the root column with the most visits, ties to the larger 2 * wins + draws, then to the lower column; nodes
+ * int32[n] (may be NULL) = the nodes made, the root not counted (at most T).  An ended board: all zeros and best = -1.
+ * Illegal columns: zeros.
+ * bgs_steps gets the transitions of the playouts played, from p' on: the moves of the descent are not counted and a
+ * terminal leaf adds nothing.  A root's results depend on (board, first_game + i) only, so sharding by first_game holds.
+ * Workspace.  The tree lives in caller-owned device memory; bgs_connect_search_workspace_bytes says how much this batch
+ * needs for T iterations (n roots of T + 1 nodes of 3 * width 32-bit words, a root's share rounded up to 256 bytes).  Its
+ * contents need no preparation and mean nothing afterwards.  on_device != 0: workspace is a 256-byte aligned device
+ * pointer of at least that size, the outputs are 16-byte aligned device pointers, and the call is an enqueue on the
+ * batch's stream with no synchronisation and no allocation.  on_device == 0: the outputs are host buffers, filled when the
+ * call returns; workspace may be NULL (the library then allocates and frees it around the call) or a device pointer as
+ * above.
+ * Refused (BGS_ERR_ARG, with a message that says why): a Bounce batch, a generic batch, T < 1, P < 1, T * P > 2^29
+ * (scores stay in int32), explore < 0 or > 2^18, max_plies < 1, an unknown policy, NULL counts, a misaligned pointer, a
+ * workspace that is too small (or NULL with on_device), n * T * P beyond int64. */
+BGS_API int bgs_connect_search_workspace_bytes(const bgs_batch* b, int32_t iterations, size_t* bytes);
+BGS_API int bgs_connect_search_actions(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                                       int32_t max_plies, int policy, int32_t* counts, int32_t* visits, int32_t* best,
+                                       int32_t* nodes, void* workspace, size_t workspace_bytes, int on_device);
 /* Flat Monte-Carlo evaluation of every legal move of every board (Bounce, bit-packed boards only: at most 64 cells,
  * piece values <= 15).  counts int32[n][width][height * width][3]: entry [i][x][c] = (wins, draws, losses) of the
  * player to move at board i over `playouts` games that start with the move of the piece in column x of the active row
