@@ -241,6 +241,29 @@ __device__ __forceinline__ bool four_in_a_row_at(uint64_t b, int h, uint32_t pos
     return ((acc_lo | acc_hi) != 0u) | ((column & 15u) == 15u);
 }
 
+// four_in_a_row_at for geometries where runs_start_low(h, w) holds (connect_unit.h): bit s of the quads is set iff cells
+// s, s + d, s + 2d and s + 3d are the mover's, a non-vertical run spans four columns, so s <= (w - 4)(h + 1) + h - 1 <= 31
+// and the high word of the quads is always zero.  Only the low word of the second shift is needed then -- one
+// v_alignbit_b32 of (ph, pl); 2d <= 2(h + 2) <= 20 < 32 for the h <= 8 of one-word rollouts -- and one accumulator:
+// per direction five VALU instead of six, and no OR of the halves (four VALU a ply less).  The vertical test is
+// four_in_a_row_at's.  (Folding the vertical hit into the accumulator as (column + 1) & 16 was not kept: see
+// docs/EXPERIMENTS.md §26 -- it is wrong on a lane that is not playing.)
+__device__ __forceinline__ bool four_in_a_row_at_low(uint64_t b, int h, uint32_t pos) {
+    const int dirs[3] = {h + 1, h + 2, h};
+    uint32_t acc = 0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const uint64_t s1 = b >> dirs[d];
+        const uint32_t pl = (uint32_t)b & (uint32_t)s1, ph = (uint32_t)(b >> 32) & (uint32_t)(s1 >> 32);
+        uint32_t s2;  // the low word of pairs >> 2d (hipcc would rebuild the 64-bit shift from the two halves)
+        asm("v_alignbit_b32 %0, %1, %2, %3" : "=v"(s2) : "v"(ph), "v"(pl), "s"(2 * dirs[d]));
+        acc = d == 0 ? (pl & s2) : and_or(pl, s2, acc);
+    }
+    uint32_t column = (uint32_t)(b >> ((pos - 3u) & 63u));
+    asm("" : "+v"(column));
+    return (acc != 0u) | ((column & 15u) == 15u);
+}
+
 // The idx-th set bit of `landing` (K1s): `landing` holds at most ONE bit per column field of S = h + 1 bits and never a field's
 // top bit, so the search is arithmetic on the fields instead of the general popcount-guided search (forty instructions of
 // the ply's hundred and fifty; round 5): a field is non-empty iff adding 2^(S-1) - 1 carries into its top bit; the number

@@ -44,6 +44,21 @@ struct Geo {
     __device__ __forceinline__ uint32_t all_columns() const { return (1u << w()) - 1u; }
 };
 
+// the run test of a full ply of the block-aligned one-word rollouts (K2a, K2o and its grouped form; K = 4): on the low
+// word alone where no run can start above it (runs_start_low, connect_unit.h) -- chosen at compile time for a static
+// geometry, by a branch on the kernel's arguments (wave-uniform, no VALU) for a run-time one.  A geometry that fails the
+// predicate keeps four_in_a_row_at.
+template <class G>
+__device__ __forceinline__ bool ply_run_of_four(const G& g, uint64_t mine, uint32_t pos) {
+    if constexpr (G::STATIC_H > 0 && G::STATIC_W > 0) {
+        if constexpr (runs_start_low(G::STATIC_H, G::STATIC_W)) return four_in_a_row_at_low(mine, g.h(), pos);
+        else return four_in_a_row_at(mine, g.h(), pos);
+    } else {
+        if (runs_start_low(g.h(), g.w())) return four_in_a_row_at_low(mine, g.h(), pos);
+        return four_in_a_row_at(mine, g.h(), pos);
+    }
+}
+
 // index of the i-th set bit of m (i < popcount(m))
 __device__ __forceinline__ int select_bit(uint32_t m, uint32_t i, int max_bits) {
     for (int j = 0; j + 1 < max_bits; ++j) {
@@ -820,7 +835,7 @@ k_connect_rollout_aligned(G g, uint64_t* __restrict__ planes, uint8_t* __restric
             open = (hts >> 3) & ONES;
             bool won;
             if (g.k() == 4) {
-                won = four_in_a_row_at(mine, g.h(), pos);
+                won = ply_run_of_four(g, mine, pos);
             } else {
                 Bits<1> b;
                 b.w[0] = mine;
@@ -982,7 +997,7 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
         op = (h4 >> 3) & ONES;
         bool won;
         if (g.k() == 4) {
-            won = four_in_a_row_at(mine, g.h(), pos);
+            won = ply_run_of_four(g, mine, pos);
         } else {
             Bits<1> b;
             b.w[0] = mine;
@@ -1272,7 +1287,7 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
         op = (h4 >> 3) & ONES;
         bool won;
         if (g.k() == 4) {
-            won = four_in_a_row_at(mine, g.h(), pos);
+            won = ply_run_of_four(g, mine, pos);
         } else {
             Bits<1> b;
             b.w[0] = mine;

@@ -16,6 +16,12 @@ constexpr int kRolloutOpeningBlocks = 3;    // K2o: 4-ply blocks played in lock 
 constexpr int kGamesPerLaneOneWord = 8;     // one-word Connect boards: games per lane a launch aims for (512 per wave at 2^20)
 constexpr int kGamesPerLane = 4;            // every other rollout
 
+// Where a four-in-a-row that is not vertical can start on a one-word board (bit(x, y) = x * (h + 1) + y): it spans four
+// columns, so its lowest cell lies in a column <= w - 4 and a row <= h - 1.  When that last start bit is below 32 the
+// rollouts' full ply tests the low word of the board only (four_in_a_row_at_low, connect_board.h): 6x7 (26), 5x8 (28),
+// 7x6 (22) -- not 6x8 (33).  Compile time for a static geometry, a wave-uniform branch for a run-time one.
+constexpr bool runs_start_low(int h, int w) { return (w - 4) * (h + 1) + h - 1 <= 31; }
+
 // Multi-step form of the K2o rollout (k_connect_rollout_opened_steps): one launch plays the batches of up to
 // kConnectGroupMax consecutive pipeline steps, every wave chunk w of each step in turn, its lanes carrying on from one
 // step's chunk into the next instead of idling until the wave's longest game has ended.  The executor hands
