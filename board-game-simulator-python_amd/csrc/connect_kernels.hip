@@ -59,6 +59,28 @@ __device__ __forceinline__ bool ply_run_of_four(const G& g, uint64_t mine, uint3
     }
 }
 
+// Four in a row ANYWHERE on a one-word board where runs_start_low(h, w) holds: non-zero iff b holds one.  The three
+// directions that are not vertical as in four_in_a_row_at_low (the low word of the quads); a vertical run can start in
+// any column, so its quads take both words.  22 VALU -- the deferred opening's one test per player.
+__device__ __forceinline__ uint32_t four_in_a_row_low_hits(uint64_t b, int h) {
+    const int dirs[3] = {h + 1, h + 2, h};
+    uint32_t acc = 0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const uint64_t s1 = b >> dirs[d];
+        const uint32_t pl = (uint32_t)b & (uint32_t)s1, ph = (uint32_t)(b >> 32) & (uint32_t)(s1 >> 32);
+        uint32_t s2;
+        asm("v_alignbit_b32 %0, %1, %2, %3" : "=v"(s2) : "v"(ph), "v"(pl), "s"(2 * dirs[d]));
+        acc = d == 0 ? (pl & s2) : and_or(pl, s2, acc);
+    }
+    const uint64_t s1 = b >> 1;
+    const uint32_t pl = (uint32_t)b & (uint32_t)s1, ph = (uint32_t)(b >> 32) & (uint32_t)(s1 >> 32);
+    const uint64_t pairs = ((uint64_t)ph << 32) | pl;
+    uint64_t s2;
+    asm("v_lshrrev_b64 %0, %1, %2" : "=v"(s2) : "s"(2), "v"(pairs));
+    return and_or(pl, (uint32_t)s2, acc) | (ph & (uint32_t)(s2 >> 32));
+}
+
 // index of the i-th set bit of m (i < popcount(m))
 __device__ __forceinline__ int select_bit(uint32_t m, uint32_t i, int max_bits) {
     for (int j = 0; j + 1 < max_bits; ++j) {
@@ -913,6 +935,116 @@ struct OpenedPool {  // per wave
     uint4 words[QUADS][SLOTS];     // the words of blocks OPEN_BLOCKS, OPEN_BLOCKS + 1, ...
 };
 
+// ---- the deferred opening (docs/EXPERIMENTS.md §27; connect_unit.h: deferred_opening_ok, kDeferredOpeningStages) of K2o
+// and its grouped form, for the compile-time geometry the predicate admits under the per-block contract.
+// The lock-step opening plays cheap plies ONLY.  Right after ply 4 every lane parks its game -- planes, column nibbles
+// with kReplayMark, the words of blocks 1 .. 8 -- in its own pool slot; nothing can have happened by then.  It then plays
+// blocks 1 and 2 blind, notes before the 12th ply whether a column is already closed, and after ply 12 makes one
+// whole-board run test per player: stones are only added, so a run made at plies 7 .. 12 is still there, and a column
+// that closed stays closed.  A lane that saw neither overwrites its slot with the ply-12 state and the words of blocks
+// 3 .. 10 (a store under the lane mask) -- the slot as the per-ply opening left it.  Stage 2 goes on from there in the
+// same way: block 3 blind, the check before ply 16, the two tests, and the lanes clean again overwrite the slot with the
+// ply-16 state and the words of blocks 4 .. 10.  A flagged game stays parked where it last was known good, and the
+// refill loop -- which plays any game exactly from any block boundary, its draws keyed by (seed, game, block) -- replays
+// it: every game ends in the loop, once, and the opening stores no board and no outcome.  What a flagged lane plays on
+// after its flag is garbage that never leaves the lane (stage 2 keeps its shifts defined with pos & 63).
+// A game replayed from block 1 holds the words of blocks 1 .. 8 only: see refetch in the kernels.
+constexpr uint32_t kReplayMark = 1u << 28;       // in a slot's column nibbles (the eighth nibble: w <= 7): parked after ply 4
+constexpr uint32_t kReplayRow = 0x80000000u;     // the same in a lane's wrow (row * BGS_WAVE drops it: unsigned wrap)
+
+template <class G, int OPEN_BLOCKS, bool PER_PLY>
+constexpr bool deferred_opening() {
+    if constexpr (G::STATIC_H > 0 && G::STATIC_W > 0 && G::STATIC_K > 0)
+        return !PER_PLY && kDeferredOpeningStages > 0 && OPEN_BLOCKS == kRolloutOpeningBlocks && kRolloutOpeningBlocks == 3 &&
+               deferred_opening_ok(G::STATIC_H, G::STATIC_W, G::STATIC_K);
+    else
+        return false;
+}
+
+// all 64 lanes open 64 games into their pool slots; `mine`: the lane's game is inside the chunk (else: a dead slot)
+template <class G, class Pool>
+__device__ __forceinline__ void open_games_deferred(const G& g, Pool& pool, uint32_t slot, uint64_t seed, uint64_t id, bool mine) {
+    constexpr uint32_t ONES = 0x11111111u;
+    const uint32_t top = (uint32_t)g.h() + 7u;
+    const uint32_t columns = ONES & ((1u << (4 * g.w())) - 1u);
+    const uint32_t stride = (uint32_t)g.h() + 1u;
+    uint64_t q[2] = {0, 0};
+    uint32_t h4 = top * columns;
+    auto cheap_ply = [&](uint32_t j, uint32_t draw, bool wrap) {
+        const uint32_t col = sample_index(draw, (uint32_t)g.w());
+        const uint32_t sh = col * 4u;
+        const uint32_t v = (h4 >> sh) & 15u;
+        uint32_t pos = col * stride + top - v;
+        if (wrap) pos &= 63u;   // (a lane flagged before may have borrowed into the nibble above: garbage, but a defined shift)
+        q[j & 1u] |= 1ull << pos;
+        h4 -= 1u << sh;
+    };
+    // a block of four cheap plies; true iff a column was already closed when the last of them drew
+    auto blind_block = [&](uint32_t word, bool wrap) -> bool {
+        cheap_ply(0u, sub_draw<0>(word), wrap);
+        cheap_ply(1u, sub_draw<1>(word), wrap);
+        cheap_ply(2u, sub_draw<2>(word), wrap);
+        const bool closed = ((h4 >> 3) & ONES) != columns;
+        cheap_ply(3u, sub_draw<3>(word), wrap);
+        return closed;
+    };
+    auto park = [&](uint32_t cols, const uint4& lo, const uint4& hi) {
+        pool.plane[0][slot] = q[0];
+        pool.plane[1][slot] = q[1];
+        pool.cols[slot] = cols;
+        pool.words[0][slot] = lo;
+        pool.words[1][slot] = hi;
+    };
+    const Philox4 a = philox4x32_10(seed, id, 0u);   // the words of blocks 0 .. 3
+    cheap_ply(0u, sub_draw<0>(a.v[0]), false);
+    cheap_ply(1u, sub_draw<1>(a.v[0]), false);
+    cheap_ply(2u, sub_draw<2>(a.v[0]), false);
+    cheap_ply(3u, sub_draw<3>(a.v[0]), false);
+    // The words do not stay in registers over the blind plies (the grouped kernel has none to spare): each goes to the slot
+    // as soon as it is made, one philox call after the other, and a lane reads back what it parked -- LDS traffic, not VALU.
+    // (The asm statements: hipcc would interleave the calls and forward the stored registers to the reads.)
+    uint32_t* const slot_words0 = reinterpret_cast<uint32_t*>(&pool.words[0][slot]);
+    uint32_t* const slot_words1 = reinterpret_cast<uint32_t*>(&pool.words[1][slot]);
+    slot_words0[0] = a.v[1]; slot_words0[1] = a.v[2]; slot_words0[2] = a.v[3];
+    uint64_t id_after = id;
+    asm volatile("" : "+v"(id_after) : : "memory");
+    uint32_t word9, word10;
+    {
+        Philox4 c = philox4x32_10(seed, id_after, 2u);   // blocks 8 .. 10
+        slot_words1[3] = c.v[0];
+        word9 = c.v[1];
+        word10 = c.v[2];
+        asm volatile("" : "+v"(id_after), "+v"(word9), "+v"(word10) : : "memory");
+    }
+    {
+        const Philox4 b = philox4x32_10(seed, id_after, 1u);   // blocks 4 .. 7
+        slot_words0[3] = b.v[0];
+        slot_words1[0] = b.v[1]; slot_words1[1] = b.v[2]; slot_words1[2] = b.v[3];
+    }
+    pool.plane[0][slot] = q[0];
+    pool.plane[1][slot] = q[1];
+    pool.cols[slot] = mine ? (h4 | kReplayMark) : 0u;
+    asm volatile("" ::: "memory");
+    blind_block(slot_words0[0], false);
+    const bool closed = blind_block(slot_words0[1], false);
+    const uint32_t hits = four_in_a_row_low_hits(q[0], g.h()) | four_in_a_row_low_hits(q[1], g.h());
+    const bool clean = mine && !closed && hits == 0u;
+    if (clean) {   // words 1 .. 8 -> 3 .. 10
+        const uint4 lo = pool.words[0][slot], hi = pool.words[1][slot];
+        park(h4, make_uint4(lo.z, lo.w, hi.x, hi.y), make_uint4(hi.z, hi.w, word9, word10));
+    }
+    if constexpr (kDeferredOpeningStages >= 2) {
+        asm volatile("" ::: "memory");
+        // (word 3 is the first word of a clean lane's slot now; a flagged lane reads some other word and plays garbage)
+        const bool closed2 = blind_block(slot_words0[0], true);
+        const uint32_t hits2 = four_in_a_row_low_hits(q[0], g.h()) | four_in_a_row_low_hits(q[1], g.h());
+        if (clean && !closed2 && hits2 == 0u) {   // words 3 .. 10 -> 4 .. 10
+            const uint4 lo = pool.words[0][slot], hi = pool.words[1][slot];
+            park(h4, make_uint4(lo.y, lo.z, lo.w, hi.x), make_uint4(hi.y, hi.z, hi.w, 0u));
+        }
+    }
+}
+
 // PER_PLY (round 6): the same kernel under the strict RNG contract -- a philox word per ply.  Nothing is parked beside a
 // board: a block makes its own philox call (its four words are its draws), the opening one per block.
 template <class G, int OPEN_BLOCKS, bool CODES, bool PER_PLY>
@@ -923,6 +1055,8 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
     using OW = OpenedWords<G, OPEN_BLOCKS, PER_PLY>;
     constexpr int NWORDS = OW::QUADS * 4;
     using Pool = OpenedPool<OW::QUADS>;
+    constexpr bool DEFER = deferred_opening<G, OPEN_BLOCKS, PER_PLY>();
+    static_assert(!DEFER || NWORDS == 8, "a replayed game refills rows 5 .. 7 with the words of blocks 8 .. 10");
     extern __shared__ uint32_t code_lds[];  // one outcome BYTE per game of the wave's chunk: games_per_wave / 4 dwords per wave
     __shared__ Pool pools[BGS_BLOCK / BGS_WAVE];
     // the words of a lane's blocks to come, [word][lane] per wave (the bank is the lane: no conflicts whatever word a lane
@@ -1021,6 +1155,21 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
         q[j & 1u] |= 1ull << pos;
         h4 -= 1u << sh;
     };
+    // The deferred opening parks a replayed game with the words of blocks 1 .. 8; it can last to block 10.  Such a lane
+    // carries kReplayRow in wrow until it is about to read its last row (the word of block 8): then, behind a wave-uniform
+    // branch almost never taken, it makes philox call 2 of its own game, lays the words of blocks 8, 9 and 10 into rows
+    // 5 .. 7 and goes on from row 5 as any other lane.  A replayed lane whose game has ended only drops the mark.
+    auto refetch = [&](uint64_t lane_seed, uint64_t id) {
+        if (wrow == (kReplayRow | 7u)) {
+            if (live != 0u) {
+                const Philox4 d = philox4x32_10(lane_seed, id, 2u);
+                my_words[5 * BGS_WAVE] = d.v[0];
+                my_words[6 * BGS_WAVE] = d.v[1];
+                my_words[7 * BGS_WAVE] = d.v[2];
+            }
+            wrow = 5u;
+        }
+    };
     // one block of four plies on this lane's board from the word w[0], then boards that ended go to memory (their status
     // and reward follow from the codes); the lane's words move down one
     auto play_block = [&]() {
@@ -1030,6 +1179,12 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
         if constexpr (PER_PLY) {
             four = philox4x32_10(seed, first_game + (uint64_t)(begin + game), myblk);
             myblk += 1u;
+        } else if constexpr (DEFER) {
+            word = wnext;
+            if (__builtin_amdgcn_ballot_w64(wrow == (kReplayRow | 7u))) refetch(seed, first_game + (uint64_t)(begin + game));
+            wnext = my_words[wrow * BGS_WAVE];   // (the product drops kReplayRow)
+            const int32_t up = (int32_t)(wrow + 1u);   // signed: a replayed lane does not saturate, it refetches at row 7
+            wrow = (uint32_t)(up < NWORDS - 1 ? up : NWORDS - 1);
         } else {
             word = wnext;
             wnext = my_words[wrow * BGS_WAVE];   // (used by the NEXT block: the read has a whole block to arrive)
@@ -1065,14 +1220,19 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
                 my_words[(4 * k + 3) * BGS_WAVE] = v.w;
             }
         }
-        wrow = 1u;
+        wrow = DEFER ? 1u | ((hts << 3) & kReplayRow) : 1u;   // (kReplayMark moves up into kReplayRow)
         anywon = false;
-        live = hts != 0u ? ~0u : 0u;  // (a dead slot: the opening stage has stored that game)
+        live = hts != 0u ? ~0u : 0u;  // (a dead slot: the opening stage has stored that game, or it lies past the chunk)
     };
     // all 64 lanes open the chunk's next 64 games (blocks 0 .. OPEN_BLOCKS - 1 in lock step) and park them with their words
     auto open_games = [&]() {
         const uint32_t og = opened + lane;
         const uint64_t id = first_game + (uint64_t)(begin + og);
+        if constexpr (DEFER) {
+            open_games_deferred(g, pool, og & (Pool::SLOTS - 1u), seed, id, og < avail);
+            opened += 64u;
+            return;
+        }
         uint64_t q[2] = {0, 0};
         uint32_t h4 = top * columns, alive = ~0u, op = columns;
         bool won_any = false;
@@ -1212,6 +1372,8 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
     using OW = OpenedWords<G, OPEN_BLOCKS, false>;
     constexpr int NWORDS = OW::QUADS * 4;
     using Pool = OpenedPool<OW::QUADS>;
+    constexpr bool DEFER = deferred_opening<G, OPEN_BLOCKS, false>();
+    static_assert(!DEFER || NWORDS == 8, "a replayed game refills rows 5 .. 7 with the words of blocks 8 .. 10");
     extern __shared__ uint32_t code_lds[];  // two outcome slices per wave, games_per_wave bytes each
     __shared__ Pool pools[BGS_BLOCK / BGS_WAVE];
     __shared__ uint32_t lane_words[BGS_BLOCK / BGS_WAVE][NWORDS][BGS_WAVE];
@@ -1237,6 +1399,7 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
     uint64_t cur_seed = tab.step[0].seed, cur_first = tab.step[0].first_game;
     uint64_t* cur_planes = tab.step[0].planes ? tab.step[0].planes + begin : nullptr;
     uint64_t* prev_planes = nullptr;
+    uint64_t prev_seed = 0, prev_first = 0;   // step cur - 1's, for the refetch of an `old` lane (deferred opening)
 
     uint64_t p[2] = {0, 0};
     uint32_t hts = 0, live = 0, game = 0;
@@ -1311,11 +1474,35 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
         q[j & 1u] |= 1ull << pos;
         h4 -= 1u << sh;
     };
+    // a replayed game's words of blocks 8 .. 10 (see k_connect_rollout_opened).  The lane's game is of step cur or of step
+    // cur - 1: a pass for each, so that the seed stays wave-uniform and philox's key schedule in SGPRs
+    auto refetch = [&]() {
+        const bool at = wrow == (kReplayRow | 7u);
+#pragma unroll
+        for (uint32_t o = 0; o < 2u; ++o) {
+            const bool here = at && live != 0u && old == o;
+            if (__builtin_amdgcn_ballot_w64(here) == 0) continue;
+            if (here) {
+                const Philox4 d = philox4x32_10(o ? prev_seed : cur_seed, (o ? prev_first : cur_first) + (uint64_t)(begin + game), 2u);
+                my_words[5 * BGS_WAVE] = d.v[0];
+                my_words[6 * BGS_WAVE] = d.v[1];
+                my_words[7 * BGS_WAVE] = d.v[2];
+            }
+        }
+        if (at) wrow = 5u;
+    };
     auto play_block = [&]() {
         const uint32_t was_live = live;
         const uint32_t word = wnext;
-        wnext = my_words[wrow * BGS_WAVE];
-        wrow = wrow + 1u < (uint32_t)NWORDS - 1u ? wrow + 1u : (uint32_t)NWORDS - 1u;
+        if constexpr (DEFER) {
+            if (__builtin_amdgcn_ballot_w64(wrow == (kReplayRow | 7u))) refetch();
+            wnext = my_words[wrow * BGS_WAVE];
+            const int32_t up = (int32_t)(wrow + 1u);
+            wrow = (uint32_t)(up < NWORDS - 1 ? up : NWORDS - 1);
+        } else {
+            wnext = my_words[wrow * BGS_WAVE];
+            wrow = wrow + 1u < (uint32_t)NWORDS - 1u ? wrow + 1u : (uint32_t)NWORDS - 1u;
+        }
         uint32_t open = (hts >> 3) & ONES;
         full_ply(std::integral_constant<uint32_t, 0>{}, sub_draw<0>(word), p, hts, open, live, anywon);
         full_ply(std::integral_constant<uint32_t, 1>{}, sub_draw<1>(word), p, hts, open, live, anywon);
@@ -1347,7 +1534,7 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
             my_words[(4 * k + 2) * BGS_WAVE] = v.z;
             my_words[(4 * k + 3) * BGS_WAVE] = v.w;
         }
-        wrow = 1u;
+        wrow = DEFER ? 1u | ((hts << 3) & kReplayRow) : 1u;
         anywon = false;
         live = hts != 0u ? ~0u : 0u;
     };
@@ -1355,6 +1542,11 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
     auto open_games = [&]() {
         const uint32_t og = opened + lane;
         const uint64_t id = cur_first + (uint64_t)(begin + og);
+        if constexpr (DEFER) {
+            open_games_deferred(g, pool, og & (Pool::SLOTS - 1u), cur_seed, id, og < avail);
+            opened += 64u;
+            return;
+        }
         uint64_t q[2] = {0, 0};
         uint32_t h4 = top * columns, alive = ~0u, op = columns;
         bool won_any = false;
@@ -1436,6 +1628,9 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
         }
         if (CODES) {
             uint8_t* __restrict__ const packed_out = reinterpret_cast<uint8_t*>(e.codes) + (begin >> 2);
+            // (two trips at 512 games a wave: unrolled by four, hipcc's choice, this loop alone took the kernel past 80 VGPRs
+            // once play_block held the refetch branch)
+#pragma unroll 1
             for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
                 const uint32_t four = reinterpret_cast<const uint32_t*>(outcome)[g4 >> 2];
                 packed_out[g4 >> 2] = (uint8_t)((four & 3u) | ((four >> 6) & 0xCu) | ((four >> 12) & 0x30u) | ((four >> 18) & 0xC0u));
@@ -1482,6 +1677,8 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
                 // open and take the first games of the next step
                 old = 1u;
                 prev_planes = cur_planes;
+                prev_seed = cur_seed;
+                prev_first = cur_first;
                 cur = __builtin_amdgcn_readfirstlane(cur + 1u);
                 pending = true;
                 cur_seed = tab.step[cur].seed;

@@ -22,6 +22,27 @@ constexpr int kGamesPerLane = 4;            // every other rollout
 // 7x6 (22) -- not 6x8 (33).  Compile time for a static geometry, a wave-uniform branch for a run-time one.
 constexpr bool runs_start_low(int h, int w) { return (w - 4) * (h + 1) + h - 1 <= 31; }
 
+// The deferred opening of K2o and its grouped form (docs/EXPERIMENTS.md §27): blocks 1 .. 2 (and 3) of the lock-step
+// opening are played with cheap plies only -- every column taken as open, no run test -- and ONE whole-board run test
+// per player after the block stands for its per-ply tests (stones are only added: a run made at an earlier ply is still
+// there, a column that closed stays closed).  A game the test or the closed-column check flags is parked at its state
+// after ply 4 (or at the stage's checkpoint) and replayed exactly by the refill loop.  What a geometry must give:
+//   * K = 4 on a one-word board whose runs start in the low word (the whole-board test is four_in_a_row_low_hits), at
+//     most 7 columns (bit 28 of the column nibbles marks a replayed game) of at most 8 rows (a nibble holds h + 7);
+//   * no win and no full column within plies 1 .. 4, what the parked state rests on: 2k - 1 > 4 and h > 4;
+//   * the column nibbles (h + 7 less the column's stones) cannot borrow within the twelve plies every lane plays, run
+//     or no run, closed column or not: h + 7 >= 12.  (Stage 2's four more plies are played on from boards whose columns
+//     held at most h stones after ply 12; the lanes flagged before keep their shifts defined with pos & 63.);
+//   * a game of at most 44 cells, blocks 0 .. 10: the eight words parked with a replayed game (blocks 1 .. 8) and the
+//     three it fetches when they run out (blocks 8 .. 10) cover it.
+constexpr bool deferred_opening_ok(int h, int w, int k) {
+    return k == 4 && w >= 4 && w <= 7 && h <= 8 && w * (h + 1) <= 64 && runs_start_low(h, w) && 2 * k - 1 > 4 && h > 4 &&
+           h + 7 >= 12 && h * w <= 44;
+}
+// speculative stages of the deferred opening: 1 = plies 5 .. 12 (blocks 1 and 2), 2 = block 3 as well, from the ply-12
+// checkpoint; 0 = the opening as it was.  kRolloutOpeningBlocks stays 3 either way: it is what every other path plays.
+constexpr int kDeferredOpeningStages = 2;
+
 // Multi-step form of the K2o rollout (k_connect_rollout_opened_steps): one launch plays the batches of up to
 // kConnectGroupMax consecutive pipeline steps, every wave chunk w of each step in turn, its lanes carrying on from one
 // step's chunk into the next instead of idling until the wave's longest game has ended.  The executor hands

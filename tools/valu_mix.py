@@ -39,12 +39,33 @@ def block_mix(body):
     return {"valu_instructions": total, "mix_cycles_per_instruction": cycles / total, "top_opcodes": dict(ops.most_common(12))}
 
 
+def straight_line_region(all_blocks, first):
+    """The blocks a wave runs through from block `first` on without a scalar decision: a block is followed by the next
+    one in layout as long as its only branch is an `s_cbranch_execz` to that next block -- a store under the lane mask
+    (the deferred opening parks its games that way: its stages are one region, not one basic block)."""
+    region = [first]
+    while region[-1] + 1 < len(all_blocks):
+        name_next = all_blocks[region[-1] + 1][0]
+        branches = [l.split() for l in all_blocks[region[-1]][1] if l.startswith(("s_cbranch", "s_branch", "s_setpc", "s_endpgm"))]
+        if not branches or any(b[0] != "s_cbranch_execz" or b[1] != name_next for b in branches):
+            break
+        region.append(region[-1] + 1)
+    return region
+
+
 def mix(path, sym):
-    """The two big basic blocks of K2o: the opening stage (run once per 64 games) and the 4-ply loop body."""
-    big = sorted(blocks(path, sym), key=lambda nb: -len(nb[1]))[:2]
-    opening, loop = (block_mix(big[0][1]), block_mix(big[1][1]))
+    """The two hot pieces of K2o: the opening stage (run once per 64 games; since the deferred opening a straight-line
+    region of several basic blocks) and the 4-ply loop body (the largest block outside it)."""
+    all_blocks = blocks(path, sym)
+    order = sorted(range(len(all_blocks)), key=lambda i: -len(all_blocks[i][1]))
+    region = straight_line_region(all_blocks, order[0])
+    second = next(i for i in order if i not in region)
+    opening = block_mix([l for i in region for l in all_blocks[i][1]])
+    loop = block_mix(all_blocks[second][1])
     if opening["valu_instructions"] < loop["valu_instructions"]:
         opening, loop = loop, opening
+    else:
+        opening["basic_blocks"] = {all_blocks[i][0]: block_mix(all_blocks[i][1])["valu_instructions"] for i in region}
     return {"opening_block": opening, "loop_body": loop,
             # (kept for readers of round-2 files: the loop body's figures under the old names)
             "valu_instructions_in_loop_body": loop["valu_instructions"],
