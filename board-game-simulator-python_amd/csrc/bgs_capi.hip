@@ -1299,6 +1299,92 @@ int bgs_bounce_evaluate_moves_halving(bgs_batch* b, uint64_t seed, int32_t budge
     return BGS_OK;
 }
 
+// the checks of both Bounce search entry points that need no device; *bytes: the workspace of the batch
+static int bounce_search_check(const bgs_batch* b, int32_t iterations, int32_t edges, size_t* bytes) {
+    NEED(b->game == BGS_GAME_BOUNCE, "search_moves: Bounce batches only (Connect boards: bgs_connect_search_actions)");
+    NEED(!b->generic, "search_moves: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
+         BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
+    NEED(iterations >= 1, "iterations must be >= 1 (got %d)", iterations);
+    const int32_t least = BGS_BOUNCE_SEARCH_MIN_EDGES(b->bg.h, b->bg.w);
+    NEED(edges >= least, "edges must be >= BGS_BOUNCE_SEARCH_MIN_EDGES(%d, %d) = %d, the most arms a position can have (got %d)", b->bg.h,
+         b->bg.w, least, edges);
+    const uint64_t root = bgs::bounce_search_root_bytes(iterations, edges);
+    NEED((uint64_t)b->n <= (uint64_t)(SIZE_MAX / 2) / root, "the workspace of %lld boards x %d iterations x %d edges overflows size_t",
+         (long long)b->n, iterations, edges);
+    *bytes = (size_t)((uint64_t)b->n * root);
+    return BGS_OK;
+}
+
+int bgs_bounce_search_workspace_bytes(const bgs_batch* b, int32_t iterations, int32_t edges, size_t* bytes) {
+    NEED(b != nullptr, "batch is NULL");
+    NEED(bytes != nullptr, "bytes is NULL");
+    return bounce_search_check(b, iterations, edges, bytes);
+}
+
+int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
+                            int policy, int32_t edges, int32_t* counts, int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used,
+                            void* workspace, size_t workspace_bytes, int on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(counts != nullptr, "counts is NULL");
+    size_t need = 0;
+    rc = bounce_search_check(b, iterations, edges, &need);
+    if (rc) return rc;
+    NEED(leaf_playouts >= 1, "leaf_playouts must be >= 1 (got %d)", leaf_playouts);
+    NEED((int64_t)iterations * leaf_playouts <= ((int64_t)1 << 29),
+         "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
+    NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "search_moves: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
+         (long long)b->n, iterations, leaf_playouts);
+    const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;
+    if (on_device) {
+        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(visits) & 15u) == 0, "device visits must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(nodes) & 15u) == 0, "device nodes must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(used) & 15u) == 0, "device used must be 16-byte aligned");
+        NEED(workspace != nullptr, "workspace is NULL (on_device: the caller owns it; bgs_bounce_search_workspace_bytes says how large)");
+        NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
+        NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
+        bgs::bounce_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, counts, visits, best, nodes, used,
+                           workspace);
+        return finish_launch();
+    }
+    if (workspace != nullptr) {
+        NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
+        NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
+    }
+    // one device buffer: counts, visits, best, nodes, used -- each 16-byte aligned -- and the workspace when the caller gave none
+    const auto up = [](size_t x, size_t a) { return (x + a - 1) & ~(a - 1); };
+    const size_t counts_bytes = cells * 3 * sizeof(int32_t), visits_bytes = cells * sizeof(int32_t), board_bytes = (size_t)b->n * sizeof(int32_t);
+    const size_t visits_off = up(counts_bytes, 16), best_off = visits_off + up(visits_bytes, 16), nodes_off = best_off + up(board_bytes, 16);
+    const size_t used_off = nodes_off + up(board_bytes, 16);
+    // the library's own workspace starts at the first 256-byte boundary behind the outputs, wherever the pool put `d`
+    const size_t tree_room = workspace ? 0 : need + 256;
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), used_off + board_bytes + tree_room, b->stream));
+    uint8_t* const own = reinterpret_cast<uint8_t*>(up(reinterpret_cast<uintptr_t>(d + used_off + board_bytes), 256));
+    bgs::bounce_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, reinterpret_cast<int32_t*>(d),
+                       visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
+                       best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr,
+                       nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr,
+                       used ? reinterpret_cast<int32_t*>(d + used_off) : nullptr, workspace ? workspace : own);
+    rc = finish_launch();
+    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
+    if (rc == BGS_OK && visits) rc = copy_to_host(b, visits, d + visits_off, visits_bytes);
+    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, board_bytes);
+    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d + nodes_off, board_bytes);
+    if (rc == BGS_OK && used) rc = copy_to_host(b, used, d + used_off, board_bytes);
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
 int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
                            int on_device) {
     int rc = enter(b);

@@ -155,6 +155,15 @@ void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_
 // given are zeroed here, best is written for every board; no scratch; enqueued on the batch's stream
 void bounce_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* d_counts,
                              int32_t* d_given, int32_t* d_best);
+// UCT tree search over packed Bounce boards (bgs_bounce_search_moves): counts int32[n][w][h * w][3], visits
+// int32[n][w][h * w], best, nodes and used int32[n] (all but counts may be NULL) on the device; counts and visits are
+// zeroed here, the per-board outputs are written for every board; edges >= BGS_BOUNCE_SEARCH_MIN_EDGES(h, w);
+// d_workspace: n * bounce_search_root_bytes(iterations, edges) bytes, 256-byte aligned, no preparation needed; enqueued
+// on the batch's stream
+uint64_t bounce_search_root_bytes(int32_t iterations, int32_t edges);
+void bounce_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
+                   int policy, int32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
+                   void* d_workspace);
 // exact horizon search of every legal move of packed Bounce boards (bgs_bounce_solve_moves): codes int8[n][w][h * w] and
 // plies int16[n][w][h * w] (may be NULL) are filled here (illegal slots NONE / 0), *d_nodes = positions visited; scratch
 // as bounce_evaluate; depth 1 .. BGS_BOUNCE_SOLVE_MAX_DEPTH; device pointers, enqueued on the batch's stream

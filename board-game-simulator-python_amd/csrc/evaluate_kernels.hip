@@ -1443,6 +1443,441 @@ void launch_bounce_evaluate_halving(const bgs_batch* b, const GEO& g, uint64_t s
     }
 }
 
+// ================================================================================================================
+// UCT tree search for Bounce (bgs_bounce_search_moves, include/bgs.h): k_connect_search's iteration with "column" read as
+// "arm", for a game whose nodes have 1 .. 512 arms and whose descents have no h * w bound.
+//
+// Shape.  One workgroup of BGS_BLOCK lanes owns one root for the whole launch, as in k_bounce_evaluate_halving (the move
+// tile's stride is BGS_BLOCK whatever the team).  The descent is team-uniform: every lane holds the position p and
+// applies the same stored moves to it.
+//
+// The tree lives in the caller's workspace, per root: a pool of `edges` edges of four words (n, s, child or outcome,
+// source cell << 8 | target cell), a node table of iterations + 1 entries (first edge, arms) and the descent path
+// (iterations + 1 edge indices: iteration t passes through the root and at most t made nodes).  A node's arms are the A
+// consecutive edges from its first edge, in canonical order; they are written once, when the node is made (movable, and
+// reach by lane x, as the halving kernel's root set-up), so a descent replays stored moves and never searches the moves
+// of a node it has been through.  The third word of an edge is 0 (no child yet), a node index 1 .. T, kEdgeEnded | the
+// BGS_ST_* code of the game the edge ends (the outcome is kept absolute, not relative to the mover: nothing needs the
+// relative form) or kEdgeCapped (p' is running and holds the cap: no node, now or later): revisiting an edge that ends the
+// game or is capped costs no move search either.
+//
+// A descent step: the lanes read the node's edges strided (at most two a lane), reduce the lowest arm with n = 0 and
+// N = sum n over the waves (shuffles) and the team (one LDS word a wave), and without an unplayed arm reduce the key
+// (U << 9 | 511 - arm) + 1 the same way (U < 2^17).  The reduction words are double-buffered by the parity of the depth:
+// every step has at least one barrier, so a wave cannot write a buffer that another wave still reads.
+//
+// The leaf's P playouts are the halving kernel's refill loop and ply, unchanged in their draws: the waves draw playouts
+// from a counter in LDS, refill idle lanes at ply boundaries, count W/D/L of the root's mover in registers and add them
+// to an LDS tally when the leaf is played out.  Lane k then updates edge k of the path.
+//
+// Ordering.  The tree, the node table and the path are written by some lanes and read by others, always of this
+// workgroup: a __syncthreads() stands between every writer and its next reader (barriers A, B, C below, and the barriers
+// of the descent).  Global memory beyond the workspace: the root, the outputs (counts and visits zeroed by the launcher:
+// illegal slots are never stored; counts is accumulated by lane 0 alone) and the step counter, the only global atomic.
+//
+// Known limit: a root has one team, so a launch of few roots leaves most CUs idle, and leaf_playouts < BGS_BLOCK leaves
+// lanes idle.
+// ================================================================================================================
+constexpr uint32_t kEdgeWords = 4;
+constexpr uint32_t kEdgeEnded = 0xFFFFFFF0u;      // | BGS_ST_*: the edge ends the game (1, 2: the winner + 1; 3: a draw)
+constexpr uint32_t kEdgeCapped = 0xFFFFFFFFu;     // the position behind the edge runs and holds the cap
+constexpr uint32_t kNoArm = 0xFFFFu;
+constexpr int kSearchTeamWaves = BGS_BLOCK / BGS_WAVE;
+static_assert(kBounceHalvingMaxArms <= 2 * BGS_BLOCK, "a lane holds at most two arms of a node");
+static_assert((uint32_t)BGS_ST_DRAW < 15u, "an outcome code fits the low bits of kEdgeEnded and stays below kEdgeCapped");
+
+// words of a root's share of the workspace: the edge pool, the node table, the path; rounded up to 256 bytes
+__host__ __device__ __forceinline__ uint64_t bounce_search_root_words(uint32_t iterations, uint32_t edges) {
+    return ((uint64_t)edges * kEdgeWords + ((uint64_t)iterations + 1u) * 3u + 63u) & ~(uint64_t)63u;
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, BGS_WAVE);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, BGS_WAVE);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, BGS_WAVE);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+template <class GEO, int NC, int POLICY>
+__global__ void __launch_bounds__(BGS_BLOCK)
+k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, const uint16_t* __restrict__ plies_buf,
+                int64_t n, uint64_t seed, uint64_t game_base, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
+                uint32_t max_plies, uint32_t edges, uint32_t slots, int64_t root_base, uint32_t* workspace, int32_t* counts,
+                int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used_out, unsigned long long* __restrict__ steps) {
+    extern __shared__ uint32_t target_tile[];                      // [2 * 8 * NC dwords][256 lanes]
+    __shared__ uint64_t node_targets[8 * NC];                      // targets of the piece in column x of the active row of p'
+    __shared__ uint64_t other_targets[8 * NC];                     // ... of the side that has just moved, when p' is blocked
+    __shared__ uint32_t red_min[2][kSearchTeamWaves], red_sum[2][kSearchTeamWaves], red_key[2][kSearchTeamWaves];
+    __shared__ uint32_t tally[3];                                  // W/D/L of the iteration's playouts, for the root's mover
+    __shared__ uint32_t next_item;                                 // the leaf's next playout
+    uint32_t* const column = target_tile + threadIdx.x;
+    const uint32_t tid = threadIdx.x, lane = threadIdx.x & (BGS_WAVE - 1), wave = threadIdx.x / BGS_WAVE;
+    const uint32_t hw = (uint32_t)(g.h * g.w);
+    const int64_t i = root_base + (int64_t)blockIdx.x;             // (the grid holds exactly the roots of this launch)
+    uint32_t* const pool = workspace + (uint64_t)i * bounce_search_root_words(iterations, edges);
+    uint32_t* const node_tab = pool + (uint64_t)edges * kEdgeWords;             // node v: first edge, arms
+    uint32_t* const path = node_tab + ((uint64_t)iterations + 1u) * 2u;         // edge k of the descent
+    const auto uniform = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+
+    // the targets of `player`'s pieces on `bd`, the piece in column x by lane x, into dst (complete behind the caller's
+    // barrier); returns the cell of column 0 of the active row
+    const auto spread = [&](const Board& bd, uint64_t occ, uint32_t player, bool live, uint64_t* dst) {
+        const uint64_t sources = live ? movable(g, occ, player) : 0ull;
+        const uint32_t first_source = sources ? (uint32_t)(__ffsll((unsigned long long)sources) - 1) : 0u;
+        const uint32_t base = ((first_source * g.inv_w) >> 16) * (uint32_t)g.w;
+        if (tid < 8 * NC) {
+            const bool piece = tid < (uint32_t)g.w && ((sources >> ((base + tid) & 63u)) & 1ull);
+            dst[tid] = piece ? reach(g, bd, occ, player, (int)(base + tid)) : 0ull;
+        }
+        return base;
+    };
+    const auto count_arms = [&](const uint64_t* t) {
+        uint32_t arms = 0;
+        for (uint32_t x = 0; x < 8 * NC; ++x) arms += (uint32_t)__popcll(t[x]);
+        return uniform(arms);
+    };
+    // the arm table of a new node: `arms` fresh edges from edge `first`, in canonical order (first + arms <= edges)
+    const auto make_arms = [&](uint32_t first, uint32_t arms, uint32_t base) {
+        for (uint32_t a = tid; a < arms; a += BGS_BLOCK) {
+            uint32_t j = a, x = 0;
+            for (; x < 8 * NC - 1; ++x) {
+                const uint32_t cnt = (uint32_t)__popcll(node_targets[x]);
+                if (j < cnt) break;
+                j -= cnt;
+            }
+            const uint32_t move = ((base + x) << 8) | select_bit64(node_targets[x], j);
+            *reinterpret_cast<uint4*>(pool + (uint64_t)(first + a) * kEdgeWords) = make_uint4(0u, 0u, 0u, move);
+        }
+    };
+
+    // ---- the root, once: node 0 and its arms
+    const Board root = load_board(planes, n, i);
+    const uint32_t rply = plies_buf[i];
+    const uint32_t root_mover = rply & 1u;
+    // (an ended root and one that holds the most plies a board can have no arms, as in k_bounce_eval_count)
+    const uint32_t root_base_cell = spread(root, occupancy(root), root_mover, status[i] == BGS_ST_RUNNING && rply < kBounceMaxPlies, node_targets);
+    __syncthreads();
+    const uint32_t root_arms = count_arms(node_targets);
+    if (root_arms == 0u) {   // nothing to search: counts and visits stay zero
+        if (tid == 0) {
+            if (best) best[i] = -1;
+            if (nodes) nodes[i] = 0;
+            if (used_out) used_out[i] = 0;
+        }
+        return;
+    }
+    make_arms(0u, root_arms, root_base_cell);
+    if (tid == 0) {
+        node_tab[0] = 0u;
+        node_tab[1] = root_arms;
+    }
+    uint32_t used = root_arms, made = 0;      // (team-uniform) pool edges in use; nodes made, the root not counted
+    __syncthreads();
+    const auto slot_of = [&](uint32_t move) { return ((move >> 8) - root_base_cell) * hw + (move & 255u); };
+
+    Board b;                         // the lane's game
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b.v[j] = 0;
+    FlatMoves<NC> mv;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) mv.counts[k] = 0;
+    mv.n = 0;
+    mv.row_base = 0;
+    uint32_t st = 0, plies = 0, stepped = 0;
+    uint64_t game = 0;
+    bool has = false, search = false, have_block = false;
+    [[maybe_unused]] bool can_win = false;   // (BGS_POLICY_DECISIVE) the list the lane holds has a target in the mover's goal row
+    Philox4 blk;
+    blk.v[0] = blk.v[1] = blk.v[2] = blk.v[3] = 0;
+
+    for (uint32_t t = 0; t < iterations; ++t) {
+        // ---- descent (team-uniform): p is the position at node v
+        Board p = root;
+        uint32_t ply = rply, v = 0, depth = 0, move0 = 0;
+        uint32_t leaf = BGS_ST_RUNNING;     // the outcome of an edge that ends the game
+        bool capped = false;                // p' runs and holds the cap
+        for (;;) {
+            const uint32_t first = uniform(node_tab[2u * v]), arms = uniform(node_tab[2u * v + 1u]);
+            const uint32_t* const node = pool + (uint64_t)first * kEdgeWords;
+            uint32_t na[2] = {0u, 0u}, sa[2] = {0u, 0u};
+            uint32_t fresh = kNoArm, sum = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 2; ++k) {
+                const uint32_t a = tid + k * BGS_BLOCK;
+                if (a < arms) {
+                    const uint2 ns = *reinterpret_cast<const uint2*>(node + (uint64_t)a * kEdgeWords);
+                    na[k] = ns.x;
+                    sa[k] = ns.y;
+                    sum += ns.x;
+                    fresh = (ns.x == 0u && a < fresh) ? a : fresh;
+                }
+            }
+            const uint32_t buf = depth & 1u;
+            fresh = wave_min(fresh);
+            sum = wave_sum(sum);
+            if (lane == 0) {
+                red_min[buf][wave] = fresh;
+                red_sum[buf][wave] = sum;
+            }
+            __syncthreads();
+            uint32_t arm = kNoArm, total = 0;
+#pragma unroll
+            for (int w = 0; w < kSearchTeamWaves; ++w) {
+                arm = red_min[buf][w] < arm ? red_min[buf][w] : arm;
+                total += red_sum[buf][w];
+            }
+            arm = uniform(arm);             // the expansion: the lowest arm never played
+            if (arm == kNoArm) {
+                const uint32_t scaled = explore * search_lg(uniform(total));
+                uint32_t key = 0;           // (U(a) << 9 | 511 - a) + 1: the largest U, then the lowest arm
+#pragma unroll
+                for (uint32_t k = 0; k < 2; ++k) {
+                    const uint32_t a = tid + k * BGS_BLOCK;
+                    if (a < arms) {
+                        const uint32_t u = search_q(sa[k], na[k]) + search_isqrt(scaled / na[k]);
+                        const uint32_t mine = ((u << 9) | (511u - a)) + 1u;
+                        key = mine > key ? mine : key;
+                    }
+                }
+                key = wave_max(key);
+                if (lane == 0) red_key[buf][wave] = key;
+                __syncthreads();
+                uint32_t top = 0;
+#pragma unroll
+                for (int w = 0; w < kSearchTeamWaves; ++w) top = red_key[buf][w] > top ? red_key[buf][w] : top;
+                arm = uniform(511u - ((top - 1u) & 511u));
+            }
+            const uint32_t e = first + arm;
+            uint32_t* const edge = pool + (uint64_t)e * kEdgeWords;
+            const uint32_t child = uniform(edge[2]), move = uniform(edge[3]);
+            if (tid == 0) path[depth] = e;
+            move0 = depth == 0u ? move : move0;
+            const int s_cell = (int)(move >> 8), t_cell = (int)(move & 255u);
+            const uint32_t mover = ply & 1u;
+            move_piece(p, s_cell, t_cell);
+            ply += 1u;
+            depth += 1u;
+            if (child == kEdgeCapped) {
+                capped = true;
+                break;
+            }
+            if (child >= kEdgeEnded) {
+                leaf = child & 15u;
+                break;
+            }
+            if (child != 0u) {
+                v = child;
+                continue;
+            }
+            // ---- the edge has no child: what p' is
+            uint32_t code = 0;              // the edge's new third word, if any
+            if ((1ull << t_cell) & (g.goal_top | g.goal_bottom)) {
+                leaf = mover + 1u;
+                code = kEdgeEnded | leaf;
+            } else {
+                const uint64_t occ = occupancy(p);
+                const uint32_t base = spread(p, occ, ply & 1u, true, node_targets);
+                __syncthreads();
+                const uint32_t fan = count_arms(node_targets);
+                if (fan == 0u) {            // the side to move is blocked: the mover wins if it could move, else a draw
+                    spread(p, occ, mover, true, other_targets);
+                    __syncthreads();
+                    leaf = count_arms(other_targets) ? mover + 1u : (uint32_t)BGS_ST_DRAW;
+                    code = kEdgeEnded | leaf;
+                } else if (ply >= max_plies) {
+                    capped = true;
+                    code = kEdgeCapped;
+                } else if (used + fan <= edges) {   // a new node for p'; without room the edge is tried again next time
+                    made += 1u;
+                    make_arms(used, fan, base);
+                    if (tid == 0) {
+                        node_tab[2u * made] = used;
+                        node_tab[2u * made + 1u] = fan;
+                    }
+                    code = made;
+                    used += fan;
+                }
+            }
+            if (tid == 0 && code) edge[2] = code;
+            break;
+        }
+
+        // ---- the leaf's playouts: the halving kernel's refill loop and ply from p'
+        const bool play = leaf == BGS_ST_RUNNING && !capped;
+        if (tid < 3u) tally[tid] = 0;
+        if (tid == 0) next_item = 0;
+        __syncthreads();            // (A) the counter and the tally are zero; the path, the new node and the edge are written
+        uint32_t wins = 0, draws = 0, losses = 0;
+        if (play) {
+            // G = ((first_game + i) * T + t) * P + j
+            const uint64_t game0 = game_base + ((uint64_t)i * iterations + t) * (uint64_t)leaf_playouts;
+            bool dry = false;        // (wave-uniform) the leaf's counter has nothing left for this wave
+            while (!dry || __builtin_amdgcn_ballot_w64(has)) {
+                const uint64_t need = __builtin_amdgcn_ballot_w64(!has);
+                if (need && !dry) {
+                    if (__builtin_amdgcn_ballot_w64(stepped >= (1u << 30))) {   // (a lane adds at most 65535 a playout)
+                        add_steps(steps, stepped);
+                        stepped = 0;
+                    }
+                    const uint32_t wanted = (uint32_t)__popcll(need);
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(&next_item, wanted);
+                    base = uniform(base);
+                    if (base + wanted >= leaf_playouts) dry = true;
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                    if (!has && base + rank < leaf_playouts) {
+                        game = game0 + (uint64_t)(base + rank);
+                        b = p;
+                        plies = ply;
+                        st = BGS_ST_RUNNING;
+                        has = true;
+                        search = true;
+                        have_block = false;
+                    }
+                }
+                if (!__builtin_amdgcn_ballot_w64(has)) continue;
+
+                if (__builtin_amdgcn_ballot_w64(search)) {
+                    const uint64_t occ = occupancy(b);
+                    enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
+                    const bool blocked = search && mv.n == 0u;
+                    if (__builtin_amdgcn_ballot_w64(blocked)) {
+                        FlatMoves<NC> other;
+#pragma unroll
+                        for (int k = 0; k < NC; ++k) other.counts[k] = 0;
+                        other.n = 0;
+                        other.row_base = 0;
+                        enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
+                        if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
+                    }
+                    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                        if (search) can_win = st == BGS_ST_RUNNING && b_can_win<NC>(mv, column, (plies & 1u) ? g.goal_bottom : g.goal_top);
+                    }
+                    search = false;
+                }
+                const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
+                if (has && !run) {       // finished (a capped game, st 0, is counted nowhere)
+                    wins += (st != 0u && st != BGS_ST_DRAW && st - 1u == root_mover) ? 1u : 0u;
+                    losses += (st != 0u && st != BGS_ST_DRAW && st - 1u != root_mover) ? 1u : 0u;
+                    draws += st == BGS_ST_DRAW ? 1u : 0u;
+                    has = false;
+                }
+                if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                    if (run && can_win) {   // every candidate ends the game for the mover: one transition, nothing drawn or moved
+                        st = (plies & 1u) + 1u;
+                        ++plies;
+                        stepped += 1u;
+                    }
+                }
+                if (POLICY == BGS_POLICY_DECISIVE ? run && !can_win : run) {
+                    if (!have_block || (plies & 3u) == 0u) {
+                        blk = philox4x32_10(seed, game, plies >> 2);
+                        have_block = true;
+                    }
+                    const uint32_t mover = plies & 1u;
+                    int s, tc;
+                    pick_flat<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, tc);
+                    move_piece(b, s, tc);
+                    ++plies;
+                    stepped += 1u;
+                    if ((1ull << tc) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
+                    else search = true;
+                }
+            }
+            if (wins) atomicAdd(tally + 0, wins);
+            if (draws) atomicAdd(tally + 1, draws);
+            if (losses) atomicAdd(tally + 2, losses);
+        }
+        __syncthreads();            // (B) the tally is complete
+        uint32_t tw = 0, td = 0, tl = 0;
+        if (play) {
+            tw = tally[0];
+            td = tally[1];
+            tl = tally[2];
+        } else if (!capped) {       // all playouts of the iteration have the edge's outcome
+            tw = (leaf != BGS_ST_DRAW && leaf - 1u == root_mover) ? leaf_playouts : 0u;
+            tl = (leaf != BGS_ST_DRAW && leaf - 1u != root_mover) ? leaf_playouts : 0u;
+            td = leaf == BGS_ST_DRAW ? leaf_playouts : 0u;
+        }
+
+        // ---- back-propagation: lane k takes edge k of the path; its mover is the root's at even k
+        for (uint32_t k = tid; k < depth; k += BGS_BLOCK) {
+            uint32_t* const edge = pool + (uint64_t)path[k] * kEdgeWords;
+            edge[0] += leaf_playouts;
+            edge[1] += td + 2u * ((k & 1u) ? tl : tw);
+        }
+        if (tid == 0) {
+            int32_t* const c = counts + (i * (int64_t)slots + slot_of(move0)) * 3;
+            c[0] += (int32_t)tw;
+            c[1] += (int32_t)td;
+            c[2] += (int32_t)tl;
+        }
+        __syncthreads();            // (C) the tree is whole again before the next descent reads it; tally and path are free
+    }
+
+    // ---- the outputs of the root (illegal slots are never stored: the launcher zeroed them)
+    if (visits) {
+        for (uint32_t a = tid; a < root_arms; a += BGS_BLOCK) {
+            const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
+            visits[i * (int64_t)slots + slot_of(edge[3])] = (int32_t)edge[0];
+        }
+    }
+    if (tid == 0) {
+        if (best) {   // the most visits, then the larger 2 * wins + draws, then the lower slot (the arms ascend by slot)
+            int32_t top = -1;
+            uint32_t top_n = 0, top_s = 0;
+            for (uint32_t a = 0; a < root_arms; ++a) {
+                const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
+                const uint32_t cn = edge[0], cs = edge[1];
+                if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
+                    top = (int32_t)slot_of(edge[3]);
+                    top_n = cn;
+                    top_s = cs;
+                }
+            }
+            best[i] = top;
+        }
+        if (nodes) nodes[i] = (int32_t)made;
+        if (used_out) used_out[i] = (int32_t)used;
+    }
+    add_steps(steps, stepped);
+}
+
+template <class GEO, int NC, int POLICY>
+void launch_bounce_search(const bgs_batch* b, const GEO& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
+                          uint32_t max_plies, uint32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes,
+                          int32_t* d_used, void* d_workspace) {
+    const uint32_t slots = (uint32_t)(b->bg.w * b->bg.h * b->bg.w);
+    (void)hipMemsetAsync(d_counts, 0, (size_t)b->n * slots * 3 * sizeof(int32_t), b->stream);
+    if (d_visits) (void)hipMemsetAsync(d_visits, 0, (size_t)b->n * slots * sizeof(int32_t), b->stream);
+    // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
+    const uint64_t game_base = b->first_game * (uint64_t)iterations * (uint64_t)leaf_playouts;
+    const size_t tile = sizeof(uint32_t) * 2 * 8 * NC * BGS_BLOCK;
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL((k_bounce_search<GEO, NC, POLICY>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), tile, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, seed, game_base,
+                           iterations, leaf_playouts, explore, max_plies, edges, slots, i0, static_cast<uint32_t*>(d_workspace), d_counts,
+                           d_visits, d_best, d_nodes, d_used, b->d_steps);
+    }
+}
+
 EvalGeom eval_geom(const bgs_batch* b) {
     EvalGeom g{};
     g.rh = b->cg.h;
@@ -2175,6 +2610,37 @@ void bounce_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, 
         bounce_evaluate_halving_policy<BGS_POLICY_DECISIVE>(b, seed, (uint32_t)budget, cap, d_counts, d_given, d_best);
     else
         bounce_evaluate_halving_policy<BGS_POLICY_UNIFORM>(b, seed, (uint32_t)budget, cap, d_counts, d_given, d_best);
+}
+
+uint64_t bounce_search_root_bytes(int32_t iterations, int32_t edges) {
+    return bounce_search_root_words((uint32_t)iterations, (uint32_t)edges) * sizeof(uint32_t);
+}
+
+template <int POLICY>
+static void bounce_search_policy(const bgs_batch* b, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
+                                 uint32_t cap, uint32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes,
+                                 int32_t* d_used, void* d_workspace) {
+    if (b->bounce_static_geom && bounce_is_default(b->bg))
+        launch_bounce_search<DefaultBounceGeom, 1, POLICY>(b, DefaultBounceGeom{}, seed, iterations, leaf_playouts, explore, cap, edges,
+                                                           d_counts, d_visits, d_best, d_nodes, d_used, d_workspace);
+    else if (b->bg.w <= 8)
+        launch_bounce_search<BounceGeom, 1, POLICY>(b, b->bg, seed, iterations, leaf_playouts, explore, cap, edges, d_counts, d_visits,
+                                                    d_best, d_nodes, d_used, d_workspace);
+    else
+        launch_bounce_search<BounceGeom, 3, POLICY>(b, b->bg, seed, iterations, leaf_playouts, explore, cap, edges, d_counts, d_visits,
+                                                    d_best, d_nodes, d_used, d_workspace);
+}
+
+void bounce_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
+                   int policy, int32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
+                   void* d_workspace) {
+    uint32_t cap = (uint32_t)max_plies;
+    if (cap > kBounceMaxPlies) cap = kBounceMaxPlies;   // plies are stored as uint16
+    const uint32_t t = (uint32_t)iterations, p = (uint32_t)leaf_playouts, e = (uint32_t)explore, pool = (uint32_t)edges;
+    if (policy == BGS_POLICY_DECISIVE)
+        bounce_search_policy<BGS_POLICY_DECISIVE>(b, seed, t, p, e, cap, pool, d_counts, d_visits, d_best, d_nodes, d_used, d_workspace);
+    else
+        bounce_search_policy<BGS_POLICY_UNIFORM>(b, seed, t, p, e, cap, pool, d_counts, d_visits, d_best, d_nodes, d_used, d_workspace);
 }
 
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,

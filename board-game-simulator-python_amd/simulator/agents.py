@@ -15,6 +15,9 @@ launch) and plays the column with the most visits.
 
 ``BounceHalvingAgent`` spends a fixed budget of playouts a Bounce position by sequential halving
 (``BounceBatch.evaluate_moves_halving``) and plays the last surviving move.
+
+``BounceTreeSearchAgent`` grows a UCT tree a Bounce position (``BounceBatch.search_moves``) and plays the move with the
+most visits.
 """
 
 from __future__ import annotations
@@ -398,6 +401,101 @@ class BounceHalvingAgent:
             by_slot = {a._source[0] * hw + a._target[1] * w + a._target[0]: a for a in s.actions}
             out.append(by_slot[int(slot)] if slot >= 0 else None)
         return out
+
+    def choose(self, state, game: int = 0):
+        """`choose_many` of one state"""
+        return self.choose_many([state], first_game=game)[0]
+
+    def close(self) -> None:
+        for b in self._batches.values():
+            b.close()
+        self._batches.clear()
+
+
+class BounceTreeSearchAgent:
+    """UCT tree search over Bounce positions (``simulator.game.bounce.State``): ``BounceBatch.search_moves`` with
+    ``iterations`` iterations and ``leaf_playouts`` playouts a leaf, ``iterations * leaf_playouts`` playouts a position,
+    one launch for all positions of a call.  The sibling of ``BounceHalvingAgent``, which spends the same playouts on one
+    ply.
+
+    ``predict`` / ``predict_many`` map every action of ``state.actions`` to its share of the root's visits (the shares of
+    a state sum to 1); ``choose`` / ``choose_many`` return the move with the most visits (ties: the larger 2 * wins +
+    draws, then the lower slot; None for a state without an action).  The playouts of the position at index k of a call
+    are the games ``((first_game + k) * iterations + t) * leaf_playouts + j`` of ``seed``.  ``explore`` is about 45426 *
+    C * C for a UCB1 constant C; ``policy`` is the playout policy, "uniform" or "decisive"; ``max_plies`` caps every
+    playout at that absolute ply count (None: ``BOUNCE_MAX_PLIES``, 1024); ``edges`` is the edge pool of a position
+    (None: ``BounceBatch.search_default_edges``).  Connect states raise ValueError: they are ``TreeSearchAgent``'s."""
+
+    def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
+                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, edges: Optional[int] = None):
+        playout_policy(policy)
+        if iterations < 1 or leaf_playouts < 1:
+            raise ValueError("iterations and leaf_playouts must be >= 1")
+        if not 0 <= explore <= 1 << 18:
+            raise ValueError("explore must be 0 .. 2**18")
+        if max_plies is not None and max_plies < 1:
+            raise ValueError("max_plies must be >= 1")
+        self.iterations = int(iterations)
+        self.leaf_playouts = int(leaf_playouts)
+        self.explore = int(explore)
+        self.policy = policy
+        self.seed = int(seed)
+        self.device = int(device)
+        self.max_plies = None if max_plies is None else int(max_plies)
+        self.edges = None if edges is None else int(edges)
+        self._batches: Dict[tuple, BounceBatch] = {}
+
+    def search(self, states: Sequence, first_game: int = 0):
+        """(counts, visits, best, nodes, used) of the launch over `states` (Bounce states that share one Config)"""
+        if isinstance(states[0], connect.State):
+            raise ValueError("BounceTreeSearchAgent: Bounce states only; Connect states: TreeSearchAgent")
+        if not isinstance(states[0], bounce.State):
+            raise TypeError(f"BounceTreeSearchAgent: Bounce states, not {type(states[0]).__name__}")
+        config = states[0].config
+        if any(type(s) is not type(states[0]) or s.config != config for s in states):
+            raise ValueError("BounceTreeSearchAgent: the states must share one Config")
+        grid = config.grid
+        key = (grid.shape, grid.tobytes(), len(states))
+        b = self._batches.get(key)
+        if b is None:
+            b = self._batches[key] = BounceBatch(grid, len(states), device=self.device)
+        boards = np.stack([s.grid for s in states])
+        player = np.array([s.player for s in states], dtype=np.int8)
+        winner = np.array([s.to_json()["winner"] for s in states], dtype=np.int8)
+        plies = np.array([s._plies for s in states], dtype=np.int32)   # a playout's draws are keyed by the absolute ply
+        if (b.write_state(boards, player, winner, plies) != 0).any():
+            raise ValueError("BounceTreeSearchAgent: a state could not be loaded")
+        b.set_first_game(first_game)
+        cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
+        return b.search_moves(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore,
+                              max_plies=cap, policy=self.policy, edges=self.edges)
+
+    def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict[bounce.Action, float]]:
+        """`predict` of every state, searched in one launch"""
+        if not states:
+            return []
+        visits = self.search(states, first_game)[1]
+        total = self.iterations * self.leaf_playouts
+        w = visits.shape[1]
+        return [{a: float(visits[k, a._source[0], a._target[1] * w + a._target[0]]) / total for a in s.actions}
+                for k, s in enumerate(states)]
+
+    def predict(self, state, game: int = 0) -> Dict[bounce.Action, float]:
+        """{action: share of the visits} for every action in ``state.actions`` (the keys are those Action objects)"""
+        return self.predict_many([state], first_game=game)[0]
+
+    def choose_many(self, states: Sequence, first_game: int = 0) -> List:
+        """the move with the most visits of every state, of the same launch `predict_many` makes (None: no action)"""
+        if not states:
+            return []
+        out = self.search(states, first_game)
+        best, w = out[2], out[1].shape[1]
+        chosen = []
+        for s, slot in zip(states, best):
+            hw = s.grid.shape[0] * w
+            by_slot = {a._source[0] * hw + a._target[1] * w + a._target[0]: a for a in s.actions}
+            chosen.append(by_slot[int(slot)] if slot >= 0 else None)
+        return chosen
 
     def choose(self, state, game: int = 0):
         """`choose_many` of one state"""

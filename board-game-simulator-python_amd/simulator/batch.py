@@ -993,6 +993,12 @@ class ConnectBatch(_Batch):
 
     evaluate_moves_halving_tensor = evaluate_moves_halving
 
+    def search_moves(self, *args, **kwargs):
+        """Not available for Connect: search_moves is the Bounce tree search; Connect has `search_actions`."""
+        raise ValueError("search_moves: Bounce batches only (Connect boards: search_actions)")
+
+    search_moves_tensor = search_moves_workspace_bytes = search_moves
+
     @property
     def legal(self) -> np.ndarray:
         out = np.empty((self.n, self.width), dtype=np.uint8)
@@ -1060,6 +1066,7 @@ class BounceBatch(_Batch):
         cfg = cfg.astype(np.int8)
         super().__init__(n, cfg.shape[0], cfg.shape[1], device, use_torch)
         self.config_grid = cfg
+        self._search_workspaces = {}   # (iterations, edges) -> the uint8 device tensor search_moves_tensor allocated
         nbytes = ctypes.c_size_t()
         _abi.check(_abi.lib().bgs_bounce_arena_bytes(self.height, self.width, self.n, ctypes.byref(nbytes)))
         arena, arena_bytes = self._make_arena(nbytes.value)
@@ -1187,6 +1194,91 @@ class BounceBatch(_Batch):
             ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["given"].data_ptr()),
             ctypes.c_void_p(outs["best"].data_ptr()), 1))
         return outs["counts"], outs["given"], outs["best"]
+
+    def search_min_edges(self) -> int:
+        """BGS_BOUNCE_SEARCH_MIN_EDGES(H, W): the most arms a position of this geometry can have, W * W * (H - 2)"""
+        return self.width * self.width * (self.height - 2) if self.height >= 3 else 1
+
+    def search_default_edges(self, iterations: int) -> int:
+        """the edge pool `search_moves` takes with edges=None: min((T + 1) * MIN, MIN + 32 * T), MIN = `search_min_edges()`.
+        The 32 edges a node are an allowance over the about 12 arms of a node of the default board; it is NOT measured:
+        docs/EXPERIMENTS.md section 28 holds the share of roots whose pool ran dry, once a GPU run has produced it."""
+        least, t = self.search_min_edges(), max(int(iterations), 0)
+        return min((t + 1) * least, least + 32 * t, 2**31 - 1)
+
+    def search_moves_workspace_bytes(self, iterations: int = 256, edges: Optional[int] = None) -> int:
+        """bytes of device memory `search_moves` needs for its trees at `iterations` and `edges` (None: the default pool;
+        bgs_bounce_search_workspace_bytes)"""
+        edges = self.search_default_edges(iterations) if edges is None else int(edges)
+        nbytes = ctypes.c_size_t()
+        _abi.check(_abi.lib().bgs_bounce_search_workspace_bytes(self._handle, ctypes.c_int32(iterations), ctypes.c_int32(edges),
+                                                                ctypes.byref(nbytes)))
+        return nbytes.value
+
+    def search_moves(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE,
+                     max_plies: int = 2**31 - 1, policy: str = "uniform", edges: Optional[int] = None):
+        """Batched UCT tree search of every board (bgs_bounce_search_moves), one launch: (counts int32[n, W, H * W, 3],
+        visits int32[n, W, H * W], best int32[n], nodes int32[n], used int32[n]); entry [i, x, c] is the move of the piece
+        in column x of the active row to cell c = ty * W + tx, as in `evaluate_moves`.  Every running board is the root of
+        a tree of its own, grown by `iterations` iterations: descend by UCB (integer arithmetic, include/bgs.h) over the
+        legal moves to an edge without a node, make its node if the pool has room, play `leaf_playouts` playouts from
+        there by `policy`, and add them to every edge of the path.  `explore` is about 45426 * C * C for a UCB1 constant
+        C on rewards in [0, 1] (0: pure exploitation; at most 2**18).  `visits` are the playouts through every root move,
+        `counts` their (wins, draws, losses) for the player to move, `best` the slot x * H * W + c with the most visits
+        (-1 for a board that has ended or has no move), `nodes` the nodes made, `used` the pool edges in use at the end.
+        `edges` is the edge pool of a root, at least `search_min_edges()`; None: `search_default_edges(iterations)`, an
+        allowance of 32 edges a node that is not measured (docs/EXPERIMENTS.md section 28).  A node that does not fit is
+        not made and its edge is tried again later: used + (the arms of some position) > edges says the pool ran dry.
+        Playout j of iteration t of board i is game ((first_game + i) * iterations + t) * leaf_playouts + j; `max_plies`
+        is clamped to 65535.  The boards are not modified; the library allocates the trees' memory around the call."""
+        code = playout_policy(policy)
+        edges = self.search_default_edges(iterations) if edges is None else int(edges)
+        shape = (self.n, self.width, self.height * self.width)
+        counts = np.empty(shape + (3,), dtype=np.int32)
+        visits = np.empty(shape, dtype=np.int32)
+        best, nodes, used = (np.empty(self.n, dtype=np.int32) for _ in range(3))
+        _abi.check(_abi.lib().bgs_bounce_search_moves(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
+            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), ctypes.c_void_p(counts.ctypes.data),
+            ctypes.c_void_p(visits.ctypes.data), ctypes.c_void_p(best.ctypes.data), ctypes.c_void_p(nodes.ctypes.data),
+            ctypes.c_void_p(used.ctypes.data), None, 0, 0))
+        return counts, visits, best, nodes, used
+
+    def search_moves_tensor(self, counts=None, visits=None, best=None, nodes=None, used=None, seed: int = DEFAULT_SEED,
+                            iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1,
+                            policy: str = "uniform", edges: Optional[int] = None, workspace=None):
+        """`search_moves` into device tensors int32[n, W, H * W, 3], int32[n, W, H * W] and three int32[n] (allocated when
+        None), enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes, used).  Every entry
+        is written.  `workspace`: a contiguous, 256-byte aligned uint8 device tensor of at least
+        `search_moves_workspace_bytes(iterations, edges)` bytes; None: a tensor of the batch's own, allocated on first use
+        and kept per (iterations, edges).  The workspace needs no preparation, and calls on one stream may share it."""
+        code = playout_policy(policy)
+        t = self._need_torch("search_moves_tensor")
+        edges = self.search_default_edges(iterations) if edges is None else int(edges)
+        slots = (self.n, self.width, self.height * self.width)
+        shapes = {"counts": slots + (3,), "visits": slots, "best": (self.n,), "nodes": (self.n,), "used": (self.n,)}
+        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "used": used}
+        for name, shape in shapes.items():
+            x = outs[name]
+            if x is None:
+                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
+            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        if workspace is None:
+            need = self.search_moves_workspace_bytes(iterations, edges)   # (refuses bad arguments before anything is allocated)
+            key = (int(iterations), edges)
+            workspace = self._search_workspaces.get(key)
+            if workspace is None:
+                workspace = self._search_workspaces[key] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
+        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        _abi.check(_abi.lib().bgs_bounce_search_moves(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
+            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), ctypes.c_void_p(outs["counts"].data_ptr()),
+            ctypes.c_void_p(outs["visits"].data_ptr()), ctypes.c_void_p(outs["best"].data_ptr()),
+            ctypes.c_void_p(outs["nodes"].data_ptr()), ctypes.c_void_p(outs["used"].data_ptr()),
+            ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
+        return outs["counts"], outs["visits"], outs["best"], outs["nodes"], outs["used"]
 
     def solve_moves(self, depth: int = DEFAULT_BOUNCE_SOLVE_DEPTH, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """Exact horizon search of every legal move of every board (bgs_bounce_solve_moves), one launch: (codes int8[n, W,

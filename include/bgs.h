@@ -344,6 +344,67 @@ BGS_API int bgs_bounce_evaluate_moves_policy(bgs_batch* b, uint64_t seed, int32_
 #define BGS_HALVING_SHORT (-2)
 BGS_API int bgs_bounce_evaluate_moves_halving(bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy,
                                               int32_t* counts, int32_t* given, int32_t* best, int on_device);
+/* Batched UCT tree search (Bounce, bit-packed boards only), one launch: bgs_connect_search_actions with "column" read as
+ * "arm".  For every running board i (the root), `iterations` (T) iterations of UCT with `leaf_playouts` (P) playouts a
+ * leaf; everything is integer arithmetic and the result is defined bit for bit.  The batch's boards are not modified.
+ * Arms and slots.  The arms of a position are its legal moves in canonical order (sources by ascending x, targets by
+ * ascending (y, x)), numbered 0 .. A-1.  Slots are those of bgs_bounce_evaluate_moves: S = width * height * width, slot
+ * s = x * height * width + c is the move of the piece in column x of the active row to cell c; the arms of a position
+ * are in ascending slot order.
+ * Tree.  A node is a position with A >= 1 arms; for every arm a it holds n[a] (the playouts that went through the edge),
+ * s[a] (the sum of 2 * wins + draws of those playouts, seen from the player to move at the node) and the child node, if
+ * any.  The root is node 0.  Every root has a pool of `edges` (E) edges: a node with A arms takes A of them when it is
+ * made, the root its own first.  BGS_BOUNCE_SEARCH_MIN_EDGES(height, width) is the most arms a position of the geometry
+ * can have (the k <= width pieces of the active row reach at most (height - 1) * width - k cells each); a call with E
+ * below it is refused, so a root always fits and no board is ever "short".
+ * Iteration t (t = 0 .. T-1), from the root, at node v with position p:
+ *   1.-3. the selection of bgs_connect_search_actions over the arms of p: the lowest arm with n[a] = 0 if there is one,
+ *      otherwise the arm with the largest U(a) = Q(a) + E(a), ties to the lowest arm, with N the sum of n[a] over the
+ *      arms of v and Q, E, lg and isqrt exactly as defined there;
+ *   4. play arm a, giving p'.
+ *      p' has ended -- the target lies in the mover's goal row, or the side to move at p' has no move and the game is
+ *      settled as bgs_step_actions settles it (the mover wins if it could move, else a draw): no node is made and no
+ *      game is played, all P playouts of the iteration have that outcome.
+ *      p' is running and holds >= min(max_plies, 65535) plies: no node is made, now or later, and the P playouts are
+ *      capped at once (they score 0 and count in n).
+ *      p' is running and the edge has a child: v becomes the child, back to step 1.
+ *      p' is running and the edge has no child: a node is made for p' if and only if (edges in use) + A(p') <= E, and
+ *      either way the iteration's P playouts start from p'.  An edge whose node could not be made is tried again the
+ *      next time it is taken: the pool only grows, but a position with fewer arms elsewhere may still fit later.
+ *      THIS DIFFERS from bgs_connect_search_actions, which makes the node when n[c] was 0: here the test is "the edge
+ *      has no child", because an edge can have been played without getting its node;
+ *   5. playout j (0 <= j < P) of iteration t of board i is the game G = ((first_game + i) * T + t) * P + j (mod 2^64),
+ *      played from p' exactly as bgs_bounce_evaluate_moves_policy plays a game after its forced first move: the policy
+ *      (BGS_POLICY_UNIFORM or BGS_POLICY_DECISIVE), a philox word per absolute ply keyed by (seed, G, ply), the cap
+ *      clamped to 65535, the settlement of a side without a move.  A capped playout scores 0 but counts in n;
+ *   6. every edge (v, a) of the path gets n[a] += P and s[a] += 2 * (playouts won by the player to move at v) + draws.
+ * Outputs.  counts int32[n][width][height * width][3] = (wins, draws, losses) of the root's mover over the playouts
+ * through the root arm of that slot, capped playouts in none of the three; visits int32[n][width][height * width] (may
+ * be NULL) = the root's n by slot; best int32[n] (may be NULL) = the slot of the root arm with the most visits, ties to
+ * the larger s, then to the lower slot, or -1; nodes int32[n] (may be NULL) = the nodes made, the root not counted (at
+ * most T); used int32[n] (may be NULL) = the pool edges in use at the end, the root's included: used + (the arms of some
+ * position) > E is how a caller sees that the pool ran dry.  Illegal slots: zeros.  A board that has ended, has no move
+ * or already holds 65535 plies: all zeros, best = -1, used = 0.
+ * bgs_steps gets the transitions of the playouts played, from p' on: the moves of the descent are not counted and a
+ * terminal leaf adds nothing.  A root's results depend on (board, first_game + i) only, so sharding by first_game holds.
+ * Workspace.  Caller-owned device memory; bgs_bounce_search_workspace_bytes says how much this batch needs for T
+ * iterations and E edges: n roots of 16 * E bytes (the edge pool: n, s, child, move), 8 * (T + 1) bytes (the node
+ * table) and 4 * (T + 1) bytes (the descent path, which can be T + 1 edges long and therefore lives here), a root's share
+ * rounded up to 256 bytes.  Its contents need no preparation and mean nothing afterwards.  on_device != 0: workspace is a
+ * 256-byte aligned device pointer of at least that size, the outputs are 16-byte aligned device pointers, and the call is
+ * an enqueue on the batch's stream with no synchronisation and no allocation.  on_device == 0: the outputs are host
+ * buffers, filled when the call returns; workspace may be NULL (the library then allocates and frees it around the
+ * call) or a device pointer as above.
+ * Refused (BGS_ERR_ARG, with a message that names the argument; every output is left untouched): a Connect batch, a
+ * generic batch, T < 1, P < 1, T * P > 2^29, explore < 0 or > 2^18, max_plies < 1, an unknown policy, E below
+ * BGS_BOUNCE_SEARCH_MIN_EDGES, NULL counts, a misaligned pointer, a workspace that is too small (or NULL with
+ * on_device), n * T * P beyond int64. */
+#define BGS_BOUNCE_SEARCH_MIN_EDGES(h, w) ((h) >= 3 ? (w) * (w) * ((h) - 2) : 1)
+BGS_API int bgs_bounce_search_workspace_bytes(const bgs_batch* b, int32_t iterations, int32_t edges, size_t* bytes);
+BGS_API int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                                    int32_t max_plies, int policy, int32_t edges, int32_t* counts, int32_t* visits,
+                                    int32_t* best, int32_t* nodes, int32_t* used, void* workspace, size_t workspace_bytes,
+                                    int on_device);
 /* Exact solve of every column of every board (Connect, bit-packed boards only): a depth-first alpha-beta search a
  * (board, column), no RNG.  Entry [i][c] is seen from the player to move at board i; the lines searched are at most
  * `depth` plies long, column c itself counted (depth >= height * width: a full solve).
