@@ -901,8 +901,9 @@ k_connect_rollout_aligned(G g, uint64_t* __restrict__ planes, uint8_t* __restric
 //     in lock step).
 //     A game that ends inside the opening is stored by the opening stage and parked as a dead slot (column word 0).
 // Status and reward are not stored per game either: a finished game leaves ONE outcome byte in the wave's LDS slice (a
-// plain ds_write_b8), and when the chunk is done a lane reads four games as one dword -- their four status bytes as they
-// go to memory -- and derives their reward pairs and their byte of 2-bit codes for the hand-over from it, coalesced.  Results are those of K2a bit for bit: the draws are keyed by (game, block).
+// plain ds_write_b8: its stones and a run flag, connect_unit.h), and when the chunk is done a lane reads four games as one
+// dword and derives their four status bytes as they go to memory, their reward pairs, their byte of 2-bit codes for the
+// hand-over and their env-steps from it, coalesced.  Results are those of K2a bit for bit: the draws are keyed by (game, block).
 //
 // (Tried and measured, not kept: sharing the drain inside a workgroup -- a wave whose chunk is exhausted parks its last
 // <= 32 boards in LDS for the waves still running and leaves.  It cut another 6 % of the instructions and made the
@@ -1083,7 +1084,7 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
     Pool& pool = pools[threadIdx.x >> 6];
 
     uint64_t p[2] = {0, 0};
-    uint32_t hts = 0, live = 0, game = 0, stepped = 0;
+    uint32_t hts = 0, live = 0, game = 0;
     bool anywon = false;   // somebody has a run on this lane's board (only read when the game has just ended)
     uint32_t wnext = 0;    // the word of this lane's next block (read from lane_words a block ahead)
     uint32_t* const my_words = &lane_words[threadIdx.x >> 6][0][lane];
@@ -1092,7 +1093,8 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
 
     if (avail == 0u) return;
     // The outcome of game i of the chunk is byte i of the wave's LDS slice (a plain byte store where the game ends, no
-    // read-modify-write): at the end a lane reads four games as one dword -- which IS their four status bytes.
+    // read-modify-write; connect_unit.h: connect_outcome_byte): at the end a lane reads four games as one dword and derives
+    // what they leave from it.
     uint8_t* const outcome = reinterpret_cast<uint8_t*>(code_lds + (threadIdx.x >> 6) * (games_per_wave >> 2));
     for (uint32_t i = lane; i < ((avail + 3u) >> 2); i += BGS_WAVE) reinterpret_cast<uint32_t*>(outcome)[i] = 0u;
     __builtin_amdgcn_wave_barrier();
@@ -1140,11 +1142,11 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
         won_any = won_any || won;   // (lane masks: scalar ORs)
         alive = (won || op == 0u) ? 0u : alive;
     };
-    // the outcome of a board that has just ended, and its plies into the step count
+    // the outcome byte of a board that has just ended: its stones, and whether somebody holds a run (no cap: a board that
+    // stopped without one is full).  Status, reward, code and env-steps follow from it when the chunk is flushed.
     auto outcome_of = [&](const uint64_t (&q)[2], bool won_any) -> uint32_t {
         const uint32_t stones = (uint32_t)__popcll(q[0]) + (uint32_t)__popcll(q[1]);
-        stepped += stones;
-        return won_any ? ((stones - 1u) & 1u) + 1u : (uint32_t)BGS_ST_DRAW;   // no cap: a board that stopped without a run is full
+        return connect_outcome_byte(stones, won_any);
     };
     // one opening ply: every column is open and nobody can win yet
     auto cheap_ply = [&](uint32_t j, uint32_t draw, uint64_t (&q)[2], uint32_t& h4) {
@@ -1324,27 +1326,26 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
     // ---- the drain: no games left to hand out, the boards in flight play to their end
     while (__builtin_amdgcn_ballot_w64(live != 0)) play_block();
 
-    // ---- the chunk is done: four games per lane -- their status dword as it lies in LDS, their reward pairs, and their
-    // byte of 2-bit codes for the hand-over (64 lanes: 64 contiguous bytes per store, into host memory when mapped)
+    // ---- the chunk is done: four games per lane -- their outcome dword as it lies in LDS gives their status bytes, their
+    // reward pairs, their byte of 2-bit codes for the hand-over (64 lanes: 64 contiguous bytes per store, into host memory
+    // when mapped) and their plies (connect_unit.h: connect_outcome4)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the byte stores of every lane before the reads below
     __builtin_amdgcn_wave_barrier();
     uint8_t* __restrict__ const status_out = status + begin;
     uint16_t* __restrict__ const reward_out = reward + begin;
     uint8_t* __restrict__ const packed_out = reinterpret_cast<uint8_t*>(codes_out) + (begin >> 2);
+    uint32_t stepped = 0;
     for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
-        const uint32_t four = reinterpret_cast<const uint32_t*>(outcome)[g4 >> 2];  // (bytes past avail are 0)
-        if (CODES) packed_out[g4 >> 2] = (uint8_t)((four & 3u) | ((four >> 6) & 0xCu) | ((four >> 12) & 0x30u) | ((four >> 18) & 0xC0u));
+        const ConnectOutcome4 o = connect_outcome4(reinterpret_cast<const uint32_t*>(outcome)[g4 >> 2]);  // (bytes past avail are 0)
+        stepped += o.plies;
+        if (CODES) packed_out[g4 >> 2] = (uint8_t)o.codes;
         if (g4 + 4u <= avail) {
-            *reinterpret_cast<uint32_t*>(status_out + g4) = four;
-            uint2 r;
-            r.x = (uint32_t)reward_pair(four & 255u) | ((uint32_t)reward_pair((four >> 8) & 255u) << 16);
-            r.y = (uint32_t)reward_pair((four >> 16) & 255u) | ((uint32_t)reward_pair(four >> 24) << 16);
-            *reinterpret_cast<uint2*>(reward_out + g4) = r;
+            *reinterpret_cast<uint32_t*>(status_out + g4) = o.status;
+            *reinterpret_cast<uint2*>(reward_out + g4) = make_uint2(o.reward[0], o.reward[1]);
         } else {
             for (uint32_t k = 0; g4 + k < avail; ++k) {
-                const uint32_t ck = (four >> (8u * k)) & 255u;
-                status_out[g4 + k] = (uint8_t)ck;
-                reward_out[g4 + k] = reward_pair(ck);
+                status_out[g4 + k] = (uint8_t)(o.status >> (8u * k));
+                reward_out[g4 + k] = (uint16_t)((((uint64_t)o.reward[1] << 32) | o.reward[0]) >> (16u * k));
             }
         }
     }
@@ -1358,8 +1359,10 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
 // the step's seed, its global id and the block), so is everything it leaves: a step's outcome bytes, reward pairs and
 // codes are flushed, in the one-step layout, when the last game of its chunk has ended.
 //   * At most two steps of a wave are open at a time: the one whose games are handed out (`cur`) and the one before it,
-//     whose last games may still be playing (`old` lanes).  Their outcome bytes live in two LDS slices (by step parity),
-//     their env-steps in two counters per lane.  A wave starts step cur + 1 only once step cur - 1 is flushed; until then
+//     whose last games may still be playing (`old` lanes).  Their outcome bytes live in two LDS slices (by step parity);
+//     a lane that takes a game takes the offset of its outcome byte, the slice of its step included, so a game that ends
+//     stores its byte without asking which step it is of, and the env-steps are summed from the bytes at the flush.  A
+//     wave starts step cur + 1 only once step cur - 1 is flushed; until then
 //     the lanes that find nothing to take sit out (never in practice: a chunk holds eight games a lane).
 //   * The pool and the lane words are K2o's: the pool only ever holds games of `cur` (a chunk's openings are padded to
 //     64 games, so when it is handed out the pool holds no game of it).
@@ -1398,21 +1401,24 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
     bool pending = false;                // step cur - 1 is not flushed yet
     uint64_t cur_seed = tab.step[0].seed, cur_first = tab.step[0].first_game;
     uint64_t* cur_planes = tab.step[0].planes ? tab.step[0].planes + begin : nullptr;
-    uint64_t* prev_planes = nullptr;
+    uint64_t* prev_planes = nullptr;     // (NULL again once step cur - 1 is flushed)
     uint64_t prev_seed = 0, prev_first = 0;   // step cur - 1's, for the refetch of an `old` lane (deferred opening)
 
     uint64_t p[2] = {0, 0};
-    uint32_t hts = 0, live = 0, game = 0;
+    uint32_t hts = 0, live = 0;
+    uint32_t game = 0;                   // the lane's game, as the offset of its outcome byte in code_lds: its step's slice + its index
     uint32_t old = 0;                    // 1: this lane's game is of step cur - 1
-    uint32_t stepped0 = 0, stepped1 = 0; // env-steps of the games of even / odd steps
     bool anywon = false;
     uint32_t wnext = 0;
     uint32_t* const my_words = &lane_words[threadIdx.x >> 6][0][lane];
     uint32_t wrow = 0;
 
     if (avail == 0u) return;
-    uint8_t* const slices = reinterpret_cast<uint8_t*>(code_lds + (threadIdx.x >> 6) * (games_per_wave >> 1));
-    auto slice_of = [&](uint32_t s) { return slices + (s & 1u) * games_per_wave; };
+    uint8_t* const outcome_bytes = reinterpret_cast<uint8_t*>(code_lds);
+    const uint32_t slices_at = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * 2u * games_per_wave);   // (wave-uniform: in an SGPR)
+    auto slice_at = [&](uint32_t s) { return slices_at + (s & 1u) * games_per_wave; };
+    auto slice_of = [&](uint32_t s) { return outcome_bytes + slice_at(s); };
+    uint32_t cur_at = slice_at(0u), prev_at = 0;   // the slices of step cur and of step cur - 1
     auto zero_slice = [&](uint32_t s) {
         uint32_t* const w = reinterpret_cast<uint32_t*>(slice_of(s));
         for (uint32_t i = lane; i < ((avail + 3u) >> 2); i += BGS_WAVE) w[i] = 0u;
@@ -1459,12 +1465,10 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
         won_any = won_any || won;
         alive = (won || op == 0u) ? 0u : alive;
     };
-    // the outcome of a board that has just ended; its plies go to the counter of its step's parity
-    auto outcome_of = [&](const uint64_t (&q)[2], bool won_any, uint32_t parity) -> uint32_t {
+    // the outcome byte of a board that has just ended (connect_unit.h: connect_outcome_byte)
+    auto outcome_of = [&](const uint64_t (&q)[2], bool won_any) -> uint32_t {
         const uint32_t stones = (uint32_t)__popcll(q[0]) + (uint32_t)__popcll(q[1]);
-        stepped0 += parity ? 0u : stones;   // (value selects: an if / else here made the two counters a stack array)
-        stepped1 += parity ? stones : 0u;
-        return won_any ? ((stones - 1u) & 1u) + 1u : (uint32_t)BGS_ST_DRAW;
+        return connect_outcome_byte(stones, won_any);
     };
     auto cheap_ply = [&](uint32_t j, uint32_t draw, uint64_t (&q)[2], uint32_t& h4) {
         const uint32_t col = sample_index(draw, (uint32_t)g.w());
@@ -1483,7 +1487,8 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
             const bool here = at && live != 0u && old == o;
             if (__builtin_amdgcn_ballot_w64(here) == 0) continue;
             if (here) {
-                const Philox4 d = philox4x32_10(o ? prev_seed : cur_seed, (o ? prev_first : cur_first) + (uint64_t)(begin + game), 2u);
+                const Philox4 d = philox4x32_10(o ? prev_seed : cur_seed,
+                                                (o ? prev_first : cur_first) + (uint64_t)(begin + (game - (o ? prev_at : cur_at))), 2u);
                 my_words[5 * BGS_WAVE] = d.v[0];
                 my_words[6 * BGS_WAVE] = d.v[1];
                 my_words[7 * BGS_WAVE] = d.v[2];
@@ -1509,18 +1514,21 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
         full_ply(std::integral_constant<uint32_t, 2>{}, sub_draw<2>(word), p, hts, open, live, anywon);
         full_ply(std::integral_constant<uint32_t, 3>{}, sub_draw<3>(word), p, hts, open, live, anywon);
         if (was_live != 0 && live == 0) {
-            uint64_t* const planes = old ? prev_planes : cur_planes;
-            if (planes) {
-                *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(planes) + (game * 8u)) = p[0];
-                *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(planes + n) + (game * 8u)) = p[1];
+            // (wave-uniform: only a call's last step on a batch leaves boards, so most launches have no store to select)
+            if (cur_planes != nullptr || prev_planes != nullptr) {
+                uint64_t* const planes = old ? prev_planes : cur_planes;
+                if (planes) {
+                    const uint32_t at = (game - (old ? prev_at : cur_at)) * 8u;
+                    *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(planes) + at) = p[0];
+                    *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(planes + n) + at) = p[1];
+                }
             }
-            const uint32_t s = cur - old;
-            slice_of(s)[game] = (uint8_t)outcome_of(p, anywon, s & 1u);
+            outcome_bytes[game] = (uint8_t)outcome_of(p, anywon);
         }
     };
     // an idle lane takes game `which` of step cur's chunk out of the pool
     auto take = [&](uint32_t which) {
-        game = which;
+        game = cur_at + which;
         old = 0u;
         const uint32_t slot = which & (Pool::SLOTS - 1u);
         p[0] = pool.plane[0][slot];
@@ -1587,7 +1595,7 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
                 cur_planes[og] = q[0];
                 cur_planes[n + og] = q[1];
             }
-            slice_of(cur)[og] = (uint8_t)outcome_of(q, won_any, cur & 1u);
+            slice_of(cur)[og] = (uint8_t)outcome_of(q, won_any);
         }
         const uint32_t slot = og & (Pool::SLOTS - 1u);
         pool.plane[0][slot] = q[0];
@@ -1600,52 +1608,44 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
         }
         opened += 64u;
     };
-    // step s's chunk is done: status, reward pairs and codes as the one-step kernel stores them, and its env-steps
+    // step s's chunk is done: status, reward pairs and codes as the one-step kernel stores them, and its env-steps -- all
+    // from the outcome dwords (connect_unit.h: connect_outcome4)
     auto flush = [&](uint32_t s) {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         const ConnectGroupStep& e = tab.step[s];
-        const uint8_t* const outcome = slice_of(s);
-        if (e.planes) {
-            uint8_t* __restrict__ const status_out = e.status + begin;
-            uint16_t* __restrict__ const reward_out = e.reward + begin;
-            for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
-                const uint32_t four = reinterpret_cast<const uint32_t*>(outcome)[g4 >> 2];
+        const uint32_t* const outcome = reinterpret_cast<const uint32_t*>(slice_of(s));
+        uint8_t* __restrict__ const status_out = e.status + begin;
+        uint16_t* __restrict__ const reward_out = e.reward + begin;
+        uint8_t* __restrict__ const packed_out = reinterpret_cast<uint8_t*>(e.codes) + (begin >> 2);
+        uint32_t stepped = 0;
+        // (two trips at 512 games a wave: unrolled by four, hipcc's choice, the codes' loop alone took the kernel past 80
+        // VGPRs once play_block held the refetch branch)
+#pragma unroll 1
+        for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
+            const ConnectOutcome4 o = connect_outcome4(outcome[g4 >> 2]);
+            stepped += o.plies;
+            if (CODES) packed_out[g4 >> 2] = (uint8_t)o.codes;
+            if (e.planes) {
                 if (g4 + 4u <= avail) {
-                    *reinterpret_cast<uint32_t*>(status_out + g4) = four;
-                    uint2 r;
-                    r.x = (uint32_t)reward_pair(four & 255u) | ((uint32_t)reward_pair((four >> 8) & 255u) << 16);
-                    r.y = (uint32_t)reward_pair((four >> 16) & 255u) | ((uint32_t)reward_pair(four >> 24) << 16);
-                    *reinterpret_cast<uint2*>(reward_out + g4) = r;
+                    *reinterpret_cast<uint32_t*>(status_out + g4) = o.status;
+                    *reinterpret_cast<uint2*>(reward_out + g4) = make_uint2(o.reward[0], o.reward[1]);
                 } else {
                     for (uint32_t k = 0; g4 + k < avail; ++k) {
-                        const uint32_t ck = (four >> (8u * k)) & 255u;
-                        status_out[g4 + k] = (uint8_t)ck;
-                        reward_out[g4 + k] = reward_pair(ck);
+                        status_out[g4 + k] = (uint8_t)(o.status >> (8u * k));
+                        reward_out[g4 + k] = (uint16_t)((((uint64_t)o.reward[1] << 32) | o.reward[0]) >> (16u * k));
                     }
                 }
             }
         }
-        if (CODES) {
-            uint8_t* __restrict__ const packed_out = reinterpret_cast<uint8_t*>(e.codes) + (begin >> 2);
-            // (two trips at 512 games a wave: unrolled by four, hipcc's choice, this loop alone took the kernel past 80 VGPRs
-            // once play_block held the refetch branch)
-#pragma unroll 1
-            for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
-                const uint32_t four = reinterpret_cast<const uint32_t*>(outcome)[g4 >> 2];
-                packed_out[g4 >> 2] = (uint8_t)((four & 3u) | ((four >> 6) & 0xCu) | ((four >> 12) & 0x30u) | ((four >> 18) & 0xC0u));
-            }
-        }
-        const uint32_t odd = s & 1u;
-        add_steps(e.steps, odd ? stepped1 : stepped0);
-        stepped0 = odd ? stepped0 : 0u;
-        stepped1 = odd ? 0u : stepped1;
+        add_steps(e.steps, stepped);
     };
     // step cur - 1 is flushed as soon as none of its games is playing any more
     auto flush_done = [&]() {
         if (pending && __builtin_amdgcn_ballot_w64(live != 0 && old != 0) == 0) {
             flush(cur - 1u);
             pending = false;
+            prev_planes = nullptr;
         }
     };
 
@@ -1679,7 +1679,9 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
                 prev_planes = cur_planes;
                 prev_seed = cur_seed;
                 prev_first = cur_first;
+                prev_at = cur_at;
                 cur = __builtin_amdgcn_readfirstlane(cur + 1u);
+                cur_at = slice_at(cur);
                 pending = true;
                 cur_seed = tab.step[cur].seed;
                 cur_first = tab.step[cur].first_game;

@@ -43,6 +43,48 @@ constexpr bool deferred_opening_ok(int h, int w, int k) {
 // checkpoint; 0 = the opening as it was.  kRolloutOpeningBlocks stays 3 either way: it is what every other path plays.
 constexpr int kDeferredOpeningStages = 2;
 
+// The outcome byte of K2o and its grouped form (docs/EXPERIMENTS.md §29).  A game that ends leaves ONE byte in its wave's
+// LDS slice: its stones (= its plies: 1 .. 48 on the boards these kernels take, 7 .. 42 on 6x7x4) with bit 6 set when
+// somebody holds a run.  0 is "no game": the padding of a chunk's last dword, never a game's byte.  Everything a game
+// leaves besides its board follows from that byte, and is derived where a chunk is flushed -- four games a dword, twice a
+// wave and step -- not where the game ends, once an iteration of the refill loop:
+//   * its status byte as it goes to memory: a run belongs to whoever placed the last stone, ((stones - 1) & 1) + 1; a
+//     board that stopped without a run is full, BGS_ST_DRAW (3); 0 for no game;
+//   * its reward pair (two int8 in a uint16, player 1's in the low byte): +1 / -1 for status 1, -1 / +1 for status 2;
+//   * its 2-bit code for the hand-over: the status;
+//   * its plies, for the env-step counter.
+// connect_outcome4 is that mapping for the four bytes of a dword at once; connect_outcome is its one-byte case.
+constexpr uint32_t kOutcomeRun = 64u;
+constexpr uint32_t connect_outcome_byte(uint32_t stones, bool run) { return stones | (run ? kOutcomeRun : 0u); }
+struct ConnectOutcome4 {
+    uint32_t status;      // four status bytes, game 0 in the low byte
+    uint32_t reward[2];   // the reward pairs of games 0, 1 and of games 2, 3
+    uint32_t codes;       // the byte of four 2-bit codes, game 0 in the low bits
+    uint32_t plies;       // the plies of the four games together (at most 4 * 63)
+};
+constexpr ConnectOutcome4 connect_outcome4(uint32_t four) {
+    constexpr uint32_t L = 0x01010101u;
+    const uint32_t run = (four >> 6) & L, odd = four & L;
+    const uint32_t game = ((four + 0x7F7F7F7Fu) >> 7) & L;    // (a byte is at most 127: no carry into the next one)
+    const uint32_t low = game & ~(run & ~odd);                // status bit 0: unless a run came with an even stone
+    const uint32_t high = game & ~(run & odd);                // status bit 1: unless a run came with an odd stone
+    const uint32_t status = low | (high << 1);
+    const uint32_t won1 = low & ~high, won2 = high & ~low;    // bit 8 k: game k has status 1 / 2
+    const uint32_t a = (won1 & 1u) | ((won1 & 0x100u) << 8), b = (won2 & 1u) | ((won2 & 0x100u) << 8);
+    const uint32_t c = ((won1 >> 16) & 1u) | ((won1 >> 8) & 0x10000u), d = ((won2 >> 16) & 1u) | ((won2 >> 8) & 0x10000u);
+    return ConnectOutcome4{status,
+                           {a * 0xFF01u | b * 0x01FFu, c * 0xFF01u | d * 0x01FFu},
+                           (status & 3u) | ((status >> 6) & 0xCu) | ((status >> 12) & 0x30u) | ((status >> 18) & 0xC0u),
+                           ((four & 0x3F3F3F3Fu) * L) >> 24};
+}
+struct ConnectOutcome {
+    uint32_t status, reward, code, plies;
+};
+constexpr ConnectOutcome connect_outcome(uint32_t byte) {
+    const ConnectOutcome4 o = connect_outcome4(byte & 255u);
+    return ConnectOutcome{o.status, o.reward[0], o.codes, o.plies};
+}
+
 // Multi-step form of the K2o rollout (k_connect_rollout_opened_steps): one launch plays the batches of up to
 // kConnectGroupMax consecutive pipeline steps, every wave chunk w of each step in turn, its lanes carrying on from one
 // step's chunk into the next instead of idling until the wave's longest game has ended.  The executor hands
