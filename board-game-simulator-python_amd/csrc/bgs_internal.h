@@ -141,6 +141,14 @@ void connect_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget,
 uint64_t connect_search_root_bytes(int width, int32_t iterations);
 void connect_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
                     int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace);
+// the same search on trees that persist (bgs_connect_forest_search / bgs_connect_forest_advance): d_forest holds n *
+// connect_forest_tree_bytes(w, capacity) bytes, 256-byte aligned; d_carried int32[n] and d_kept int32[n] may be NULL;
+// d_columns int32[n] on the device; both are enqueued on the batch's stream and neither touches the boards
+uint64_t connect_forest_tree_bytes(int width, int32_t capacity);
+void connect_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                           int32_t max_plies, int policy, int32_t capacity, int restart, int32_t* d_counts, int32_t* d_visits,
+                           int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest);
+void connect_forest_advance(const bgs_batch* b, const int32_t* d_columns, int32_t capacity, int32_t* d_kept, void* d_forest);
 // exact alpha-beta solve of every column of packed Connect boards (bgs_connect_solve_actions): codes int8[n][w], plies
 // int16[n][w] (may be NULL), *d_nodes = positions visited; device pointers, enqueued on the batch's stream
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,

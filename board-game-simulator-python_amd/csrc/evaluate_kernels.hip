@@ -842,6 +842,442 @@ void launch_search(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_
 }
 
 // ================================================================================================================
+// The forest (bgs_connect_forest_search / bgs_connect_forest_advance, include/bgs.h): the trees of k_connect_search kept
+// from launch to launch in the caller's memory, `capacity` nodes a tree, and re-rooted between the launches.
+//
+// A tree's share of the forest, in 32-bit words, rounded up to 256 bytes:
+//   word 0         the nodes in use, the root counted (0: an emptied tree)
+//   word 1         unused
+//   words 2 ..     the position the root stands for: the 2 * NW plane words of the batch (player 0's, then player 1's),
+//                  64 bits each, 8-byte aligned
+//   words 16 ..    `capacity` nodes in k_connect_search's format (3 * width words: n, s, child)
+// The re-rooting needs a bit a node and a prefix count a 32 nodes; both live in LDS, which is what bounds `capacity`
+// (BGS_CONNECT_FOREST_MAX_CAPACITY), so the forest holds no scratch.
+//
+// k_connect_forest_search is k_connect_search with three differences: the carried check (or the emptying) at the start,
+// step 4 read as the Bounce search reads it (a node is made when the edge has no child AND the tree has room; an edge
+// whose node did not fit plays its playouts from p' all the same and is tried again the next time), and the header
+// written back at the end.  The iteration -- descent, playout block, back-propagation -- is that kernel's, line for line.
+// ================================================================================================================
+constexpr uint32_t kForestHeaderWords = 16;
+
+__host__ __device__ __forceinline__ uint64_t forest_tree_words(uint32_t width, uint32_t capacity) {
+    return (kForestHeaderWords + (uint64_t)capacity * width * 3u + 63u) & ~(uint64_t)63u;
+}
+
+template <int NW, bool PER_PLY, int POLICY>
+__global__ void __launch_bounds__(BGS_WAVE)
+k_connect_forest_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n, uint64_t seed,
+                        uint64_t game_base, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore, uint32_t max_plies,
+                        int64_t root_base, uint32_t capacity, uint32_t restart, uint32_t* forest, int32_t* __restrict__ counts,
+                        int32_t* __restrict__ visits, int32_t* __restrict__ best, int32_t* __restrict__ nodes,
+                        int32_t* __restrict__ carried, unsigned long long* __restrict__ steps) {
+    __shared__ uint32_t path_node[kSearchMaxPath];   // the descent: edge k leaves node path_node[k] by column path_col[k]
+    __shared__ uint32_t path_col[kSearchMaxPath];
+    __shared__ uint32_t tally[3];                    // W/D/L of the iteration's playouts, for the root's mover
+    __shared__ unsigned long long step_sum;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t width = (uint32_t)g.w();
+    const uint32_t stride = (uint32_t)g.h() + 1u;
+    const uint32_t node_words = width * 3u;
+    const int64_t i = root_base + (int64_t)blockIdx.x;       // (the grid holds exactly the roots of this launch)
+    uint32_t* const head = forest + (uint64_t)i * forest_tree_words(width, capacity);
+    uint64_t* const head_planes = reinterpret_cast<uint64_t*>(head + 2);
+    uint32_t* const tree = head + kForestHeaderWords;
+
+    Bits<NW> r0, r1;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        r0.w[j] = planes[(int64_t)j * n + i];
+        r1.w[j] = planes[(int64_t)(NW + j) * n + i];
+    }
+    const uint32_t rply = popcount(r0) + popcount(r1);
+    const uint32_t root_mover = rply & 1u;
+    const bool running = status[i] == BGS_ST_RUNNING;
+    uint32_t cw = 0, cd = 0, cl = 0;    // lane c: W/D/L of the playouts through root column c
+    uint64_t stepped = 0;
+    if (lane == 0) step_sum = 0;
+
+    // ---- the carried check (wave-uniform: every lane reads the same header): a tree that fails it is emptied
+    uint32_t used = head[0];            // (uniform) nodes in the tree, the root counted
+    bool keep = restart == 0u && running && used >= 1u && used <= capacity;
+    if (keep) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) keep = keep && head_planes[j] == r0.w[j] && head_planes[NW + j] == r1.w[j];
+    }
+    if (keep) {                         // N + T * P < 2^31: the root's n[c] stay in int32
+        const uint32_t nc = lane < width ? tree[lane] : 0u;
+        uint64_t total = 0;
+        for (uint32_t c = 0; c < width; ++c) total += (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)c);
+        keep = total + (uint64_t)iterations * leaf_playouts < (1ull << 31);
+    }
+    keep = __builtin_amdgcn_readfirstlane((int)keep) != 0;
+    if (!keep) {
+        used = running ? 1u : 0u;
+        if (running && lane < node_words) tree[lane] = 0;     // the root is node 0 (3 * width <= 48 words)
+        if (running && lane == 0) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) {
+                head_planes[j] = r0.w[j];
+                head_planes[NW + j] = r1.w[j];
+            }
+        }
+    }
+    used = (uint32_t)__builtin_amdgcn_readfirstlane((int)used);
+    const uint32_t brought = used ? used - 1u : 0u;
+    __syncthreads();
+
+    Bits<NW> q[2];                      // the lane's playout: stones of player 0 / player 1
+#pragma unroll
+    for (int j = 0; j < NW; ++j) q[0].w[j] = q[1].w[j] = 0;
+    Philox4 ph;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ph.v[j] = 0;
+
+    for (uint32_t t = 0; running && t < iterations; ++t) {
+        // ---- descent (wave-uniform): p is the position at node v
+        Bits<NW> p[2] = {r0, r1};
+        uint32_t ply = rply, v = 0, depth = 0, leaf = BGS_ST_RUNNING, col0 = 0;
+        for (;;) {
+            const Bits<NW> occ = p[0] | p[1];
+            uint32_t height = (uint32_t)g.h();
+            if (lane < width) height = (uint32_t)__popcll(shr(occ, (int)(lane * stride)).w[0] & ((1ull << g.h()) - 1ull));
+            const bool legal = height < (uint32_t)g.h();
+            uint32_t* const node = tree + (uint64_t)v * node_words;
+            uint32_t nc = 0, sc = 0, ch = 0;
+            if (legal) {
+                nc = node[lane];
+                sc = node[width + lane];
+                ch = node[2u * width + lane];
+            }
+            const uint64_t unvisited = __builtin_amdgcn_ballot_w64(legal && nc == 0u);
+            uint32_t col;
+            if (unvisited) {
+                col = (uint32_t)__builtin_ctzll(unvisited);            // the expansion: the lowest column never played
+            } else {
+                uint32_t total = 0;
+                for (uint32_t c = 0; c < width; ++c) total += (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)c);
+                uint32_t key = 0;                                      // (U(c) << 4 | 15 - c) + 1: the largest U, then the lowest column
+                if (legal) {
+                    const uint32_t u = search_q(sc, nc) + search_isqrt(explore * search_lg(total) / nc);
+                    key = ((u << 4) | (15u - lane)) + 1u;
+                }
+                uint32_t top = 0;
+                for (uint32_t c = 0; c < width; ++c) {
+                    const uint32_t other = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)c);
+                    top = other > top ? other : top;
+                }
+                col = 15u - ((top - 1u) & 15u);
+            }
+            col = (uint32_t)__builtin_amdgcn_readfirstlane((int)col);
+            const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)height, (int)col);
+            const uint32_t child = (uint32_t)__builtin_amdgcn_readlane((int)ch, (int)col);
+            if (lane == 0) {
+                path_node[depth] = v;
+                path_col[depth] = col;
+            }
+            col0 = depth == 0u ? col : col0;
+            const uint32_t mover = ply & 1u;
+            Bits<NW>& mine = mover ? p[1] : p[0];
+            const bool won = drop_and_test(g, mine, col * stride + at, ~0u);
+            ply += 1u;
+            depth += 1u;
+            leaf = won ? mover + 1u : (ply == g.cells_total ? (uint32_t)BGS_ST_DRAW : (uint32_t)BGS_ST_RUNNING);
+            leaf = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf);
+            if (leaf != BGS_ST_RUNNING) break;                         // a terminal edge: no node, no game
+            if (child == 0u) {                                         // no node for p' yet: one is made if it fits
+                if (used < capacity) {
+                    if (lane < node_words) tree[(uint64_t)used * node_words + lane] = 0;
+                    if (lane == col) node[2u * width + lane] = used;
+                    used += 1u;
+                }
+                break;
+            }
+            v = child;
+        }
+
+        // ---- the leaf's playouts: the lanes take them in order, idle lanes refill at 4-ply block boundaries
+        uint32_t wins = 0, draws = 0, losses = 0, played = 0;
+        if (lane < 3u) tally[lane] = 0;
+        if (leaf != BGS_ST_RUNNING) {
+            if (lane == 0) {       // all playouts of the iteration have the edge's outcome
+                wins = (leaf != BGS_ST_DRAW && leaf - 1u == root_mover) ? leaf_playouts : 0u;
+                losses = (leaf != BGS_ST_DRAW && leaf - 1u != root_mover) ? leaf_playouts : 0u;
+                draws = leaf == BGS_ST_DRAW ? leaf_playouts : 0u;
+            }
+        } else if (ply < max_plies) {
+            // G = ((first_game + i) * T + t) * P + j
+            const uint64_t game0 = game_base + ((uint64_t)i * iterations + t) * (uint64_t)leaf_playouts;
+            uint64_t game = 0;
+            uint32_t taken = 0, blk = 0, skip = 0, live = 0, st = 0, fresh = 0;
+            while (taken < leaf_playouts || __builtin_amdgcn_ballot_w64(live != 0)) {
+                const uint64_t need = __builtin_amdgcn_ballot_w64(live == 0);
+                if (need != 0 && taken < leaf_playouts) {
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                    if (live == 0 && rank < leaf_playouts - taken) {
+                        q[0] = p[0];
+                        q[1] = p[1];
+                        game = game0 + (uint64_t)(taken + rank);
+                        blk = ply >> 2;
+                        skip = ply & 3u;
+                        live = ~0u;
+                        fresh = 1u;
+                        st = 0;
+                    }
+                    const uint32_t wanted = (uint32_t)__popcll(need);
+                    taken = leaf_playouts - taken < wanted ? leaf_playouts : taken + wanted;
+                }
+
+                // ---- the 4-ply block of k_connect_evaluate: the same draws, the same ply code
+                if (PER_PLY) {
+                    ph = philox4x32_10(seed, game, blk);
+                } else {
+                    const bool want = live && (fresh || (blk & 3u) == 0u);
+                    if (__builtin_amdgcn_ballot_w64(want)) {
+                        if (want) ph = philox4x32_10(seed, game, blk >> 2);
+                    }
+                }
+                fresh = 0;
+                const uint32_t word = PER_PLY ? 0u : philox_word(ph, blk);
+                const uint32_t was_live = live;
+#pragma unroll
+                for (uint32_t j = 0; j < 4; ++j) {
+                    const uint32_t draw = PER_PLY ? ph.v[j] : sub_draw(word, j);
+                    const uint32_t act = j >= skip ? live : 0u;
+                    const uint32_t at = 4u * blk + j;          // stones before this sub-step; its mover is player j & 1
+                    bool won;
+                    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                        const uint32_t pos = decisive_position(g, q[j & 1u], q[(j & 1u) ^ 1u], draw, won);
+                        drop(q[j & 1u], pos, act);
+                        won = won && act;
+                    } else {
+                        const uint32_t pos = draw_position(g, q[0] | q[1], draw);
+                        won = drop_and_test(g, q[j & 1u], pos, act);
+                    }
+                    const bool full = at + 1u == g.cells_total;
+                    if (act) {
+                        st = won ? (j & 1u) + 1u : (full ? BGS_ST_DRAW : BGS_ST_RUNNING);
+                        live = (won || full || at + 1u >= max_plies) ? 0u : live;
+                        played += 1u;
+                    }
+                }
+                blk += 1u;
+                skip = 0;
+                if (was_live && !live) {      // (st == 0: capped, counted nowhere)
+                    wins += (st != 0u && st != BGS_ST_DRAW && st - 1u == root_mover) ? 1u : 0u;
+                    losses += (st != 0u && st != BGS_ST_DRAW && st - 1u != root_mover) ? 1u : 0u;
+                    draws += st == BGS_ST_DRAW ? 1u : 0u;
+                }
+            }
+        }
+        stepped += played;
+        __syncthreads();            // the tally is zero, the path and the new node are written
+        if (wins) atomicAdd(tally + 0, wins);
+        if (draws) atomicAdd(tally + 1, draws);
+        if (losses) atomicAdd(tally + 2, losses);
+        __syncthreads();
+        const uint32_t tw = tally[0], td = tally[1], tl = tally[2];
+
+        // ---- back-propagation: lane k takes edge k of the path; its mover is the root's at even k
+        for (uint32_t k = lane; k < depth; k += BGS_WAVE) {
+            uint32_t* const node = tree + (uint64_t)path_node[k] * node_words;
+            const uint32_t c = path_col[k];
+            node[c] += leaf_playouts;
+            node[width + c] += td + 2u * ((k & 1u) ? tl : tw);
+        }
+        if (lane == col0) {
+            cw += tw;
+            cd += td;
+            cl += tl;
+        }
+        __syncthreads();            // the tree is whole again before the next descent reads it; tally and path are free
+    }
+
+    // ---- the outputs of the root (an illegal column was never played: its words of the root are zero)
+    uint32_t nv = 0, sv = 0;
+    if (running && lane < width) {
+        nv = tree[lane];
+        sv = tree[width + lane];
+    }
+    if (lane < width) {
+        counts[(i * (int64_t)width + lane) * 3 + 0] = (int32_t)cw;
+        counts[(i * (int64_t)width + lane) * 3 + 1] = (int32_t)cd;
+        counts[(i * (int64_t)width + lane) * 3 + 2] = (int32_t)cl;
+        if (visits) visits[i * (int64_t)width + lane] = (int32_t)nv;
+    }
+    if (best) {
+        // the most visits, then the larger 2 * wins + draws, then the lower column; an illegal column has no visits
+        int32_t top = -1;
+        uint32_t top_n = 0, top_s = 0;
+        for (uint32_t c = 0; running && c < width; ++c) {
+            const uint32_t cn = (uint32_t)__builtin_amdgcn_readlane((int)nv, (int)c);
+            const uint32_t cs = (uint32_t)__builtin_amdgcn_readlane((int)sv, (int)c);
+            if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
+                top = (int32_t)c;
+                top_n = cn;
+                top_s = cs;
+            }
+        }
+        if (lane == 0) best[i] = top;
+    }
+    if (lane == 0) {
+        head[0] = used;             // the header: the planes were recorded when the tree was emptied, or carried with it
+        if (nodes) nodes[i] = (int32_t)(used ? used - 1u : 0u);
+        if (carried) carried[i] = (int32_t)brought;
+    }
+    if (stepped) atomicAdd(&step_sum, (unsigned long long)stepped);
+    __syncthreads();
+    if (lane == 0 && step_sum) atomicAdd(steps + (size_t)(blockIdx.x % BGS_STEP_SHARDS) * BGS_STEP_STRIDE, step_sum);
+}
+
+template <int NW, bool PER_PLY, int POLICY>
+void launch_forest_search(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts,
+                          uint32_t explore, uint32_t max_plies, uint32_t capacity, uint32_t restart, int32_t* d_counts, int32_t* d_visits,
+                          int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest) {
+    const uint64_t game_base = b->first_game * (uint64_t)iterations * (uint64_t)leaf_playouts;
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL((k_connect_forest_search<NW, PER_PLY, POLICY>), dim3((uint32_t)blocks), dim3(BGS_WAVE), 0, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, seed, game_base, iterations, leaf_playouts,
+                           explore, max_plies, i0, capacity, restart, static_cast<uint32_t*>(d_forest), d_counts, d_visits, d_best,
+                           d_nodes, d_carried, b->d_steps);
+    }
+}
+
+// The re-rooting (bgs_connect_forest_advance): one wave a tree, in place, one launch.  Nodes are made in increasing index
+// order, so a child's index is above its parent's, and a compaction that keeps the order keeps that property:
+//   mark     the subtree of r = the root's child[c] in a bit mask (LDS), by an ascending sweep from r over chunks of 64
+//            nodes: a chunk's words come in coalesced, lane l then marks the children of node base + l if that node is
+//            marked, and the chunk is swept again while a lane finds its node newly marked (a chain inside the chunk);
+//   number   new[v] = the marked nodes below v: a prefix popcount, one entry a mask word;
+//   move     chunk by chunk in ascending order: the chunk is read into LDS, a barrier, then every marked node goes to
+//            new[v] <= v with its child words mapped -- a slot of this chunk or an earlier one, never one still to be read;
+//   header   one lane, last, behind a barrier: the count, and the stone of column c dropped on the recorded position.
+// Chunks without a marked node are neither read nor written.  The work is that of the nodes in use, not of `capacity`.
+__global__ void __launch_bounds__(BGS_WAVE)
+k_connect_forest_advance(uint32_t height, uint32_t width, uint32_t nw, const int32_t* __restrict__ columns, uint32_t capacity,
+                         uint32_t* forest, int32_t* __restrict__ kept, int64_t root_base) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t forest_lds[];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t node_words = width * 3u;
+    const uint32_t mask_room = (((capacity + 31u) >> 5) + 3u) & ~3u;
+    uint32_t* const mask = forest_lds;              // bit v: node v stays
+    uint32_t* const below = mask + mask_room;       // the marked nodes in the mask words before this one
+    uint32_t* const chunk = below + mask_room;      // 64 nodes
+    const int64_t i = root_base + (int64_t)blockIdx.x;
+    uint32_t* const head = forest + (uint64_t)i * forest_tree_words(width, capacity);
+    uint32_t* const tree = head + kForestHeaderWords;
+
+    const int32_t c = columns[i];
+    uint32_t used = head[0];
+    used = (uint32_t)__builtin_amdgcn_readfirstlane((int)(used <= capacity ? used : 0u));
+    if (c < 0) {                                    // untouched
+        if (kept && lane == 0) kept[i] = (int32_t)(used ? used - 1u : 0u);
+        return;
+    }
+    // the new root: the child of the root's edge c (0: never played, terminal, did not fit, a full column)
+    uint32_t r = (used != 0u && (uint32_t)c < width) ? tree[2u * width + (uint32_t)c] : 0u;
+    r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(r < used ? r : 0u));
+    // the cell the stone takes on the recorded position, and its mover: plane bits are counted in 32-bit words
+    const uint32_t plane_words = 2u * nw;           // 32-bit words a player
+    uint32_t stones = lane < 2u * plane_words ? (uint32_t)__popc(head[2u + lane]) : 0u;
+    for (int d = 32; d >= 1; d >>= 1) stones += (uint32_t)__shfl_xor((int)stones, d);
+    uint32_t at = 0;
+    if ((uint32_t)c < width) {
+        for (uint32_t y0 = 0; y0 < height; y0 += BGS_WAVE) {
+            const uint32_t bit = (uint32_t)c * (height + 1u) + y0 + lane;
+            const bool taken = y0 + lane < height &&
+                               (((head[2u + (bit >> 5)] | head[2u + plane_words + (bit >> 5)]) >> (bit & 31u)) & 1u) != 0u;
+            at += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(taken));
+        }
+    }
+    if (r == 0u || at >= height) {                  // emptied: the next search starts anew from the batch's board
+        if (lane == 0) {
+            head[0] = 0;
+            if (kept) kept[i] = 0;
+        }
+        return;
+    }
+
+    // ---- mark
+    const uint32_t mask_words = (used + 31u) >> 5;
+    for (uint32_t k = lane; k < mask_words; k += BGS_WAVE) mask[k] = 0;
+    __syncthreads();
+    if (lane == 0) mask[r >> 5] = 1u << (r & 31u);
+    __syncthreads();
+    for (uint32_t base = r & ~63u; base < used; base += 64u) {
+        const uint32_t m0 = mask[base >> 5], m1 = (base >> 5) + 1u < mask_words ? mask[(base >> 5) + 1u] : 0u;
+        if ((m0 | m1) == 0u) continue;              // (uniform) nothing of this chunk is in the subtree
+        const uint32_t count = used - base < 64u ? used - base : 64u;
+        for (uint32_t k = lane; k < count * node_words; k += BGS_WAVE) chunk[k] = tree[(uint64_t)base * node_words + k];
+        __syncthreads();
+        bool done = false;
+        for (;;) {
+            const uint32_t v = base + lane;
+            const bool go = !done && lane < count && ((mask[v >> 5] >> (v & 31u)) & 1u) != 0u;
+            if (__builtin_amdgcn_ballot_w64(go) == 0) break;
+            if (go) {
+                for (uint32_t x = 0; x < width; ++x) {
+                    const uint32_t ch = chunk[lane * node_words + 2u * width + x];
+                    if (ch > v && ch < used) atomicOr(mask + (ch >> 5), 1u << (ch & 31u));
+                }
+                done = true;
+            }
+            __syncthreads();
+        }
+        __syncthreads();                            // the chunk is free for the next one
+    }
+
+    // ---- number
+    uint32_t total = 0;
+    for (uint32_t k0 = 0; k0 < mask_words; k0 += BGS_WAVE) {
+        const uint32_t k = k0 + lane;
+        const uint32_t bits = k < mask_words ? (uint32_t)__popc(mask[k]) : 0u;
+        uint32_t upto = bits;                       // the inclusive scan of the wave
+        for (int d = 1; d < BGS_WAVE; d <<= 1) {
+            const uint32_t other = (uint32_t)__shfl_up((int)upto, d);
+            upto += lane >= (uint32_t)d ? other : 0u;
+        }
+        if (k < mask_words) below[k] = total + upto - bits;
+        total += (uint32_t)__shfl((int)upto, BGS_WAVE - 1);
+    }
+    __syncthreads();
+
+    // ---- move
+    for (uint32_t base = r & ~63u; base < used; base += 64u) {
+        const uint32_t m0 = mask[base >> 5], m1 = (base >> 5) + 1u < mask_words ? mask[(base >> 5) + 1u] : 0u;
+        if ((m0 | m1) == 0u) continue;
+        const uint32_t count = used - base < 64u ? used - base : 64u;
+        for (uint32_t k = lane; k < count * node_words; k += BGS_WAVE) chunk[k] = tree[(uint64_t)base * node_words + k];
+        __syncthreads();                            // every word of the chunk is read before one is written
+        for (uint32_t l = 0; l < count; ++l) {
+            const uint32_t v = base + l;
+            const uint32_t word = mask[v >> 5];
+            if (((word >> (v & 31u)) & 1u) == 0u) continue;
+            const uint32_t to = below[v >> 5] + (uint32_t)__popc(word & ((1u << (v & 31u)) - 1u));
+            if (lane < node_words) {
+                uint32_t x = chunk[l * node_words + lane];
+                if (lane >= 2u * width) {           // a child word: the child's new index (a kept node's children are kept)
+                    x = (x > v && x < used) ? below[x >> 5] + (uint32_t)__popc(mask[x >> 5] & ((1u << (x & 31u)) - 1u)) : 0u;
+                }
+                tree[(uint64_t)to * node_words + lane] = x;
+            }
+        }
+        __syncthreads();                            // the chunk is free for the next one
+    }
+
+    // ---- header (the tree's writes are issued; the count and the stone go last)
+    __syncthreads();
+    if (lane == 0) {
+        const uint32_t bit = (uint32_t)c * (height + 1u) + at;
+        head[0] = total;
+        head[2u + ((stones & 1u) ? plane_words : 0u) + (bit >> 5)] |= 1u << (bit & 31u);
+        if (kept) kept[i] = (int32_t)(total - 1u);
+    }
+}
+
+// ================================================================================================================
 // Bounce (bgs_bounce_evaluate_moves): for root i and slot s = x * H * W + c -- the move of the piece in column x of the
 // active row to cell c, bit c of the root's targets[x] -- `playouts` games that start with that move and continue by the
 // uniform random policy, reduced to (wins, draws, losses) of the player to move at root i.  Playout p of slot s of root i
@@ -2726,6 +3162,55 @@ void connect_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32
         case 1: search_nw<1>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
         case 2: search_nw<2>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
         default: search_nw<3>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
+    }
+}
+
+uint64_t connect_forest_tree_bytes(int width, int32_t capacity) {
+    return forest_tree_words((uint32_t)width, (uint32_t)capacity) * sizeof(uint32_t);
+}
+
+template <int NW>
+static void forest_search_nw(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts,
+                             uint32_t explore, uint32_t cap, int policy, uint32_t capacity, uint32_t restart, int32_t* d_counts,
+                             int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest) {
+    constexpr int U = BGS_POLICY_UNIFORM, D = BGS_POLICY_DECISIVE;
+    const bool per_ply = b->rng_per_ply != 0;
+    if (policy == D) {
+        per_ply ? launch_forest_search<NW, true, D>(b, g, seed, iterations, leaf_playouts, explore, cap, capacity, restart, d_counts,
+                                                    d_visits, d_best, d_nodes, d_carried, d_forest)
+                : launch_forest_search<NW, false, D>(b, g, seed, iterations, leaf_playouts, explore, cap, capacity, restart, d_counts,
+                                                     d_visits, d_best, d_nodes, d_carried, d_forest);
+    } else {
+        per_ply ? launch_forest_search<NW, true, U>(b, g, seed, iterations, leaf_playouts, explore, cap, capacity, restart, d_counts,
+                                                    d_visits, d_best, d_nodes, d_carried, d_forest)
+                : launch_forest_search<NW, false, U>(b, g, seed, iterations, leaf_playouts, explore, cap, capacity, restart, d_counts,
+                                                     d_visits, d_best, d_nodes, d_carried, d_forest);
+    }
+}
+
+void connect_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                           int32_t max_plies, int policy, int32_t capacity, int restart, int32_t* d_counts, int32_t* d_visits,
+                           int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest) {
+    const EvalGeom g = eval_geom(b);
+    const uint32_t t = (uint32_t)iterations, p = (uint32_t)leaf_playouts, e = (uint32_t)explore, cap = (uint32_t)max_plies;
+    const uint32_t room = (uint32_t)capacity, anew = restart ? 1u : 0u;
+    switch (b->cg.nw) {
+        case 1: forest_search_nw<1>(b, g, seed, t, p, e, cap, policy, room, anew, d_counts, d_visits, d_best, d_nodes, d_carried, d_forest); break;
+        case 2: forest_search_nw<2>(b, g, seed, t, p, e, cap, policy, room, anew, d_counts, d_visits, d_best, d_nodes, d_carried, d_forest); break;
+        default: forest_search_nw<3>(b, g, seed, t, p, e, cap, policy, room, anew, d_counts, d_visits, d_best, d_nodes, d_carried, d_forest); break;
+    }
+}
+
+void connect_forest_advance(const bgs_batch* b, const int32_t* d_columns, int32_t capacity, int32_t* d_kept, void* d_forest) {
+    const uint32_t width = (uint32_t)b->cg.w, room = (uint32_t)capacity;
+    // LDS: the mask and the prefix counts (a bit and a 32nd of a word a node, each rounded up to 16 bytes), a chunk of 64 nodes
+    const uint32_t mask_room = (((room + 31u) >> 5) + 3u) & ~3u;
+    const size_t lds = ((size_t)2 * mask_room + (size_t)64 * width * 3u) * sizeof(uint32_t);
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL(k_connect_forest_advance, dim3((uint32_t)blocks), dim3(BGS_WAVE), lds, b->stream, (uint32_t)b->cg.h, width,
+                           (uint32_t)b->cg.nw, d_columns, room, static_cast<uint32_t*>(d_forest), d_kept, i0);
     }
 }
 

@@ -11,7 +11,8 @@ and counted in ONE launch: ``ConnectBatch.evaluate_actions`` for Connect states 
 Bounce positions go to the horizon search ``BounceBatch.solve_moves`` in the same way (dispatched on the state's type).
 
 ``TreeSearchAgent`` grows a UCT tree a Connect position (``ConnectBatch.search_actions``: all positions of a call in one
-launch) and plays the column with the most visits.
+launch) and plays the column with the most visits; with ``reuse=True`` it keeps the trees from call to call
+(``ConnectBatch.search_forest``) and carries the subtree under the moves played into the next search.
 
 ``BounceHalvingAgent`` spends a fixed budget of playouts a Bounce position by sequential halving
 (``BounceBatch.evaluate_moves_halving``) and plays the last surviving move.
@@ -242,10 +243,23 @@ class TreeSearchAgent:
     draws, then the lower column; None for a state without an action).  The playouts of the position at index k of a call
     are the games ``((first_game + k) * iterations + t) * leaf_playouts + j`` of ``seed``.  ``explore`` is about 45426 *
     C * C for a UCB1 constant C; ``policy`` is the playout policy, "uniform" or "decisive"; ``max_plies`` caps every
-    playout at that absolute ply count (None: no cap).  Bounce states raise ValueError: the search covers Connect."""
+    playout at that absolute ply count (None: no cap).  Bounce states raise ValueError: the search covers Connect.
+
+    ``reuse=True`` keeps the trees between calls (``ConnectBatch.search_forest``): the agent holds a forest per (Config,
+    number of states) and remembers the grids it last searched there.  Before a search it advances the tree at index k by
+    the one or two stones that lead from the remembered grid k to the new one -- the remembered mover's stone first, and
+    the lower stone first when both share a column --, so the subtree under the moves played is carried into the search;
+    an equal grid is searched on, and any other difference makes the search start that tree anew.  So the states of
+    successive calls must keep their indices.  Search number m on a forest (from 0) draws with ``seed + m`` (mod 2^64),
+    ``visits`` include the carried ones (the shares ``predict`` gives still sum to 1), and ``search`` returns ``carried`` --
+    the nodes every tree started with -- as a fifth element.  ``capacity`` is the room of a tree in nodes; None:
+    ``2 * iterations + 1``, the nodes one search can make plus as many carried ones.  That is an allowance and not a
+    measurement: a tree that is full stops growing until the next advance frees room.  Without ``reuse`` the agent is
+    what it was, code path included."""
 
     def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
-                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None):
+                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, reuse: bool = False,
+                 capacity: Optional[int] = None):
         playout_policy(policy)
         if iterations < 1 or leaf_playouts < 1:
             raise ValueError("iterations and leaf_playouts must be >= 1")
@@ -253,6 +267,11 @@ class TreeSearchAgent:
             raise ValueError("explore must be 0 .. 2**18")
         if max_plies is not None and max_plies < 1:
             raise ValueError("max_plies must be >= 1")
+        if capacity is not None and capacity < 2:
+            raise ValueError("capacity must be >= 2")
+        self.reuse = bool(reuse)
+        self.capacity = 2 * int(iterations) + 1 if capacity is None else int(capacity)
+        self._forests: Dict[tuple, list] = {}   # key -> [SearchForest, grids last searched, their movers, searches so far]
         self.iterations = int(iterations)
         self.leaf_playouts = int(leaf_playouts)
         self.explore = int(explore)
@@ -263,7 +282,8 @@ class TreeSearchAgent:
         self._batches: Dict[tuple, ConnectBatch] = {}
 
     def search(self, states: Sequence, first_game: int = 0):
-        """(counts, visits, best, nodes) of the launch over `states` (Connect states that share one Config)"""
+        """(counts, visits, best, nodes) of the launch over `states` (Connect states that share one Config); with `reuse`
+        (counts, visits, best, nodes, carried)"""
         if isinstance(states[0], bounce.State):
             raise ValueError("TreeSearchAgent: Connect states only; the tree search does not cover Bounce")
         if not isinstance(states[0], connect.State):
@@ -282,14 +302,52 @@ class TreeSearchAgent:
             raise ValueError("TreeSearchAgent: a state could not be loaded")
         b.set_first_game(first_game)
         cap = 2**31 - 1 if self.max_plies is None else self.max_plies
+        if self.reuse:
+            return self._search_on(key, b, grid, player, cap)
         return b.search_actions(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore,
                                 max_plies=cap, policy=self.policy)
+
+    @staticmethod
+    def stones_between(old: np.ndarray, mover: int, new: np.ndarray):
+        """the columns (first, second; -1: none) of the one or two stones that lead from grid `old` with `mover` to move
+        to grid `new`: the mover's stone first, the lower stone first when both share a column.  (-1, -1) for equal grids
+        and for any other difference."""
+        rows, cols = np.nonzero(old != new)
+        if not 1 <= rows.size <= 2 or (old[rows, cols] != -1).any():
+            return -1, -1
+        stones = [(int(r), int(c), int(new[r, c])) for r, c in zip(rows, cols)]   # (row, column, owner); row 0 is the bottom
+        if len(stones) == 1:
+            return (stones[0][1], -1) if stones[0][2] == mover else (-1, -1)
+        if sorted(s[2] for s in stones) != [0, 1]:
+            return -1, -1
+        stacked = stones[0][1] == stones[1][1]
+        stones.sort(key=lambda s: s[0] if stacked else s[2] != mover)
+        return stones[0][1], stones[1][1]
+
+    def _search_on(self, key, b: ConnectBatch, grid: np.ndarray, player: np.ndarray, cap: int):
+        """the search of `reuse`: advance the forest of `key` from the grids it last searched to `grid`, then search on"""
+        entry = self._forests.get(key)
+        if entry is None:
+            entry = self._forests[key] = [b.search_forest(self.capacity), None, None, 0]
+        forest, last_grid, last_player, searches = entry
+        if last_grid is not None:
+            plies = np.array([self.stones_between(last_grid[k], int(last_player[k]), grid[k]) for k in range(len(grid))],
+                             dtype=np.int32)
+            for columns in (plies[:, 0], plies[:, 1]):
+                if (columns >= 0).any():
+                    forest.advance(columns)
+        out = forest.search(seed=(self.seed + searches) % 2**64, iterations=self.iterations, leaf_playouts=self.leaf_playouts,
+                            explore=self.explore, max_plies=cap, policy=self.policy)
+        entry[1:] = [grid, player, searches + 1]
+        return out
 
     def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict]:
         """`predict` of every state, searched in one launch"""
         if not states:
             return []
         visits = self.search(states, first_game)[1]
+        if self.reuse:      # the root's visits include the carried ones
+            return [{a: float(visits[k, a.column]) / int(visits[k].sum()) for a in s.actions} for k, s in enumerate(states)]
         total = self.iterations * self.leaf_playouts
         return [{a: float(visits[k, a.column]) / total for a in s.actions} for k, s in enumerate(states)]
 
@@ -309,6 +367,9 @@ class TreeSearchAgent:
         return self.choose_many([state], first_game=game)[0]
 
     def close(self) -> None:
+        for entry in self._forests.values():
+            entry[0].close()
+        self._forests.clear()
         for b in self._batches.values():
             b.close()
         self._batches.clear()

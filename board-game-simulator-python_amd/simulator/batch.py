@@ -946,6 +946,17 @@ class ConnectBatch(_Batch):
             ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
         return outs["counts"], outs["visits"], outs["best"], outs["nodes"]
 
+    def forest_bytes(self, capacity: int) -> int:
+        """bytes of device memory a forest of this batch takes at `capacity` nodes a tree (bgs_connect_forest_bytes)"""
+        nbytes = ctypes.c_size_t()
+        _abi.check(_abi.lib().bgs_connect_forest_bytes(self._handle, ctypes.c_int32(capacity), ctypes.byref(nbytes)))
+        return nbytes.value
+
+    def search_forest(self, capacity: int) -> "SearchForest":
+        """A forest for this batch: one search tree per board with room for `capacity` nodes, kept on the device from
+        search to search (`SearchForest`).  The forest belongs to this batch's shape; close it before the batch."""
+        return SearchForest(self, capacity)
+
     def solve_actions(self, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """Exact solve of every column of every board (bgs_connect_solve_actions), one launch: (codes int8[n, width],
         plies int16[n, width] or None).  Seen from the player to move; lines of at most `depth` plies from the board,
@@ -1013,6 +1024,105 @@ class ConnectBatch(_Batch):
             out = t.empty((self.n, self.width), dtype=t.uint8, device=f"cuda:{self.device}")
         _abi.check(_abi.lib().bgs_export_device(self._handle, ord("l"), ctypes.c_void_p(out.data_ptr())))
         return out
+
+
+class SearchForest:
+    """One UCT tree per board of a ConnectBatch, kept on the device from search to search (bgs_connect_forest_search /
+    bgs_connect_forest_advance, include/bgs.h): `ConnectBatch.search_forest(capacity)` makes one.  A tree has room for
+    `capacity` nodes, the root included.
+
+    The loop of an agent: `search`, play a column a board (`ConnectBatch.step_actions`), `advance` by the same columns --
+    the subtree under the column played becomes the tree --, and after the opponent's reply `advance` again and `search`:
+    the nodes that were carried are counted in `carried`.  A tree whose recorded root is not its board's position when a
+    search starts (the board was loaded, reset or stepped without `advance`) is started anew by that search.
+
+    The object owns the device buffer (a torch tensor) and belongs to the batch it was made from; its first search
+    restarts every tree, whatever `restart` says, because fresh memory holds no trees."""
+
+    def __init__(self, batch: ConnectBatch, capacity: int):
+        self.batch = batch
+        self.capacity = int(capacity)
+        nbytes = batch.forest_bytes(self.capacity)         # (refuses Bounce, generic boards and a bad capacity)
+        t = batch._need_torch("search_forest")
+        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")   # (zeros: every tree empty)
+        self._fresh = True
+
+    def close(self) -> None:
+        self._buffer = None
+
+    def _call(self, seed, iterations, leaf_playouts, explore, max_plies, policy, restart, pointers, on_device):
+        if self._buffer is None:
+            raise RuntimeError("the forest is closed")
+        code = playout_policy(policy)
+        _abi.check(_abi.lib().bgs_connect_forest_search(
+            self.batch._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts),
+            ctypes.c_int32(explore), ctypes.c_int32(max_plies), code, ctypes.c_int32(self.capacity),
+            1 if restart or self._fresh else 0, *(ctypes.c_void_p(p) for p in pointers), ctypes.c_void_p(self._buffer.data_ptr()),
+            ctypes.c_size_t(self._buffer.numel()), on_device))
+        self._fresh = False
+
+    def search(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE,
+               max_plies: int = 2**31 - 1, policy: str = "uniform", restart: bool = False):
+        """`iterations` further iterations on every tree (bgs_connect_forest_search), one launch: (counts int32[n, width,
+        3], visits int32[n, width], best int32[n], nodes int32[n], carried int32[n]).  `counts` are those of this call's
+        playouts, `visits` the root's, carried visits included, `nodes` the nodes in the tree afterwards and `carried`
+        the nodes it started with, the root not counted in either.  Vary `seed` from call to call: playout j of iteration
+        t of board i is game ((first_game + i) * iterations + t) * leaf_playouts + j of every call.  `restart` empties
+        every tree first."""
+        n, w = self.batch.n, self.batch.width
+        outs = (np.empty((n, w, 3), dtype=np.int32), np.empty((n, w), dtype=np.int32), np.empty(n, dtype=np.int32),
+                np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
+        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [o.ctypes.data for o in outs], 0)
+        return outs
+
+    def search_tensor(self, counts=None, visits=None, best=None, nodes=None, carried=None, seed: int = DEFAULT_SEED,
+                      iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1,
+                      policy: str = "uniform", restart: bool = False):
+        """`search` into device tensors int32[n, width, 3], int32[n, width] and three int32[n] (allocated when None),
+        enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes, carried)."""
+        t = self.batch._need_torch("search_tensor")
+        n, w = self.batch.n, self.batch.width
+        shapes = {"counts": (n, w, 3), "visits": (n, w), "best": (n,), "nodes": (n,), "carried": (n,)}
+        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "carried": carried}
+        for name, shape in shapes.items():
+            x = outs[name]
+            if x is None:
+                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.batch.device}")
+            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [outs[k].data_ptr() for k in shapes], 1)
+        return tuple(outs[k] for k in shapes)
+
+    def _advance(self, columns: int, kept: int, on_device: int) -> None:
+        if self._buffer is None:
+            raise RuntimeError("the forest is closed")
+        _abi.check(_abi.lib().bgs_connect_forest_advance(
+            self.batch._handle, ctypes.c_void_p(columns), ctypes.c_int32(self.capacity), ctypes.c_void_p(kept),
+            ctypes.c_void_p(self._buffer.data_ptr()), ctypes.c_size_t(self._buffer.numel()), on_device))
+
+    def advance(self, columns) -> np.ndarray:
+        """Re-root every tree by its board's column (bgs_connect_forest_advance): columns int32[n], a negative entry
+        leaves the tree as it is.  Returns kept int32[n], the nodes a tree holds afterwards, the root not counted: the
+        subtree under the column, or 0 where there was none (the next search starts that tree anew).  The boards are
+        neither read nor stepped: play the same columns with `ConnectBatch.step_actions`."""
+        columns = np.ascontiguousarray(columns, dtype=np.int32)
+        if columns.shape != (self.batch.n,):
+            raise TypeError(f"columns must be int32[{self.batch.n}]")
+        kept = np.empty(self.batch.n, dtype=np.int32)
+        self._advance(columns.ctypes.data, kept.ctypes.data, 0)
+        return kept
+
+    def advance_tensor(self, columns, kept=None):
+        """`advance` with `columns` and `kept` as int32[n] device tensors (kept allocated when None), enqueued on the
+        batch's stream with no synchronisation: kept."""
+        t = self.batch._need_torch("advance_tensor")
+        if kept is None:
+            kept = t.empty((self.batch.n,), dtype=t.int32, device=f"cuda:{self.batch.device}")
+        for name, x in (("columns", columns), ("kept", kept)):
+            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == (self.batch.n,) and x.is_contiguous()):
+                raise TypeError(f"{name} must be a contiguous int32 device tensor of shape ({self.batch.n},)")
+        self._advance(columns.data_ptr(), kept.data_ptr(), 1)
+        return kept
 
 
 class BounceBatch(_Batch):
@@ -1095,6 +1205,12 @@ class BounceBatch(_Batch):
         raise ValueError("search_actions: Connect batches only (Bounce boards: evaluate_moves_halving)")
 
     search_actions_tensor = search_workspace_bytes = search_actions
+
+    def search_forest(self, *args, **kwargs):
+        """Not available for Bounce: trees that persist between searches cover bit-packed Connect boards."""
+        raise ValueError("search_forest: Connect batches only (Bounce boards: search_moves)")
+
+    forest_bytes = search_forest
 
     def solve_actions(self, *args, **kwargs):
         """Not available for Bounce: the exact solver covers bit-packed Connect boards (Bounce games can cycle)."""

@@ -271,6 +271,54 @@ BGS_API int bgs_connect_search_workspace_bytes(const bgs_batch* b, int32_t itera
 BGS_API int bgs_connect_search_actions(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
                                        int32_t max_plies, int policy, int32_t* counts, int32_t* visits, int32_t* best,
                                        int32_t* nodes, void* workspace, size_t workspace_bytes, int on_device);
+/* The same search on trees that outlive a launch (Connect, bit-packed boards only): a FOREST is caller-owned device
+ * memory that holds one tree per board of the batch, each with room for `capacity` (C) nodes, the root included, and
+ * persists from launch to launch.  An agent that plays a game searches, plays, advances the trees by the columns played
+ * and searches again: the subtree under the move played is carried into the next search.
+ * Layout.  Opaque; bgs_connect_forest_bytes says how large (per tree: a header -- the nodes in use and the position the
+ * root stands for, as the planes of the batch --, C nodes of 3 * width 32-bit words, a tree's share rounded up to 256
+ * bytes).  The re-rooting keeps its scratch on the chip, which bounds C: 2 <= C <= BGS_CONNECT_FOREST_MAX_CAPACITY.
+ * bgs_connect_forest_search.  For board i, at the start of the launch, tree i is CARRIED if restart == 0, the board is
+ * running, the header's node count is in [1, C], the recorded root position equals board i's planes, and the root's N
+ * (the sum of its n[c]) plus T * P is below 2^31.  Otherwise the tree is emptied: a running board is left with one zeroed
+ * root node and board i recorded as the root position; an ended board gets an emptied tree, all-zero outputs and
+ * best = -1.  THE FIRST LAUNCH ON FRESH MEMORY MUST PASS restart != 0: memory that was never written may pass the check by
+ * accident.  Then T iterations of bgs_connect_search_actions, word for word, with step 4 read as
+ * bgs_bounce_search_moves reads it: p' has ended: no node and no game; p' runs and the edge has a child: descend; p' runs
+ * and the edge has no child: a node is made if and only if the tree holds fewer than C nodes, and either way the P
+ * playouts start from p' (an edge whose node did not fit is tried again the next time it is taken).  Node 0 is the root
+ * and never a child, so a child word of 0 means "none".  Playout j of iteration t is the game
+ * G = ((first_game + i) * T + t) * P + j with this launch's T, played as bgs_connect_search_actions plays it: the caller
+ * varies `seed` from launch to launch.  Selection, Q, E, lg(N), isqrt, the back-propagation, bgs_steps and sharding by
+ * first_game are unchanged.
+ * Outputs: counts int32[n][width][3] = W/D/L through each root column of THIS launch's playouts; visits int32[n][width] =
+ * the root's n[c], carried visits included; best int32[n] by the rule of bgs_connect_search_actions over those visits and
+ * s; nodes int32[n] = the nodes in the tree at the end, the root not counted (<= C - 1); carried int32[n] = the nodes in
+ * the tree at the start after the check, the root not counted (0 for a tree that was emptied).  visits, best, nodes and
+ * carried may be NULL.  With restart != 0 and C >= T + 1 the outputs and bgs_steps are those of
+ * bgs_connect_search_actions, bit for bit, and carried is all zeros.
+ * `forest` is always a 256-byte aligned device pointer.  on_device != 0: the outputs are 16-byte aligned device pointers
+ * and the call is an enqueue on the batch's stream with no synchronisation and no allocation; otherwise they are host
+ * buffers, filled when the call returns.
+ * bgs_connect_forest_advance re-roots every tree: columns int32[n], for tree i with c = columns[i]: c < 0: the tree is
+ * untouched.  The root's edge c has a child r: the subtree of r becomes the tree and r becomes node 0; n, s and the
+ * parent/child relations of every kept node are unchanged, and the recorded position becomes the position after c (a plain
+ * drop, no win test).  Anything else -- an edge never played, a terminal edge, a node that did not fit, a full column,
+ * c >= width, a tree that is already empty --: the tree is emptied, and the next search starts it anew from the batch's
+ * board.  kept int32[n] (may be NULL) = the nodes after the call, the root not counted.  The call neither reads nor
+ * modifies the batch's boards: the caller plays the same columns with bgs_step_actions, before or after.  Two plies (the
+ * own move, then the reply) are two calls.  on_device: where columns and kept live, as above.
+ * Refused (BGS_ERR_ARG, with a message that says why; the outputs and the forest are untouched): a Bounce batch, a generic
+ * batch, C < 2 or C > BGS_CONNECT_FOREST_MAX_CAPACITY, what bgs_connect_search_actions refuses for T, P, explore,
+ * max_plies, the policy and the pointers, a NULL or misaligned forest, forest_bytes too small, NULL columns. */
+#define BGS_CONNECT_FOREST_MAX_CAPACITY 65536
+BGS_API int bgs_connect_forest_bytes(const bgs_batch* b, int32_t capacity, size_t* bytes);
+BGS_API int bgs_connect_forest_search(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                                      int32_t max_plies, int policy, int32_t capacity, int restart, int32_t* counts, int32_t* visits,
+                                      int32_t* best, int32_t* nodes, int32_t* carried, void* forest, size_t forest_bytes,
+                                      int on_device);
+BGS_API int bgs_connect_forest_advance(bgs_batch* b, const int32_t* columns, int32_t capacity, int32_t* kept, void* forest,
+                                       size_t forest_bytes, int on_device);
 /* Flat Monte-Carlo evaluation of every legal move of every board (Bounce, bit-packed boards only: at most 64 cells,
  * piece values <= 15).  counts int32[n][width][height * width][3]: entry [i][x][c] = (wins, draws, losses) of the
  * player to move at board i over `playouts` games that start with the move of the piece in column x of the active row
