@@ -1503,6 +1503,135 @@ int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterations, int
     return BGS_OK;
 }
 
+// the checks of the three Bounce forest entry points that need no device; *bytes: the forest of the batch
+static int bounce_forest_check(const bgs_batch* b, int32_t nodes_cap, int32_t edges, size_t* bytes) {
+    NEED(b->game == BGS_GAME_BOUNCE, "bounce_forest: Bounce batches only (Connect boards: bgs_connect_forest_search)");
+    NEED(!b->generic, "bounce_forest: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
+         BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
+    NEED(nodes_cap >= 2 && nodes_cap <= BGS_BOUNCE_FOREST_MAX_NODES, "nodes_cap must be 2 .. %d nodes a tree (got %d)",
+         BGS_BOUNCE_FOREST_MAX_NODES, nodes_cap);
+    const int32_t least = BGS_BOUNCE_SEARCH_MIN_EDGES(b->bg.h, b->bg.w);
+    NEED(edges >= least && edges <= BGS_BOUNCE_FOREST_MAX_EDGES,
+         "edges must be BGS_BOUNCE_SEARCH_MIN_EDGES(%d, %d) = %d, the most arms a position can have, .. %d (got %d)", b->bg.h, b->bg.w,
+         least, BGS_BOUNCE_FOREST_MAX_EDGES, edges);
+    const uint64_t tree = bgs::bounce_forest_tree_bytes(nodes_cap, edges);
+    NEED((uint64_t)b->n <= (uint64_t)(SIZE_MAX / 2) / tree, "the forest of %lld boards x %d nodes x %d edges overflows size_t",
+         (long long)b->n, nodes_cap, edges);
+    *bytes = (size_t)((uint64_t)b->n * tree);
+    return BGS_OK;
+}
+
+static int bounce_forest_pointer(const void* forest, size_t forest_bytes, size_t need) {
+    NEED(forest != nullptr, "forest is NULL (the caller owns it; bgs_bounce_forest_bytes says how large)");
+    NEED((reinterpret_cast<uintptr_t>(forest) & 255u) == 0, "the forest must be 256-byte aligned");
+    NEED(forest_bytes >= need, "the forest is too small: %zu bytes, %zu needed", forest_bytes, need);
+    return BGS_OK;
+}
+
+int bgs_bounce_forest_bytes(const bgs_batch* b, int32_t nodes, int32_t edges, size_t* bytes) {
+    NEED(b != nullptr, "batch is NULL");
+    NEED(bytes != nullptr, "bytes is NULL");
+    size_t need = 0;
+    const int rc = bounce_forest_check(b, nodes, edges, &need);
+    if (rc) return rc;
+    *bytes = need;
+    return BGS_OK;
+}
+
+int bgs_bounce_forest_search(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
+                             int policy, int32_t nodes_cap, int32_t edges, int restart, int32_t* counts, int32_t* visits, int32_t* best,
+                             int32_t* nodes, int32_t* used, int32_t* carried, void* forest, size_t forest_bytes, int on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(counts != nullptr, "counts is NULL");
+    size_t need = 0;
+    rc = bounce_forest_check(b, nodes_cap, edges, &need);
+    if (rc) return rc;
+    NEED(iterations >= 1, "iterations must be >= 1 (got %d)", iterations);
+    NEED(leaf_playouts >= 1, "leaf_playouts must be >= 1 (got %d)", leaf_playouts);
+    NEED((int64_t)iterations * leaf_playouts <= ((int64_t)1 << 29),
+         "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
+    NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "bounce_forest_search: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
+         (long long)b->n, iterations, leaf_playouts);
+    rc = bounce_forest_pointer(forest, forest_bytes, need);
+    if (rc) return rc;
+    const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;
+    if (on_device) {
+        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(visits) & 15u) == 0, "device visits must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(nodes) & 15u) == 0, "device nodes must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(used) & 15u) == 0, "device used must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(carried) & 15u) == 0, "device carried must be 16-byte aligned");
+        bgs::bounce_forest_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, nodes_cap, edges, restart, counts,
+                                  visits, best, nodes, used, carried, forest);
+        return finish_launch();
+    }
+    // one device buffer: counts, visits, best, nodes, used, carried -- each 16-byte aligned
+    const auto up = [](size_t x, size_t a) { return (x + a - 1) & ~(a - 1); };
+    const size_t counts_bytes = cells * 3 * sizeof(int32_t), visits_bytes = cells * sizeof(int32_t), board_bytes = (size_t)b->n * sizeof(int32_t);
+    const size_t visits_off = up(counts_bytes, 16), best_off = visits_off + up(visits_bytes, 16), nodes_off = best_off + up(board_bytes, 16);
+    const size_t used_off = nodes_off + up(board_bytes, 16), carried_off = used_off + up(board_bytes, 16);
+    uint8_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), carried_off + board_bytes, b->stream));
+    bgs::bounce_forest_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, nodes_cap, edges, restart,
+                              reinterpret_cast<int32_t*>(d), visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
+                              best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr,
+                              nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr,
+                              used ? reinterpret_cast<int32_t*>(d + used_off) : nullptr,
+                              carried ? reinterpret_cast<int32_t*>(d + carried_off) : nullptr, forest);
+    rc = finish_launch();
+    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
+    if (rc == BGS_OK && visits) rc = copy_to_host(b, visits, d + visits_off, visits_bytes);
+    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, board_bytes);
+    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d + nodes_off, board_bytes);
+    if (rc == BGS_OK && used) rc = copy_to_host(b, used, d + used_off, board_bytes);
+    if (rc == BGS_OK && carried) rc = copy_to_host(b, carried, d + carried_off, board_bytes);
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
+int bgs_bounce_forest_advance(bgs_batch* b, const int32_t* slots, int32_t nodes_cap, int32_t edges, int32_t* kept, void* forest,
+                              size_t forest_bytes, int on_device) {
+    int rc = enter(b);
+    if (rc) return rc;
+    NEED(slots != nullptr, "slots is NULL");
+    size_t need = 0;
+    rc = bounce_forest_check(b, nodes_cap, edges, &need);
+    if (rc) return rc;
+    rc = bounce_forest_pointer(forest, forest_bytes, need);
+    if (rc) return rc;
+    if (on_device) {
+        NEED((reinterpret_cast<uintptr_t>(slots) & 3u) == 0, "device slots must be 4-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(kept) & 3u) == 0, "device kept must be 4-byte aligned");
+        bgs::bounce_forest_advance(b, slots, nodes_cap, edges, kept, forest);
+        return finish_launch();
+    }
+    // one device buffer: slots, kept
+    const size_t board_bytes = (size_t)b->n * sizeof(int32_t);
+    int32_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), 2 * board_bytes, b->stream));
+    rc = to_device(b, d, slots, (size_t)b->n);
+    if (rc == BGS_OK) {
+        bgs::bounce_forest_advance(b, d, nodes_cap, edges, kept ? d + b->n : nullptr, forest);
+        rc = finish_launch();
+    }
+    if (rc == BGS_OK && kept) rc = copy_to_host(b, kept, d + b->n, board_bytes);
+    // (without kept no copy back waits for the stream, and the caller's `slots` must have been read when the call returns)
+    if (rc == BGS_OK && !kept && hipStreamSynchronize(b->stream) != hipSuccess) rc = bgs::fail(BGS_ERR_RUNTIME, "hipStreamSynchronize failed");
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
 int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
                            int on_device) {
     int rc = enter(b);

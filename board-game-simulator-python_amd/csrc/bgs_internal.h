@@ -172,6 +172,14 @@ uint64_t bounce_search_root_bytes(int32_t iterations, int32_t edges);
 void bounce_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
                    int policy, int32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
                    void* d_workspace);
+// the same search on trees that persist (bgs_bounce_forest_search / bgs_bounce_forest_advance): d_forest holds n *
+// bounce_forest_tree_bytes(capacity, edges) bytes, 256-byte aligned; all outputs but d_counts may be NULL; d_slots int32[n]
+// on the device; both are enqueued on the batch's stream and neither touches the boards
+uint64_t bounce_forest_tree_bytes(int32_t capacity, int32_t edges);
+void bounce_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                          int32_t max_plies, int policy, int32_t capacity, int32_t edges, int restart, int32_t* d_counts,
+                          int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int32_t* d_carried, void* d_forest);
+void bounce_forest_advance(const bgs_batch* b, const int32_t* d_slots, int32_t capacity, int32_t edges, int32_t* d_kept, void* d_forest);
 // exact horizon search of every legal move of packed Bounce boards (bgs_bounce_solve_moves): codes int8[n][w][h * w] and
 // plies int16[n][w][h * w] (may be NULL) are filled here (illegal slots NONE / 0), *d_nodes = positions visited; scratch
 // as bounce_evaluate; depth 1 .. BGS_BOUNCE_SOLVE_MAX_DEPTH; device pointers, enqueued on the batch's stream

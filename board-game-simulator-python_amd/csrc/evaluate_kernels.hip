@@ -2314,6 +2314,669 @@ void launch_bounce_search(const bgs_batch* b, const GEO& g, uint64_t seed, uint3
     }
 }
 
+// ================================================================================================================
+// The Bounce forest (bgs_bounce_forest_search / bgs_bounce_forest_advance, include/bgs.h): the trees of k_bounce_search
+// kept from launch to launch in the caller's memory, `capacity` (C) nodes and `edges` (E) pool edges a tree, and re-rooted
+// between the launches.
+//
+// A tree's share of the forest, in 32-bit words, rounded up to 256 bytes:
+//   word 0         the nodes in use, the root counted (0: an emptied tree)
+//   word 1         the pool edges in use
+//   word 2         the absolute ply count of the position the root stands for
+//   word 3         the effective cap (min(max_plies, 65535)) the tree's kEdgeCapped sentinels were written under
+//   words 4 .. 11  the position the root stands for: the four 64-bit planes of the batch, 8-byte aligned
+//   words 16 ..    E edges in k_bounce_search's format (n, s, child or outcome, source cell << 8 | target cell)
+//   then           C node-table entries (first edge, arms)
+//   then           C words of descent path: a descent leaves every node at most once, so it has at most C edges; the
+//                  words mean nothing between launches
+// With C <= 65536 and E <= BGS_BOUNCE_FOREST_MAX_EDGES = 2^29 a share has fewer than 2^32 words.
+//
+// k_bounce_forest_search is k_bounce_search with four differences: the carried check (or the emptying) at the start, "a
+// node is made when the edge has no child, the tree holds fewer than C nodes AND the pool has room for its arms", the
+// tables and the path in the forest's share, and the header written back at the end, behind a barrier.  The iteration --
+// descent, refill loop, ply, back-propagation -- is that kernel's, line for line.
+// ================================================================================================================
+constexpr uint32_t kBounceForestHeaderWords = 16;
+
+__host__ __device__ __forceinline__ uint64_t bounce_forest_tree_words(uint32_t capacity, uint32_t edges) {
+    return (kBounceForestHeaderWords + (uint64_t)edges * kEdgeWords + (uint64_t)capacity * 3u + 63u) & ~(uint64_t)63u;
+}
+
+template <class GEO, int NC, int POLICY>
+__global__ void __launch_bounds__(BGS_BLOCK)
+k_bounce_forest_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status,
+                       const uint16_t* __restrict__ plies_buf, int64_t n, uint64_t seed, uint64_t game_base, uint32_t iterations,
+                       uint32_t leaf_playouts, uint32_t explore, uint32_t max_plies, uint32_t capacity, uint32_t edges, uint32_t restart,
+                       uint32_t slots, int64_t root_base, uint32_t* forest, int32_t* counts, int32_t* visits, int32_t* best,
+                       int32_t* nodes, int32_t* used_out, int32_t* carried, unsigned long long* __restrict__ steps) {
+    extern __shared__ uint32_t target_tile[];                      // [2 * 8 * NC dwords][256 lanes]
+    __shared__ uint64_t node_targets[8 * NC];                      // targets of the piece in column x of the active row of p'
+    __shared__ uint64_t other_targets[8 * NC];                     // ... of the side that has just moved, when p' is blocked
+    __shared__ uint32_t red_min[2][kSearchTeamWaves], red_sum[2][kSearchTeamWaves], red_key[2][kSearchTeamWaves];
+    __shared__ uint32_t tally[3];                                  // W/D/L of the iteration's playouts, for the root's mover
+    __shared__ uint32_t next_item;                                 // the leaf's next playout
+    uint32_t* const column = target_tile + threadIdx.x;
+    const uint32_t tid = threadIdx.x, lane = threadIdx.x & (BGS_WAVE - 1), wave = threadIdx.x / BGS_WAVE;
+    const uint32_t hw = (uint32_t)(g.h * g.w);
+    const int64_t i = root_base + (int64_t)blockIdx.x;             // (the grid holds exactly the roots of this launch)
+    uint32_t* const head = forest + (uint64_t)i * bounce_forest_tree_words(capacity, edges);
+    uint64_t* const head_planes = reinterpret_cast<uint64_t*>(head + 4);
+    uint32_t* const pool = head + kBounceForestHeaderWords;
+    uint32_t* const node_tab = pool + (uint64_t)edges * kEdgeWords;             // node v: first edge, arms
+    uint32_t* const path = node_tab + (uint64_t)capacity * 2u;                  // edge k of the descent
+    const auto uniform = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+
+    // the targets of `player`'s pieces on `bd`, the piece in column x by lane x, into dst (complete behind the caller's
+    // barrier); returns the cell of column 0 of the active row
+    const auto spread = [&](const Board& bd, uint64_t occ, uint32_t player, bool live, uint64_t* dst) {
+        const uint64_t sources = live ? movable(g, occ, player) : 0ull;
+        const uint32_t first_source = sources ? (uint32_t)(__ffsll((unsigned long long)sources) - 1) : 0u;
+        const uint32_t base = ((first_source * g.inv_w) >> 16) * (uint32_t)g.w;
+        if (tid < 8 * NC) {
+            const bool piece = tid < (uint32_t)g.w && ((sources >> ((base + tid) & 63u)) & 1ull);
+            dst[tid] = piece ? reach(g, bd, occ, player, (int)(base + tid)) : 0ull;
+        }
+        return base;
+    };
+    const auto count_arms = [&](const uint64_t* t) {
+        uint32_t arms = 0;
+        for (uint32_t x = 0; x < 8 * NC; ++x) arms += (uint32_t)__popcll(t[x]);
+        return uniform(arms);
+    };
+    // the arm table of a new node: `arms` fresh edges from edge `first`, in canonical order (first + arms <= edges)
+    const auto make_arms = [&](uint32_t first, uint32_t arms, uint32_t base) {
+        for (uint32_t a = tid; a < arms; a += BGS_BLOCK) {
+            uint32_t j = a, x = 0;
+            for (; x < 8 * NC - 1; ++x) {
+                const uint32_t cnt = (uint32_t)__popcll(node_targets[x]);
+                if (j < cnt) break;
+                j -= cnt;
+            }
+            const uint32_t move = ((base + x) << 8) | select_bit64(node_targets[x], j);
+            *reinterpret_cast<uint4*>(pool + (uint64_t)(first + a) * kEdgeWords) = make_uint4(0u, 0u, 0u, move);
+        }
+    };
+
+    // ---- the root: its arms say whether there is anything to search
+    const Board root = load_board(planes, n, i);
+    const uint32_t rply = plies_buf[i];
+    const uint32_t root_mover = rply & 1u;
+    // (an ended root and one that holds the most plies a board can have no arms, as in k_bounce_eval_count)
+    const uint32_t root_base_cell = spread(root, occupancy(root), root_mover, status[i] == BGS_ST_RUNNING && rply < kBounceMaxPlies, node_targets);
+    __syncthreads();
+    const uint32_t root_arms = count_arms(node_targets);
+    if (root_arms == 0u) {   // nothing to search: an emptied tree; counts and visits stay zero
+        if (tid == 0) {
+            head[0] = 0;
+            head[1] = 0;
+            if (best) best[i] = -1;
+            if (nodes) nodes[i] = 0;
+            if (used_out) used_out[i] = 0;
+            if (carried) carried[i] = 0;
+        }
+        return;
+    }
+
+    // ---- the carried check: a tree that fails it is emptied.  Every wave reads the header and decides for itself; the
+    // decision is the team's because the words it reads do not change while it is made: nothing of the header, the table or
+    // the pool is written before barrier (H) below, which every wave passes with its reads returned (readfirstlane needs
+    // them) whatever it decided.  Behind (H) the waves hold the same `keep`, so the branches that follow -- and the barriers
+    // inside them -- are taken by all four waves or by none.
+    uint32_t count = uniform(head[0]), used = uniform(head[1]);     // nodes in use, the root counted; pool edges in use
+    bool keep = restart == 0u && count >= 1u && count <= capacity && used >= root_arms && used <= edges && head[2] == rply &&
+                head[3] == max_plies;
+    if (keep) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) keep = keep && head_planes[j] == root.v[j];
+    }
+    keep = uniform(keep ? 1u : 0u) != 0u;
+    __syncthreads();                    // (H) every wave has read the header before any wave rewrites it
+    if (keep) {                         // N + T * P < 2^31: the root's n stay in int32 (the root's block starts at edge 0)
+        uint32_t sum = 0;
+        for (uint32_t a = tid; a < root_arms; a += BGS_BLOCK) sum += pool[(uint64_t)a * kEdgeWords];
+        sum = wave_sum(sum);
+        if (lane == 0) red_sum[0][wave] = sum;
+        __syncthreads();
+        uint64_t total = 0;
+#pragma unroll
+        for (int w = 0; w < kSearchTeamWaves; ++w) total += red_sum[0][w];
+        keep = total + (uint64_t)iterations * leaf_playouts < (1ull << 31);
+        keep = uniform(keep ? 1u : 0u) != 0u;
+        __syncthreads();                // (red_sum[0] is free for the first descent step)
+    }
+    if (!keep) {                        // node 0 and its arms; board i recorded
+        make_arms(0u, root_arms, root_base_cell);
+        if (tid == 0) {
+            node_tab[0] = 0u;
+            node_tab[1] = root_arms;
+            head[2] = rply;
+            head[3] = max_plies;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) head_planes[j] = root.v[j];
+        }
+        count = 1u;
+        used = root_arms;
+    }
+    const uint32_t brought = count - 1u;
+    __syncthreads();
+    const auto slot_of = [&](uint32_t move) { return ((move >> 8) - root_base_cell) * hw + (move & 255u); };
+
+    Board b;                         // the lane's game
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b.v[j] = 0;
+    FlatMoves<NC> mv;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) mv.counts[k] = 0;
+    mv.n = 0;
+    mv.row_base = 0;
+    uint32_t st = 0, plies = 0, stepped = 0;
+    uint64_t game = 0;
+    bool has = false, search = false, have_block = false;
+    [[maybe_unused]] bool can_win = false;   // (BGS_POLICY_DECISIVE) the list the lane holds has a target in the mover's goal row
+    Philox4 blk;
+    blk.v[0] = blk.v[1] = blk.v[2] = blk.v[3] = 0;
+
+    for (uint32_t t = 0; t < iterations; ++t) {
+        // ---- descent (team-uniform): p is the position at node v
+        Board p = root;
+        uint32_t ply = rply, v = 0, depth = 0, move0 = 0;
+        uint32_t leaf = BGS_ST_RUNNING;     // the outcome of an edge that ends the game
+        bool capped = false;                // p' runs and holds the cap
+        for (;;) {
+            const uint32_t first = uniform(node_tab[2u * v]), arms = uniform(node_tab[2u * v + 1u]);
+            const uint32_t* const node = pool + (uint64_t)first * kEdgeWords;
+            uint32_t na[2] = {0u, 0u}, sa[2] = {0u, 0u};
+            uint32_t fresh = kNoArm, sum = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 2; ++k) {
+                const uint32_t a = tid + k * BGS_BLOCK;
+                if (a < arms) {
+                    const uint2 ns = *reinterpret_cast<const uint2*>(node + (uint64_t)a * kEdgeWords);
+                    na[k] = ns.x;
+                    sa[k] = ns.y;
+                    sum += ns.x;
+                    fresh = (ns.x == 0u && a < fresh) ? a : fresh;
+                }
+            }
+            const uint32_t buf = depth & 1u;
+            fresh = wave_min(fresh);
+            sum = wave_sum(sum);
+            if (lane == 0) {
+                red_min[buf][wave] = fresh;
+                red_sum[buf][wave] = sum;
+            }
+            __syncthreads();
+            uint32_t arm = kNoArm, total = 0;
+#pragma unroll
+            for (int w = 0; w < kSearchTeamWaves; ++w) {
+                arm = red_min[buf][w] < arm ? red_min[buf][w] : arm;
+                total += red_sum[buf][w];
+            }
+            arm = uniform(arm);             // the expansion: the lowest arm never played
+            if (arm == kNoArm) {
+                const uint32_t scaled = explore * search_lg(uniform(total));
+                uint32_t key = 0;           // (U(a) << 9 | 511 - a) + 1: the largest U, then the lowest arm
+#pragma unroll
+                for (uint32_t k = 0; k < 2; ++k) {
+                    const uint32_t a = tid + k * BGS_BLOCK;
+                    if (a < arms) {
+                        const uint32_t u = search_q(sa[k], na[k]) + search_isqrt(scaled / na[k]);
+                        const uint32_t mine = ((u << 9) | (511u - a)) + 1u;
+                        key = mine > key ? mine : key;
+                    }
+                }
+                key = wave_max(key);
+                if (lane == 0) red_key[buf][wave] = key;
+                __syncthreads();
+                uint32_t top = 0;
+#pragma unroll
+                for (int w = 0; w < kSearchTeamWaves; ++w) top = red_key[buf][w] > top ? red_key[buf][w] : top;
+                arm = uniform(511u - ((top - 1u) & 511u));
+            }
+            const uint32_t e = first + arm;
+            uint32_t* const edge = pool + (uint64_t)e * kEdgeWords;
+            const uint32_t child = uniform(edge[2]), move = uniform(edge[3]);
+            if (tid == 0) path[depth] = e;
+            move0 = depth == 0u ? move : move0;
+            const int s_cell = (int)(move >> 8), t_cell = (int)(move & 255u);
+            const uint32_t mover = ply & 1u;
+            move_piece(p, s_cell, t_cell);
+            ply += 1u;
+            depth += 1u;
+            if (child == kEdgeCapped) {
+                capped = true;
+                break;
+            }
+            if (child >= kEdgeEnded) {
+                leaf = child & 15u;
+                break;
+            }
+            if (child != 0u) {
+                v = child;
+                continue;
+            }
+            // ---- the edge has no child: what p' is
+            uint32_t code = 0;              // the edge's new third word, if any
+            if ((1ull << t_cell) & (g.goal_top | g.goal_bottom)) {
+                leaf = mover + 1u;
+                code = kEdgeEnded | leaf;
+            } else {
+                const uint64_t occ = occupancy(p);
+                const uint32_t base = spread(p, occ, ply & 1u, true, node_targets);
+                __syncthreads();
+                const uint32_t fan = count_arms(node_targets);
+                if (fan == 0u) {            // the side to move is blocked: the mover wins if it could move, else a draw
+                    spread(p, occ, mover, true, other_targets);
+                    __syncthreads();
+                    leaf = count_arms(other_targets) ? mover + 1u : (uint32_t)BGS_ST_DRAW;
+                    code = kEdgeEnded | leaf;
+                } else if (ply >= max_plies) {
+                    capped = true;
+                    code = kEdgeCapped;
+                } else if (count < capacity && used + fan <= edges) {   // a new node for p'; without room the edge is tried again next time
+                    make_arms(used, fan, base);
+                    if (tid == 0) {
+                        node_tab[2u * count] = used;
+                        node_tab[2u * count + 1u] = fan;
+                    }
+                    code = count;
+                    count += 1u;
+                    used += fan;
+                }
+            }
+            if (tid == 0 && code) edge[2] = code;
+            break;
+        }
+
+        // ---- the leaf's playouts: the halving kernel's refill loop and ply from p'
+        const bool play = leaf == BGS_ST_RUNNING && !capped;
+        if (tid < 3u) tally[tid] = 0;
+        if (tid == 0) next_item = 0;
+        __syncthreads();            // (A) the counter and the tally are zero; the path, the new node and the edge are written
+        uint32_t wins = 0, draws = 0, losses = 0;
+        if (play) {
+            // G = ((first_game + i) * T + t) * P + j
+            const uint64_t game0 = game_base + ((uint64_t)i * iterations + t) * (uint64_t)leaf_playouts;
+            bool dry = false;        // (wave-uniform) the leaf's counter has nothing left for this wave
+            while (!dry || __builtin_amdgcn_ballot_w64(has)) {
+                const uint64_t need = __builtin_amdgcn_ballot_w64(!has);
+                if (need && !dry) {
+                    if (__builtin_amdgcn_ballot_w64(stepped >= (1u << 30))) {   // (a lane adds at most 65535 a playout)
+                        add_steps(steps, stepped);
+                        stepped = 0;
+                    }
+                    const uint32_t wanted = (uint32_t)__popcll(need);
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(&next_item, wanted);
+                    base = uniform(base);
+                    if (base + wanted >= leaf_playouts) dry = true;
+                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
+                    if (!has && base + rank < leaf_playouts) {
+                        game = game0 + (uint64_t)(base + rank);
+                        b = p;
+                        plies = ply;
+                        st = BGS_ST_RUNNING;
+                        has = true;
+                        search = true;
+                        have_block = false;
+                    }
+                }
+                if (!__builtin_amdgcn_ballot_w64(has)) continue;
+
+                if (__builtin_amdgcn_ballot_w64(search)) {
+                    const uint64_t occ = occupancy(b);
+                    enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
+                    const bool blocked = search && mv.n == 0u;
+                    if (__builtin_amdgcn_ballot_w64(blocked)) {
+                        FlatMoves<NC> other;
+#pragma unroll
+                        for (int k = 0; k < NC; ++k) other.counts[k] = 0;
+                        other.n = 0;
+                        other.row_base = 0;
+                        enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
+                        if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
+                    }
+                    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                        if (search) can_win = st == BGS_ST_RUNNING && b_can_win<NC>(mv, column, (plies & 1u) ? g.goal_bottom : g.goal_top);
+                    }
+                    search = false;
+                }
+                const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
+                if (has && !run) {       // finished (a capped game, st 0, is counted nowhere)
+                    wins += (st != 0u && st != BGS_ST_DRAW && st - 1u == root_mover) ? 1u : 0u;
+                    losses += (st != 0u && st != BGS_ST_DRAW && st - 1u != root_mover) ? 1u : 0u;
+                    draws += st == BGS_ST_DRAW ? 1u : 0u;
+                    has = false;
+                }
+                if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+                    if (run && can_win) {   // every candidate ends the game for the mover: one transition, nothing drawn or moved
+                        st = (plies & 1u) + 1u;
+                        ++plies;
+                        stepped += 1u;
+                    }
+                }
+                if (POLICY == BGS_POLICY_DECISIVE ? run && !can_win : run) {
+                    if (!have_block || (plies & 3u) == 0u) {
+                        blk = philox4x32_10(seed, game, plies >> 2);
+                        have_block = true;
+                    }
+                    const uint32_t mover = plies & 1u;
+                    int s, tc;
+                    pick_flat<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, tc);
+                    move_piece(b, s, tc);
+                    ++plies;
+                    stepped += 1u;
+                    if ((1ull << tc) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
+                    else search = true;
+                }
+            }
+            if (wins) atomicAdd(tally + 0, wins);
+            if (draws) atomicAdd(tally + 1, draws);
+            if (losses) atomicAdd(tally + 2, losses);
+        }
+        __syncthreads();            // (B) the tally is complete
+        uint32_t tw = 0, td = 0, tl = 0;
+        if (play) {
+            tw = tally[0];
+            td = tally[1];
+            tl = tally[2];
+        } else if (!capped) {       // all playouts of the iteration have the edge's outcome
+            tw = (leaf != BGS_ST_DRAW && leaf - 1u == root_mover) ? leaf_playouts : 0u;
+            tl = (leaf != BGS_ST_DRAW && leaf - 1u != root_mover) ? leaf_playouts : 0u;
+            td = leaf == BGS_ST_DRAW ? leaf_playouts : 0u;
+        }
+
+        // ---- back-propagation: lane k takes edge k of the path; its mover is the root's at even k
+        for (uint32_t k = tid; k < depth; k += BGS_BLOCK) {
+            uint32_t* const edge = pool + (uint64_t)path[k] * kEdgeWords;
+            edge[0] += leaf_playouts;
+            edge[1] += td + 2u * ((k & 1u) ? tl : tw);
+        }
+        if (tid == 0) {
+            int32_t* const c = counts + (i * (int64_t)slots + slot_of(move0)) * 3;
+            c[0] += (int32_t)tw;
+            c[1] += (int32_t)td;
+            c[2] += (int32_t)tl;
+        }
+        __syncthreads();            // (C) the tree is whole again before the next descent reads it; tally and path are free
+    }
+
+    // ---- the outputs of the root (illegal slots are never stored: the launcher zeroed them)
+    if (visits) {
+        for (uint32_t a = tid; a < root_arms; a += BGS_BLOCK) {
+            const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
+            visits[i * (int64_t)slots + slot_of(edge[3])] = (int32_t)edge[0];
+        }
+    }
+    __syncthreads();                // the tree's last writes are issued by every wave before the header says what it holds
+    if (tid == 0) {
+        if (best) {   // the most visits, then the larger 2 * wins + draws, then the lower slot (the arms ascend by slot)
+            int32_t top = -1;
+            uint32_t top_n = 0, top_s = 0;
+            for (uint32_t a = 0; a < root_arms; ++a) {
+                const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
+                const uint32_t cn = edge[0], cs = edge[1];
+                if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
+                    top = (int32_t)slot_of(edge[3]);
+                    top_n = cn;
+                    top_s = cs;
+                }
+            }
+            best[i] = top;
+        }
+        head[0] = count;            // the header: ply, cap and planes were recorded when the tree was emptied, or carried with it
+        head[1] = used;
+        if (nodes) nodes[i] = (int32_t)(count - 1u);
+        if (used_out) used_out[i] = (int32_t)used;
+        if (carried) carried[i] = (int32_t)brought;
+    }
+    add_steps(steps, stepped);
+}
+
+template <class GEO, int NC, int POLICY>
+void launch_bounce_forest_search(const bgs_batch* b, const GEO& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts,
+                                 uint32_t explore, uint32_t max_plies, uint32_t capacity, uint32_t edges, uint32_t restart,
+                                 int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
+                                 int32_t* d_carried, void* d_forest) {
+    const uint32_t slots = (uint32_t)(b->bg.w * b->bg.h * b->bg.w);
+    (void)hipMemsetAsync(d_counts, 0, (size_t)b->n * slots * 3 * sizeof(int32_t), b->stream);
+    if (d_visits) (void)hipMemsetAsync(d_visits, 0, (size_t)b->n * slots * sizeof(int32_t), b->stream);
+    // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
+    const uint64_t game_base = b->first_game * (uint64_t)iterations * (uint64_t)leaf_playouts;
+    const size_t tile = sizeof(uint32_t) * 2 * 8 * NC * BGS_BLOCK;
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL((k_bounce_forest_search<GEO, NC, POLICY>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), tile, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, seed, game_base,
+                           iterations, leaf_playouts, explore, max_plies, capacity, edges, restart, slots, i0,
+                           static_cast<uint32_t*>(d_forest), d_counts, d_visits, d_best, d_nodes, d_used, d_carried, b->d_steps);
+    }
+}
+
+// The re-rooting (bgs_bounce_forest_advance): one wave a tree, in place, one launch.  Two arrays that refer to each other
+// are compacted: the node table (first edge, arms) and the edge pool (whose third words are node indices).  Nodes are made
+// in increasing index order and a node's edge block is allocated when it is made, so a child's index is above its parent's
+// and the first-edge offsets ascend with the node index; a compaction that keeps the order keeps both properties:
+//   mark     the subtree of r = the child word of the root's arm with the slot played, in a bit mask (LDS, a bit a node), by
+//            an ascending sweep from r over chunks of 64 nodes: lane l walks the child words of node base + l if that node
+//            is marked and has not been walked, and the chunk is swept again while some lane found its node newly marked
+//            (a chain inside the chunk).  Marks only get set and a lane walks its node once, so a chunk takes at most 65
+//            sweeps; a child index is above its parent's, so a mark never lands in a chunk that has been left.
+//   number   new[v] = the marked nodes below v: a prefix popcount, one entry a mask word (LDS).
+//   move     chunk by chunk in ascending order.  The table entries of the chunk's 64 nodes are read, then -- behind a
+//            barrier -- written to new[v] <= v with the new first-edge offsets: a running sum of the kept nodes' arms,
+//            carried from chunk to chunk (a scan inside the chunk).  The chunk's kept edges are one contiguous range of
+//            destinations; it is moved in batches of 256 edges, each lane four: all reads of a batch, a barrier, all of its
+//            writes, a barrier.  A destination never exceeds its source and sources ascend with destinations, so a batch
+//            writes below everything that later batches read.  Child words are mapped to new[child]; 0 and the ended /
+//            capped sentinels stay.
+//   header   one lane, last, behind a barrier: the counts, the ply + 1, the move applied to the recorded planes.
+// Chunks without a marked node are neither read nor written: the work is that of the nodes and edges in use.
+// One wave, not a workgroup of four: the phases are separated by barriers (free in one wave), the sweep is serial along a
+// chain of parents and children whatever the team, and a batch of boards brings a tree a CU's SIMD anyway; what a tree's
+// move phase needs is loads in flight, which the four edges a lane give.
+// Rubbish: every count, offset and index read from the forest is checked against the share's bounds before it is used as
+// one, so memory that never held a tree is emptied or shuffled inside its own share, never indexed out of it.
+constexpr uint32_t kAdvanceBatch = 4;      // edges a lane moves between two barriers
+
+__global__ void __launch_bounds__(BGS_WAVE)
+k_bounce_forest_advance(uint32_t height, uint32_t width, const int32_t* __restrict__ slot_in, uint32_t capacity, uint32_t edges,
+                        uint32_t* forest, int32_t* __restrict__ kept, int64_t root_base) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t forest_lds[];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t mask_room = (((capacity + 31u) >> 5) + 3u) & ~3u;
+    uint32_t* const mask = forest_lds;              // bit v: node v stays
+    uint32_t* const below = mask + mask_room;       // the marked nodes in the mask words before this one
+    uint32_t* const cum = below + mask_room;        // [65] the kept edges of the chunk before node l (cum[64]: all of them)
+    uint32_t* const from = cum + 68;                // [64] the old first edge of node l of the chunk
+    uint32_t* const self = from + 64;               // [64] 1: node l of the chunk stays
+    const int64_t i = root_base + (int64_t)blockIdx.x;
+    uint32_t* const head = forest + (uint64_t)i * bounce_forest_tree_words(capacity, edges);
+    uint32_t* const pool = head + kBounceForestHeaderWords;
+    uint32_t* const node_tab = pool + (uint64_t)edges * kEdgeWords;
+    const auto uniform = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+
+    const int32_t slot = slot_in[i];
+    uint32_t count = uniform(head[0]), used = uniform(head[1]);
+    if (count > capacity || used > edges) count = used = 0u;        // a header out of range: none
+    if (slot < 0) {                                 // untouched
+        if (kept && lane == 0) kept[i] = (int32_t)(count ? count - 1u : 0u);
+        return;
+    }
+    // a node's block, checked: (first, arms) with first + arms <= used, else no arms
+    const auto block_of = [&](uint32_t v, uint32_t& first, uint32_t& arms) {
+        const uint2 fa = *reinterpret_cast<const uint2*>(node_tab + 2u * (uint64_t)v);
+        const bool fits = fa.x <= used && fa.y <= used - fa.x;
+        first = fits ? fa.x : 0u;
+        arms = fits ? fa.y : 0u;
+    };
+
+    // ---- the new root: the child of the root's arm whose move is that of the slot (source column, target cell)
+    const uint32_t hw = height * width;
+    uint32_t r = 0, played = 0;                     // 0: none (never expanded, ended, capped, did not fit, no such arm)
+    if (count != 0u && (uint32_t)slot < width * hw) {
+        const uint32_t x = (uint32_t)slot / hw, cell = (uint32_t)slot % hw;
+        uint32_t first0, arms0;
+        block_of(0u, first0, arms0);
+        first0 = uniform(first0);
+        arms0 = uniform(arms0);
+        for (uint32_t a0 = 0; a0 < arms0 && r == 0u; a0 += BGS_WAVE) {
+            const uint32_t a = a0 + lane;
+            uint32_t child = 0, move = 0;
+            bool hit = false;
+            if (a < arms0) {
+                const uint32_t* const edge = pool + (uint64_t)(first0 + a) * kEdgeWords;
+                child = edge[2];
+                move = edge[3];
+                hit = (move & 255u) == cell && (move >> 8) < hw && (move >> 8) % width == x;
+            }
+            const uint64_t hits = __builtin_amdgcn_ballot_w64(hit);
+            if (hits) {
+                const int at = __builtin_ctzll(hits);
+                const uint32_t ch = (uint32_t)__builtin_amdgcn_readlane((int)child, at);
+                played = (uint32_t)__builtin_amdgcn_readlane((int)move, at);
+                r = (ch > 0u && ch < count) ? ch : 0u;
+                break;
+            }
+        }
+    }
+    r = uniform(r);
+    if (r == 0u) {                                  // emptied: the next search starts anew from the batch's board
+        if (lane == 0) {
+            head[0] = 0;
+            head[1] = 0;
+            if (kept) kept[i] = 0;
+        }
+        return;
+    }
+
+    // ---- mark
+    const uint32_t mask_words = (count + 31u) >> 5;
+    for (uint32_t k = lane; k < mask_words; k += BGS_WAVE) mask[k] = 0;
+    __syncthreads();
+    if (lane == 0) mask[r >> 5] = 1u << (r & 31u);
+    __syncthreads();
+    for (uint32_t base = r & ~63u; base < count; base += 64u) {
+        const uint32_t m0 = mask[base >> 5], m1 = (base >> 5) + 1u < mask_words ? mask[(base >> 5) + 1u] : 0u;
+        if ((m0 | m1) == 0u) continue;              // (uniform) nothing of this chunk is in the subtree
+        const uint32_t v = base + lane;
+        bool done = false;
+        for (;;) {
+            const bool go = !done && v < count && ((mask[v >> 5] >> (v & 31u)) & 1u) != 0u;
+            if (__builtin_amdgcn_ballot_w64(go) == 0) break;
+            if (go) {
+                uint32_t first, arms;
+                block_of(v, first, arms);
+                for (uint32_t a = 0; a < arms; ++a) {
+                    const uint32_t ch = pool[(uint64_t)(first + a) * kEdgeWords + 2u];
+                    if (ch > v && ch < count) atomicOr(mask + (ch >> 5), 1u << (ch & 31u));
+                }
+                done = true;
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+
+    // ---- number
+    uint32_t total = 0;
+    for (uint32_t k0 = 0; k0 < mask_words; k0 += BGS_WAVE) {
+        const uint32_t k = k0 + lane;
+        const uint32_t bits = k < mask_words ? (uint32_t)__popc(mask[k]) : 0u;
+        uint32_t upto = bits;                       // the inclusive scan of the wave
+        for (int d = 1; d < BGS_WAVE; d <<= 1) {
+            const uint32_t other = (uint32_t)__shfl_up((int)upto, d);
+            upto += lane >= (uint32_t)d ? other : 0u;
+        }
+        if (k < mask_words) below[k] = total + upto - bits;
+        total += (uint32_t)__shfl((int)upto, BGS_WAVE - 1);
+    }
+    __syncthreads();
+    // the new index of a marked node
+    const auto renumber = [&](uint32_t v) { return below[v >> 5] + (uint32_t)__popc(mask[v >> 5] & ((1u << (v & 31u)) - 1u)); };
+
+    // ---- move
+    uint32_t run = 0;                               // (uniform) the edges of the kept nodes before this chunk
+    bool bad = false;
+    for (uint32_t base = r & ~63u; base < count; base += 64u) {
+        const uint32_t m0 = mask[base >> 5], m1 = (base >> 5) + 1u < mask_words ? mask[(base >> 5) + 1u] : 0u;
+        if ((m0 | m1) == 0u) continue;
+        const uint32_t v = base + lane;
+        const bool stays = v < count && ((mask[v >> 5] >> (v & 31u)) & 1u) != 0u;
+        uint32_t first = 0, arms = 0;
+        if (stays) block_of(v, first, arms);
+        uint32_t upto = arms;                       // the inclusive scan of the wave, saturating: rubbish cannot wrap it
+        for (int d = 1; d < BGS_WAVE; d <<= 1) {
+            const uint32_t other = (uint32_t)__shfl_up((int)upto, d);
+            const uint32_t sum = upto + (lane >= (uint32_t)d ? other : 0u);          // (both below 2^31)
+            upto = sum < 0x7FFFFFFFu ? sum : 0x7FFFFFFFu;
+        }
+        const uint32_t moved = (uint32_t)__shfl((int)upto, BGS_WAVE - 1);
+        if ((uint64_t)run + moved > used) {         // (uniform; rubbish only: the blocks of a tree are disjoint) none
+            bad = true;
+            break;
+        }
+        cum[lane] = upto - arms;
+        from[lane] = first;
+        self[lane] = stays ? v : 0u;
+        if (lane == 0) cum[64] = moved;
+        __syncthreads();                            // every table entry of the chunk is read before one is written
+        if (stays) *reinterpret_cast<uint2*>(node_tab + 2u * (uint64_t)renumber(v)) = make_uint2(run + upto - arms, arms);
+        for (uint32_t k0 = 0; k0 < moved; k0 += kAdvanceBatch * BGS_WAVE) {
+            uint4 e[kAdvanceBatch];
+#pragma unroll
+            for (uint32_t j = 0; j < kAdvanceBatch; ++j) {
+                const uint32_t k = k0 + j * BGS_WAVE + lane;       // the k-th kept edge of the chunk
+                e[j] = make_uint4(0u, 0u, 0u, 0u);
+                if (k < moved) {
+                    uint32_t l = 0;                 // its node: the last l with cum[l] <= k (so node l has arms)
+#pragma unroll
+                    for (uint32_t step = 32; step > 0; step >>= 1) l += cum[l + step] <= k ? step : 0u;
+                    e[j] = *reinterpret_cast<const uint4*>(pool + (uint64_t)(from[l] + (k - cum[l])) * kEdgeWords);
+                    const uint32_t ch = e[j].z, parent = self[l];
+                    if (ch != 0u && ch < kEdgeEnded) {              // a node index: a kept node's children are kept
+                        const bool marked = ch > parent && ch < count && ((mask[ch >> 5] >> (ch & 31u)) & 1u) != 0u;
+                        e[j].z = marked ? renumber(ch) : 0u;
+                    }
+                }
+            }
+            __syncthreads();                        // every edge of the batch is read before one is written
+#pragma unroll
+            for (uint32_t j = 0; j < kAdvanceBatch; ++j) {
+                const uint32_t k = k0 + j * BGS_WAVE + lane;
+                const uint64_t to = (uint64_t)run + k;
+                if (k < moved) *reinterpret_cast<uint4*>(pool + to * kEdgeWords) = e[j];     // (to < run + moved <= used <= E)
+            }
+            __syncthreads();
+        }
+        run += moved;
+        __syncthreads();                            // cum, from and self are free for the next chunk
+    }
+
+    // ---- header (the tree's writes are issued; the counts and the move go last)
+    __syncthreads();
+    if (lane == 0) {
+        if (bad) {
+            head[0] = 0;
+            head[1] = 0;
+            if (kept) kept[i] = 0;
+        } else {
+            Board p;
+            uint64_t* const head_planes = reinterpret_cast<uint64_t*>(head + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p.v[j] = head_planes[j];
+            move_piece(p, (int)((played >> 8) & 63u), (int)(played & 63u));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) head_planes[j] = p.v[j];
+            head[0] = total;
+            head[1] = run;
+            head[2] += 1u;
+            if (kept) kept[i] = (int32_t)(total - 1u);
+        }
+    }
+}
+
 EvalGeom eval_geom(const bgs_batch* b) {
     EvalGeom g{};
     g.rh = b->cg.h;
@@ -3077,6 +3740,56 @@ void bounce_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_
         bounce_search_policy<BGS_POLICY_DECISIVE>(b, seed, t, p, e, cap, pool, d_counts, d_visits, d_best, d_nodes, d_used, d_workspace);
     else
         bounce_search_policy<BGS_POLICY_UNIFORM>(b, seed, t, p, e, cap, pool, d_counts, d_visits, d_best, d_nodes, d_used, d_workspace);
+}
+
+uint64_t bounce_forest_tree_bytes(int32_t capacity, int32_t edges) {
+    return bounce_forest_tree_words((uint32_t)capacity, (uint32_t)edges) * sizeof(uint32_t);
+}
+
+template <int POLICY>
+static void bounce_forest_search_policy(const bgs_batch* b, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
+                                        uint32_t cap, uint32_t capacity, uint32_t edges, uint32_t restart, int32_t* d_counts,
+                                        int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int32_t* d_carried,
+                                        void* d_forest) {
+    if (b->bounce_static_geom && bounce_is_default(b->bg))
+        launch_bounce_forest_search<DefaultBounceGeom, 1, POLICY>(b, DefaultBounceGeom{}, seed, iterations, leaf_playouts, explore, cap,
+                                                                  capacity, edges, restart, d_counts, d_visits, d_best, d_nodes, d_used,
+                                                                  d_carried, d_forest);
+    else if (b->bg.w <= 8)
+        launch_bounce_forest_search<BounceGeom, 1, POLICY>(b, b->bg, seed, iterations, leaf_playouts, explore, cap, capacity, edges, restart,
+                                                           d_counts, d_visits, d_best, d_nodes, d_used, d_carried, d_forest);
+    else
+        launch_bounce_forest_search<BounceGeom, 3, POLICY>(b, b->bg, seed, iterations, leaf_playouts, explore, cap, capacity, edges, restart,
+                                                           d_counts, d_visits, d_best, d_nodes, d_used, d_carried, d_forest);
+}
+
+void bounce_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                          int32_t max_plies, int policy, int32_t capacity, int32_t edges, int restart, int32_t* d_counts,
+                          int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int32_t* d_carried, void* d_forest) {
+    uint32_t cap = (uint32_t)max_plies;
+    if (cap > kBounceMaxPlies) cap = kBounceMaxPlies;   // plies are stored as uint16
+    const uint32_t t = (uint32_t)iterations, p = (uint32_t)leaf_playouts, e = (uint32_t)explore;
+    const uint32_t room = (uint32_t)capacity, pool = (uint32_t)edges, anew = restart ? 1u : 0u;
+    if (policy == BGS_POLICY_DECISIVE)
+        bounce_forest_search_policy<BGS_POLICY_DECISIVE>(b, seed, t, p, e, cap, room, pool, anew, d_counts, d_visits, d_best, d_nodes,
+                                                         d_used, d_carried, d_forest);
+    else
+        bounce_forest_search_policy<BGS_POLICY_UNIFORM>(b, seed, t, p, e, cap, room, pool, anew, d_counts, d_visits, d_best, d_nodes,
+                                                        d_used, d_carried, d_forest);
+}
+
+void bounce_forest_advance(const bgs_batch* b, const int32_t* d_slots, int32_t capacity, int32_t edges, int32_t* d_kept, void* d_forest) {
+    const uint32_t room = (uint32_t)capacity;
+    // LDS: the mask and the prefix counts (a bit and a 32nd of a word a node, each rounded up to 16 bytes), the chunk's scan
+    // (65 words, rounded), old offsets and node indices (64 words each)
+    const uint32_t mask_room = (((room + 31u) >> 5) + 3u) & ~3u;
+    const size_t lds = ((size_t)2 * mask_room + 68u + 64u + 64u) * sizeof(uint32_t);
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL(k_bounce_forest_advance, dim3((uint32_t)blocks), dim3(BGS_WAVE), lds, b->stream, (uint32_t)b->bg.h,
+                           (uint32_t)b->bg.w, d_slots, room, (uint32_t)edges, static_cast<uint32_t*>(d_forest), d_kept, i0);
+    }
 }
 
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,

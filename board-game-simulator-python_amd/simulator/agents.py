@@ -18,7 +18,8 @@ launch) and plays the column with the most visits; with ``reuse=True`` it keeps 
 (``BounceBatch.evaluate_moves_halving``) and plays the last surviving move.
 
 ``BounceTreeSearchAgent`` grows a UCT tree a Bounce position (``BounceBatch.search_moves``) and plays the move with the
-most visits.
+most visits; with ``reuse=True`` it keeps the trees from call to call (``BounceBatch.search_moves_forest``) as
+``TreeSearchAgent`` does.
 """
 
 from __future__ import annotations
@@ -485,11 +486,29 @@ class BounceTreeSearchAgent:
     are the games ``((first_game + k) * iterations + t) * leaf_playouts + j`` of ``seed``.  ``explore`` is about 45426 *
     C * C for a UCB1 constant C; ``policy`` is the playout policy, "uniform" or "decisive"; ``max_plies`` caps every
     playout at that absolute ply count (None: ``BOUNCE_MAX_PLIES``, 1024); ``edges`` is the edge pool of a position
-    (None: ``BounceBatch.search_default_edges``).  Connect states raise ValueError: they are ``TreeSearchAgent``'s."""
+    (None: ``BounceBatch.search_default_edges``).  Connect states raise ValueError: they are ``TreeSearchAgent``'s.
+
+    ``reuse=True`` keeps the trees between calls (``BounceBatch.search_moves_forest``): the agent holds a forest per
+    (Config, number of states) and remembers the grids, movers and ply counts it last searched there.  Before a search it
+    advances the tree at index k by the one or two moves that lead from the remembered grid k to the new one -- its own
+    move, then the reply --, inferred from the grid difference (``moves_between``); where the difference is not one or
+    two clean piece moves it advances nothing, and the search's own check starts that tree anew.  So the states of
+    successive calls must keep their indices.  Search number m on a forest (from 0) draws with ``seed + m`` (mod 2^64),
+    ``visits`` include the carried ones (the shares ``predict`` gives still sum to 1), and ``search`` returns ``carried``
+    -- the nodes every tree started with -- as a sixth element.  ``capacity`` is the room of a tree in nodes; None: ``2 *
+    iterations + 1``, the nodes one search can make plus as many carried ones; the pool is ``edges`` or the default pool
+    of ``capacity - 1`` iterations.  Both are allowances and not measurements: a tree that is full stops growing until
+    the next advance frees room.  Without ``reuse`` the agent is what it was, code path included."""
 
     def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
-                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, edges: Optional[int] = None):
+                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, edges: Optional[int] = None,
+                 reuse: bool = False, capacity: Optional[int] = None):
         playout_policy(policy)
+        if capacity is not None and capacity < 2:
+            raise ValueError("capacity must be >= 2")
+        self.reuse = bool(reuse)
+        self.capacity = 2 * int(iterations) + 1 if capacity is None else int(capacity)
+        self._forests: Dict[tuple, list] = {}   # key -> [MovesForest, grids last searched, their movers, their plies, searches so far]
         if iterations < 1 or leaf_playouts < 1:
             raise ValueError("iterations and leaf_playouts must be >= 1")
         if not 0 <= explore <= 1 << 18:
@@ -507,7 +526,8 @@ class BounceTreeSearchAgent:
         self._batches: Dict[tuple, BounceBatch] = {}
 
     def search(self, states: Sequence, first_game: int = 0):
-        """(counts, visits, best, nodes, used) of the launch over `states` (Bounce states that share one Config)"""
+        """(counts, visits, best, nodes, used) of the launch over `states` (Bounce states that share one Config); with `reuse`
+        (counts, visits, best, nodes, used, carried)"""
         if isinstance(states[0], connect.State):
             raise ValueError("BounceTreeSearchAgent: Bounce states only; Connect states: TreeSearchAgent")
         if not isinstance(states[0], bounce.State):
@@ -528,16 +548,83 @@ class BounceTreeSearchAgent:
             raise ValueError("BounceTreeSearchAgent: a state could not be loaded")
         b.set_first_game(first_game)
         cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
+        if self.reuse:
+            return self._search_on(key, b, boards, player, plies, cap)
         return b.search_moves(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore,
                               max_plies=cap, policy=self.policy, edges=self.edges)
+
+    @staticmethod
+    def moves_between(old: np.ndarray, mover: int, new: np.ndarray, plies: int):
+        """the slots (first, second; -1: none) of the one or two piece moves that lead from grid `old` with `mover` to
+        move to grid `new`, `plies` (1 or 2) plies later: the mover's move first.  A clean move empties one cell and fills
+        an empty one with the same value.  Two pieces of one value leave the pairing of sources and targets open; both
+        pairings give the same position after the two plies, so the one whose moves are nearer to an unbounced walk
+        (|dx| + |dy| = the piece's value, never backwards) is taken, and a pairing that is no legal pair of moves finds
+        no such arm in the tree, which is then started anew as if nothing had been advanced.  (-1, -1) for anything else:
+        equal grids, another ply difference, a reply that moved the piece just played or landed on the cell it left, two
+        moves whose sources share a row (the order would be a guess), two pairings that are equally near."""
+        h, w = old.shape
+        ys, xs = np.nonzero(old != new)
+        gone = [(int(y), int(x)) for y, x in zip(ys, xs) if old[y, x] != 0 and new[y, x] == 0]
+        come = [(int(y), int(x)) for y, x in zip(ys, xs) if old[y, x] == 0 and new[y, x] != 0]
+        if plies not in (1, 2) or len(gone) != plies or len(come) != plies or ys.size != 2 * plies:
+            return -1, -1
+
+        def slot(source, target):
+            return source[1] * h * w + target[0] * w + target[1]
+
+        if plies == 1:
+            return (slot(gone[0], come[0]), -1) if old[gone[0]] == new[come[0]] else (-1, -1)
+        if gone[0][0] == gone[1][0]:
+            return -1, -1
+        # player 0 picks from the lowest occupied interior row, player 1 from the highest: the mover's source is the one nearer its side
+        gone.sort(key=lambda c: c[0] if mover == 0 else -c[0])
+
+        def off(source, target, player):
+            """how far the move is from an unbounced walk of `player`; None: backwards, or another value"""
+            forward = target[0] - source[0] if player == 0 else source[0] - target[0]
+            if forward < 0 or old[source] != new[target]:
+                return None
+            return abs(forward + abs(target[1] - source[1]) - int(old[source]))
+
+        pairings = []
+        for targets in (come, come[::-1]):
+            offs = [off(gone[0], targets[0], mover), off(gone[1], targets[1], 1 - mover)]
+            if None not in offs:
+                pairings.append((sum(offs), targets))
+        pairings.sort(key=lambda x: x[0])
+        if not pairings or (len(pairings) == 2 and pairings[0][0] == pairings[1][0]):
+            return -1, -1
+        targets = pairings[0][1]
+        return slot(gone[0], targets[0]), slot(gone[1], targets[1])
+
+    def _search_on(self, key, b: BounceBatch, grid: np.ndarray, player: np.ndarray, plies: np.ndarray, cap: int):
+        """the search of `reuse`: advance the forest of `key` from the grids it last searched to `grid`, then search on"""
+        entry = self._forests.get(key)
+        if entry is None:
+            entry = self._forests[key] = [b.search_moves_forest(self.capacity, self.edges), None, None, None, 0]
+        forest, last_grid, last_player, last_plies, searches = entry
+        if last_grid is not None:
+            slots = np.array([self.moves_between(last_grid[k], int(last_player[k]), grid[k], int(plies[k]) - int(last_plies[k]))
+                              for k in range(len(grid))], dtype=np.int32)
+            for ply in (slots[:, 0], slots[:, 1]):
+                if (ply >= 0).any():
+                    forest.advance(ply)
+        out = forest.search(seed=(self.seed + searches) % 2**64, iterations=self.iterations, leaf_playouts=self.leaf_playouts,
+                            explore=self.explore, max_plies=cap, policy=self.policy)
+        entry[1:] = [grid, player, plies, searches + 1]
+        return out
 
     def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict[bounce.Action, float]]:
         """`predict` of every state, searched in one launch"""
         if not states:
             return []
         visits = self.search(states, first_game)[1]
-        total = self.iterations * self.leaf_playouts
         w = visits.shape[1]
+        if self.reuse:      # the root's visits include the carried ones
+            return [{a: float(visits[k, a._source[0], a._target[1] * w + a._target[0]]) / int(visits[k].sum()) for a in s.actions}
+                    for k, s in enumerate(states)]
+        total = self.iterations * self.leaf_playouts
         return [{a: float(visits[k, a._source[0], a._target[1] * w + a._target[0]]) / total for a in s.actions}
                 for k, s in enumerate(states)]
 
@@ -563,6 +650,9 @@ class BounceTreeSearchAgent:
         return self.choose_many([state], first_game=game)[0]
 
     def close(self) -> None:
+        for entry in self._forests.values():
+            entry[0].close()
+        self._forests.clear()
         for b in self._batches.values():
             b.close()
         self._batches.clear()

@@ -1396,6 +1396,53 @@ class BounceBatch(_Batch):
             ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
         return outs["counts"], outs["visits"], outs["best"], outs["nodes"], outs["used"]
 
+    def moves_forest_bytes(self, nodes: int, edges: Optional[int] = None) -> int:
+        """bytes of device memory a forest of this batch takes at `nodes` nodes and `edges` pool edges a tree (None: the
+        default pool of `search_moves_forest`; bgs_bounce_forest_bytes)"""
+        edges = self.search_default_edges(int(nodes) - 1) if edges is None else int(edges)
+        nbytes = ctypes.c_size_t()
+        _abi.check(_abi.lib().bgs_bounce_forest_bytes(self._handle, ctypes.c_int32(nodes), ctypes.c_int32(edges), ctypes.byref(nbytes)))
+        return nbytes.value
+
+    def search_moves_forest(self, nodes: int, edges: Optional[int] = None) -> "MovesForest":
+        """A forest for this batch: one search tree per board with room for `nodes` nodes, the root included, and `edges`
+        pool edges, kept on the device from search to search (`MovesForest`).  edges=None: `search_default_edges(nodes -
+        1)`, the pool `search_moves` takes for as many iterations as the tree can make nodes -- the allowance of 32 edges
+        a node that is NOT measured (docs/EXPERIMENTS.md section 28).  The forest belongs to this batch's shape; close it
+        before the batch."""
+        return MovesForest(self, nodes, edges)
+
+    def slots_to_moves(self, slots) -> np.ndarray:
+        """moves int32[n, 4] (source x, y, target x, y: what `step_actions` takes) of slots int32[n] -- the encoding of
+        `best`, x * H * W + c -- on the batch's CURRENT boards: the source row is the active row of board i, which the
+        slot does not hold.  A negative slot, and a board whose side to move cannot move, give a row of -1 (skipped by
+        `step_actions`).  The slot is not checked against the legal moves: `step_actions` does that."""
+        slots = np.asarray(slots, dtype=np.int64)
+        if slots.shape != (self.n,):
+            raise TypeError(f"slots must be int32[{self.n}]")
+        hw = self.height * self.width
+        row = self.targets[:, self.width]
+        moves = np.full((self.n, 4), -1, dtype=np.int32)
+        ok = (slots >= 0) & (slots < self.width * hw) & (row < np.uint64(self.height))
+        cell = slots[ok] % hw
+        moves[ok] = np.stack([slots[ok] // hw, row[ok].astype(np.int64), cell % self.width, cell // self.width], axis=1)
+        return moves
+
+    def slots_to_moves_tensor(self, slots, targets=None):
+        """`slots_to_moves` on the device: int32[n, 4] of slots int32[n] (a device tensor).  `targets` are the target
+        masks int64[n, W + 1] of the batch's current boards (`targets_tensor()`, or what `step_actions_observe` returned
+        last); None: they are exported here.  No synchronisation; the result feeds `step_actions_observe`."""
+        t = self._need_torch("slots_to_moves_tensor")
+        if targets is None:
+            targets = self.targets_tensor()
+        hw = self.height * self.width
+        slot = slots.to(t.int64)
+        row = targets[:, self.width].to(t.int64)
+        cell = slot % hw
+        moves = t.stack([slot // hw, row, cell % self.width, cell // self.width], dim=1)
+        ok = (slot >= 0) & (slot < self.width * hw) & (row >= 0) & (row < self.height)      # (all ones: nothing can move)
+        return t.where(ok[:, None], moves, t.full_like(moves, -1)).to(t.int32).contiguous()
+
     def solve_moves(self, depth: int = DEFAULT_BOUNCE_SOLVE_DEPTH, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """Exact horizon search of every legal move of every board (bgs_bounce_solve_moves), one launch: (codes int8[n, W,
         H * W], plies int16[n, W, H * W] or None); entry [i, x, c] is the move of the piece in column x of the active row
@@ -1454,3 +1501,108 @@ class BounceBatch(_Batch):
         out = np.empty((self.n, self.width + 1), dtype=np.uint64)
         _abi.check(_abi.lib().bgs_bounce_read_targets(self._handle, _ptr(out, ctypes.c_uint64)))
         return out
+
+
+class MovesForest:
+    """One UCT tree per board of a BounceBatch, kept on the device from search to search (bgs_bounce_forest_search /
+    bgs_bounce_forest_advance, include/bgs.h): `BounceBatch.search_moves_forest(nodes, edges)` makes one.  A tree has room
+    for `nodes` nodes, the root included, and `edges` pool edges.
+
+    The loop of an agent: `search`, play a move a board (`BounceBatch.step_actions`; `BounceBatch.slots_to_moves` turns
+    `best` into its moves BEFORE the boards are stepped), `advance` by the same slots -- the subtree under the move played
+    becomes the tree --, and after the opponent's reply `advance` again and `search`: the nodes that were carried are
+    counted in `carried`.  A tree whose recorded root is not its board's position and ply count when a search starts (the
+    board was loaded, reset or stepped without `advance`), or that was grown under another `max_plies`, is started anew
+    by that search.
+
+    The object owns the device buffer (a torch tensor) and belongs to the batch it was made from; its first search
+    restarts every tree, whatever `restart` says, because fresh memory holds no trees."""
+
+    def __init__(self, batch: BounceBatch, nodes: int, edges: Optional[int] = None):
+        self.batch = batch
+        self.nodes = int(nodes)
+        self.edges = batch.search_default_edges(self.nodes - 1) if edges is None else int(edges)
+        nbytes = batch.moves_forest_bytes(self.nodes, self.edges)     # (refuses Connect, generic boards, bad nodes or edges)
+        t = batch._need_torch("search_moves_forest")
+        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")   # (zeros: every tree empty)
+        self._fresh = True
+
+    def close(self) -> None:
+        self._buffer = None
+
+    def _call(self, seed, iterations, leaf_playouts, explore, max_plies, policy, restart, pointers, on_device):
+        if self._buffer is None:
+            raise RuntimeError("the forest is closed")
+        code = playout_policy(policy)
+        _abi.check(_abi.lib().bgs_bounce_forest_search(
+            self.batch._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts),
+            ctypes.c_int32(explore), ctypes.c_int32(max_plies), code, ctypes.c_int32(self.nodes), ctypes.c_int32(self.edges),
+            1 if restart or self._fresh else 0, *(ctypes.c_void_p(p) for p in pointers), ctypes.c_void_p(self._buffer.data_ptr()),
+            ctypes.c_size_t(self._buffer.numel()), on_device))
+        self._fresh = False
+
+    def search(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE,
+               max_plies: int = 2**31 - 1, policy: str = "uniform", restart: bool = False):
+        """`iterations` further iterations on every tree (bgs_bounce_forest_search), one launch: (counts int32[n, W, H * W,
+        3], visits int32[n, W, H * W], best int32[n], nodes int32[n], used int32[n], carried int32[n]); entry [i, x, c] is
+        the move of the piece in column x of the active row to cell c, as in `BounceBatch.search_moves`.  `counts` are
+        those of this call's playouts, `visits` the root's, carried visits included, `nodes` the nodes in the tree
+        afterwards, `used` its pool edges in use and `carried` the nodes it started with, the root counted in neither
+        node count.  Vary `seed` from call to call: playout j of iteration t of board i is game ((first_game + i) *
+        iterations + t) * leaf_playouts + j of every call.  `max_plies` is clamped to 65535, and a tree grown under
+        another cap is started anew.  `restart` empties every tree first."""
+        n, w, hw = self.batch.n, self.batch.width, self.batch.height * self.batch.width
+        outs = (np.empty((n, w, hw, 3), dtype=np.int32), np.empty((n, w, hw), dtype=np.int32)) + tuple(
+            np.empty(n, dtype=np.int32) for _ in range(4))
+        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [o.ctypes.data for o in outs], 0)
+        return outs
+
+    def search_tensor(self, counts=None, visits=None, best=None, nodes=None, used=None, carried=None, seed: int = DEFAULT_SEED,
+                      iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1,
+                      policy: str = "uniform", restart: bool = False):
+        """`search` into device tensors int32[n, W, H * W, 3], int32[n, W, H * W] and four int32[n] (allocated when None),
+        enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes, used, carried)."""
+        t = self.batch._need_torch("search_tensor")
+        n, w, hw = self.batch.n, self.batch.width, self.batch.height * self.batch.width
+        shapes = {"counts": (n, w, hw, 3), "visits": (n, w, hw), "best": (n,), "nodes": (n,), "used": (n,), "carried": (n,)}
+        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "used": used, "carried": carried}
+        for name, shape in shapes.items():
+            x = outs[name]
+            if x is None:
+                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.batch.device}")
+            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [outs[k].data_ptr() for k in shapes], 1)
+        return tuple(outs[k] for k in shapes)
+
+    def _advance(self, slots: int, kept: int, on_device: int) -> None:
+        if self._buffer is None:
+            raise RuntimeError("the forest is closed")
+        _abi.check(_abi.lib().bgs_bounce_forest_advance(
+            self.batch._handle, ctypes.c_void_p(slots), ctypes.c_int32(self.nodes), ctypes.c_int32(self.edges), ctypes.c_void_p(kept),
+            ctypes.c_void_p(self._buffer.data_ptr()), ctypes.c_size_t(self._buffer.numel()), on_device))
+
+    def advance(self, slots) -> np.ndarray:
+        """Re-root every tree by its board's move (bgs_bounce_forest_advance): slots int32[n] in the encoding of `best`
+        (x * H * W + c on the position the tree's root stands for), a negative entry leaves the tree as it is.  Returns
+        kept int32[n], the nodes a tree holds afterwards, the root not counted: the subtree under the move, or 0 where
+        there was none (the next search starts that tree anew).  The boards are neither read nor stepped: play the same
+        moves with `BounceBatch.step_actions`."""
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        if slots.shape != (self.batch.n,):
+            raise TypeError(f"slots must be int32[{self.batch.n}]")
+        kept = np.empty(self.batch.n, dtype=np.int32)
+        self._advance(slots.ctypes.data, kept.ctypes.data, 0)
+        return kept
+
+    def advance_tensor(self, slots, kept=None):
+        """`advance` with `slots` and `kept` as int32[n] device tensors (kept allocated when None), enqueued on the
+        batch's stream with no synchronisation: kept."""
+        t = self.batch._need_torch("advance_tensor")
+        if kept is None:
+            kept = t.empty((self.batch.n,), dtype=t.int32, device=f"cuda:{self.batch.device}")
+        for name, x in (("slots", slots), ("kept", kept)):
+            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == (self.batch.n,) and x.is_contiguous()):
+                raise TypeError(f"{name} must be a contiguous int32 device tensor of shape ({self.batch.n},)")
+        self._advance(slots.data_ptr(), kept.data_ptr(), 1)
+        return kept

@@ -28,6 +28,8 @@ RNG_PER_BLOCK, RNG_PER_PLY = 0, 1   # bgs_set_rng_contract
 ENV_AUTO_RESET = 1
 POLICY_UNIFORM, POLICY_DECISIVE = 0, 1   # bgs_connect_evaluate_actions_policy, bgs_bounce_evaluate_moves_policy
 CONNECT_FOREST_MAX_CAPACITY = 65536   # BGS_CONNECT_FOREST_MAX_CAPACITY: the nodes a tree of a forest may hold
+BOUNCE_FOREST_MAX_NODES = 65536   # BGS_BOUNCE_FOREST_MAX_NODES: the nodes a tree of a Bounce forest may hold
+BOUNCE_FOREST_MAX_EDGES = 1 << 29   # BGS_BOUNCE_FOREST_MAX_EDGES: the pool edges a tree of a Bounce forest may hold
 HALVING_SHORT = -2   # bgs_bounce_evaluate_moves_halving: best[i] of a running board the budget is too small for
 
 GAME_CONNECT = 1
@@ -225,6 +227,17 @@ SIGNATURES = {
     ),
     "bgs_connect_forest_advance": (
         ctypes.c_int, [c_handle, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    ),
+    "bgs_bounce_forest_bytes": (ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]),
+    "bgs_bounce_forest_search": (
+        ctypes.c_int,
+        [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int],
+    ),
+    "bgs_bounce_forest_advance": (
+        ctypes.c_int,
+        [c_handle, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int],
     ),
     "bgs_bounce_search_workspace_bytes": (
         ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]

@@ -453,6 +453,70 @@ BGS_API int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterati
                                     int32_t max_plies, int policy, int32_t edges, int32_t* counts, int32_t* visits,
                                     int32_t* best, int32_t* nodes, int32_t* used, void* workspace, size_t workspace_bytes,
                                     int on_device);
+/* The same search on trees that outlive a launch (Bounce, bit-packed boards only), the sibling of
+ * bgs_connect_forest_*: a FOREST is caller-owned device memory that holds one tree per board of the batch, each with room
+ * for `nodes_cap` (C) nodes, the root included, and `edges` (E) pool edges, and persists from launch to launch.  An agent
+ * that plays a game searches, plays, advances the trees by the moves played and searches again: the subtree under the
+ * move played is carried into the next search.
+ * Layout.  Opaque, 256-byte aligned; bgs_bounce_forest_bytes says how large.  Per tree: a 64-byte header (the nodes in
+ * use, 0 for an emptied tree; the edges in use; the absolute ply count of the position the root stands for; the effective
+ * cap min(max_plies, 65535) under which the tree's "capped" edges were written; that position as the batch's four 64-bit
+ * planes), E edges of four 32-bit words (n, s, child, move), C node-table entries (first edge, arms) and C words of
+ * descent path (a descent leaves every node at most once; the words mean nothing between launches), a tree's share
+ * rounded up to 256 bytes.  2 <= C <= BGS_BOUNCE_FOREST_MAX_NODES (the re-rooting keeps a bit a node on the chip) and
+ * BGS_BOUNCE_SEARCH_MIN_EDGES(height, width) <= E <= BGS_BOUNCE_FOREST_MAX_EDGES (every word index of a share fits 32
+ * bits).
+ * bgs_bounce_forest_search.  For board i, at the start of the launch, tree i is CARRIED if restart == 0, board i is
+ * running and has arms, the nodes in use are in [1, C], the edges in use are in [the arms of the root, E], the recorded
+ * planes and the recorded ply count equal board i's (the ply keys the draws and decides the cap, so it is part of the
+ * position), the recorded cap equals min(max_plies, 65535) of this launch (a carried "capped" edge is only true under
+ * the cap it was written with), and the root's N (the sum of its n[a]) plus T * P is below 2^31.  Otherwise the tree is
+ * emptied: a running board with arms is left with its root node and the root's arms, and board i is recorded; a board
+ * without arms (ended, no move, 65535 plies) gets an emptied tree, all-zero outputs, best = -1 and used = 0.  THE FIRST
+ * LAUNCH ON FRESH MEMORY MUST PASS restart != 0: memory that was never written may pass the check by accident.  Then T
+ * iterations of bgs_bounce_search_moves, word for word, with one change in step 4: a node is made for p' if and only if
+ * the edge has no child, the tree holds fewer than C nodes and (edges in use) + A(p') <= E; either way the P playouts
+ * start from p', and an edge whose node did not fit is tried again the next time it is taken.  Playout j of iteration t
+ * is the game G = ((first_game + i) * T + t) * P + j with this launch's T: the caller varies `seed` from launch to
+ * launch.  Selection, Q, E, lg, isqrt, the sentinels of ended and capped edges, the back-propagation, bgs_steps and
+ * sharding by first_game are unchanged.
+ * Outputs: counts int32[n][width][height * width][3] = W/D/L through each root slot of THIS launch's playouts; visits
+ * int32[n][width][height * width] = the root's n by slot, carried visits included; best int32[n] by the rule of
+ * bgs_bounce_search_moves over those visits and s; nodes int32[n] = the nodes in the tree at the end, the root not counted
+ * (<= C - 1); used int32[n] = the pool edges in use at the end; carried int32[n] = the nodes in the tree at the start
+ * after the check, the root not counted (0 for a tree that was emptied).  All but counts may be NULL.  With restart != 0,
+ * C >= T + 1 and the same E the outputs and bgs_steps are those of bgs_bounce_search_moves, bit for bit, and carried is
+ * all zeros.
+ * `forest` is always a 256-byte aligned device pointer.  on_device != 0: the outputs are 16-byte aligned device pointers
+ * and the call is an enqueue on the batch's stream with no synchronisation and no allocation; otherwise they are host
+ * buffers, filled when the call returns.
+ * bgs_bounce_forest_advance re-roots every tree: slots int32[n] in the encoding of `best`, slot x * height * width + c of
+ * the position the tree's root stands for.  For tree i with s = slots[i]: s < 0: the tree is untouched.  The root has an
+ * arm of that slot (its stored move's target cell is c and its source cell lies in column x) whose child word is a node
+ * r in (0, nodes in use): the subtree of r becomes the tree and r becomes node 0; every kept node keeps its arms, n, s,
+ * moves and ended / capped sentinels, child words are renumbered, kept nodes stay in their relative order and their edge
+ * blocks are packed from edge 0 in that order; the header gets the new counts, the move is applied to the recorded planes
+ * and the recorded ply count goes up by 1.  Anything else -- a slot out of range, no such arm, an arm never expanded, an
+ * edge that ends the game or is capped, a node that did not fit, a tree that is already empty --: the tree is emptied,
+ * and the next search starts it anew from the batch's board.  kept int32[n] (may be NULL) = the nodes after the call, the
+ * root not counted.  The call neither reads nor modifies the batch's boards: the caller plays the same moves with
+ * bgs_step_actions, before or after, and a tree whose board went another way fails the next search's check.  Two plies
+ * (the own move, then the reply) are two calls.  A header that is out of range, or a child index at or beyond the nodes
+ * in use, is read as "none": memory that never held a tree is never indexed out of its own share.  The work is that of
+ * the nodes and edges in use, one launch, in place.  on_device: where slots and kept live, as above.
+ * Refused (BGS_ERR_ARG, with a message that names the argument; the outputs and the forest are untouched): a Connect
+ * batch, a generic batch, C < 2 or C > BGS_BOUNCE_FOREST_MAX_NODES, E below BGS_BOUNCE_SEARCH_MIN_EDGES or above
+ * BGS_BOUNCE_FOREST_MAX_EDGES, what bgs_bounce_search_moves refuses for T, P, explore, max_plies, the policy and the
+ * pointers, a NULL or misaligned forest, forest_bytes too small, NULL slots. */
+#define BGS_BOUNCE_FOREST_MAX_NODES 65536
+#define BGS_BOUNCE_FOREST_MAX_EDGES (1 << 29)
+BGS_API int bgs_bounce_forest_bytes(const bgs_batch* b, int32_t nodes, int32_t edges, size_t* bytes);
+BGS_API int bgs_bounce_forest_search(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                                     int32_t max_plies, int policy, int32_t nodes_cap, int32_t edges, int restart,
+                                     int32_t* counts, int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used,
+                                     int32_t* carried, void* forest, size_t forest_bytes, int on_device);
+BGS_API int bgs_bounce_forest_advance(bgs_batch* b, const int32_t* slots, int32_t nodes_cap, int32_t edges, int32_t* kept,
+                                      void* forest, size_t forest_bytes, int on_device);
 /* Exact solve of every column of every board (Connect, bit-packed boards only): a depth-first alpha-beta search a
  * (board, column), no RNG.  Entry [i][c] is seen from the player to move at board i; the lines searched are at most
  * `depth` plies long, column c itself counted (depth >= height * width: a full solve).
