@@ -308,12 +308,17 @@ static bool codes_hold_a_zero(const uint8_t* codes, int64_t first, int64_t count
 struct bgs_reward_sink {
     int device = 0;
     int64_t max_games = 0;
-    int slots = 0;
+    int slots = 0;                    // the caller's: how many hand-overs may be outstanding (claimed and not yet completed)
+                                      // before a claim blocks -- every claim but a grouped launch's
+    int ring = 0;                     // entries of the ring below, >= slots: ticket t lives in entry t % ring.  A code sink has
+                                      // at least kSinkGroupRing of them, and only a grouped launch (sink_rollout_group) claims
+                                      // past `slots`, up to `ring` outstanding: a launch of eight steps on each of three streams
+                                      // and the next one being enqueued, none of them waiting for an expansion
     int threads = 0;
-    std::vector<uint8_t*> pinned;     // [slots] page-locked code buffers, (max_games + 3) / 4 bytes each
-    std::vector<uint8_t*> mapped;     // [slots] the same buffers as the device sees them: the pack kernel stores its
-                                      //         codes straight into host memory (one PCIe write per 16 B, no copy call)
-    std::vector<hipEvent_t> landed;   // [slots] recorded behind the copy into pinned[slot]
+    std::vector<uint8_t*> pinned;     // [ring] page-locked code buffers, (max_games + 3) / 4 bytes each
+    std::vector<uint8_t*> mapped;     // [ring] the same buffers as the device sees them: the pack kernel stores its
+                                      //        codes straight into host memory (one PCIe write per 16 B, no copy call)
+    std::vector<hipEvent_t> landed;   // [ring] recorded behind the copy into pinned[slot]
     bool grids = false;               // a grid sink: the slots carry boards in the wire format `cells` describes
     CellFormat cells;
     size_t slot_bytes = 0;
@@ -327,7 +332,7 @@ struct bgs_reward_sink {
                                         // ("still running") among them says that a rank's step failed -- its message was zeros
                                         // (bgs_multi.hip) -- and the job is reported as failed (round-5 advisor)
     };
-    std::vector<Job> jobs;            // [slots]
+    std::vector<Job> jobs;            // [ring]
     std::mutex mu;
     std::condition_variable cv_submit;   // a job was published / shutdown
     std::condition_variable cv_landed;   // a job's codes have arrived in its slot / shutdown
@@ -337,8 +342,8 @@ struct bgs_reward_sink {
     volatile int64_t* progress = nullptr;  // optional progress word (bgs_sink_set_progress): receives `completed`
     int64_t landed_upto = 0;             // the codes of jobs [0, landed_upto) are in their slots
     int64_t completed = 0;               // jobs [0, completed) are in their host arrays
-    std::vector<int> parts_done;         // [slots] workers that finished their share of the slot's job
-    std::vector<char> slot_ok;           // [slots] the slot's current job arrived intact (worker 0 -> the expanders)
+    std::vector<int> parts_done;         // [ring] workers that finished their share of the slot's job
+    std::vector<char> slot_ok;           // [ring] the slot's current job arrived intact (worker 0 -> the expanders)
     bool stop = false;
     // Failures belong to TICKETS, not to the sink: a hand-over that could not be enqueued (or whose event failed) is
     // reported once, to the first bgs_sink_wait for that ticket or a later one, and the deliveries after it are as good
@@ -379,7 +384,7 @@ struct bgs_reward_sink {
     void work(int t) {
         (void)hipSetDevice(device);
         for (int64_t ticket = 0;; ++ticket) {
-            const int slot = (int)(ticket % slots);
+            const int slot = (int)(ticket % ring);
             Job job;
             bool ok = true;
             if (t == 0) {
@@ -460,7 +465,12 @@ struct bgs_reward_sink {
                 std::lock_guard<std::mutex> lock(mu);
                 if (++parts_done[slot] == expanders) {
                     parts_done[slot] = 0;
-                    ++completed;  // jobs complete in ticket order: every worker walks the tickets in order
+                    // INVARIANT (delivery order): jobs complete in ticket order, and more than that -- every worker walks
+                    // the tickets in order and expands the SAME byte range of every job of a given size, so two jobs in
+                    // flight that deliver into the same host array are ordered range by range: the later ticket writes
+                    // every range last.  The executor's grouped path rests on it (bgs_pipeline.hip: it no longer waits for
+                    // a host array's previous delivery before it enqueues the next step into that array).
+                    ++completed;
                     a_completed.store(completed, std::memory_order_release);
                     cv_done.notify_all();
                     if (progress) progress_store_max(progress, completed);  // sleepers in this or another process
@@ -475,10 +485,12 @@ namespace {
 // Reserve the next ticket and its slot, waiting while the ring is full.  The ticket is taken HERE, under the lock, so
 // two threads submitting to one sink (say one per stream) never share a slot; what they enqueue for their tickets may
 // interleave freely, publish() puts the jobs back in ticket order.
-int64_t claim(bgs_reward_sink* s) {
-    s->spin_for(s->a_completed, s->a_submitted.load(std::memory_order_relaxed) - s->slots);
+// `ahead` (a grouped launch only): up to the whole ring may be outstanding, not just the caller's `slots`.
+int64_t claim(bgs_reward_sink* s, bool ahead = false) {
+    const int bound = ahead ? s->ring : s->slots;
+    s->spin_for(s->a_completed, s->a_submitted.load(std::memory_order_relaxed) - bound);
     std::unique_lock<std::mutex> lock(s->mu);
-    s->cv_done.wait(lock, [&] { return s->claimed - s->completed < s->slots; });
+    s->cv_done.wait(lock, [&] { return s->claimed - s->completed < bound; });
     return s->claimed++;
 }
 
@@ -489,10 +501,10 @@ void publish(bgs_reward_sink* s, int64_t ticket, int64_t n_games, int8_t* host_r
     {
         std::unique_lock<std::mutex> lock(s->mu);
         s->cv_done.wait(lock, [&] { return s->submitted == ticket; });  // (tickets of other threads publish first)
-        s->jobs[ticket % s->slots].n_games = ok ? n_games : 0;
-        s->jobs[ticket % s->slots].all_end = all_end;
-        s->jobs[ticket % s->slots].host_reward = host_reward;
-        s->jobs[ticket % s->slots].event_slot = (int)((event_ticket >= 0 ? event_ticket : ticket) % s->slots);
+        s->jobs[ticket % s->ring].n_games = ok ? n_games : 0;
+        s->jobs[ticket % s->ring].all_end = all_end;
+        s->jobs[ticket % s->ring].host_reward = host_reward;
+        s->jobs[ticket % s->ring].event_slot = (int)((event_ticket >= 0 ? event_ticket : ticket) % s->ring);
         if (!ok) s->failed_tickets.push_back(ticket);
         s->submitted = ticket + 1;
         s->a_submitted.store(ticket + 1, std::memory_order_release);
@@ -506,9 +518,9 @@ void publish(bgs_reward_sink* s, int64_t ticket, int64_t n_games, int8_t* host_r
 // ---- the sink as the in-library gather uses it (bgs_multi.hip) ------------------------------------------------------
 namespace bgs {
 int64_t sink_claim(bgs_reward_sink* s) { return claim(s); }
-uint8_t* sink_slot_device(bgs_reward_sink* s, int64_t ticket) { return s->mapped[ticket % s->slots]; }
-uint8_t* sink_slot_host(bgs_reward_sink* s, int64_t ticket) { return s->pinned[ticket % s->slots]; }
-hipEvent_t sink_slot_event(bgs_reward_sink* s, int64_t ticket) { return s->landed[ticket % s->slots]; }
+uint8_t* sink_slot_device(bgs_reward_sink* s, int64_t ticket) { return s->mapped[ticket % s->ring]; }
+uint8_t* sink_slot_host(bgs_reward_sink* s, int64_t ticket) { return s->pinned[ticket % s->ring]; }
+hipEvent_t sink_slot_event(bgs_reward_sink* s, int64_t ticket) { return s->landed[ticket % s->ring]; }
 void sink_publish(bgs_reward_sink* s, int64_t ticket, int64_t n_games, int8_t* host_reward, bool ok, int64_t event_ticket, bool all_end) {
     publish(s, ticket, n_games, host_reward, ok, event_ticket, all_end);
 }
@@ -516,24 +528,25 @@ void sink_publish(bgs_reward_sink* s, int64_t ticket, int64_t n_games, int8_t* h
 // the caller spins a little before it sleeps -- the last deliveries are a few tens of microseconds away and overlap
 // with nothing, while a wake-up out of hipEventSynchronize or a condition variable costs as much again.  In the steady
 // state (waits that only throttle the launching thread) nobody spins.
-bool sink_takes_group(const bgs_reward_sink* s, int count) { return s != nullptr && !s->grids && s->slots >= count; }
+bool sink_takes_group(const bgs_reward_sink* s, int count) { return s != nullptr && !s->grids && count <= s->ring; }
+int sink_ring(const bgs_reward_sink* s) { return s->ring; }
 int sink_rollout_group(bgs_reward_sink* s, bgs_batch* const* bs, const uint64_t* seeds, const bool* writes, int count,
                        hipStream_t stream, int8_t* const* host_rewards, int64_t* tickets) {
-    NEED(count >= 1 && count <= kConnectGroupMax && count <= s->slots, "bad step group");
+    NEED(count >= 1 && count <= kConnectGroupMax && count <= s->ring && !s->grids, "bad step group");
     for (int i = 0; i < count; ++i)   // (before any ticket exists: a claimed ticket is always published)
         NEED(bs[i]->device == s->device && bs[i]->n <= s->max_games, "the batch does not fit the sink");
     uint32_t* codes[kConnectGroupMax];
     for (int i = 0; i < count; ++i) {
-        tickets[i] = claim(s);
-        codes[i] = reinterpret_cast<uint32_t*>(s->mapped[tickets[i] % s->slots]);
+        tickets[i] = claim(s, true);
+        codes[i] = reinterpret_cast<uint32_t*>(s->mapped[tickets[i] % s->ring]);
     }
     connect_rollout_steps(bs, seeds, codes, writes, count, stream);
     hipError_t err = hipGetLastError();
-    // every step's codes are in its slot when the launch completes: the events all follow it
-    for (int i = 0; i < count; ++i) {
-        if (err == hipSuccess) err = hipEventRecord(s->landed[tickets[i] % s->slots], stream);
-        publish(s, tickets[i], bs[i]->n, host_rewards[i], err == hipSuccess);
-    }
+    // Every step's codes are in its slot when the launch completes: ONE event behind it, the last ticket's, announces them
+    // all (publish with an event ticket, as the gather's groups do).  An event per step put `count` markers between two
+    // launches of a stream, 5-6 us each: the gap between launches grew with the steps a launch held (EXPERIMENTS §32).
+    if (err == hipSuccess) err = hipEventRecord(s->landed[tickets[count - 1] % s->ring], stream);
+    for (int i = 0; i < count; ++i) publish(s, tickets[i], bs[i]->n, host_rewards[i], err == hipSuccess, tickets[count - 1]);
     if (err != hipSuccess) return fail(BGS_ERR_RUNTIME, "grouped rollout could not be enqueued: %s", hipGetErrorString(err));
     return BGS_OK;
 }
@@ -708,8 +721,11 @@ static int make_sink(int device, int64_t max_games, int slots, int threads, size
         s->cells = *cells;
     }
     s->slots = slots;
+    // (a grid sink's slot is a batch of boards, tens of MiB: its ring stays the caller's slots; nothing groups its steps)
+    s->ring = cells ? slots : std::max(slots, bgs::kSinkGroupRing);
+    const int ring = s->ring;
     s->threads = threads;
-    s->jobs.resize(slots);
+    s->jobs.resize(ring);
     if (const char* env = bgs::experiment("sink_poll")) s->poll = atoi(env) != 0;
     if (const char* env = bgs::experiment("sink_wait_spin_us")) {
         const int v = atoi(env);
@@ -719,8 +735,8 @@ static int make_sink(int device, int64_t max_games, int slots, int threads, size
         const int v = atoi(env);
         if (v >= 0 && v <= 1000000) s->spin_us = v;
     }
-    s->parts_done.assign(slots, 0);
-    s->slot_ok.assign(slots, 1);
+    s->parts_done.assign(ring, 0);
+    s->slot_ok.assign(ring, 1);
     const size_t bytes = slot_bytes;
     hipError_t err = hipSuccess;
     // The page-locked slots are written by the GPU and read by the workers, which sit on the GPU's NUMA node: allocate
@@ -731,7 +747,7 @@ static int make_sink(int device, int64_t max_games, int slots, int threads, size
     cpu_set_t node_cpus, caller_cpus;
     const bool moved = place && device_node_cpus(device, &node_cpus) && sched_getaffinity(0, sizeof caller_cpus, &caller_cpus) == 0 &&
                        sched_setaffinity(0, sizeof node_cpus, &node_cpus) == 0;
-    for (int k = 0; k < slots && err == hipSuccess; ++k) {
+    for (int k = 0; k < ring && err == hipSuccess; ++k) {
         void* host = nullptr;
         void* dev = nullptr;
         hipEvent_t ev = nullptr;
@@ -941,7 +957,7 @@ int bgs_sink_submit(bgs_reward_sink* s, bgs_batch* b, int8_t* host_reward, int64
     if (rc) return rc;
     if (s->grids && (rc = grid_sink_matches(s, b))) return rc;
     const int64_t t = claim(s);
-    const int slot = (int)(t % s->slots);
+    const int slot = (int)(t % s->ring);
     hipError_t err;
     if (s->grids) {
         err = enqueue_grids(s, b, slot);
@@ -973,7 +989,7 @@ int bgs_sink_rollout(bgs_reward_sink* s, bgs_batch* b, uint64_t seed, int32_t ma
         if (rc0) return rc0;
     }
     const int64_t t = claim(s);
-    const int slot = (int)(t % s->slots);
+    const int slot = (int)(t % s->ring);
     // the rollout kernel stores the outcome codes of the games it finishes straight into the page-locked slot (or the
     // pack kernel does, for kernels without that epilogue): when the event fires the codes are in host memory.  A grid
     // sink: the final boards follow the rollout in the wire format, one asynchronous copy
@@ -998,7 +1014,7 @@ int bgs_sink_submit_packed(bgs_reward_sink* s, void* hip_stream, const void* dev
     if (rc) return rc;
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const int64_t t = claim(s);
-    const int slot = (int)(t % s->slots);
+    const int slot = (int)(t % s->ring);
     hipError_t err = hipMemcpyAsync(s->pinned[slot], device_packed, (size_t)(n_games + 3) / 4, hipMemcpyDeviceToHost, stream);
     if (err == hipSuccess) err = hipEventRecord(s->landed[slot], stream);
     publish(s, t, n_games, host_reward, err == hipSuccess);

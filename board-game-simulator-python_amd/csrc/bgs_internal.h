@@ -237,10 +237,16 @@ hipEvent_t sink_slot_event(bgs_reward_sink* s, int64_t ticket);
 void sink_publish(bgs_reward_sink* s, int64_t ticket, int64_t n_games, int8_t* host_reward, bool ok, int64_t event_ticket = -1,
                   bool all_end = false);
 int sink_wait(bgs_reward_sink* s, int64_t ticket, bool urgent);  // urgent: poll / spin (the end of a run)
-// a reward sink (not a grid sink) with at least `count` slots: bgs_pipeline.hip may hand it grouped steps
+// The ring of a code sink has at least this many entries whatever `slots` the caller asked for: `slots` stays the caller's
+// back-pressure bound for every hand-over but a grouped launch's, which may claim until the whole ring is outstanding
+// (four launches of kConnectGroupMax steps: one on each of three streams and the one being enqueued).
+constexpr int kSinkGroupRing = 4 * kConnectGroupMax;
+// a reward sink (not a grid sink) whose ring holds `count` steps: bgs_pipeline.hip may hand it grouped steps
 bool sink_takes_group(const bgs_reward_sink* s, int count);
-// bgs_sink_rollout for `count` steps of a multi-step Connect launch on `stream` (connect_rollout_steps): one ticket, slot,
-// host array and `landed` event per step, claimed and published in step order; tickets[i] receives step i's
+int sink_ring(const bgs_reward_sink* s);   // entries of the ring: how many tickets grouped launches may have outstanding
+// bgs_sink_rollout for `count` steps of a multi-step Connect launch on `stream` (connect_rollout_steps): one ticket, ring
+// slot and host array per step, claimed (up to the whole ring outstanding) and published in step order, ONE `landed` event
+// behind the launch for all of them; tickets[i] receives step i's
 int sink_rollout_group(bgs_reward_sink* s, bgs_batch* const* bs, const uint64_t* seeds, const bool* writes, int count,
                        hipStream_t stream, int8_t* const* host_rewards, int64_t* tickets);
 int gather_wait(bgs_gather* g, int64_t ticket, bool urgent);     // bgs_multi.hip

@@ -26,6 +26,7 @@
 #include "bgs_capi_util.h"
 #include "bgs_common.h"
 #include "bgs_internal.h"
+#include "connect_group_plan.h"
 
 using bgs::fail;
 
@@ -181,9 +182,9 @@ static int consume(bgs_pipeline* p, int64_t j) {
     return bgs_progress_store(p->consumed, j + 1);
 }
 
-// Steps per launch (S) of a call of `count` steps: kConnectGroupSteps when the call has at least kConnectGroupMinCall
-// steps, every batch runs the multi-step kernel (connect_steps_ok) and the hand-over is a reward sink with a slot and a
-// host array for each step of a group, else 1.  Experiment connect_group=N (the test library): N steps per launch in a
+// Steps per launch (S) of a call of `count` steps, the most a launch of the call's plan holds (connect_group_plan.h):
+// kConnectGroupSteps when the call has at least kConnectGroupMinCall steps, every batch runs the multi-step kernel
+// (connect_steps_ok) and the hand-over is a reward sink with a ring entry and a host array for each step of a group, else 1.  Experiment connect_group=N (the test library): N steps per launch in a
 // call of any length instead, 1 = one launch per step.
 static int group_size(const bgs_pipeline* p, int64_t count, int handover, bool from_feeder) {
     int s = count >= kConnectGroupMinCall ? kConnectGroupSteps : 1;
@@ -197,8 +198,9 @@ static int group_size(const bgs_pipeline* p, int64_t count, int handover, bool f
 }
 
 // Grouped steps and the batches' arenas.  Step s still plays the boards of batches[s % depth] with seed seed0 + s, but a
-// group of S consecutive steps is ONE launch, on the stream of batches[g % depth] (g counts grouped launches), and with
-// three groups in flight a batch is the batch of several steps in flight.  So only the LAST step of the call on a batch
+// group of up to S consecutive steps is ONE launch, on the stream of batches[g % depth] (g counts grouped launches), and with
+// three groups in flight a batch is the batch of several steps in flight.  How a call is cut into launches -- launches
+// of S, a taper of halving launches, the last `depth` steps one by one -- is connect_group_plan.h's.  So only the LAST step of the call on a batch
 // stores its boards, status and rewards -- the last `depth` steps of a call are one-step launches on their own batch's
 // stream -- and a grouped step delivers its outcome codes and env-steps and nothing else (nobody can read its boards:
 // a later step of the call overwrites them before the call returns).  What a
@@ -206,6 +208,13 @@ static int group_size(const bgs_pipeline* p, int64_t count, int handover, bool f
 // per step leaves.  A grouped launch waits for what was enqueued on the streams of the batches it plays before the call
 // (start_ev), and at the end of the call every batch's stream waits for the launches that played it (end_ev): work the
 // caller enqueues on a batch's stream afterwards is ordered behind the batch's steps, as before.
+// Host arrays: a grouped step does NOT wait for the previous delivery into its host array.  The sink completes its jobs in
+// ticket order and every worker expands the same byte range of every job (the delivery-order invariant, bgs_host.hip), so
+// of two steps in flight into one array the later one writes every range last; what bounds the steps in flight is the
+// sink's ring (sink_rollout_group claims until the whole ring is outstanding), not the number of host arrays.
+// ticket[h] names the LATEST step delivered into array h, which is what bgs_pipeline_wait, the drain and
+// last_host_array ask for.  The one-step launches (the last `depth` of a grouped call, every step of any other call, the
+// feeder's, a shared array's, a gather's) wait for the array's previous delivery at launch time, as before.
 static int enqueue_steps(bgs_pipeline* p, const uint64_t* seeds, int64_t count, int handover, int time_stride, bool from_feeder = false) {
     NEED(p != nullptr && count >= 0, "bad argument");
     NEED(!handover || p->sink || p->gather, "this pipeline has no hand-over");
@@ -246,14 +255,16 @@ static int enqueue_steps(bgs_pipeline* p, const uint64_t* seeds, int64_t count, 
         played.clear();
         return BGS_OK;
     };
+    // (without a hand-over a launch needs no host array and no ring entry of its steps)
+    ConnectGroupPlan plan = connect_group_plan(count, depth, group, handover ? n_host : kConnectGroupMax,
+                                               handover && p->sink ? bgs::sink_ring(p->sink) : kConnectGroupMax);
     for (int64_t i = 0; i < count;) {
         // (the last `depth` steps of the call -- the last of each batch, the ones that leave its boards -- are one launch
-        // each on their batch's stream: the end of a call, where the launches in flight thin out, stays one step deep)
-        const int64_t left = count - depth - i;
-        const int64_t k_steps = left < group ? left : group;
-        if (k_steps >= 2) {
-            // ---- S steps, one launch
-            const int k = (int)k_steps;
+        // each on their batch's stream; every step in front of them goes out in the plan's launches, a launch of one too)
+        const int k_steps = connect_group_next(plan);
+        if (group > 1 && i + depth < count) {
+            // ---- up to S steps, one launch
+            const int k = k_steps;
             const int y = (int)(p->launches % depth);
             hipStream_t stream = p->batches[y]->stream;
             bgs_batch* bs[kConnectGroupMax];
@@ -288,20 +299,11 @@ static int enqueue_steps(bgs_pipeline* p, const uint64_t* seeds, int64_t count, 
             }
             int rc;
             if (handover) {
+                // (no wait for the arrays' previous deliveries: the sink orders them, see above)
                 for (int q = 0; q < k; ++q) {
-                    const int h = (int)((p->handed + q) % n_host);
-                    hosts[q] = p->host[h];
-                    lock.lock();
-                    const int64_t before = p->ticket[h];
-                    lock.unlock();
-                    if (before >= 0) {   // the array is about to be overwritten: its previous delivery must be over
-                        if ((rc = wait_ticket(p, before))) { (void)join(); return rc; }
-                        lock.lock();
-                        if (p->ticket[h] == before) p->ticket[h] = -1;
-                        lock.unlock();
-                    }
+                    hosts[q] = p->host[(p->handed + q) % n_host];
+                    tickets[q] = -1;
                 }
-                for (int q = 0; q < k; ++q) tickets[q] = -1;
                 rc = bgs::sink_rollout_group(p->sink, bs, sd, writes, k, stream, hosts, tickets);
                 if (tickets[0] < 0) { (void)join(); return rc; }   // (refused before any ticket was claimed)
                 lock.lock();

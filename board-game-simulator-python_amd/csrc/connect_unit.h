@@ -89,10 +89,16 @@ constexpr ConnectOutcome connect_outcome(uint32_t byte) {
 // kConnectGroupMax consecutive pipeline steps, every wave chunk w of each step in turn, its lanes carrying on from one
 // step's chunk into the next instead of idling until the wave's longest game has ended.  The executor hands
 // kConnectGroupSteps steps to a launch (S; bgs_pipeline.hip).
-// Measured on one MI355X (bench.py, 2^20 boards, three batches, docs/EXPERIMENTS.md §17): S = 2 and 3 read the same
-// (+8 % on 200-step regions); a call of 20 steps gains nothing -- its ramp and tail are most of it -- and its first
-// region read 3-5 % lower, so a call groups its steps only from kConnectGroupMinCall steps on.
-constexpr int kConnectGroupSteps = 2;
+// Measured on one MI355X (bench.py, 2^20 boards, three batches).  docs/EXPERIMENTS.md §17 read S = 2 and 3 the same (+8 %
+// on 200-step regions) and kept 2, but that S = 3 was starved: the sink had nine code slots, a launch's deliveries all
+// complete at its end, and the executor waited at launch time for the previous delivery into each host array, so a
+// stream's next launch could not be enqueued before its previous one had been expanded on the host.  With the sink's ring
+// of 32 code slots, no launch-time wait and the call planned as a whole (connect_group_plan.h) the sweep of §32 reads
+// S = 4, 6 and 8 alike and above 2 and 3, and 4 -- the smallest of them -- is kept: a launch of eight leaves the ring
+// room for one launch ahead of the three in flight, and the host's expansion of eight deliveries at once (16 MiB) then
+// holds the next launch back by 40-50 us a launch.  A call of 20 steps gains nothing -- its ramp and tail are most of it
+// -- so a call groups its steps only from kConnectGroupMinCall steps on (§17; not lowered in §32).
+constexpr int kConnectGroupSteps = 4;
 constexpr int kConnectGroupMax = 8;
 constexpr int kConnectGroupMinCall = 48;
 
