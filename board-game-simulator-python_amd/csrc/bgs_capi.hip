@@ -1089,6 +1089,25 @@ int bgs_connect_evaluate_actions_halving(bgs_batch* b, uint64_t seed, int32_t bu
     return BGS_OK;
 }
 
+// the checks of the search parameters, the same in the four search entry points; `entry` names the caller in the messages
+// (the plain entry points come here behind *_search_check, which has refused iterations < 1 already: the first check is
+// the forest entry points')
+static int search_params_check(const char* entry, const bgs_batch* b, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                               int32_t max_plies, int policy) {
+    NEED(iterations >= 1, "iterations must be >= 1 (got %d)", iterations);
+    NEED(leaf_playouts >= 1, "leaf_playouts must be >= 1 (got %d)", leaf_playouts);
+    NEED((int64_t)iterations * leaf_playouts <= ((int64_t)1 << 29),
+         "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
+    NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "%s: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", entry, policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
+         (long long)b->n, iterations, leaf_playouts);
+    return BGS_OK;
+}
+
 // the checks of both search entry points that need no device; *bytes: the workspace of the batch
 static int connect_search_check(const bgs_batch* b, int32_t iterations, size_t* bytes) {
     NEED(b->game == BGS_GAME_CONNECT, "search_actions: Connect batches only");
@@ -1117,16 +1136,8 @@ int bgs_connect_search_actions(bgs_batch* b, uint64_t seed, int32_t iterations, 
     size_t need = 0;
     rc = connect_search_check(b, iterations, &need);
     if (rc) return rc;
-    NEED(leaf_playouts >= 1, "leaf_playouts must be >= 1 (got %d)", leaf_playouts);
-    NEED((int64_t)iterations * leaf_playouts <= ((int64_t)1 << 29),
-         "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
-    NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
-    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "search_actions: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
-    NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
-         (long long)b->n, iterations, leaf_playouts);
+    rc = search_params_check("search_actions", b, iterations, leaf_playouts, explore, max_plies, policy);
+    if (rc) return rc;
     const size_t cells = (size_t)b->n * b->cg.w;
     if (on_device) {
         NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
@@ -1203,17 +1214,8 @@ int bgs_connect_forest_search(bgs_batch* b, uint64_t seed, int32_t iterations, i
     size_t need = 0;
     rc = connect_forest_check(b, capacity, &need);
     if (rc) return rc;
-    NEED(iterations >= 1, "iterations must be >= 1 (got %d)", iterations);
-    NEED(leaf_playouts >= 1, "leaf_playouts must be >= 1 (got %d)", leaf_playouts);
-    NEED((int64_t)iterations * leaf_playouts <= ((int64_t)1 << 29),
-         "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
-    NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
-    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "forest_search: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
-    NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
-         (long long)b->n, iterations, leaf_playouts);
+    rc = search_params_check("forest_search", b, iterations, leaf_playouts, explore, max_plies, policy);
+    if (rc) return rc;
     rc = connect_forest_pointer(forest, forest_bytes, need);
     if (rc) return rc;
     const size_t cells = (size_t)b->n * b->cg.w;
@@ -1448,16 +1450,8 @@ int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterations, int
     size_t need = 0;
     rc = bounce_search_check(b, iterations, edges, &need);
     if (rc) return rc;
-    NEED(leaf_playouts >= 1, "leaf_playouts must be >= 1 (got %d)", leaf_playouts);
-    NEED((int64_t)iterations * leaf_playouts <= ((int64_t)1 << 29),
-         "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
-    NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
-    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "search_moves: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
-    NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
-         (long long)b->n, iterations, leaf_playouts);
+    rc = search_params_check("search_moves", b, iterations, leaf_playouts, explore, max_plies, policy);
+    if (rc) return rc;
     const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;
     if (on_device) {
         NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
@@ -1547,17 +1541,8 @@ int bgs_bounce_forest_search(bgs_batch* b, uint64_t seed, int32_t iterations, in
     size_t need = 0;
     rc = bounce_forest_check(b, nodes_cap, edges, &need);
     if (rc) return rc;
-    NEED(iterations >= 1, "iterations must be >= 1 (got %d)", iterations);
-    NEED(leaf_playouts >= 1, "leaf_playouts must be >= 1 (got %d)", leaf_playouts);
-    NEED((int64_t)iterations * leaf_playouts <= ((int64_t)1 << 29),
-         "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
-    NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
-    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "bounce_forest_search: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
-    NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
-         (long long)b->n, iterations, leaf_playouts);
+    rc = search_params_check("bounce_forest_search", b, iterations, leaf_playouts, explore, max_plies, policy);
+    if (rc) return rc;
     rc = bounce_forest_pointer(forest, forest_bytes, need);
     if (rc) return rc;
     const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;

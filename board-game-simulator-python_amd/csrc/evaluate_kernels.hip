@@ -558,19 +558,44 @@ void launch_evaluate_halving(const bgs_batch* b, const EvalGeom& g, uint64_t see
 // k_connect_evaluate: idle lanes take the leaf's next playouts at block boundaries), W/D/L are reduced by LDS atomics,
 // and lane k updates edge k of the path.
 //
-// The tree lives in the caller's workspace, (iterations + 1) nodes a root; a node is 3 * width words: n[c], s[c],
-// child[c].  A node is zeroed when it is made (the root at the start), so a workspace needs no preparation.  The tree is
-// written by some lanes (lane k of the back-propagation, the lanes that zero a new node) and read by others (lane c of
-// the next descent): a __syncthreads() of the one-wave workgroup stands between every such pair.
+// A node is 3 * width words: n[c], s[c], child[c] (0: no child yet).  A node is zeroed when it is made (the root at the
+// start), so the caller's memory needs no preparation.  The tree is written by some lanes (lane k of the back-propagation,
+// the lanes that zero a new node) and read by others (lane c of the next descent): a __syncthreads() of the one-wave
+// workgroup stands between every such pair.
+//
+// One kernel, two places for the tree (the template parameter FOREST):
+//   the plain search (bgs_connect_search_actions): the tree lives in the caller's workspace, iterations + 1 nodes a root,
+//     starts empty and is forgotten after the launch;
+//   the forest (bgs_connect_forest_search / bgs_connect_forest_advance): the trees are kept from launch to launch in the
+//     caller's memory, `capacity` nodes a tree, and re-rooted between the launches.  A tree's share of the forest, in
+//     32-bit words, rounded up to 256 bytes:
+//       word 0         the nodes in use, the root counted (0: an emptied tree)
+//       word 1         unused
+//       words 2 ..     the position the root stands for: the 2 * NW plane words of the batch (player 0's, then player
+//                      1's), 64 bits each, 8-byte aligned
+//       words 16 ..    `capacity` nodes
+//     The re-rooting needs a bit a node and a prefix count a 32 nodes; both live in LDS, which is what bounds `capacity`
+//     (BGS_CONNECT_FOREST_MAX_CAPACITY), so the forest holds no scratch.
+// FOREST changes four things and nothing else: where the tree is; the start (the carried check, or the emptying, where
+// the plain search zeroes node 0); whether a new node fits (a node is made when the edge has no child AND the tree has
+// room; an edge whose node did not fit plays its playouts from p' all the same and is tried again the next time -- the
+// plain tree has room for a node an iteration, so there the question is settled when the kernel is compiled); and the
+// header and `carried` written at the end.  The iteration -- descent, playout block, back-propagation -- is one text.
 //
 // Known limit: a root has one wave, so a launch of few roots uses few CUs, and leaf_playouts < 64 leaves lanes idle
 // (DESIGN.md §9).
 // ================================================================================================================
 constexpr uint32_t kSearchMaxPath = 64 * BGS_CONNECT_MAX_WORDS;   // a descent drops at most h * w stones
+constexpr uint32_t kForestHeaderWords = 16;
 
 // words of a root's tree in the workspace: iterations + 1 nodes, rounded up to 256 bytes
 __host__ __device__ __forceinline__ uint64_t search_root_words(uint32_t width, uint32_t iterations) {
     return (((uint64_t)iterations + 1u) * width * 3u + 63u) & ~(uint64_t)63u;
+}
+
+// words of a tree's share of the forest: the header and `capacity` nodes, rounded up to 256 bytes
+__host__ __device__ __forceinline__ uint64_t forest_tree_words(uint32_t width, uint32_t capacity) {
+    return (kForestHeaderWords + (uint64_t)capacity * width * 3u + 63u) & ~(uint64_t)63u;
 }
 
 // floor(sqrt(x)), exact
@@ -596,12 +621,14 @@ __host__ __device__ __forceinline__ uint32_t search_lg(uint32_t total) {
     return 256u * e + (uint32_t)(((uint64_t)total << 8) >> e) - 256u;
 }
 
-template <int NW, bool PER_PLY, int POLICY>
+// (the plain launch passes capacity = iterations + 1, restart = 1 and carried = nullptr; its instantiation reads none of them)
+template <int NW, bool PER_PLY, int POLICY, bool FOREST>
 __global__ void __launch_bounds__(BGS_WAVE)
 k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n, uint64_t seed,
                  uint64_t game_base, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore, uint32_t max_plies,
-                 int64_t root_base, uint32_t* workspace, int32_t* __restrict__ counts, int32_t* __restrict__ visits,
-                 int32_t* __restrict__ best, int32_t* __restrict__ nodes, unsigned long long* __restrict__ steps) {
+                 int64_t root_base, uint32_t capacity, uint32_t restart, uint32_t* trees, int32_t* __restrict__ counts,
+                 int32_t* __restrict__ visits, int32_t* __restrict__ best, int32_t* __restrict__ nodes,
+                 int32_t* __restrict__ carried, unsigned long long* __restrict__ steps) {
     __shared__ uint32_t path_node[kSearchMaxPath];   // the descent: edge k leaves node path_node[k] by column path_col[k]
     __shared__ uint32_t path_col[kSearchMaxPath];
     __shared__ uint32_t tally[3];                    // W/D/L of the iteration's playouts, for the root's mover
@@ -611,279 +638,16 @@ k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t*
     const uint32_t stride = (uint32_t)g.h() + 1u;
     const uint32_t node_words = width * 3u;
     const int64_t i = root_base + (int64_t)blockIdx.x;       // (the grid holds exactly the roots of this launch)
-    uint32_t* const tree = workspace + (uint64_t)i * search_root_words(width, iterations);
-
-    Bits<NW> r0, r1;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) {
-        r0.w[j] = planes[(int64_t)j * n + i];
-        r1.w[j] = planes[(int64_t)(NW + j) * n + i];
+    // ---- where the tree is: behind the header of its share of the forest, or bare in the workspace
+    uint32_t *head = nullptr, *tree;
+    uint64_t* head_planes = nullptr;
+    if constexpr (FOREST) {
+        head = trees + (uint64_t)i * forest_tree_words(width, capacity);
+        head_planes = reinterpret_cast<uint64_t*>(head + 2);
+        tree = head + kForestHeaderWords;
+    } else {
+        tree = trees + (uint64_t)i * search_root_words(width, iterations);
     }
-    const uint32_t rply = popcount(r0) + popcount(r1);
-    const uint32_t root_mover = rply & 1u;
-    const bool running = status[i] == BGS_ST_RUNNING;
-    uint32_t cw = 0, cd = 0, cl = 0;    // lane c: W/D/L of the playouts through root column c
-    uint32_t made = 0;                  // (uniform) nodes made, the root not counted
-    uint64_t stepped = 0;
-    if (lane == 0) step_sum = 0;
-    if (running && lane < node_words) tree[lane] = 0;         // the root is node 0 (3 * width <= 48 words)
-    __syncthreads();
-
-    Bits<NW> q[2];                      // the lane's playout: stones of player 0 / player 1
-#pragma unroll
-    for (int j = 0; j < NW; ++j) q[0].w[j] = q[1].w[j] = 0;
-    Philox4 ph;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) ph.v[j] = 0;
-
-    for (uint32_t t = 0; running && t < iterations; ++t) {
-        // ---- descent (wave-uniform): p is the position at node v
-        Bits<NW> p[2] = {r0, r1};
-        uint32_t ply = rply, v = 0, depth = 0, leaf = BGS_ST_RUNNING, col0 = 0;
-        for (;;) {
-            const Bits<NW> occ = p[0] | p[1];
-            uint32_t height = (uint32_t)g.h();
-            if (lane < width) height = (uint32_t)__popcll(shr(occ, (int)(lane * stride)).w[0] & ((1ull << g.h()) - 1ull));
-            const bool legal = height < (uint32_t)g.h();
-            uint32_t* const node = tree + (uint64_t)v * node_words;
-            uint32_t nc = 0, sc = 0, ch = 0;
-            if (legal) {
-                nc = node[lane];
-                sc = node[width + lane];
-                ch = node[2u * width + lane];
-            }
-            const uint64_t unvisited = __builtin_amdgcn_ballot_w64(legal && nc == 0u);
-            uint32_t col;
-            if (unvisited) {
-                col = (uint32_t)__builtin_ctzll(unvisited);            // the expansion: the lowest column never played
-            } else {
-                uint32_t total = 0;
-                for (uint32_t c = 0; c < width; ++c) total += (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)c);
-                uint32_t key = 0;                                      // (U(c) << 4 | 15 - c) + 1: the largest U, then the lowest column
-                if (legal) {
-                    const uint32_t u = search_q(sc, nc) + search_isqrt(explore * search_lg(total) / nc);
-                    key = ((u << 4) | (15u - lane)) + 1u;
-                }
-                uint32_t top = 0;
-                for (uint32_t c = 0; c < width; ++c) {
-                    const uint32_t other = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)c);
-                    top = other > top ? other : top;
-                }
-                col = 15u - ((top - 1u) & 15u);
-            }
-            col = (uint32_t)__builtin_amdgcn_readfirstlane((int)col);
-            const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)height, (int)col);
-            const uint32_t before = (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)col);
-            const uint32_t child = (uint32_t)__builtin_amdgcn_readlane((int)ch, (int)col);
-            if (lane == 0) {
-                path_node[depth] = v;
-                path_col[depth] = col;
-            }
-            col0 = depth == 0u ? col : col0;
-            const uint32_t mover = ply & 1u;
-            Bits<NW>& mine = mover ? p[1] : p[0];
-            const bool won = drop_and_test(g, mine, col * stride + at, ~0u);
-            ply += 1u;
-            depth += 1u;
-            leaf = won ? mover + 1u : (ply == g.cells_total ? (uint32_t)BGS_ST_DRAW : (uint32_t)BGS_ST_RUNNING);
-            leaf = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf);
-            if (leaf != BGS_ST_RUNNING) break;                         // a terminal edge: no node, no game
-            if (before == 0u) {                                        // a new node for p'
-                made += 1u;
-                if (lane < node_words) tree[(uint64_t)made * node_words + lane] = 0;
-                if (lane == col) node[2u * width + lane] = made;
-                break;
-            }
-            v = child;
-        }
-
-        // ---- the leaf's playouts: the lanes take them in order, idle lanes refill at 4-ply block boundaries
-        uint32_t wins = 0, draws = 0, losses = 0, played = 0;
-        if (lane < 3u) tally[lane] = 0;
-        if (leaf != BGS_ST_RUNNING) {
-            if (lane == 0) {       // all playouts of the iteration have the edge's outcome
-                wins = (leaf != BGS_ST_DRAW && leaf - 1u == root_mover) ? leaf_playouts : 0u;
-                losses = (leaf != BGS_ST_DRAW && leaf - 1u != root_mover) ? leaf_playouts : 0u;
-                draws = leaf == BGS_ST_DRAW ? leaf_playouts : 0u;
-            }
-        } else if (ply < max_plies) {
-            // G = ((first_game + i) * T + t) * P + j
-            const uint64_t game0 = game_base + ((uint64_t)i * iterations + t) * (uint64_t)leaf_playouts;
-            uint64_t game = 0;
-            uint32_t taken = 0, blk = 0, skip = 0, live = 0, st = 0, fresh = 0;
-            while (taken < leaf_playouts || __builtin_amdgcn_ballot_w64(live != 0)) {
-                const uint64_t need = __builtin_amdgcn_ballot_w64(live == 0);
-                if (need != 0 && taken < leaf_playouts) {
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-                    if (live == 0 && rank < leaf_playouts - taken) {
-                        q[0] = p[0];
-                        q[1] = p[1];
-                        game = game0 + (uint64_t)(taken + rank);
-                        blk = ply >> 2;
-                        skip = ply & 3u;
-                        live = ~0u;
-                        fresh = 1u;
-                        st = 0;
-                    }
-                    const uint32_t wanted = (uint32_t)__popcll(need);
-                    taken = leaf_playouts - taken < wanted ? leaf_playouts : taken + wanted;
-                }
-
-                // ---- the 4-ply block of k_connect_evaluate: the same draws, the same ply code
-                if (PER_PLY) {
-                    ph = philox4x32_10(seed, game, blk);
-                } else {
-                    const bool want = live && (fresh || (blk & 3u) == 0u);
-                    if (__builtin_amdgcn_ballot_w64(want)) {
-                        if (want) ph = philox4x32_10(seed, game, blk >> 2);
-                    }
-                }
-                fresh = 0;
-                const uint32_t word = PER_PLY ? 0u : philox_word(ph, blk);
-                const uint32_t was_live = live;
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    const uint32_t draw = PER_PLY ? ph.v[j] : sub_draw(word, j);
-                    const uint32_t act = j >= skip ? live : 0u;
-                    const uint32_t at = 4u * blk + j;          // stones before this sub-step; its mover is player j & 1
-                    bool won;
-                    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
-                        const uint32_t pos = decisive_position(g, q[j & 1u], q[(j & 1u) ^ 1u], draw, won);
-                        drop(q[j & 1u], pos, act);
-                        won = won && act;
-                    } else {
-                        const uint32_t pos = draw_position(g, q[0] | q[1], draw);
-                        won = drop_and_test(g, q[j & 1u], pos, act);
-                    }
-                    const bool full = at + 1u == g.cells_total;
-                    if (act) {
-                        st = won ? (j & 1u) + 1u : (full ? BGS_ST_DRAW : BGS_ST_RUNNING);
-                        live = (won || full || at + 1u >= max_plies) ? 0u : live;
-                        played += 1u;
-                    }
-                }
-                blk += 1u;
-                skip = 0;
-                if (was_live && !live) {      // (st == 0: capped, counted nowhere)
-                    wins += (st != 0u && st != BGS_ST_DRAW && st - 1u == root_mover) ? 1u : 0u;
-                    losses += (st != 0u && st != BGS_ST_DRAW && st - 1u != root_mover) ? 1u : 0u;
-                    draws += st == BGS_ST_DRAW ? 1u : 0u;
-                }
-            }
-        }
-        stepped += played;
-        __syncthreads();            // the tally is zero, the path and the new node are written
-        if (wins) atomicAdd(tally + 0, wins);
-        if (draws) atomicAdd(tally + 1, draws);
-        if (losses) atomicAdd(tally + 2, losses);
-        __syncthreads();
-        const uint32_t tw = tally[0], td = tally[1], tl = tally[2];
-
-        // ---- back-propagation: lane k takes edge k of the path; its mover is the root's at even k
-        for (uint32_t k = lane; k < depth; k += BGS_WAVE) {
-            uint32_t* const node = tree + (uint64_t)path_node[k] * node_words;
-            const uint32_t c = path_col[k];
-            node[c] += leaf_playouts;
-            node[width + c] += td + 2u * ((k & 1u) ? tl : tw);
-        }
-        if (lane == col0) {
-            cw += tw;
-            cd += td;
-            cl += tl;
-        }
-        __syncthreads();            // the tree is whole again before the next descent reads it; tally and path are free
-    }
-
-    // ---- the outputs of the root (an illegal column was never played: its words of the root are zero)
-    uint32_t nv = 0, sv = 0;
-    if (running && lane < width) {
-        nv = tree[lane];
-        sv = tree[width + lane];
-    }
-    if (lane < width) {
-        counts[(i * (int64_t)width + lane) * 3 + 0] = (int32_t)cw;
-        counts[(i * (int64_t)width + lane) * 3 + 1] = (int32_t)cd;
-        counts[(i * (int64_t)width + lane) * 3 + 2] = (int32_t)cl;
-        if (visits) visits[i * (int64_t)width + lane] = (int32_t)nv;
-    }
-    if (best) {
-        // the most visits, then the larger 2 * wins + draws, then the lower column; an illegal column has no visits
-        int32_t top = -1;
-        uint32_t top_n = 0, top_s = 0;
-        for (uint32_t c = 0; running && c < width; ++c) {
-            const uint32_t cn = (uint32_t)__builtin_amdgcn_readlane((int)nv, (int)c);
-            const uint32_t cs = (uint32_t)__builtin_amdgcn_readlane((int)sv, (int)c);
-            if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
-                top = (int32_t)c;
-                top_n = cn;
-                top_s = cs;
-            }
-        }
-        if (lane == 0) best[i] = top;
-    }
-    if (nodes && lane == 0) nodes[i] = (int32_t)made;
-    if (stepped) atomicAdd(&step_sum, (unsigned long long)stepped);
-    __syncthreads();
-    if (lane == 0 && step_sum) atomicAdd(steps + (size_t)(blockIdx.x % BGS_STEP_SHARDS) * BGS_STEP_STRIDE, step_sum);
-}
-
-template <int NW, bool PER_PLY, int POLICY>
-void launch_search(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
-                   uint32_t max_plies, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace) {
-    // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
-    const uint64_t game_base = b->first_game * (uint64_t)iterations * (uint64_t)leaf_playouts;
-    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
-    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
-        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
-        hipLaunchKernelGGL((k_connect_search<NW, PER_PLY, POLICY>), dim3((uint32_t)blocks), dim3(BGS_WAVE), 0, b->stream, g,
-                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, seed, game_base, iterations, leaf_playouts,
-                           explore, max_plies, i0, static_cast<uint32_t*>(d_workspace), d_counts, d_visits, d_best, d_nodes, b->d_steps);
-    }
-}
-
-// ================================================================================================================
-// The forest (bgs_connect_forest_search / bgs_connect_forest_advance, include/bgs.h): the trees of k_connect_search kept
-// from launch to launch in the caller's memory, `capacity` nodes a tree, and re-rooted between the launches.
-//
-// A tree's share of the forest, in 32-bit words, rounded up to 256 bytes:
-//   word 0         the nodes in use, the root counted (0: an emptied tree)
-//   word 1         unused
-//   words 2 ..     the position the root stands for: the 2 * NW plane words of the batch (player 0's, then player 1's),
-//                  64 bits each, 8-byte aligned
-//   words 16 ..    `capacity` nodes in k_connect_search's format (3 * width words: n, s, child)
-// The re-rooting needs a bit a node and a prefix count a 32 nodes; both live in LDS, which is what bounds `capacity`
-// (BGS_CONNECT_FOREST_MAX_CAPACITY), so the forest holds no scratch.
-//
-// k_connect_forest_search is k_connect_search with three differences: the carried check (or the emptying) at the start,
-// step 4 read as the Bounce search reads it (a node is made when the edge has no child AND the tree has room; an edge
-// whose node did not fit plays its playouts from p' all the same and is tried again the next time), and the header
-// written back at the end.  The iteration -- descent, playout block, back-propagation -- is that kernel's, line for line.
-// ================================================================================================================
-constexpr uint32_t kForestHeaderWords = 16;
-
-__host__ __device__ __forceinline__ uint64_t forest_tree_words(uint32_t width, uint32_t capacity) {
-    return (kForestHeaderWords + (uint64_t)capacity * width * 3u + 63u) & ~(uint64_t)63u;
-}
-
-template <int NW, bool PER_PLY, int POLICY>
-__global__ void __launch_bounds__(BGS_WAVE)
-k_connect_forest_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n, uint64_t seed,
-                        uint64_t game_base, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore, uint32_t max_plies,
-                        int64_t root_base, uint32_t capacity, uint32_t restart, uint32_t* forest, int32_t* __restrict__ counts,
-                        int32_t* __restrict__ visits, int32_t* __restrict__ best, int32_t* __restrict__ nodes,
-                        int32_t* __restrict__ carried, unsigned long long* __restrict__ steps) {
-    __shared__ uint32_t path_node[kSearchMaxPath];   // the descent: edge k leaves node path_node[k] by column path_col[k]
-    __shared__ uint32_t path_col[kSearchMaxPath];
-    __shared__ uint32_t tally[3];                    // W/D/L of the iteration's playouts, for the root's mover
-    __shared__ unsigned long long step_sum;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t width = (uint32_t)g.w();
-    const uint32_t stride = (uint32_t)g.h() + 1u;
-    const uint32_t node_words = width * 3u;
-    const int64_t i = root_base + (int64_t)blockIdx.x;       // (the grid holds exactly the roots of this launch)
-    uint32_t* const head = forest + (uint64_t)i * forest_tree_words(width, capacity);
-    uint64_t* const head_planes = reinterpret_cast<uint64_t*>(head + 2);
-    uint32_t* const tree = head + kForestHeaderWords;
 
     Bits<NW> r0, r1;
 #pragma unroll
@@ -898,33 +662,40 @@ k_connect_forest_search(EvalGeom g, const uint64_t* __restrict__ planes, const u
     uint64_t stepped = 0;
     if (lane == 0) step_sum = 0;
 
-    // ---- the carried check (wave-uniform: every lane reads the same header): a tree that fails it is emptied
-    uint32_t used = head[0];            // (uniform) nodes in the tree, the root counted
-    bool keep = restart == 0u && running && used >= 1u && used <= capacity;
-    if (keep) {
+    // ---- the start.  FOREST: the carried check (wave-uniform: every lane reads the same header); a tree that fails it
+    // is emptied.  The plain tree starts empty.
+    uint32_t used = 0;                  // (uniform) nodes in the tree, the root counted
+    bool keep = false;
+    if constexpr (FOREST) {
+        used = head[0];
+        keep = restart == 0u && running && used >= 1u && used <= capacity;
+        if (keep) {
 #pragma unroll
-        for (int j = 0; j < NW; ++j) keep = keep && head_planes[j] == r0.w[j] && head_planes[NW + j] == r1.w[j];
+            for (int j = 0; j < NW; ++j) keep = keep && head_planes[j] == r0.w[j] && head_planes[NW + j] == r1.w[j];
+        }
+        if (keep) {                     // N + T * P < 2^31: the root's n[c] stay in int32
+            const uint32_t nc = lane < width ? tree[lane] : 0u;
+            uint64_t total = 0;
+            for (uint32_t c = 0; c < width; ++c) total += (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)c);
+            keep = total + (uint64_t)iterations * leaf_playouts < (1ull << 31);
+        }
+        keep = __builtin_amdgcn_readfirstlane((int)keep) != 0;
     }
-    if (keep) {                         // N + T * P < 2^31: the root's n[c] stay in int32
-        const uint32_t nc = lane < width ? tree[lane] : 0u;
-        uint64_t total = 0;
-        for (uint32_t c = 0; c < width; ++c) total += (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)c);
-        keep = total + (uint64_t)iterations * leaf_playouts < (1ull << 31);
-    }
-    keep = __builtin_amdgcn_readfirstlane((int)keep) != 0;
     if (!keep) {
         used = running ? 1u : 0u;
         if (running && lane < node_words) tree[lane] = 0;     // the root is node 0 (3 * width <= 48 words)
-        if (running && lane == 0) {
+        if constexpr (FOREST) {
+            if (running && lane == 0) {
 #pragma unroll
-            for (int j = 0; j < NW; ++j) {
-                head_planes[j] = r0.w[j];
-                head_planes[NW + j] = r1.w[j];
+                for (int j = 0; j < NW; ++j) {
+                    head_planes[j] = r0.w[j];
+                    head_planes[NW + j] = r1.w[j];
+                }
             }
         }
     }
     used = (uint32_t)__builtin_amdgcn_readfirstlane((int)used);
-    const uint32_t brought = used ? used - 1u : 0u;
+    [[maybe_unused]] const uint32_t brought = used ? used - 1u : 0u;
     __syncthreads();
 
     Bits<NW> q[2];                      // the lane's playout: stones of player 0 / player 1
@@ -986,7 +757,9 @@ k_connect_forest_search(EvalGeom g, const uint64_t* __restrict__ planes, const u
             leaf = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf);
             if (leaf != BGS_ST_RUNNING) break;                         // a terminal edge: no node, no game
             if (child == 0u) {                                         // no node for p' yet: one is made if it fits
-                if (used < capacity) {
+                bool fits = true;                                      // (the plain tree has iterations + 1 nodes: room for every iteration's)
+                if constexpr (FOREST) fits = used < capacity;
+                if (fits) {
                     if (lane < node_words) tree[(uint64_t)used * node_words + lane] = 0;
                     if (lane == col) node[2u * width + lane] = used;
                     used += 1u;
@@ -1121,27 +894,38 @@ k_connect_forest_search(EvalGeom g, const uint64_t* __restrict__ planes, const u
         if (lane == 0) best[i] = top;
     }
     if (lane == 0) {
-        head[0] = used;             // the header: the planes were recorded when the tree was emptied, or carried with it
+        if constexpr (FOREST) {
+            head[0] = used;         // the header: the planes were recorded when the tree was emptied, or carried with it
+            if (carried) carried[i] = (int32_t)brought;
+        }
         if (nodes) nodes[i] = (int32_t)(used ? used - 1u : 0u);
-        if (carried) carried[i] = (int32_t)brought;
     }
     if (stepped) atomicAdd(&step_sum, (unsigned long long)stepped);
     __syncthreads();
     if (lane == 0 && step_sum) atomicAdd(steps + (size_t)(blockIdx.x % BGS_STEP_SHARDS) * BGS_STEP_STRIDE, step_sum);
 }
 
-template <int NW, bool PER_PLY, int POLICY>
-void launch_forest_search(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts,
-                          uint32_t explore, uint32_t max_plies, uint32_t capacity, uint32_t restart, int32_t* d_counts, int32_t* d_visits,
-                          int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest) {
-    const uint64_t game_base = b->first_game * (uint64_t)iterations * (uint64_t)leaf_playouts;
+// what a search launch is given beyond the batch (connect_search / connect_forest_search fill it)
+struct ConnectSearchArgs {
+    uint64_t seed;
+    uint32_t iterations, leaf_playouts, explore, max_plies;
+    uint32_t capacity, restart;             // the plain search: iterations + 1, 1
+    int32_t *counts, *visits, *best, *nodes;
+    int32_t* carried;                       // the plain search: nullptr
+    void* trees;                            // the workspace, or the forest
+};
+
+template <int NW, bool PER_PLY, int POLICY, bool FOREST>
+void launch_search(const bgs_batch* b, const EvalGeom& g, const ConnectSearchArgs& a) {
+    // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
+    const uint64_t game_base = b->first_game * (uint64_t)a.iterations * (uint64_t)a.leaf_playouts;
     constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
     for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
         const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
-        hipLaunchKernelGGL((k_connect_forest_search<NW, PER_PLY, POLICY>), dim3((uint32_t)blocks), dim3(BGS_WAVE), 0, b->stream, g,
-                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, seed, game_base, iterations, leaf_playouts,
-                           explore, max_plies, i0, capacity, restart, static_cast<uint32_t*>(d_forest), d_counts, d_visits, d_best,
-                           d_nodes, d_carried, b->d_steps);
+        hipLaunchKernelGGL((k_connect_search<NW, PER_PLY, POLICY, FOREST>), dim3((uint32_t)blocks), dim3(BGS_WAVE), 0, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, a.seed, game_base, a.iterations,
+                           a.leaf_playouts, a.explore, a.max_plies, i0, a.capacity, a.restart, static_cast<uint32_t*>(a.trees),
+                           a.counts, a.visits, a.best, a.nodes, a.carried, b->d_steps);
     }
 }
 
@@ -1887,15 +1671,37 @@ void launch_bounce_evaluate_halving(const bgs_batch* b, const GEO& g, uint64_t s
 // tile's stride is BGS_BLOCK whatever the team).  The descent is team-uniform: every lane holds the position p and
 // applies the same stored moves to it.
 //
-// The tree lives in the caller's workspace, per root: a pool of `edges` edges of four words (n, s, child or outcome,
-// source cell << 8 | target cell), a node table of iterations + 1 entries (first edge, arms) and the descent path
-// (iterations + 1 edge indices: iteration t passes through the root and at most t made nodes).  A node's arms are the A
-// consecutive edges from its first edge, in canonical order; they are written once, when the node is made (movable, and
-// reach by lane x, as the halving kernel's root set-up), so a descent replays stored moves and never searches the moves
-// of a node it has been through.  The third word of an edge is 0 (no child yet), a node index 1 .. T, kEdgeEnded | the
-// BGS_ST_* code of the game the edge ends (the outcome is kept absolute, not relative to the mover: nothing needs the
-// relative form) or kEdgeCapped (p' is running and holds the cap: no node, now or later): revisiting an edge that ends the
-// game or is capped costs no move search either.
+// The tree, per root: a pool of `edges` (E) edges of four words (n, s, child or outcome, source cell << 8 | target cell), a
+// node table of C entries (first edge, arms) and the descent path (C edge indices: a descent leaves every node at most
+// once).  A node's arms are the A consecutive edges from its first edge, in canonical order; they are written once, when
+// the node is made (movable, and reach by lane x, as the halving kernel's root set-up), so a descent replays stored moves
+// and never searches the moves of a node it has been through.  The third word of an edge is 0 (no child yet), a node
+// index 1 .. C - 1, kEdgeEnded | the BGS_ST_* code of the game the edge ends (the outcome is kept absolute, not relative to
+// the mover: nothing needs the relative form) or kEdgeCapped (p' is running and holds the cap: no node, now or later):
+// revisiting an edge that ends the game or is capped costs no move search either.
+//
+// One kernel, two places for the tree (the template parameter FOREST):
+//   the plain search (bgs_bounce_search_moves): the tree lives in the caller's workspace with C = iterations + 1 (iteration
+//     t passes through the root and at most t made nodes), starts empty and is forgotten after the launch.  A root's
+//     share: the pool, the node table, the path; rounded up to 256 bytes;
+//   the forest (bgs_bounce_forest_search / bgs_bounce_forest_advance): the trees are kept from launch to launch in the
+//     caller's memory, C = `capacity` nodes a tree, and re-rooted between the launches.  A tree's share of the forest, in
+//     32-bit words, rounded up to 256 bytes:
+//       word 0         the nodes in use, the root counted (0: an emptied tree)
+//       word 1         the pool edges in use
+//       word 2         the absolute ply count of the position the root stands for
+//       word 3         the effective cap (min(max_plies, 65535)) the tree's kEdgeCapped sentinels were written under
+//       words 4 .. 11  the position the root stands for: the four 64-bit planes of the batch, 8-byte aligned
+//       words 16 ..    the E edges
+//       then           the C node-table entries
+//       then           the C words of descent path; they mean nothing between launches
+//     With C <= 65536 and E <= BGS_BOUNCE_FOREST_MAX_EDGES = 2^29 a share has fewer than 2^32 words.
+// FOREST changes these things and nothing else: where the share and its parts are; the exit of a root without arms (the
+// forest's also empties the tree and writes `carried`); the start (the carried check, or the emptying, where the plain
+// search makes node 0); "a node is made when the edge has no child, the tree holds fewer than C nodes AND the pool has
+// room for its arms" (the plain tree has a node an iteration, so there only the pool is asked); and the header written
+// back at the end, behind a barrier, with `carried`.  The iteration -- descent, refill loop, ply, back-propagation -- is
+// one text.
 //
 // A descent step: the lanes read the node's edges strided (at most two a lane), reduce the lowest arm with n = 0 and
 // N = sum n over the waves (shuffles) and the team (one LDS word a wave), and without an unplayed arm reduce the key
@@ -1922,9 +1728,16 @@ constexpr int kSearchTeamWaves = BGS_BLOCK / BGS_WAVE;
 static_assert(kBounceHalvingMaxArms <= 2 * BGS_BLOCK, "a lane holds at most two arms of a node");
 static_assert((uint32_t)BGS_ST_DRAW < 15u, "an outcome code fits the low bits of kEdgeEnded and stays below kEdgeCapped");
 
+constexpr uint32_t kBounceForestHeaderWords = 16;
+
 // words of a root's share of the workspace: the edge pool, the node table, the path; rounded up to 256 bytes
 __host__ __device__ __forceinline__ uint64_t bounce_search_root_words(uint32_t iterations, uint32_t edges) {
     return ((uint64_t)edges * kEdgeWords + ((uint64_t)iterations + 1u) * 3u + 63u) & ~(uint64_t)63u;
+}
+
+// words of a tree's share of the forest: the header before the same three parts; rounded up to 256 bytes
+__host__ __device__ __forceinline__ uint64_t bounce_forest_tree_words(uint32_t capacity, uint32_t edges) {
+    return (kBounceForestHeaderWords + (uint64_t)edges * kEdgeWords + (uint64_t)capacity * 3u + 63u) & ~(uint64_t)63u;
 }
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
@@ -1949,12 +1762,24 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
     return v;
 }
 
-template <class GEO, int NC, int POLICY>
+// what the forest's instantiation alone is given, last in the list; the plain one's is empty, so the plain kernel's
+// arguments keep the offsets they have without the forest (these kernels sit at the SGPR ceiling, and the arguments are
+// the first SGPRs loaded: docs/EXPERIMENTS.md §33)
+template <bool FOREST>
+struct BounceForestArgs {};
+template <>
+struct BounceForestArgs<true> {
+    uint32_t capacity, restart;
+    int32_t* carried;
+};
+
+template <class GEO, int NC, int POLICY, bool FOREST>
 __global__ void __launch_bounds__(BGS_BLOCK)
 k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, const uint16_t* __restrict__ plies_buf,
                 int64_t n, uint64_t seed, uint64_t game_base, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
-                uint32_t max_plies, uint32_t edges, uint32_t slots, int64_t root_base, uint32_t* workspace, int32_t* counts,
-                int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used_out, unsigned long long* __restrict__ steps) {
+                uint32_t max_plies, uint32_t edges, uint32_t slots, int64_t root_base, uint32_t* trees, int32_t* counts,
+                int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used_out, unsigned long long* __restrict__ steps,
+                BounceForestArgs<FOREST> forest) {
     extern __shared__ uint32_t target_tile[];                      // [2 * 8 * NC dwords][256 lanes]
     __shared__ uint64_t node_targets[8 * NC];                      // targets of the piece in column x of the active row of p'
     __shared__ uint64_t other_targets[8 * NC];                     // ... of the side that has just moved, when p' is blocked
@@ -1965,405 +1790,21 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
     const uint32_t tid = threadIdx.x, lane = threadIdx.x & (BGS_WAVE - 1), wave = threadIdx.x / BGS_WAVE;
     const uint32_t hw = (uint32_t)(g.h * g.w);
     const int64_t i = root_base + (int64_t)blockIdx.x;             // (the grid holds exactly the roots of this launch)
-    uint32_t* const pool = workspace + (uint64_t)i * bounce_search_root_words(iterations, edges);
+    // ---- where the tree is: behind the header of its share of the forest, or bare in the workspace
+    uint32_t *head = nullptr, *pool;
+    uint64_t* head_planes = nullptr;
+    uint64_t table_room;                                                        // the node table's entries (C)
+    if constexpr (FOREST) {
+        head = trees + (uint64_t)i * bounce_forest_tree_words(forest.capacity, edges);
+        head_planes = reinterpret_cast<uint64_t*>(head + 4);
+        pool = head + kBounceForestHeaderWords;
+        table_room = forest.capacity;
+    } else {
+        pool = trees + (uint64_t)i * bounce_search_root_words(iterations, edges);
+        table_room = (uint64_t)iterations + 1u;
+    }
     uint32_t* const node_tab = pool + (uint64_t)edges * kEdgeWords;             // node v: first edge, arms
-    uint32_t* const path = node_tab + ((uint64_t)iterations + 1u) * 2u;         // edge k of the descent
-    const auto uniform = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
-
-    // the targets of `player`'s pieces on `bd`, the piece in column x by lane x, into dst (complete behind the caller's
-    // barrier); returns the cell of column 0 of the active row
-    const auto spread = [&](const Board& bd, uint64_t occ, uint32_t player, bool live, uint64_t* dst) {
-        const uint64_t sources = live ? movable(g, occ, player) : 0ull;
-        const uint32_t first_source = sources ? (uint32_t)(__ffsll((unsigned long long)sources) - 1) : 0u;
-        const uint32_t base = ((first_source * g.inv_w) >> 16) * (uint32_t)g.w;
-        if (tid < 8 * NC) {
-            const bool piece = tid < (uint32_t)g.w && ((sources >> ((base + tid) & 63u)) & 1ull);
-            dst[tid] = piece ? reach(g, bd, occ, player, (int)(base + tid)) : 0ull;
-        }
-        return base;
-    };
-    const auto count_arms = [&](const uint64_t* t) {
-        uint32_t arms = 0;
-        for (uint32_t x = 0; x < 8 * NC; ++x) arms += (uint32_t)__popcll(t[x]);
-        return uniform(arms);
-    };
-    // the arm table of a new node: `arms` fresh edges from edge `first`, in canonical order (first + arms <= edges)
-    const auto make_arms = [&](uint32_t first, uint32_t arms, uint32_t base) {
-        for (uint32_t a = tid; a < arms; a += BGS_BLOCK) {
-            uint32_t j = a, x = 0;
-            for (; x < 8 * NC - 1; ++x) {
-                const uint32_t cnt = (uint32_t)__popcll(node_targets[x]);
-                if (j < cnt) break;
-                j -= cnt;
-            }
-            const uint32_t move = ((base + x) << 8) | select_bit64(node_targets[x], j);
-            *reinterpret_cast<uint4*>(pool + (uint64_t)(first + a) * kEdgeWords) = make_uint4(0u, 0u, 0u, move);
-        }
-    };
-
-    // ---- the root, once: node 0 and its arms
-    const Board root = load_board(planes, n, i);
-    const uint32_t rply = plies_buf[i];
-    const uint32_t root_mover = rply & 1u;
-    // (an ended root and one that holds the most plies a board can have no arms, as in k_bounce_eval_count)
-    const uint32_t root_base_cell = spread(root, occupancy(root), root_mover, status[i] == BGS_ST_RUNNING && rply < kBounceMaxPlies, node_targets);
-    __syncthreads();
-    const uint32_t root_arms = count_arms(node_targets);
-    if (root_arms == 0u) {   // nothing to search: counts and visits stay zero
-        if (tid == 0) {
-            if (best) best[i] = -1;
-            if (nodes) nodes[i] = 0;
-            if (used_out) used_out[i] = 0;
-        }
-        return;
-    }
-    make_arms(0u, root_arms, root_base_cell);
-    if (tid == 0) {
-        node_tab[0] = 0u;
-        node_tab[1] = root_arms;
-    }
-    uint32_t used = root_arms, made = 0;      // (team-uniform) pool edges in use; nodes made, the root not counted
-    __syncthreads();
-    const auto slot_of = [&](uint32_t move) { return ((move >> 8) - root_base_cell) * hw + (move & 255u); };
-
-    Board b;                         // the lane's game
-#pragma unroll
-    for (int j = 0; j < 4; ++j) b.v[j] = 0;
-    FlatMoves<NC> mv;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) mv.counts[k] = 0;
-    mv.n = 0;
-    mv.row_base = 0;
-    uint32_t st = 0, plies = 0, stepped = 0;
-    uint64_t game = 0;
-    bool has = false, search = false, have_block = false;
-    [[maybe_unused]] bool can_win = false;   // (BGS_POLICY_DECISIVE) the list the lane holds has a target in the mover's goal row
-    Philox4 blk;
-    blk.v[0] = blk.v[1] = blk.v[2] = blk.v[3] = 0;
-
-    for (uint32_t t = 0; t < iterations; ++t) {
-        // ---- descent (team-uniform): p is the position at node v
-        Board p = root;
-        uint32_t ply = rply, v = 0, depth = 0, move0 = 0;
-        uint32_t leaf = BGS_ST_RUNNING;     // the outcome of an edge that ends the game
-        bool capped = false;                // p' runs and holds the cap
-        for (;;) {
-            const uint32_t first = uniform(node_tab[2u * v]), arms = uniform(node_tab[2u * v + 1u]);
-            const uint32_t* const node = pool + (uint64_t)first * kEdgeWords;
-            uint32_t na[2] = {0u, 0u}, sa[2] = {0u, 0u};
-            uint32_t fresh = kNoArm, sum = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < 2; ++k) {
-                const uint32_t a = tid + k * BGS_BLOCK;
-                if (a < arms) {
-                    const uint2 ns = *reinterpret_cast<const uint2*>(node + (uint64_t)a * kEdgeWords);
-                    na[k] = ns.x;
-                    sa[k] = ns.y;
-                    sum += ns.x;
-                    fresh = (ns.x == 0u && a < fresh) ? a : fresh;
-                }
-            }
-            const uint32_t buf = depth & 1u;
-            fresh = wave_min(fresh);
-            sum = wave_sum(sum);
-            if (lane == 0) {
-                red_min[buf][wave] = fresh;
-                red_sum[buf][wave] = sum;
-            }
-            __syncthreads();
-            uint32_t arm = kNoArm, total = 0;
-#pragma unroll
-            for (int w = 0; w < kSearchTeamWaves; ++w) {
-                arm = red_min[buf][w] < arm ? red_min[buf][w] : arm;
-                total += red_sum[buf][w];
-            }
-            arm = uniform(arm);             // the expansion: the lowest arm never played
-            if (arm == kNoArm) {
-                const uint32_t scaled = explore * search_lg(uniform(total));
-                uint32_t key = 0;           // (U(a) << 9 | 511 - a) + 1: the largest U, then the lowest arm
-#pragma unroll
-                for (uint32_t k = 0; k < 2; ++k) {
-                    const uint32_t a = tid + k * BGS_BLOCK;
-                    if (a < arms) {
-                        const uint32_t u = search_q(sa[k], na[k]) + search_isqrt(scaled / na[k]);
-                        const uint32_t mine = ((u << 9) | (511u - a)) + 1u;
-                        key = mine > key ? mine : key;
-                    }
-                }
-                key = wave_max(key);
-                if (lane == 0) red_key[buf][wave] = key;
-                __syncthreads();
-                uint32_t top = 0;
-#pragma unroll
-                for (int w = 0; w < kSearchTeamWaves; ++w) top = red_key[buf][w] > top ? red_key[buf][w] : top;
-                arm = uniform(511u - ((top - 1u) & 511u));
-            }
-            const uint32_t e = first + arm;
-            uint32_t* const edge = pool + (uint64_t)e * kEdgeWords;
-            const uint32_t child = uniform(edge[2]), move = uniform(edge[3]);
-            if (tid == 0) path[depth] = e;
-            move0 = depth == 0u ? move : move0;
-            const int s_cell = (int)(move >> 8), t_cell = (int)(move & 255u);
-            const uint32_t mover = ply & 1u;
-            move_piece(p, s_cell, t_cell);
-            ply += 1u;
-            depth += 1u;
-            if (child == kEdgeCapped) {
-                capped = true;
-                break;
-            }
-            if (child >= kEdgeEnded) {
-                leaf = child & 15u;
-                break;
-            }
-            if (child != 0u) {
-                v = child;
-                continue;
-            }
-            // ---- the edge has no child: what p' is
-            uint32_t code = 0;              // the edge's new third word, if any
-            if ((1ull << t_cell) & (g.goal_top | g.goal_bottom)) {
-                leaf = mover + 1u;
-                code = kEdgeEnded | leaf;
-            } else {
-                const uint64_t occ = occupancy(p);
-                const uint32_t base = spread(p, occ, ply & 1u, true, node_targets);
-                __syncthreads();
-                const uint32_t fan = count_arms(node_targets);
-                if (fan == 0u) {            // the side to move is blocked: the mover wins if it could move, else a draw
-                    spread(p, occ, mover, true, other_targets);
-                    __syncthreads();
-                    leaf = count_arms(other_targets) ? mover + 1u : (uint32_t)BGS_ST_DRAW;
-                    code = kEdgeEnded | leaf;
-                } else if (ply >= max_plies) {
-                    capped = true;
-                    code = kEdgeCapped;
-                } else if (used + fan <= edges) {   // a new node for p'; without room the edge is tried again next time
-                    made += 1u;
-                    make_arms(used, fan, base);
-                    if (tid == 0) {
-                        node_tab[2u * made] = used;
-                        node_tab[2u * made + 1u] = fan;
-                    }
-                    code = made;
-                    used += fan;
-                }
-            }
-            if (tid == 0 && code) edge[2] = code;
-            break;
-        }
-
-        // ---- the leaf's playouts: the halving kernel's refill loop and ply from p'
-        const bool play = leaf == BGS_ST_RUNNING && !capped;
-        if (tid < 3u) tally[tid] = 0;
-        if (tid == 0) next_item = 0;
-        __syncthreads();            // (A) the counter and the tally are zero; the path, the new node and the edge are written
-        uint32_t wins = 0, draws = 0, losses = 0;
-        if (play) {
-            // G = ((first_game + i) * T + t) * P + j
-            const uint64_t game0 = game_base + ((uint64_t)i * iterations + t) * (uint64_t)leaf_playouts;
-            bool dry = false;        // (wave-uniform) the leaf's counter has nothing left for this wave
-            while (!dry || __builtin_amdgcn_ballot_w64(has)) {
-                const uint64_t need = __builtin_amdgcn_ballot_w64(!has);
-                if (need && !dry) {
-                    if (__builtin_amdgcn_ballot_w64(stepped >= (1u << 30))) {   // (a lane adds at most 65535 a playout)
-                        add_steps(steps, stepped);
-                        stepped = 0;
-                    }
-                    const uint32_t wanted = (uint32_t)__popcll(need);
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(&next_item, wanted);
-                    base = uniform(base);
-                    if (base + wanted >= leaf_playouts) dry = true;
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
-                    if (!has && base + rank < leaf_playouts) {
-                        game = game0 + (uint64_t)(base + rank);
-                        b = p;
-                        plies = ply;
-                        st = BGS_ST_RUNNING;
-                        has = true;
-                        search = true;
-                        have_block = false;
-                    }
-                }
-                if (!__builtin_amdgcn_ballot_w64(has)) continue;
-
-                if (__builtin_amdgcn_ballot_w64(search)) {
-                    const uint64_t occ = occupancy(b);
-                    enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
-                    const bool blocked = search && mv.n == 0u;
-                    if (__builtin_amdgcn_ballot_w64(blocked)) {
-                        FlatMoves<NC> other;
-#pragma unroll
-                        for (int k = 0; k < NC; ++k) other.counts[k] = 0;
-                        other.n = 0;
-                        other.row_base = 0;
-                        enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
-                        if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
-                    }
-                    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
-                        if (search) can_win = st == BGS_ST_RUNNING && b_can_win<NC>(mv, column, (plies & 1u) ? g.goal_bottom : g.goal_top);
-                    }
-                    search = false;
-                }
-                const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
-                if (has && !run) {       // finished (a capped game, st 0, is counted nowhere)
-                    wins += (st != 0u && st != BGS_ST_DRAW && st - 1u == root_mover) ? 1u : 0u;
-                    losses += (st != 0u && st != BGS_ST_DRAW && st - 1u != root_mover) ? 1u : 0u;
-                    draws += st == BGS_ST_DRAW ? 1u : 0u;
-                    has = false;
-                }
-                if constexpr (POLICY == BGS_POLICY_DECISIVE) {
-                    if (run && can_win) {   // every candidate ends the game for the mover: one transition, nothing drawn or moved
-                        st = (plies & 1u) + 1u;
-                        ++plies;
-                        stepped += 1u;
-                    }
-                }
-                if (POLICY == BGS_POLICY_DECISIVE ? run && !can_win : run) {
-                    if (!have_block || (plies & 3u) == 0u) {
-                        blk = philox4x32_10(seed, game, plies >> 2);
-                        have_block = true;
-                    }
-                    const uint32_t mover = plies & 1u;
-                    int s, tc;
-                    pick_flat<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, tc);
-                    move_piece(b, s, tc);
-                    ++plies;
-                    stepped += 1u;
-                    if ((1ull << tc) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
-                    else search = true;
-                }
-            }
-            if (wins) atomicAdd(tally + 0, wins);
-            if (draws) atomicAdd(tally + 1, draws);
-            if (losses) atomicAdd(tally + 2, losses);
-        }
-        __syncthreads();            // (B) the tally is complete
-        uint32_t tw = 0, td = 0, tl = 0;
-        if (play) {
-            tw = tally[0];
-            td = tally[1];
-            tl = tally[2];
-        } else if (!capped) {       // all playouts of the iteration have the edge's outcome
-            tw = (leaf != BGS_ST_DRAW && leaf - 1u == root_mover) ? leaf_playouts : 0u;
-            tl = (leaf != BGS_ST_DRAW && leaf - 1u != root_mover) ? leaf_playouts : 0u;
-            td = leaf == BGS_ST_DRAW ? leaf_playouts : 0u;
-        }
-
-        // ---- back-propagation: lane k takes edge k of the path; its mover is the root's at even k
-        for (uint32_t k = tid; k < depth; k += BGS_BLOCK) {
-            uint32_t* const edge = pool + (uint64_t)path[k] * kEdgeWords;
-            edge[0] += leaf_playouts;
-            edge[1] += td + 2u * ((k & 1u) ? tl : tw);
-        }
-        if (tid == 0) {
-            int32_t* const c = counts + (i * (int64_t)slots + slot_of(move0)) * 3;
-            c[0] += (int32_t)tw;
-            c[1] += (int32_t)td;
-            c[2] += (int32_t)tl;
-        }
-        __syncthreads();            // (C) the tree is whole again before the next descent reads it; tally and path are free
-    }
-
-    // ---- the outputs of the root (illegal slots are never stored: the launcher zeroed them)
-    if (visits) {
-        for (uint32_t a = tid; a < root_arms; a += BGS_BLOCK) {
-            const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
-            visits[i * (int64_t)slots + slot_of(edge[3])] = (int32_t)edge[0];
-        }
-    }
-    if (tid == 0) {
-        if (best) {   // the most visits, then the larger 2 * wins + draws, then the lower slot (the arms ascend by slot)
-            int32_t top = -1;
-            uint32_t top_n = 0, top_s = 0;
-            for (uint32_t a = 0; a < root_arms; ++a) {
-                const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
-                const uint32_t cn = edge[0], cs = edge[1];
-                if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
-                    top = (int32_t)slot_of(edge[3]);
-                    top_n = cn;
-                    top_s = cs;
-                }
-            }
-            best[i] = top;
-        }
-        if (nodes) nodes[i] = (int32_t)made;
-        if (used_out) used_out[i] = (int32_t)used;
-    }
-    add_steps(steps, stepped);
-}
-
-template <class GEO, int NC, int POLICY>
-void launch_bounce_search(const bgs_batch* b, const GEO& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
-                          uint32_t max_plies, uint32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes,
-                          int32_t* d_used, void* d_workspace) {
-    const uint32_t slots = (uint32_t)(b->bg.w * b->bg.h * b->bg.w);
-    (void)hipMemsetAsync(d_counts, 0, (size_t)b->n * slots * 3 * sizeof(int32_t), b->stream);
-    if (d_visits) (void)hipMemsetAsync(d_visits, 0, (size_t)b->n * slots * sizeof(int32_t), b->stream);
-    // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
-    const uint64_t game_base = b->first_game * (uint64_t)iterations * (uint64_t)leaf_playouts;
-    const size_t tile = sizeof(uint32_t) * 2 * 8 * NC * BGS_BLOCK;
-    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
-    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
-        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
-        hipLaunchKernelGGL((k_bounce_search<GEO, NC, POLICY>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), tile, b->stream, g,
-                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, seed, game_base,
-                           iterations, leaf_playouts, explore, max_plies, edges, slots, i0, static_cast<uint32_t*>(d_workspace), d_counts,
-                           d_visits, d_best, d_nodes, d_used, b->d_steps);
-    }
-}
-
-// ================================================================================================================
-// The Bounce forest (bgs_bounce_forest_search / bgs_bounce_forest_advance, include/bgs.h): the trees of k_bounce_search
-// kept from launch to launch in the caller's memory, `capacity` (C) nodes and `edges` (E) pool edges a tree, and re-rooted
-// between the launches.
-//
-// A tree's share of the forest, in 32-bit words, rounded up to 256 bytes:
-//   word 0         the nodes in use, the root counted (0: an emptied tree)
-//   word 1         the pool edges in use
-//   word 2         the absolute ply count of the position the root stands for
-//   word 3         the effective cap (min(max_plies, 65535)) the tree's kEdgeCapped sentinels were written under
-//   words 4 .. 11  the position the root stands for: the four 64-bit planes of the batch, 8-byte aligned
-//   words 16 ..    E edges in k_bounce_search's format (n, s, child or outcome, source cell << 8 | target cell)
-//   then           C node-table entries (first edge, arms)
-//   then           C words of descent path: a descent leaves every node at most once, so it has at most C edges; the
-//                  words mean nothing between launches
-// With C <= 65536 and E <= BGS_BOUNCE_FOREST_MAX_EDGES = 2^29 a share has fewer than 2^32 words.
-//
-// k_bounce_forest_search is k_bounce_search with four differences: the carried check (or the emptying) at the start, "a
-// node is made when the edge has no child, the tree holds fewer than C nodes AND the pool has room for its arms", the
-// tables and the path in the forest's share, and the header written back at the end, behind a barrier.  The iteration --
-// descent, refill loop, ply, back-propagation -- is that kernel's, line for line.
-// ================================================================================================================
-constexpr uint32_t kBounceForestHeaderWords = 16;
-
-__host__ __device__ __forceinline__ uint64_t bounce_forest_tree_words(uint32_t capacity, uint32_t edges) {
-    return (kBounceForestHeaderWords + (uint64_t)edges * kEdgeWords + (uint64_t)capacity * 3u + 63u) & ~(uint64_t)63u;
-}
-
-template <class GEO, int NC, int POLICY>
-__global__ void __launch_bounds__(BGS_BLOCK)
-k_bounce_forest_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status,
-                       const uint16_t* __restrict__ plies_buf, int64_t n, uint64_t seed, uint64_t game_base, uint32_t iterations,
-                       uint32_t leaf_playouts, uint32_t explore, uint32_t max_plies, uint32_t capacity, uint32_t edges, uint32_t restart,
-                       uint32_t slots, int64_t root_base, uint32_t* forest, int32_t* counts, int32_t* visits, int32_t* best,
-                       int32_t* nodes, int32_t* used_out, int32_t* carried, unsigned long long* __restrict__ steps) {
-    extern __shared__ uint32_t target_tile[];                      // [2 * 8 * NC dwords][256 lanes]
-    __shared__ uint64_t node_targets[8 * NC];                      // targets of the piece in column x of the active row of p'
-    __shared__ uint64_t other_targets[8 * NC];                     // ... of the side that has just moved, when p' is blocked
-    __shared__ uint32_t red_min[2][kSearchTeamWaves], red_sum[2][kSearchTeamWaves], red_key[2][kSearchTeamWaves];
-    __shared__ uint32_t tally[3];                                  // W/D/L of the iteration's playouts, for the root's mover
-    __shared__ uint32_t next_item;                                 // the leaf's next playout
-    uint32_t* const column = target_tile + threadIdx.x;
-    const uint32_t tid = threadIdx.x, lane = threadIdx.x & (BGS_WAVE - 1), wave = threadIdx.x / BGS_WAVE;
-    const uint32_t hw = (uint32_t)(g.h * g.w);
-    const int64_t i = root_base + (int64_t)blockIdx.x;             // (the grid holds exactly the roots of this launch)
-    uint32_t* const head = forest + (uint64_t)i * bounce_forest_tree_words(capacity, edges);
-    uint64_t* const head_planes = reinterpret_cast<uint64_t*>(head + 4);
-    uint32_t* const pool = head + kBounceForestHeaderWords;
-    uint32_t* const node_tab = pool + (uint64_t)edges * kEdgeWords;             // node v: first edge, arms
-    uint32_t* const path = node_tab + (uint64_t)capacity * 2u;                  // edge k of the descent
+    uint32_t* const path = node_tab + table_room * 2u;                          // edge k of the descent
     const auto uniform = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
 
     // the targets of `player`'s pieces on `bd`, the piece in column x by lane x, into dst (complete behind the caller's
@@ -2405,59 +1846,69 @@ k_bounce_forest_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t
     const uint32_t root_base_cell = spread(root, occupancy(root), root_mover, status[i] == BGS_ST_RUNNING && rply < kBounceMaxPlies, node_targets);
     __syncthreads();
     const uint32_t root_arms = count_arms(node_targets);
-    if (root_arms == 0u) {   // nothing to search: an emptied tree; counts and visits stay zero
+    if (root_arms == 0u) {   // nothing to search (FOREST: an emptied tree); counts and visits stay zero
         if (tid == 0) {
-            head[0] = 0;
-            head[1] = 0;
+            if constexpr (FOREST) {
+                head[0] = 0;
+                head[1] = 0;
+                if (forest.carried) forest.carried[i] = 0;
+            }
             if (best) best[i] = -1;
             if (nodes) nodes[i] = 0;
             if (used_out) used_out[i] = 0;
-            if (carried) carried[i] = 0;
         }
         return;
     }
 
-    // ---- the carried check: a tree that fails it is emptied.  Every wave reads the header and decides for itself; the
-    // decision is the team's because the words it reads do not change while it is made: nothing of the header, the table or
-    // the pool is written before barrier (H) below, which every wave passes with its reads returned (readfirstlane needs
-    // them) whatever it decided.  Behind (H) the waves hold the same `keep`, so the branches that follow -- and the barriers
-    // inside them -- are taken by all four waves or by none.
-    uint32_t count = uniform(head[0]), used = uniform(head[1]);     // nodes in use, the root counted; pool edges in use
-    bool keep = restart == 0u && count >= 1u && count <= capacity && used >= root_arms && used <= edges && head[2] == rply &&
-                head[3] == max_plies;
-    if (keep) {
+    // ---- the start.  The plain tree starts empty.  FOREST: the carried check; a tree that fails it is emptied.  Every wave
+    // reads the header and decides for itself; the decision is the team's because the words it reads do not change while it
+    // is made: nothing of the header, the table or the pool is written before barrier (H) below, which every wave passes
+    // with its reads returned (readfirstlane needs them) whatever it decided.  Behind (H) the waves hold the same `keep`, so
+    // the branches that follow -- and the barriers inside them -- are taken by all four waves or by none.
+    uint32_t made = 0, used = 0;        // (team-uniform) nodes in the tree, the root not counted; pool edges in use
+    bool keep = false;
+    if constexpr (FOREST) {
+        const uint32_t count = uniform(head[0]);                    // (the header counts the root)
+        used = uniform(head[1]);
+        keep = forest.restart == 0u && count >= 1u && count <= forest.capacity && used >= root_arms && used <= edges && head[2] == rply &&
+               head[3] == max_plies;
+        if (keep) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) keep = keep && head_planes[j] == root.v[j];
-    }
-    keep = uniform(keep ? 1u : 0u) != 0u;
-    __syncthreads();                    // (H) every wave has read the header before any wave rewrites it
-    if (keep) {                         // N + T * P < 2^31: the root's n stay in int32 (the root's block starts at edge 0)
-        uint32_t sum = 0;
-        for (uint32_t a = tid; a < root_arms; a += BGS_BLOCK) sum += pool[(uint64_t)a * kEdgeWords];
-        sum = wave_sum(sum);
-        if (lane == 0) red_sum[0][wave] = sum;
-        __syncthreads();
-        uint64_t total = 0;
-#pragma unroll
-        for (int w = 0; w < kSearchTeamWaves; ++w) total += red_sum[0][w];
-        keep = total + (uint64_t)iterations * leaf_playouts < (1ull << 31);
+            for (int j = 0; j < 4; ++j) keep = keep && head_planes[j] == root.v[j];
+        }
         keep = uniform(keep ? 1u : 0u) != 0u;
-        __syncthreads();                // (red_sum[0] is free for the first descent step)
+        __syncthreads();                // (H) every wave has read the header before any wave rewrites it
+        if (keep) {                     // N + T * P < 2^31: the root's n stay in int32 (the root's block starts at edge 0)
+            uint32_t sum = 0;
+            for (uint32_t a = tid; a < root_arms; a += BGS_BLOCK) sum += pool[(uint64_t)a * kEdgeWords];
+            sum = wave_sum(sum);
+            if (lane == 0) red_sum[0][wave] = sum;
+            __syncthreads();
+            uint64_t total = 0;
+#pragma unroll
+            for (int w = 0; w < kSearchTeamWaves; ++w) total += red_sum[0][w];
+            keep = total + (uint64_t)iterations * leaf_playouts < (1ull << 31);
+            keep = uniform(keep ? 1u : 0u) != 0u;
+            __syncthreads();            // (red_sum[0] is free for the first descent step)
+        }
+        made = count - 1u;
     }
-    if (!keep) {                        // node 0 and its arms; board i recorded
+    if (!keep) {                        // node 0 and its arms; FOREST: board i recorded
         make_arms(0u, root_arms, root_base_cell);
         if (tid == 0) {
             node_tab[0] = 0u;
             node_tab[1] = root_arms;
-            head[2] = rply;
-            head[3] = max_plies;
+            if constexpr (FOREST) {
+                head[2] = rply;
+                head[3] = max_plies;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) head_planes[j] = root.v[j];
+                for (int j = 0; j < 4; ++j) head_planes[j] = root.v[j];
+            }
         }
-        count = 1u;
+        made = 0u;
         used = root_arms;
     }
-    const uint32_t brought = count - 1u;
+    [[maybe_unused]] const uint32_t brought = made;
     __syncthreads();
     const auto slot_of = [&](uint32_t move) { return ((move >> 8) - root_base_cell) * hw + (move & 255u); };
 
@@ -2573,15 +2024,19 @@ k_bounce_forest_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t
                 } else if (ply >= max_plies) {
                     capped = true;
                     code = kEdgeCapped;
-                } else if (count < capacity && used + fan <= edges) {   // a new node for p'; without room the edge is tried again next time
-                    make_arms(used, fan, base);
-                    if (tid == 0) {
-                        node_tab[2u * count] = used;
-                        node_tab[2u * count + 1u] = fan;
+                } else {
+                    bool fits = used + fan <= edges;                 // (the plain table has iterations + 1 entries: room for every iteration's)
+                    if constexpr (FOREST) fits = made + 1u < forest.capacity && fits;
+                    if (fits) {             // a new node for p'; without room the edge is tried again next time
+                        made += 1u;
+                        make_arms(used, fan, base);
+                        if (tid == 0) {
+                            node_tab[2u * made] = used;
+                            node_tab[2u * made + 1u] = fan;
+                        }
+                        code = made;
+                        used += fan;
                     }
-                    code = count;
-                    count += 1u;
-                    used += fan;
                 }
             }
             if (tid == 0 && code) edge[2] = code;
@@ -2708,7 +2163,7 @@ k_bounce_forest_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t
             visits[i * (int64_t)slots + slot_of(edge[3])] = (int32_t)edge[0];
         }
     }
-    __syncthreads();                // the tree's last writes are issued by every wave before the header says what it holds
+    if constexpr (FOREST) __syncthreads();   // the tree's last writes are issued by every wave before the header says what it holds
     if (tid == 0) {
         if (best) {   // the most visits, then the larger 2 * wins + draws, then the lower slot (the arms ascend by slot)
             int32_t top = -1;
@@ -2724,33 +2179,44 @@ k_bounce_forest_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t
             }
             best[i] = top;
         }
-        head[0] = count;            // the header: ply, cap and planes were recorded when the tree was emptied, or carried with it
-        head[1] = used;
-        if (nodes) nodes[i] = (int32_t)(count - 1u);
+        if constexpr (FOREST) {
+            head[0] = made + 1u;    // the header: ply, cap and planes were recorded when the tree was emptied, or carried with it
+            head[1] = used;
+            if (forest.carried) forest.carried[i] = (int32_t)brought;
+        }
+        if (nodes) nodes[i] = (int32_t)made;
         if (used_out) used_out[i] = (int32_t)used;
-        if (carried) carried[i] = (int32_t)brought;
     }
     add_steps(steps, stepped);
 }
 
-template <class GEO, int NC, int POLICY>
-void launch_bounce_forest_search(const bgs_batch* b, const GEO& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts,
-                                 uint32_t explore, uint32_t max_plies, uint32_t capacity, uint32_t edges, uint32_t restart,
-                                 int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
-                                 int32_t* d_carried, void* d_forest) {
+// what a search launch is given beyond the batch (bounce_search / bounce_forest_search fill it)
+struct BounceSearchArgs {
+    uint64_t seed;
+    uint32_t iterations, leaf_playouts, explore, max_plies;
+    uint32_t capacity, edges, restart;      // (the plain search reads neither capacity nor restart)
+    int32_t *counts, *visits, *best, *nodes, *used;
+    int32_t* carried;                       // (nor carried)
+    void* trees;                            // the workspace, or the forest
+};
+
+template <class GEO, int NC, int POLICY, bool FOREST>
+void launch_bounce_search(const bgs_batch* b, const GEO& g, const BounceSearchArgs& a) {
     const uint32_t slots = (uint32_t)(b->bg.w * b->bg.h * b->bg.w);
-    (void)hipMemsetAsync(d_counts, 0, (size_t)b->n * slots * 3 * sizeof(int32_t), b->stream);
-    if (d_visits) (void)hipMemsetAsync(d_visits, 0, (size_t)b->n * slots * sizeof(int32_t), b->stream);
+    (void)hipMemsetAsync(a.counts, 0, (size_t)b->n * slots * 3 * sizeof(int32_t), b->stream);
+    if (a.visits) (void)hipMemsetAsync(a.visits, 0, (size_t)b->n * slots * sizeof(int32_t), b->stream);
     // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
-    const uint64_t game_base = b->first_game * (uint64_t)iterations * (uint64_t)leaf_playouts;
+    const uint64_t game_base = b->first_game * (uint64_t)a.iterations * (uint64_t)a.leaf_playouts;
     const size_t tile = sizeof(uint32_t) * 2 * 8 * NC * BGS_BLOCK;
+    BounceForestArgs<FOREST> forest;
+    if constexpr (FOREST) forest = {a.capacity, a.restart, a.carried};
     constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
     for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
         const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
-        hipLaunchKernelGGL((k_bounce_forest_search<GEO, NC, POLICY>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), tile, b->stream, g,
-                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, seed, game_base,
-                           iterations, leaf_playouts, explore, max_plies, capacity, edges, restart, slots, i0,
-                           static_cast<uint32_t*>(d_forest), d_counts, d_visits, d_best, d_nodes, d_used, d_carried, b->d_steps);
+        hipLaunchKernelGGL((k_bounce_search<GEO, NC, POLICY, FOREST>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), tile, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, a.seed,
+                           game_base, a.iterations, a.leaf_playouts, a.explore, a.max_plies, a.edges, slots, i0,
+                           static_cast<uint32_t*>(a.trees), a.counts, a.visits, a.best, a.nodes, a.used, b->d_steps, forest);
     }
 }
 
@@ -3715,67 +3181,43 @@ uint64_t bounce_search_root_bytes(int32_t iterations, int32_t edges) {
     return bounce_search_root_words((uint32_t)iterations, (uint32_t)edges) * sizeof(uint32_t);
 }
 
-template <int POLICY>
-static void bounce_search_policy(const bgs_batch* b, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
-                                 uint32_t cap, uint32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes,
-                                 int32_t* d_used, void* d_workspace) {
+template <int POLICY, bool FOREST>
+static void bounce_search_policy(const bgs_batch* b, const BounceSearchArgs& a) {
     if (b->bounce_static_geom && bounce_is_default(b->bg))
-        launch_bounce_search<DefaultBounceGeom, 1, POLICY>(b, DefaultBounceGeom{}, seed, iterations, leaf_playouts, explore, cap, edges,
-                                                           d_counts, d_visits, d_best, d_nodes, d_used, d_workspace);
+        launch_bounce_search<DefaultBounceGeom, 1, POLICY, FOREST>(b, DefaultBounceGeom{}, a);
     else if (b->bg.w <= 8)
-        launch_bounce_search<BounceGeom, 1, POLICY>(b, b->bg, seed, iterations, leaf_playouts, explore, cap, edges, d_counts, d_visits,
-                                                    d_best, d_nodes, d_used, d_workspace);
+        launch_bounce_search<BounceGeom, 1, POLICY, FOREST>(b, b->bg, a);
     else
-        launch_bounce_search<BounceGeom, 3, POLICY>(b, b->bg, seed, iterations, leaf_playouts, explore, cap, edges, d_counts, d_visits,
-                                                    d_best, d_nodes, d_used, d_workspace);
+        launch_bounce_search<BounceGeom, 3, POLICY, FOREST>(b, b->bg, a);
+}
+
+template <bool FOREST>
+static void bounce_search_any(const bgs_batch* b, int policy, BounceSearchArgs a) {
+    if (a.max_plies > kBounceMaxPlies) a.max_plies = kBounceMaxPlies;   // plies are stored as uint16
+    if (policy == BGS_POLICY_DECISIVE)
+        bounce_search_policy<BGS_POLICY_DECISIVE, FOREST>(b, a);
+    else
+        bounce_search_policy<BGS_POLICY_UNIFORM, FOREST>(b, a);
 }
 
 void bounce_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
                    int policy, int32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
                    void* d_workspace) {
-    uint32_t cap = (uint32_t)max_plies;
-    if (cap > kBounceMaxPlies) cap = kBounceMaxPlies;   // plies are stored as uint16
-    const uint32_t t = (uint32_t)iterations, p = (uint32_t)leaf_playouts, e = (uint32_t)explore, pool = (uint32_t)edges;
-    if (policy == BGS_POLICY_DECISIVE)
-        bounce_search_policy<BGS_POLICY_DECISIVE>(b, seed, t, p, e, cap, pool, d_counts, d_visits, d_best, d_nodes, d_used, d_workspace);
-    else
-        bounce_search_policy<BGS_POLICY_UNIFORM>(b, seed, t, p, e, cap, pool, d_counts, d_visits, d_best, d_nodes, d_used, d_workspace);
+    bounce_search_any<false>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore, (uint32_t)max_plies,
+                                         (uint32_t)iterations + 1u, (uint32_t)edges, 1u, d_counts, d_visits, d_best, d_nodes, d_used,
+                                         nullptr, d_workspace});
 }
 
 uint64_t bounce_forest_tree_bytes(int32_t capacity, int32_t edges) {
     return bounce_forest_tree_words((uint32_t)capacity, (uint32_t)edges) * sizeof(uint32_t);
 }
 
-template <int POLICY>
-static void bounce_forest_search_policy(const bgs_batch* b, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
-                                        uint32_t cap, uint32_t capacity, uint32_t edges, uint32_t restart, int32_t* d_counts,
-                                        int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int32_t* d_carried,
-                                        void* d_forest) {
-    if (b->bounce_static_geom && bounce_is_default(b->bg))
-        launch_bounce_forest_search<DefaultBounceGeom, 1, POLICY>(b, DefaultBounceGeom{}, seed, iterations, leaf_playouts, explore, cap,
-                                                                  capacity, edges, restart, d_counts, d_visits, d_best, d_nodes, d_used,
-                                                                  d_carried, d_forest);
-    else if (b->bg.w <= 8)
-        launch_bounce_forest_search<BounceGeom, 1, POLICY>(b, b->bg, seed, iterations, leaf_playouts, explore, cap, capacity, edges, restart,
-                                                           d_counts, d_visits, d_best, d_nodes, d_used, d_carried, d_forest);
-    else
-        launch_bounce_forest_search<BounceGeom, 3, POLICY>(b, b->bg, seed, iterations, leaf_playouts, explore, cap, capacity, edges, restart,
-                                                           d_counts, d_visits, d_best, d_nodes, d_used, d_carried, d_forest);
-}
-
 void bounce_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
                           int32_t max_plies, int policy, int32_t capacity, int32_t edges, int restart, int32_t* d_counts,
                           int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int32_t* d_carried, void* d_forest) {
-    uint32_t cap = (uint32_t)max_plies;
-    if (cap > kBounceMaxPlies) cap = kBounceMaxPlies;   // plies are stored as uint16
-    const uint32_t t = (uint32_t)iterations, p = (uint32_t)leaf_playouts, e = (uint32_t)explore;
-    const uint32_t room = (uint32_t)capacity, pool = (uint32_t)edges, anew = restart ? 1u : 0u;
-    if (policy == BGS_POLICY_DECISIVE)
-        bounce_forest_search_policy<BGS_POLICY_DECISIVE>(b, seed, t, p, e, cap, room, pool, anew, d_counts, d_visits, d_best, d_nodes,
-                                                         d_used, d_carried, d_forest);
-    else
-        bounce_forest_search_policy<BGS_POLICY_UNIFORM>(b, seed, t, p, e, cap, room, pool, anew, d_counts, d_visits, d_best, d_nodes,
-                                                        d_used, d_carried, d_forest);
+    bounce_search_any<true>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore, (uint32_t)max_plies,
+                                        (uint32_t)capacity, (uint32_t)edges, restart ? 1u : 0u, d_counts, d_visits, d_best, d_nodes,
+                                        d_used, d_carried, d_forest});
 }
 
 void bounce_forest_advance(const bgs_batch* b, const int32_t* d_slots, int32_t capacity, int32_t edges, int32_t* d_kept, void* d_forest) {
@@ -3853,65 +3295,42 @@ uint64_t connect_search_root_bytes(int width, int32_t iterations) {
     return search_root_words((uint32_t)width, (uint32_t)iterations) * sizeof(uint32_t);
 }
 
-template <int NW>
-static void search_nw(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
-                      uint32_t cap, int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace) {
+template <int NW, bool FOREST>
+static void search_nw(const bgs_batch* b, const EvalGeom& g, int policy, const ConnectSearchArgs& a) {
     constexpr int U = BGS_POLICY_UNIFORM, D = BGS_POLICY_DECISIVE;
     const bool per_ply = b->rng_per_ply != 0;
     if (policy == D) {
-        per_ply ? launch_search<NW, true, D>(b, g, seed, iterations, leaf_playouts, explore, cap, d_counts, d_visits, d_best, d_nodes, d_workspace)
-                : launch_search<NW, false, D>(b, g, seed, iterations, leaf_playouts, explore, cap, d_counts, d_visits, d_best, d_nodes, d_workspace);
+        per_ply ? launch_search<NW, true, D, FOREST>(b, g, a) : launch_search<NW, false, D, FOREST>(b, g, a);
     } else {
-        per_ply ? launch_search<NW, true, U>(b, g, seed, iterations, leaf_playouts, explore, cap, d_counts, d_visits, d_best, d_nodes, d_workspace)
-                : launch_search<NW, false, U>(b, g, seed, iterations, leaf_playouts, explore, cap, d_counts, d_visits, d_best, d_nodes, d_workspace);
+        per_ply ? launch_search<NW, true, U, FOREST>(b, g, a) : launch_search<NW, false, U, FOREST>(b, g, a);
+    }
+}
+
+template <bool FOREST>
+static void search_any(const bgs_batch* b, int policy, const ConnectSearchArgs& a) {
+    const EvalGeom g = eval_geom(b);
+    switch (b->cg.nw) {
+        case 1: search_nw<1, FOREST>(b, g, policy, a); break;
+        case 2: search_nw<2, FOREST>(b, g, policy, a); break;
+        default: search_nw<3, FOREST>(b, g, policy, a); break;
     }
 }
 
 void connect_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
                     int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace) {
-    const EvalGeom g = eval_geom(b);
-    const uint32_t t = (uint32_t)iterations, p = (uint32_t)leaf_playouts, e = (uint32_t)explore, cap = (uint32_t)max_plies;
-    switch (b->cg.nw) {
-        case 1: search_nw<1>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
-        case 2: search_nw<2>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
-        default: search_nw<3>(b, g, seed, t, p, e, cap, policy, d_counts, d_visits, d_best, d_nodes, d_workspace); break;
-    }
+    search_any<false>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore, (uint32_t)max_plies,
+                                  (uint32_t)iterations + 1u, 1u, d_counts, d_visits, d_best, d_nodes, nullptr, d_workspace});
 }
 
 uint64_t connect_forest_tree_bytes(int width, int32_t capacity) {
     return forest_tree_words((uint32_t)width, (uint32_t)capacity) * sizeof(uint32_t);
 }
 
-template <int NW>
-static void forest_search_nw(const bgs_batch* b, const EvalGeom& g, uint64_t seed, uint32_t iterations, uint32_t leaf_playouts,
-                             uint32_t explore, uint32_t cap, int policy, uint32_t capacity, uint32_t restart, int32_t* d_counts,
-                             int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest) {
-    constexpr int U = BGS_POLICY_UNIFORM, D = BGS_POLICY_DECISIVE;
-    const bool per_ply = b->rng_per_ply != 0;
-    if (policy == D) {
-        per_ply ? launch_forest_search<NW, true, D>(b, g, seed, iterations, leaf_playouts, explore, cap, capacity, restart, d_counts,
-                                                    d_visits, d_best, d_nodes, d_carried, d_forest)
-                : launch_forest_search<NW, false, D>(b, g, seed, iterations, leaf_playouts, explore, cap, capacity, restart, d_counts,
-                                                     d_visits, d_best, d_nodes, d_carried, d_forest);
-    } else {
-        per_ply ? launch_forest_search<NW, true, U>(b, g, seed, iterations, leaf_playouts, explore, cap, capacity, restart, d_counts,
-                                                    d_visits, d_best, d_nodes, d_carried, d_forest)
-                : launch_forest_search<NW, false, U>(b, g, seed, iterations, leaf_playouts, explore, cap, capacity, restart, d_counts,
-                                                     d_visits, d_best, d_nodes, d_carried, d_forest);
-    }
-}
-
 void connect_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
                            int32_t max_plies, int policy, int32_t capacity, int restart, int32_t* d_counts, int32_t* d_visits,
                            int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest) {
-    const EvalGeom g = eval_geom(b);
-    const uint32_t t = (uint32_t)iterations, p = (uint32_t)leaf_playouts, e = (uint32_t)explore, cap = (uint32_t)max_plies;
-    const uint32_t room = (uint32_t)capacity, anew = restart ? 1u : 0u;
-    switch (b->cg.nw) {
-        case 1: forest_search_nw<1>(b, g, seed, t, p, e, cap, policy, room, anew, d_counts, d_visits, d_best, d_nodes, d_carried, d_forest); break;
-        case 2: forest_search_nw<2>(b, g, seed, t, p, e, cap, policy, room, anew, d_counts, d_visits, d_best, d_nodes, d_carried, d_forest); break;
-        default: forest_search_nw<3>(b, g, seed, t, p, e, cap, policy, room, anew, d_counts, d_visits, d_best, d_nodes, d_carried, d_forest); break;
-    }
+    search_any<true>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore, (uint32_t)max_plies,
+                                 (uint32_t)capacity, restart ? 1u : 0u, d_counts, d_visits, d_best, d_nodes, d_carried, d_forest});
 }
 
 void connect_forest_advance(const bgs_batch* b, const int32_t* d_columns, int32_t capacity, int32_t* d_kept, void* d_forest) {
