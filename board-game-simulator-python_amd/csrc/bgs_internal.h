@@ -141,6 +141,11 @@ void connect_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget,
 uint64_t connect_search_root_bytes(int width, int32_t iterations);
 void connect_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
                     int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace);
+// the same search with game-end facts kept on the edges (bgs_connect_search_actions_proving): d_proved int8[n][w] and
+// d_done int32[n] may be NULL as well; the workspace is connect_search's
+void connect_search_proving(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                            int32_t max_plies, int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes,
+                            int8_t* d_proved, int32_t* d_done, void* d_workspace);
 // the same search on trees that persist (bgs_connect_forest_search / bgs_connect_forest_advance): d_forest holds n *
 // connect_forest_tree_bytes(w, capacity) bytes, 256-byte aligned; d_carried int32[n] and d_kept int32[n] may be NULL;
 // d_columns int32[n] on the device; both are enqueued on the batch's stream and neither touches the boards

@@ -582,9 +582,21 @@ void launch_evaluate_halving(const bgs_batch* b, const EvalGeom& g, uint64_t see
 // plain tree has room for a node an iteration, so there the question is settled when the kernel is compiled); and the
 // header and `carried` written at the end.  The iteration -- descent, playout block, back-propagation -- is one text.
 //
+// The proving search (bgs_connect_search_actions_proving; the template parameter PROVE, the plain tree only) keeps
+// game-end facts on the edges: bits 31:30 of an edge's child word hold its tag, seen from the player to move at the node
+// (kTagOpen = 0, so a zeroed node is all OPEN and an OPEN edge's word is its child index as before).  PROVE changes five
+// things and nothing else: a lane's column is a candidate of the selection only while its tag is OPEN; an edge that
+// ends the game is tagged when it is played; the legal columns of every path node go to LDS beside the path; after an
+// iteration that tagged its last edge the tags are backed up the path (lane c reads column c's tag, ballots give the
+// node's value, lane 0 tags the parent's edge, a barrier follows every such write); and a root whose value is no longer
+// OPEN stops iterating.  A tagged edge is never descended again, so the descent never meets a child word with tag bits.
+//
 // Known limit: a root has one wave, so a launch of few roots uses few CUs, and leaf_playouts < 64 leaves lanes idle
 // (DESIGN.md §9).
 // ================================================================================================================
+constexpr uint32_t kTagOpen = 0u, kTagWin = 1u, kTagDraw = 2u, kTagLoss = 3u;   // bits 31:30 of a child word
+constexpr uint32_t kTagShift = 30u;
+static_assert(((uint64_t)1 << 29) + 1u < ((uint64_t)1 << kTagShift), "a child index (at most T <= 2^29, plus the root) stays below the tag bits");
 constexpr uint32_t kSearchMaxPath = 64 * BGS_CONNECT_MAX_WORDS;   // a descent drops at most h * w stones
 constexpr uint32_t kForestHeaderWords = 16;
 
@@ -622,15 +634,18 @@ __host__ __device__ __forceinline__ uint32_t search_lg(uint32_t total) {
 }
 
 // (the plain launch passes capacity = iterations + 1, restart = 1 and carried = nullptr; its instantiation reads none of them)
-template <int NW, bool PER_PLY, int POLICY, bool FOREST>
+template <int NW, bool PER_PLY, int POLICY, bool FOREST, bool PROVE = false>
 __global__ void __launch_bounds__(BGS_WAVE)
 k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n, uint64_t seed,
                  uint64_t game_base, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore, uint32_t max_plies,
                  int64_t root_base, uint32_t capacity, uint32_t restart, uint32_t* trees, int32_t* __restrict__ counts,
                  int32_t* __restrict__ visits, int32_t* __restrict__ best, int32_t* __restrict__ nodes,
-                 int32_t* __restrict__ carried, unsigned long long* __restrict__ steps) {
+                 int32_t* __restrict__ carried, unsigned long long* __restrict__ steps, int8_t* __restrict__ proved = nullptr,
+                 int32_t* __restrict__ done = nullptr) {
+    static_assert(!(PROVE && FOREST), "the forest does not prove");
     __shared__ uint32_t path_node[kSearchMaxPath];   // the descent: edge k leaves node path_node[k] by column path_col[k]
     __shared__ uint32_t path_col[kSearchMaxPath];
+    __shared__ uint32_t path_legal[PROVE ? kSearchMaxPath : 1u];   // PROVE: the legal columns of path_node[k], a bit a column
     __shared__ uint32_t tally[3];                    // W/D/L of the iteration's playouts, for the root's mover
     __shared__ unsigned long long step_sum;
     const uint32_t lane = threadIdx.x;
@@ -705,7 +720,13 @@ k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t*
 #pragma unroll
     for (int j = 0; j < 4; ++j) ph.v[j] = 0;
 
+    [[maybe_unused]] uint32_t ran = 0;            // PROVE (uniform): the iterations run, and whether the root's value is proved
+    [[maybe_unused]] bool decided = false;
     for (uint32_t t = 0; running && t < iterations; ++t) {
+        if constexpr (PROVE) {
+            if (decided) break;
+            ran = t + 1u;
+        }
         // ---- descent (wave-uniform): p is the position at node v
         Bits<NW> p[2] = {r0, r1};
         uint32_t ply = rply, v = 0, depth = 0, leaf = BGS_ST_RUNNING, col0 = 0;
@@ -713,13 +734,19 @@ k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t*
             const Bits<NW> occ = p[0] | p[1];
             uint32_t height = (uint32_t)g.h();
             if (lane < width) height = (uint32_t)__popcll(shr(occ, (int)(lane * stride)).w[0] & ((1ull << g.h()) - 1ull));
-            const bool legal = height < (uint32_t)g.h();
+            bool legal = height < (uint32_t)g.h();
             uint32_t* const node = tree + (uint64_t)v * node_words;
             uint32_t nc = 0, sc = 0, ch = 0;
             if (legal) {
                 nc = node[lane];
                 sc = node[width + lane];
                 ch = node[2u * width + lane];
+            }
+            if constexpr (PROVE) {                                     // the candidates: legal and OPEN (nc counts in N for those alone)
+                const uint32_t legal_columns = (uint32_t)__builtin_amdgcn_ballot_w64(legal);
+                if (lane == 0) path_legal[depth] = legal_columns;
+                legal = legal && (ch >> kTagShift) == kTagOpen;
+                nc = legal ? nc : 0u;
             }
             const uint64_t unvisited = __builtin_amdgcn_ballot_w64(legal && nc == 0u);
             uint32_t col;
@@ -755,6 +782,9 @@ k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t*
             depth += 1u;
             leaf = won ? mover + 1u : (ply == g.cells_total ? (uint32_t)BGS_ST_DRAW : (uint32_t)BGS_ST_RUNNING);
             leaf = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf);
+            if constexpr (PROVE) {                                     // an edge that ends the game is a fact (it had no child: ch = 0)
+                if (leaf != BGS_ST_RUNNING && lane == col) node[2u * width + lane] = (won ? kTagWin : kTagDraw) << kTagShift;
+            }
             if (leaf != BGS_ST_RUNNING) break;                         // a terminal edge: no node, no game
             if (child == 0u) {                                         // no node for p' yet: one is made if it fits
                 bool fits = true;                                      // (the plain tree has iterations + 1 nodes: room for every iteration's)
@@ -863,6 +893,29 @@ k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t*
             cd += td;
             cl += tl;
         }
+        if constexpr (PROVE) {
+            // ---- the tags go up the path (wave-uniform), while the node at hand has a value: lane c reads column c's tag
+            // (the last edge's was written during the descent, barriers ago; an upper one by lane 0, a barrier ago)
+            if (leaf != BGS_ST_RUNNING) {
+                for (uint32_t k = depth; k-- > 0u;) {
+                    const uint32_t* const node = tree + (uint64_t)path_node[k] * node_words;
+                    const bool legal = lane < width && ((path_legal[k] >> lane) & 1u) != 0u;
+                    const uint32_t tag = legal ? node[2u * width + lane] >> kTagShift : kTagLoss;
+                    const bool wins_here = __builtin_amdgcn_ballot_w64(legal && tag == kTagWin) != 0;
+                    const bool open_here = __builtin_amdgcn_ballot_w64(legal && tag == kTagOpen) != 0;
+                    const bool draw_here = __builtin_amdgcn_ballot_w64(legal && tag == kTagDraw) != 0;
+                    if (!wins_here && open_here) break;                // the value is OPEN: nothing is known further up
+                    if (k == 0u) {
+                        decided = true;
+                        break;
+                    }
+                    // the parent's edge, seen from the parent's mover: a won node is a lost move, a lost node a winning one
+                    const uint32_t up = wins_here ? kTagLoss : (draw_here ? kTagDraw : kTagWin);
+                    if (lane == 0) tree[(uint64_t)path_node[k - 1u] * node_words + 2u * width + path_col[k - 1u]] |= up << kTagShift;
+                    __syncthreads();
+                }
+            }
+        }
         __syncthreads();            // the tree is whole again before the next descent reads it; tally and path are free
     }
 
@@ -878,6 +931,22 @@ k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t*
         counts[(i * (int64_t)width + lane) * 3 + 2] = (int32_t)cl;
         if (visits) visits[i * (int64_t)width + lane] = (int32_t)nv;
     }
+    // PROVE: the root's tags; `among` = the columns `best` is taken over (those not proved lost, or all when all are)
+    [[maybe_unused]] uint64_t among = ~0ull, won_columns = 0;
+    if constexpr (PROVE) {
+        uint32_t height = (uint32_t)g.h();
+        if (lane < width) height = (uint32_t)__popcll(shr(r0 | r1, (int)(lane * stride)).w[0] & ((1ull << g.h()) - 1ull));
+        const bool legal = running && height < (uint32_t)g.h();
+        const uint32_t tag = legal ? tree[2u * width + lane] >> kTagShift : kTagOpen;
+        if (lane < width && proved) {
+            const int code = tag == kTagWin ? BGS_SOLVE_WIN : (tag == kTagDraw ? BGS_SOLVE_DRAW : (tag == kTagLoss ? BGS_SOLVE_LOSS : BGS_SOLVE_UNKNOWN));
+            proved[i * (int64_t)width + lane] = (int8_t)(legal ? code : BGS_SOLVE_NONE);
+        }
+        if (lane == 0 && done) done[i] = (int32_t)ran;
+        won_columns = __builtin_amdgcn_ballot_w64(legal && tag == kTagWin);
+        among = __builtin_amdgcn_ballot_w64(legal && tag != kTagLoss);
+        among = among ? among : ~0ull;
+    }
     if (best) {
         // the most visits, then the larger 2 * wins + draws, then the lower column; an illegal column has no visits
         int32_t top = -1;
@@ -885,11 +954,17 @@ k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t*
         for (uint32_t c = 0; running && c < width; ++c) {
             const uint32_t cn = (uint32_t)__builtin_amdgcn_readlane((int)nv, (int)c);
             const uint32_t cs = (uint32_t)__builtin_amdgcn_readlane((int)sv, (int)c);
+            if constexpr (PROVE) {
+                if (!((among >> c) & 1ull)) continue;
+            }
             if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
                 top = (int32_t)c;
                 top_n = cn;
                 top_s = cs;
             }
+        }
+        if constexpr (PROVE) {      // a proved win is the move (there is one at most: the search stopped at the first)
+            if (won_columns) top = (int32_t)__builtin_ctzll(won_columns);
         }
         if (lane == 0) best[i] = top;
     }
@@ -913,19 +988,21 @@ struct ConnectSearchArgs {
     int32_t *counts, *visits, *best, *nodes;
     int32_t* carried;                       // the plain search: nullptr
     void* trees;                            // the workspace, or the forest
+    int8_t* proved = nullptr;               // the proving search alone: the root's tags and the iterations run
+    int32_t* done = nullptr;
 };
 
-template <int NW, bool PER_PLY, int POLICY, bool FOREST>
+template <int NW, bool PER_PLY, int POLICY, bool FOREST, bool PROVE = false>
 void launch_search(const bgs_batch* b, const EvalGeom& g, const ConnectSearchArgs& a) {
     // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
     const uint64_t game_base = b->first_game * (uint64_t)a.iterations * (uint64_t)a.leaf_playouts;
     constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
     for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
         const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
-        hipLaunchKernelGGL((k_connect_search<NW, PER_PLY, POLICY, FOREST>), dim3((uint32_t)blocks), dim3(BGS_WAVE), 0, b->stream, g,
-                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, a.seed, game_base, a.iterations,
+        hipLaunchKernelGGL((k_connect_search<NW, PER_PLY, POLICY, FOREST, PROVE>), dim3((uint32_t)blocks), dim3(BGS_WAVE), 0, b->stream,
+                           g, (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, a.seed, game_base, a.iterations,
                            a.leaf_playouts, a.explore, a.max_plies, i0, a.capacity, a.restart, static_cast<uint32_t*>(a.trees),
-                           a.counts, a.visits, a.best, a.nodes, a.carried, b->d_steps);
+                           a.counts, a.visits, a.best, a.nodes, a.carried, b->d_steps, a.proved, a.done);
     }
 }
 
@@ -3295,24 +3372,24 @@ uint64_t connect_search_root_bytes(int width, int32_t iterations) {
     return search_root_words((uint32_t)width, (uint32_t)iterations) * sizeof(uint32_t);
 }
 
-template <int NW, bool FOREST>
+template <int NW, bool FOREST, bool PROVE = false>
 static void search_nw(const bgs_batch* b, const EvalGeom& g, int policy, const ConnectSearchArgs& a) {
     constexpr int U = BGS_POLICY_UNIFORM, D = BGS_POLICY_DECISIVE;
     const bool per_ply = b->rng_per_ply != 0;
     if (policy == D) {
-        per_ply ? launch_search<NW, true, D, FOREST>(b, g, a) : launch_search<NW, false, D, FOREST>(b, g, a);
+        per_ply ? launch_search<NW, true, D, FOREST, PROVE>(b, g, a) : launch_search<NW, false, D, FOREST, PROVE>(b, g, a);
     } else {
-        per_ply ? launch_search<NW, true, U, FOREST>(b, g, a) : launch_search<NW, false, U, FOREST>(b, g, a);
+        per_ply ? launch_search<NW, true, U, FOREST, PROVE>(b, g, a) : launch_search<NW, false, U, FOREST, PROVE>(b, g, a);
     }
 }
 
-template <bool FOREST>
+template <bool FOREST, bool PROVE = false>
 static void search_any(const bgs_batch* b, int policy, const ConnectSearchArgs& a) {
     const EvalGeom g = eval_geom(b);
     switch (b->cg.nw) {
-        case 1: search_nw<1, FOREST>(b, g, policy, a); break;
-        case 2: search_nw<2, FOREST>(b, g, policy, a); break;
-        default: search_nw<3, FOREST>(b, g, policy, a); break;
+        case 1: search_nw<1, FOREST, PROVE>(b, g, policy, a); break;
+        case 2: search_nw<2, FOREST, PROVE>(b, g, policy, a); break;
+        default: search_nw<3, FOREST, PROVE>(b, g, policy, a); break;
     }
 }
 
@@ -3320,6 +3397,14 @@ void connect_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32
                     int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, void* d_workspace) {
     search_any<false>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore, (uint32_t)max_plies,
                                   (uint32_t)iterations + 1u, 1u, d_counts, d_visits, d_best, d_nodes, nullptr, d_workspace});
+}
+
+void connect_search_proving(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                            int32_t max_plies, int policy, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes,
+                            int8_t* d_proved, int32_t* d_done, void* d_workspace) {
+    search_any<false, true>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore, (uint32_t)max_plies,
+                                        (uint32_t)iterations + 1u, 1u, d_counts, d_visits, d_best, d_nodes, nullptr, d_workspace,
+                                        d_proved, d_done});
 }
 
 uint64_t connect_forest_tree_bytes(int width, int32_t capacity) {

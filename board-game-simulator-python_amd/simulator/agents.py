@@ -256,12 +256,22 @@ class TreeSearchAgent:
     the nodes every tree started with -- as a fifth element.  ``capacity`` is the room of a tree in nodes; None:
     ``2 * iterations + 1``, the nodes one search can make plus as many carried ones.  That is an allowance and not a
     measurement: a tree that is full stops growing until the next advance frees room.  Without ``reuse`` the agent is
-    what it was, code path included."""
+    what it was, code path included.
+
+    ``prove=True`` searches with ``ConnectBatch.search_actions_proving``: game-end facts are kept on the edges and backed
+    up by minimax, a root whose value is proved stops iterating, and ``search`` returns (counts, visits, best, nodes,
+    proved, done).  ``choose`` follows that launch's ``best`` (a proved win, else the most visited column among those not
+    proved lost).  ``predict`` gives a proved win 1.0 and every other column 0; otherwise the columns proved lost get 0
+    and the rest are renormalised, and where every column is proved lost the shares are what the visits give.  The forest
+    does not prove yet: ``prove=True`` with ``reuse=True`` raises ValueError.  Without ``prove`` the code path is what it
+    was."""
 
     def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
-                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, reuse: bool = False,
-                 capacity: Optional[int] = None):
+                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, prove: bool = False,
+                 reuse: bool = False, capacity: Optional[int] = None):
         playout_policy(policy)
+        if prove and reuse:
+            raise ValueError("prove=True with reuse=True: the forest does not prove yet")
         if iterations < 1 or leaf_playouts < 1:
             raise ValueError("iterations and leaf_playouts must be >= 1")
         if not 0 <= explore <= 1 << 18:
@@ -270,6 +280,7 @@ class TreeSearchAgent:
             raise ValueError("max_plies must be >= 1")
         if capacity is not None and capacity < 2:
             raise ValueError("capacity must be >= 2")
+        self.prove = bool(prove)
         self.reuse = bool(reuse)
         self.capacity = 2 * int(iterations) + 1 if capacity is None else int(capacity)
         self._forests: Dict[tuple, list] = {}   # key -> [SearchForest, grids last searched, their movers, searches so far]
@@ -284,7 +295,7 @@ class TreeSearchAgent:
 
     def search(self, states: Sequence, first_game: int = 0):
         """(counts, visits, best, nodes) of the launch over `states` (Connect states that share one Config); with `reuse`
-        (counts, visits, best, nodes, carried)"""
+        (counts, visits, best, nodes, carried), with `prove` (counts, visits, best, nodes, proved, done)"""
         if isinstance(states[0], bounce.State):
             raise ValueError("TreeSearchAgent: Connect states only; the tree search does not cover Bounce")
         if not isinstance(states[0], connect.State):
@@ -305,6 +316,9 @@ class TreeSearchAgent:
         cap = 2**31 - 1 if self.max_plies is None else self.max_plies
         if self.reuse:
             return self._search_on(key, b, grid, player, cap)
+        if self.prove:
+            return b.search_actions_proving(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts,
+                                            explore=self.explore, max_plies=cap, policy=self.policy)
         return b.search_actions(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore,
                                 max_plies=cap, policy=self.policy)
 
@@ -346,11 +360,28 @@ class TreeSearchAgent:
         """`predict` of every state, searched in one launch"""
         if not states:
             return []
+        if self.prove:
+            return self._predict_proved(states, first_game)
         visits = self.search(states, first_game)[1]
         if self.reuse:      # the root's visits include the carried ones
             return [{a: float(visits[k, a.column]) / int(visits[k].sum()) for a in s.actions} for k, s in enumerate(states)]
         total = self.iterations * self.leaf_playouts
         return [{a: float(visits[k, a.column]) / total for a in s.actions} for k, s in enumerate(states)]
+
+    def _predict_proved(self, states: Sequence, first_game: int) -> List[Dict]:
+        """`predict_many` of `prove`: a proved win takes everything, columns proved lost nothing (unless all are)"""
+        _, visits, _, _, proved, _ = self.search(states, first_game)
+        out = []
+        for k, s in enumerate(states):
+            columns = [a.column for a in s.actions]
+            share = {c: float(visits[k, c]) for c in columns}
+            if any(proved[k, c] == SOLVE_WIN for c in columns):
+                share = {c: 1.0 if proved[k, c] == SOLVE_WIN else 0.0 for c in columns}
+            elif any(proved[k, c] != SOLVE_LOSS for c in columns):
+                share = {c: 0.0 if proved[k, c] == SOLVE_LOSS else share[c] for c in columns}
+            total = sum(share.values())
+            out.append({a: share[a.column] / total for a in s.actions})
+        return out
 
     def predict(self, state, game: int = 0) -> Dict:
         """{action: share of the visits} for every action in ``state.actions`` (the keys are those Action objects)"""

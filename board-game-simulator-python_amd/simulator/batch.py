@@ -946,6 +946,66 @@ class ConnectBatch(_Batch):
             ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
         return outs["counts"], outs["visits"], outs["best"], outs["nodes"]
 
+    def search_actions_proving(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
+                               explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1, policy: str = "uniform"):
+        """`search_actions` that keeps the game-end facts it meets (bgs_connect_search_actions_proving; MCTS-Solver), one
+        launch: (counts, visits, best, nodes, proved int8[n, width], done int32[n]).  An edge that ends the game is tagged
+        a win or a draw, the tags are backed up by minimax beside the averages, a tagged edge is never descended again,
+        and a root whose value is proved stops iterating.  `proved` holds the root's tags in the solver's codes:
+        SOLVE_WIN / SOLVE_DRAW / SOLVE_LOSS for a proved column, SOLVE_UNKNOWN for a legal column still open, SOLVE_NONE
+        for an illegal column or an ended board.  `done` is the number of iterations run (`iterations` for a root left
+        undecided, 0 for an ended board).  `best` is the proved win if there is one, else the most visited column among
+        those not proved lost.  A root whose search tags nothing returns what `search_actions` returns.  The workspace is
+        `search_actions`'s."""
+        code = playout_policy(policy)
+        counts = np.empty((self.n, self.width, 3), dtype=np.int32)
+        visits = np.empty((self.n, self.width), dtype=np.int32)
+        best = np.empty(self.n, dtype=np.int32)
+        nodes = np.empty(self.n, dtype=np.int32)
+        proved = np.empty((self.n, self.width), dtype=np.int8)
+        done = np.empty(self.n, dtype=np.int32)
+        _abi.check(_abi.lib().bgs_connect_search_actions_proving(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
+            ctypes.c_int32(max_plies), code, ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(visits.ctypes.data),
+            ctypes.c_void_p(best.ctypes.data), ctypes.c_void_p(nodes.ctypes.data), ctypes.c_void_p(proved.ctypes.data),
+            ctypes.c_void_p(done.ctypes.data), None, 0, 0))
+        return counts, visits, best, nodes, proved, done
+
+    def search_actions_proving_tensor(self, counts=None, visits=None, best=None, nodes=None, proved=None, done=None,
+                                      seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
+                                      explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1, policy: str = "uniform",
+                                      workspace=None):
+        """`search_actions_proving` into device tensors (allocated when None; `proved` is int8[n, width], the others int32
+        as in `search_actions_tensor`), enqueued on the batch's stream with no synchronisation: (counts, visits, best,
+        nodes, proved, done).  Every entry is written.  `workspace` is `search_actions_tensor`'s, and the batch's own
+        cached workspace serves both."""
+        code = playout_policy(policy)
+        t = self._need_torch("search_actions_proving_tensor")
+        shapes = {"counts": (self.n, self.width, 3), "visits": (self.n, self.width), "best": (self.n,), "nodes": (self.n,),
+                  "proved": (self.n, self.width), "done": (self.n,)}
+        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "proved": proved, "done": done}
+        for name, shape in shapes.items():
+            dtype = t.int8 if name == "proved" else t.int32
+            x = outs[name]
+            if x is None:
+                x = outs[name] = t.empty(shape, dtype=dtype, device=f"cuda:{self.device}")
+            if not (x.is_cuda and x.dtype == dtype and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned {str(dtype).split('.')[-1]} device tensor of shape {shape}")
+        if workspace is None:
+            need = self.search_workspace_bytes(iterations)     # (refuses iterations < 1 before anything is allocated)
+            workspace = self._search_workspaces.get(int(iterations))
+            if workspace is None:
+                workspace = self._search_workspaces[int(iterations)] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
+        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        _abi.check(_abi.lib().bgs_connect_search_actions_proving(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
+            ctypes.c_int32(max_plies), code, ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["visits"].data_ptr()),
+            ctypes.c_void_p(outs["best"].data_ptr()), ctypes.c_void_p(outs["nodes"].data_ptr()),
+            ctypes.c_void_p(outs["proved"].data_ptr()), ctypes.c_void_p(outs["done"].data_ptr()),
+            ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
+        return outs["counts"], outs["visits"], outs["best"], outs["nodes"], outs["proved"], outs["done"]
+
     def forest_bytes(self, capacity: int) -> int:
         """bytes of device memory a forest of this batch takes at `capacity` nodes a tree (bgs_connect_forest_bytes)"""
         nbytes = ctypes.c_size_t()
@@ -1205,6 +1265,12 @@ class BounceBatch(_Batch):
         raise ValueError("search_actions: Connect batches only (Bounce boards: evaluate_moves_halving)")
 
     search_actions_tensor = search_workspace_bytes = search_actions
+
+    def search_actions_proving(self, *args, **kwargs):
+        """Not available for Bounce: the proving tree search covers bit-packed Connect boards; Bounce has `search_moves`."""
+        raise ValueError("search_actions_proving: Connect batches only (Bounce boards: search_moves)")
+
+    search_actions_proving_tensor = search_actions_proving
 
     def search_forest(self, *args, **kwargs):
         """Not available for Bounce: trees that persist between searches cover bit-packed Connect boards."""

@@ -218,6 +218,12 @@ SIGNATURES = {
         [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int],
     ),
+    "bgs_connect_search_actions_proving": (
+        ctypes.c_int,
+        [c_handle, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+         ctypes.c_int],
+    ),
     "bgs_connect_forest_bytes": (ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]),
     "bgs_connect_forest_search": (
         ctypes.c_int,

@@ -271,6 +271,43 @@ BGS_API int bgs_connect_search_workspace_bytes(const bgs_batch* b, int32_t itera
 BGS_API int bgs_connect_search_actions(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
                                        int32_t max_plies, int policy, int32_t* counts, int32_t* visits, int32_t* best,
                                        int32_t* nodes, void* workspace, size_t workspace_bytes, int on_device);
+/* The same search, proving wins, draws and losses in its tree (MCTS-Solver: Winands, Bjornsson and Saito 2008; Connect,
+ * bit-packed boards only), one launch.  What stays as in bgs_connect_search_actions: the workspace and its size
+ * (bgs_connect_search_workspace_bytes serves both entry points), the argument checks and refusals, the on_device rules,
+ * the game ids G = ((first_game + i) * T + t) * P + j with the T that was asked for, the RNG contracts, the policies,
+ * bgs_steps, and sharding by first_game.  proved and done may be NULL, like visits, best and nodes.
+ * Tags.  Every edge (v, c) has a tag, seen from the player to move at v: OPEN (the initial state), WIN, DRAW or LOSS.
+ * The value of a node is WIN if a legal column is tagged WIN; otherwise OPEN if a legal column is OPEN (a legal column
+ * that has never been visited is OPEN); otherwise DRAW if a legal column is tagged DRAW; otherwise LOSS.
+ * Iteration t (t = 0 .. T-1):
+ *   0. if the root's value is not OPEN, this root's search is over: done[i] = t, and the remaining iterations and their
+ *      game ids are not used;
+ *   1.-3. the selection of bgs_connect_search_actions, word for word, with L read as "the legal columns of p whose tag
+ *      is OPEN, ascending"; N is the sum of n[c] over those columns.  A node the descent stands on always has such a
+ *      column: that is the invariant of step 7;
+ *   4. as there.  In addition, an edge that ends the game is tagged WIN if c won and DRAW if c filled the board; all P
+ *      playouts of the iteration still carry that outcome.  A position at or beyond max_plies is not an end and tags
+ *      nothing;
+ *   5.-6. as there;
+ *   7. only after an iteration whose last edge was tagged in step 4: go up the path, for k = depth-1 down to 0 (edge k
+ *      leaves path_node[k]).  If the value of path_node[k] is OPEN, stop.  If k = 0, the root is decided.  Otherwise
+ *      edge k-1 of the path is tagged with the negation of that value: a WIN node makes its parent's edge LOSS, a LOSS
+ *      node makes it WIN, DRAW stays DRAW.  A decided node is therefore never entered again.
+ * Outputs.  counts, visits and nodes mean what they mean there.  proved int8[n][width] (may be NULL) = the root's tags in
+ * the solver's codes: BGS_SOLVE_WIN, BGS_SOLVE_DRAW or BGS_SOLVE_LOSS for a tagged column, BGS_SOLVE_UNKNOWN for a legal
+ * OPEN column, BGS_SOLVE_NONE for an illegal column or an ended board.  done int32[n] (may be NULL) = the iterations
+ * run: T for an undecided root, 0 for an ended board.  best: if a root column is tagged WIN, that column (there is at
+ * most one: the search stops at the first); otherwise the rule of bgs_connect_search_actions (the most visits, then the
+ * larger s, then the lower column) over the legal columns not tagged LOSS; if every legal column is tagged LOSS, that
+ * rule over all legal columns.
+ * Equal to the plain search.  While no edge of a root's tree has been tagged, that root's state is the plain search's,
+ * bit for bit: a root whose search tags nothing returns the outputs of bgs_connect_search_actions, and done = T.
+ * Known weakness: a column proved DRAW stops collecting visits, so an undecided root can prefer an OPEN column whose Q
+ * is below a draw's.  The forest (bgs_connect_forest_search) and Bounce do not prove. */
+BGS_API int bgs_connect_search_actions_proving(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts,
+                                               int32_t explore, int32_t max_plies, int policy, int32_t* counts,
+                                               int32_t* visits, int32_t* best, int32_t* nodes, int8_t* proved, int32_t* done,
+                                               void* workspace, size_t workspace_bytes, int on_device);
 /* The same search on trees that outlive a launch (Connect, bit-packed boards only): a FOREST is caller-owned device
  * memory that holds one tree per board of the batch, each with room for `capacity` (C) nodes, the root included, and
  * persists from launch to launch.  An agent that plays a game searches, plays, advances the trees by the columns played
