@@ -1477,17 +1477,30 @@ int bgs_bounce_search_workspace_bytes(const bgs_batch* b, int32_t iterations, in
     return bounce_search_check(b, iterations, edges, bytes);
 }
 
-int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
-                            int policy, int32_t edges, int32_t* counts, int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used,
-                            void* workspace, size_t workspace_bytes, int on_device) {
+// bgs_bounce_search_moves and bgs_bounce_search_moves_proving: the same checks, workspace and buffer plan; `entry` names
+// the caller in the messages, and the plain entry point has neither proved nor done
+static int bounce_search_entry(const char* entry, bool proving, bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts,
+                               int32_t explore, int32_t max_plies, int policy, int32_t edges, int32_t* counts, int32_t* visits,
+                               int32_t* best, int32_t* nodes, int32_t* used, int8_t* proved, int32_t* done, void* workspace,
+                               size_t workspace_bytes, int on_device) {
     int rc = enter(b);
     if (rc) return rc;
     NEED(counts != nullptr, "counts is NULL");
     size_t need = 0;
     rc = bounce_search_check(b, iterations, edges, &need);
     if (rc) return rc;
-    rc = search_params_check("search_moves", b, iterations, leaf_playouts, explore, max_plies, policy);
+    rc = search_params_check(entry, b, iterations, leaf_playouts, explore, max_plies, policy);
     if (rc) return rc;
+    const auto launch = [&](int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int8_t* d_proved,
+                            int32_t* d_done, void* d_workspace) {
+        if (proving) {
+            bgs::bounce_search_proving(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, d_counts, d_visits, d_best,
+                                       d_nodes, d_used, d_proved, d_done, d_workspace);
+        } else {
+            bgs::bounce_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, d_counts, d_visits, d_best, d_nodes,
+                               d_used, d_workspace);
+        }
+    };
     const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;
     if (on_device) {
         NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
@@ -1495,42 +1508,63 @@ int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterations, int
         NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
         NEED((reinterpret_cast<uintptr_t>(nodes) & 15u) == 0, "device nodes must be 16-byte aligned");
         NEED((reinterpret_cast<uintptr_t>(used) & 15u) == 0, "device used must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(proved) & 15u) == 0, "device proved must be 16-byte aligned");
+        NEED((reinterpret_cast<uintptr_t>(done) & 15u) == 0, "device done must be 16-byte aligned");
         NEED(workspace != nullptr, "workspace is NULL (on_device: the caller owns it; bgs_bounce_search_workspace_bytes says how large)");
         NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
         NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
-        bgs::bounce_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, counts, visits, best, nodes, used,
-                           workspace);
+        launch(counts, visits, best, nodes, used, proved, done, workspace);
         return finish_launch();
     }
     if (workspace != nullptr) {
         NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
         NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
     }
-    // one device buffer: counts, visits, best, nodes, used -- each 16-byte aligned -- and the workspace when the caller gave none
+    // one device buffer: counts, visits, best, nodes, used (proving: and done, proved) -- each 16-byte aligned -- and the
+    // workspace when the caller gave none
     const auto up = [](size_t x, size_t a) { return (x + a - 1) & ~(a - 1); };
     const size_t counts_bytes = cells * 3 * sizeof(int32_t), visits_bytes = cells * sizeof(int32_t), board_bytes = (size_t)b->n * sizeof(int32_t);
+    const size_t proved_bytes = cells * sizeof(int8_t);
     const size_t visits_off = up(counts_bytes, 16), best_off = visits_off + up(visits_bytes, 16), nodes_off = best_off + up(board_bytes, 16);
     const size_t used_off = nodes_off + up(board_bytes, 16);
+    const size_t done_off = used_off + up(board_bytes, 16), proved_off = done_off + up(board_bytes, 16);
+    const size_t outputs_end = proving ? proved_off + proved_bytes : used_off + board_bytes;
     // the library's own workspace starts at the first 256-byte boundary behind the outputs, wherever the pool put `d`
     const size_t tree_room = workspace ? 0 : need + 256;
     uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), used_off + board_bytes + tree_room, b->stream));
-    uint8_t* const own = reinterpret_cast<uint8_t*>(up(reinterpret_cast<uintptr_t>(d + used_off + board_bytes), 256));
-    bgs::bounce_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, reinterpret_cast<int32_t*>(d),
-                       visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
-                       best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr,
-                       nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr,
-                       used ? reinterpret_cast<int32_t*>(d + used_off) : nullptr, workspace ? workspace : own);
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), outputs_end + tree_room, b->stream));
+    uint8_t* const own = reinterpret_cast<uint8_t*>(up(reinterpret_cast<uintptr_t>(d + outputs_end), 256));
+    launch(reinterpret_cast<int32_t*>(d), visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
+           best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr, nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr,
+           used ? reinterpret_cast<int32_t*>(d + used_off) : nullptr, proved ? reinterpret_cast<int8_t*>(d + proved_off) : nullptr,
+           done ? reinterpret_cast<int32_t*>(d + done_off) : nullptr, workspace ? workspace : own);
     rc = finish_launch();
     if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
     if (rc == BGS_OK && visits) rc = copy_to_host(b, visits, d + visits_off, visits_bytes);
     if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, board_bytes);
     if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d + nodes_off, board_bytes);
     if (rc == BGS_OK && used) rc = copy_to_host(b, used, d + used_off, board_bytes);
+    if (rc == BGS_OK && proved) rc = copy_to_host(b, proved, d + proved_off, proved_bytes);
+    if (rc == BGS_OK && done) rc = copy_to_host(b, done, d + done_off, board_bytes);
     const hipError_t e = hipFreeAsync(d, b->stream);
     if (rc) return rc;
     HIP_TRY(e);
     return BGS_OK;
+}
+
+int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
+                            int policy, int32_t edges, int32_t* counts, int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used,
+                            void* workspace, size_t workspace_bytes, int on_device) {
+    return bounce_search_entry("search_moves", false, b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, counts, visits,
+                               best, nodes, used, nullptr, nullptr, workspace, workspace_bytes, on_device);
+}
+
+int bgs_bounce_search_moves_proving(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                                    int32_t max_plies, int policy, int32_t edges, int32_t* counts, int32_t* visits, int32_t* best,
+                                    int32_t* nodes, int32_t* used, int8_t* proved, int32_t* done, void* workspace,
+                                    size_t workspace_bytes, int on_device) {
+    return bounce_search_entry("search_moves_proving", true, b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, counts,
+                               visits, best, nodes, used, proved, done, workspace, workspace_bytes, on_device);
 }
 
 // the checks of the three Bounce forest entry points that need no device; *bytes: the forest of the batch

@@ -177,6 +177,11 @@ uint64_t bounce_search_root_bytes(int32_t iterations, int32_t edges);
 void bounce_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
                    int policy, int32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
                    void* d_workspace);
+// the same search with game-end facts kept on the edges (bgs_bounce_search_moves_proving): d_proved int8[n][w][h * w]
+// (filled with BGS_SOLVE_NONE here) and d_done int32[n] may be NULL as well; the workspace is bounce_search's
+void bounce_search_proving(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                           int32_t max_plies, int policy, int32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best,
+                           int32_t* d_nodes, int32_t* d_used, int8_t* d_proved, int32_t* d_done, void* d_workspace);
 // the same search on trees that persist (bgs_bounce_forest_search / bgs_bounce_forest_advance): d_forest holds n *
 // bounce_forest_tree_bytes(capacity, edges) bytes, 256-byte aligned; all outputs but d_counts may be NULL; d_slots int32[n]
 // on the device; both are enqueued on the batch's stream and neither touches the boards

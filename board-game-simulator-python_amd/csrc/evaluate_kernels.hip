@@ -21,6 +21,8 @@
 // takes.  W/D/L are counted in registers, flushed to the wave's LDS tally when the lane moves to the next segment, and
 // the wave writes its segments once at the end (sliced segments: one integer atomic per wave and counter into counts the
 // launcher zeroed).
+#include <type_traits>
+
 #include "../../include/bgs.h"
 #include "bgs_common.h"
 #include "bgs_internal.h"
@@ -1794,14 +1796,37 @@ void launch_bounce_evaluate_halving(const bgs_batch* b, const GEO& g, uint64_t s
 // of the descent).  Global memory beyond the workspace: the root, the outputs (counts and visits zeroed by the launcher:
 // illegal slots are never stored; counts is accumulated by lane 0 alone) and the step counter, the only global atomic.
 //
+// The proving search (bgs_bounce_search_moves_proving; the template parameter PROVE, the plain tree only) keeps game-end
+// facts on the edges, in the third word: kEdgeEnded | outcome is a fact as it stands, and a value backed up from the node
+// below overwrites the child index with kEdgeProved | outcome (the outcome absolute in both, so the tag seen from a node
+// is "outcome - 1 == its mover"; a decided node is never entered again, so its index is not missed).  kEdgeCapped and
+// every word below kEdgeProved are OPEN.  PROVE changes five things and nothing else: a lane's arm is a candidate of the
+// selection -- counts in N, can be the unplayed arm, has a key -- only while its tag is OPEN; after an iteration whose
+// last edge ended the game the values go up the path (the node of path edge k is the child word of path edge k - 1,
+// still intact while the walk goes upwards, so the path holds edges only, as before); a root whose value is no longer
+// OPEN stops iterating; `proved` and `done` are written; and `best` looks at the root's tags.  The edge stays four words
+// and the workspace is the plain search's.  A tagged edge is never selected, so the descent never reads an ended or a
+// proved word as a child.
+//
 // Known limit: a root has one team, so a launch of few roots leaves most CUs idle, and leaf_playouts < BGS_BLOCK leaves
 // lanes idle.
 // ================================================================================================================
 constexpr uint32_t kEdgeWords = 4;
 constexpr uint32_t kEdgeEnded = 0xFFFFFFF0u;      // | BGS_ST_*: the edge ends the game (1, 2: the winner + 1; 3: a draw)
 constexpr uint32_t kEdgeCapped = 0xFFFFFFFFu;     // the position behind the edge runs and holds the cap
+constexpr uint32_t kEdgeProved = 0xFFFFFFE0u;     // | BGS_ST_*: (PROVE) a value backed up from below, the outcome absolute as in kEdgeEnded
 constexpr uint32_t kNoArm = 0xFFFFu;
 constexpr int kSearchTeamWaves = BGS_BLOCK / BGS_WAVE;
+static_assert(((uint64_t)1 << 29) + 1u < kEdgeProved, "a child index (at most T <= 2^29) stays below the reserved ranges");
+
+// (PROVE) the tag of an edge with third word `word`, seen from `mover`, the player to move at its node: every word of the
+// two reserved ranges but kEdgeCapped is a fact (an edge that ends the game, or a value backed up), and its low bits are
+// the absolute outcome
+__device__ __forceinline__ uint32_t bounce_edge_tag(uint32_t word, uint32_t mover) {
+    if (word < kEdgeProved || word == kEdgeCapped) return kTagOpen;
+    const uint32_t outcome = word & 15u;
+    return outcome == (uint32_t)BGS_ST_DRAW ? kTagDraw : (outcome - 1u == mover ? kTagWin : kTagLoss);
+}
 static_assert(kBounceHalvingMaxArms <= 2 * BGS_BLOCK, "a lane holds at most two arms of a node");
 static_assert((uint32_t)BGS_ST_DRAW < 15u, "an outcome code fits the low bits of kEdgeEnded and stays below kEdgeCapped");
 
@@ -1850,13 +1875,24 @@ struct BounceForestArgs<true> {
     int32_t* carried;
 };
 
-template <class GEO, int NC, int POLICY, bool FOREST>
+// what the proving instantiation alone is given, in the forest's place (the forest does not prove, so the last argument is
+// one or the other and the plain and the forest kernels keep the arguments they had): the root's tags and the
+// iterations run (either may be nullptr)
+struct BounceProveArgs {
+    int8_t* proved;
+    int32_t* done;
+};
+template <bool FOREST, bool PROVE>
+using BounceExtraArgs = std::conditional_t<PROVE, BounceProveArgs, BounceForestArgs<FOREST>>;
+
+template <class GEO, int NC, int POLICY, bool FOREST, bool PROVE = false>
 __global__ void __launch_bounds__(BGS_BLOCK)
 k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, const uint16_t* __restrict__ plies_buf,
                 int64_t n, uint64_t seed, uint64_t game_base, uint32_t iterations, uint32_t leaf_playouts, uint32_t explore,
                 uint32_t max_plies, uint32_t edges, uint32_t slots, int64_t root_base, uint32_t* trees, int32_t* counts,
                 int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used_out, unsigned long long* __restrict__ steps,
-                BounceForestArgs<FOREST> forest) {
+                BounceExtraArgs<FOREST, PROVE> extra) {
+    static_assert(!(PROVE && FOREST), "the forest does not prove");
     extern __shared__ uint32_t target_tile[];                      // [2 * 8 * NC dwords][256 lanes]
     __shared__ uint64_t node_targets[8 * NC];                      // targets of the piece in column x of the active row of p'
     __shared__ uint64_t other_targets[8 * NC];                     // ... of the side that has just moved, when p' is blocked
@@ -1872,10 +1908,10 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
     uint64_t* head_planes = nullptr;
     uint64_t table_room;                                                        // the node table's entries (C)
     if constexpr (FOREST) {
-        head = trees + (uint64_t)i * bounce_forest_tree_words(forest.capacity, edges);
+        head = trees + (uint64_t)i * bounce_forest_tree_words(extra.capacity, edges);
         head_planes = reinterpret_cast<uint64_t*>(head + 4);
         pool = head + kBounceForestHeaderWords;
-        table_room = forest.capacity;
+        table_room = extra.capacity;
     } else {
         pool = trees + (uint64_t)i * bounce_search_root_words(iterations, edges);
         table_room = (uint64_t)iterations + 1u;
@@ -1928,11 +1964,14 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
             if constexpr (FOREST) {
                 head[0] = 0;
                 head[1] = 0;
-                if (forest.carried) forest.carried[i] = 0;
+                if (extra.carried) extra.carried[i] = 0;
             }
             if (best) best[i] = -1;
             if (nodes) nodes[i] = 0;
             if (used_out) used_out[i] = 0;
+            if constexpr (PROVE) {      // (every slot of `proved` stays BGS_SOLVE_NONE, as the launcher filled it)
+                if (extra.done) extra.done[i] = 0;
+            }
         }
         return;
     }
@@ -1947,7 +1986,7 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
     if constexpr (FOREST) {
         const uint32_t count = uniform(head[0]);                    // (the header counts the root)
         used = uniform(head[1]);
-        keep = forest.restart == 0u && count >= 1u && count <= forest.capacity && used >= root_arms && used <= edges && head[2] == rply &&
+        keep = extra.restart == 0u && count >= 1u && count <= extra.capacity && used >= root_arms && used <= edges && head[2] == rply &&
                head[3] == max_plies;
         if (keep) {
 #pragma unroll
@@ -2004,7 +2043,13 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
     Philox4 blk;
     blk.v[0] = blk.v[1] = blk.v[2] = blk.v[3] = 0;
 
+    [[maybe_unused]] uint32_t ran = 0;      // PROVE (team-uniform): the iterations run, and whether the root's value is proved
+    [[maybe_unused]] bool decided = false;
     for (uint32_t t = 0; t < iterations; ++t) {
+        if constexpr (PROVE) {
+            if (decided) break;
+            ran = t + 1u;
+        }
         // ---- descent (team-uniform): p is the position at node v
         Board p = root;
         uint32_t ply = rply, v = 0, depth = 0, move0 = 0;
@@ -2015,15 +2060,25 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
             const uint32_t* const node = pool + (uint64_t)first * kEdgeWords;
             uint32_t na[2] = {0u, 0u}, sa[2] = {0u, 0u};
             uint32_t fresh = kNoArm, sum = 0;
+            [[maybe_unused]] bool open[2] = {false, false};   // PROVE: the lane's arm is a candidate (its tag is OPEN)
 #pragma unroll
             for (uint32_t k = 0; k < 2; ++k) {
                 const uint32_t a = tid + k * BGS_BLOCK;
                 if (a < arms) {
-                    const uint2 ns = *reinterpret_cast<const uint2*>(node + (uint64_t)a * kEdgeWords);
-                    na[k] = ns.x;
-                    sa[k] = ns.y;
-                    sum += ns.x;
-                    fresh = (ns.x == 0u && a < fresh) ? a : fresh;
+                    if constexpr (PROVE) {  // a tagged arm is in neither N, the unplayed arms nor the keys (the tag's sign is not needed)
+                        const uint4 whole = *reinterpret_cast<const uint4*>(node + (uint64_t)a * kEdgeWords);
+                        open[k] = whole.z < kEdgeProved || whole.z == kEdgeCapped;
+                        na[k] = whole.x;
+                        sa[k] = whole.y;
+                        sum += open[k] ? whole.x : 0u;
+                        fresh = (open[k] && whole.x == 0u && a < fresh) ? a : fresh;
+                    } else {
+                        const uint2 ns = *reinterpret_cast<const uint2*>(node + (uint64_t)a * kEdgeWords);
+                        na[k] = ns.x;
+                        sa[k] = ns.y;
+                        sum += ns.x;
+                        fresh = (ns.x == 0u && a < fresh) ? a : fresh;
+                    }
                 }
             }
             const uint32_t buf = depth & 1u;
@@ -2047,7 +2102,7 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
 #pragma unroll
                 for (uint32_t k = 0; k < 2; ++k) {
                     const uint32_t a = tid + k * BGS_BLOCK;
-                    if (a < arms) {
+                    if (PROVE ? open[k] : a < arms) {
                         const uint32_t u = search_q(sa[k], na[k]) + search_isqrt(scaled / na[k]);
                         const uint32_t mine = ((u << 9) | (511u - a)) + 1u;
                         key = mine > key ? mine : key;
@@ -2103,7 +2158,7 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
                     code = kEdgeCapped;
                 } else {
                     bool fits = used + fan <= edges;                 // (the plain table has iterations + 1 entries: room for every iteration's)
-                    if constexpr (FOREST) fits = made + 1u < forest.capacity && fits;
+                    if constexpr (FOREST) fits = made + 1u < extra.capacity && fits;
                     if (fits) {             // a new node for p'; without room the edge is tried again next time
                         made += 1u;
                         make_arms(used, fan, base);
@@ -2230,6 +2285,49 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
             c[1] += (int32_t)td;
             c[2] += (int32_t)tl;
         }
+        if constexpr (PROVE) {
+            // ---- the tags go up the path (team-uniform), while the node at hand has a value.  `leaf` is the team's (every
+            // lane read the same words behind the descent's barriers), and only a fresh edge sets it here: a tagged edge is
+            // never selected.  The last edge's word was written before barrier (A); an upper one by lane 0, behind barrier
+            // (V) of the step below.  A step's flags -- 1: an arm is WIN, 2: an arm is OPEN, 4: an arm is DRAW -- go through
+            // red_min[0], which is free from barrier (A) to the next descent: (U) stands between its writers and its readers,
+            // (V) between its readers and the next step's writers.  Every lane reads the same four words behind (U), so the
+            // break, the trip count and both barriers are the team's.
+            if (leaf != BGS_ST_RUNNING) {
+                for (uint32_t k = depth; k-- > 0u;) {
+                    // the node edge k leaves: the root, or the child word of edge k - 1, which is tagged only further down
+                    const uint32_t at = k ? uniform(pool[(uint64_t)path[k - 1u] * kEdgeWords + 2u]) : 0u;
+                    const uint32_t first = uniform(node_tab[2u * at]), arms = uniform(node_tab[2u * at + 1u]);
+                    const uint32_t mover = (rply + k) & 1u;
+                    uint32_t flags = 0;
+#pragma unroll
+                    for (uint32_t j = 0; j < 2; ++j) {
+                        const uint32_t a = tid + j * BGS_BLOCK;
+                        if (a < arms) {
+                            const uint32_t tag = bounce_edge_tag(pool[(uint64_t)(first + a) * kEdgeWords + 2u], mover);
+                            flags |= tag == kTagWin ? 1u : (tag == kTagOpen ? 2u : (tag == kTagDraw ? 4u : 0u));
+                        }
+                    }
+                    flags = (__builtin_amdgcn_ballot_w64((flags & 1u) != 0u) ? 1u : 0u) | (__builtin_amdgcn_ballot_w64((flags & 2u) != 0u) ? 2u : 0u) |
+                            (__builtin_amdgcn_ballot_w64((flags & 4u) != 0u) ? 4u : 0u);
+                    if (lane == 0) red_min[0][wave] = flags;
+                    __syncthreads();        // (U)
+                    uint32_t value = 0;
+#pragma unroll
+                    for (int w = 0; w < kSearchTeamWaves; ++w) value |= red_min[0][w];
+                    value = uniform(value);
+                    if (!(value & 1u) && (value & 2u)) break;      // the value is OPEN: nothing is known further up
+                    if (k == 0u) {
+                        decided = true;
+                        break;
+                    }
+                    // the parent's edge takes the node's value as an absolute outcome: a won node is its mover's
+                    const uint32_t outcome = (value & 1u) ? mover + 1u : ((value & 4u) ? (uint32_t)BGS_ST_DRAW : (1u - mover) + 1u);
+                    if (tid == 0) pool[(uint64_t)path[k - 1u] * kEdgeWords + 2u] = kEdgeProved | outcome;
+                    __syncthreads();        // (V)
+                }
+            }
+        }
         __syncthreads();            // (C) the tree is whole again before the next descent reads it; tally and path are free
     }
 
@@ -2240,26 +2338,53 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
             visits[i * (int64_t)slots + slot_of(edge[3])] = (int32_t)edge[0];
         }
     }
+    if constexpr (PROVE) {      // the root's tags in the solver's codes, by slot (every other slot stays BGS_SOLVE_NONE)
+        if (extra.proved) {
+            for (uint32_t a = tid; a < root_arms; a += BGS_BLOCK) {
+                const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
+                const uint32_t tag = bounce_edge_tag(edge[2], root_mover);
+                const int code = tag == kTagWin ? BGS_SOLVE_WIN : (tag == kTagDraw ? BGS_SOLVE_DRAW : (tag == kTagLoss ? BGS_SOLVE_LOSS : BGS_SOLVE_UNKNOWN));
+                extra.proved[i * (int64_t)slots + slot_of(edge[3])] = (int8_t)code;
+            }
+        }
+        if (tid == 0 && extra.done) extra.done[i] = (int32_t)ran;
+    }
     if constexpr (FOREST) __syncthreads();   // the tree's last writes are issued by every wave before the header says what it holds
     if (tid == 0) {
         if (best) {   // the most visits, then the larger 2 * wins + draws, then the lower slot (the arms ascend by slot)
             int32_t top = -1;
             uint32_t top_n = 0, top_s = 0;
+            // PROVE: a proved win is the move (at most one: the search stops at the first); otherwise the rule runs over the
+            // arms not proved lost, or over all when all are
+            [[maybe_unused]] int32_t won = -1;
+            [[maybe_unused]] bool spare = false;
+            if constexpr (PROVE) {
+                for (uint32_t a = 0; a < root_arms; ++a) {
+                    const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
+                    const uint32_t tag = bounce_edge_tag(edge[2], root_mover);
+                    if (tag == kTagWin && won < 0) won = (int32_t)slot_of(edge[3]);
+                    spare = spare || tag != kTagLoss;
+                }
+            }
             for (uint32_t a = 0; a < root_arms; ++a) {
                 const uint32_t* const edge = pool + (uint64_t)a * kEdgeWords;
                 const uint32_t cn = edge[0], cs = edge[1];
+                if constexpr (PROVE) {
+                    if (spare && bounce_edge_tag(edge[2], root_mover) == kTagLoss) continue;
+                }
                 if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
                     top = (int32_t)slot_of(edge[3]);
                     top_n = cn;
                     top_s = cs;
                 }
             }
+            if constexpr (PROVE) top = won >= 0 ? won : top;
             best[i] = top;
         }
         if constexpr (FOREST) {
             head[0] = made + 1u;    // the header: ply, cap and planes were recorded when the tree was emptied, or carried with it
             head[1] = used;
-            if (forest.carried) forest.carried[i] = (int32_t)brought;
+            if (extra.carried) extra.carried[i] = (int32_t)brought;
         }
         if (nodes) nodes[i] = (int32_t)made;
         if (used_out) used_out[i] = (int32_t)used;
@@ -2275,9 +2400,11 @@ struct BounceSearchArgs {
     int32_t *counts, *visits, *best, *nodes, *used;
     int32_t* carried;                       // (nor carried)
     void* trees;                            // the workspace, or the forest
+    int8_t* proved = nullptr;               // the proving search alone: the root's tags and the iterations run
+    int32_t* done = nullptr;
 };
 
-template <class GEO, int NC, int POLICY, bool FOREST>
+template <class GEO, int NC, int POLICY, bool FOREST, bool PROVE = false>
 void launch_bounce_search(const bgs_batch* b, const GEO& g, const BounceSearchArgs& a) {
     const uint32_t slots = (uint32_t)(b->bg.w * b->bg.h * b->bg.w);
     (void)hipMemsetAsync(a.counts, 0, (size_t)b->n * slots * 3 * sizeof(int32_t), b->stream);
@@ -2285,15 +2412,20 @@ void launch_bounce_search(const bgs_batch* b, const GEO& g, const BounceSearchAr
     // game ids: ((first_game + i) * T + t) * P + j = first_game * T * P + (i * T + t) * P + j, mod 2^64
     const uint64_t game_base = b->first_game * (uint64_t)a.iterations * (uint64_t)a.leaf_playouts;
     const size_t tile = sizeof(uint32_t) * 2 * 8 * NC * BGS_BLOCK;
-    BounceForestArgs<FOREST> forest;
-    if constexpr (FOREST) forest = {a.capacity, a.restart, a.carried};
+    BounceExtraArgs<FOREST, PROVE> extra;
+    if constexpr (FOREST) extra = {a.capacity, a.restart, a.carried};
+    if constexpr (PROVE) {      // every slot BGS_SOLVE_NONE; the kernel stores the legal ones
+        static_assert((uint8_t)(int8_t)BGS_SOLVE_NONE == 0xFEu, "the fill byte is BGS_SOLVE_NONE");
+        if (a.proved) (void)hipMemsetAsync(a.proved, 0xFE, (size_t)b->n * slots * sizeof(int8_t), b->stream);
+        extra = {a.proved, a.done};
+    }
     constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
     for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
         const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
-        hipLaunchKernelGGL((k_bounce_search<GEO, NC, POLICY, FOREST>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), tile, b->stream, g,
+        hipLaunchKernelGGL((k_bounce_search<GEO, NC, POLICY, FOREST, PROVE>), dim3((uint32_t)blocks), dim3(BGS_BLOCK), tile, b->stream, g,
                            (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, (const uint16_t*)b->d_plies, b->n, a.seed,
                            game_base, a.iterations, a.leaf_playouts, a.explore, a.max_plies, a.edges, slots, i0,
-                           static_cast<uint32_t*>(a.trees), a.counts, a.visits, a.best, a.nodes, a.used, b->d_steps, forest);
+                           static_cast<uint32_t*>(a.trees), a.counts, a.visits, a.best, a.nodes, a.used, b->d_steps, extra);
     }
 }
 
@@ -3258,23 +3390,23 @@ uint64_t bounce_search_root_bytes(int32_t iterations, int32_t edges) {
     return bounce_search_root_words((uint32_t)iterations, (uint32_t)edges) * sizeof(uint32_t);
 }
 
-template <int POLICY, bool FOREST>
+template <int POLICY, bool FOREST, bool PROVE>
 static void bounce_search_policy(const bgs_batch* b, const BounceSearchArgs& a) {
     if (b->bounce_static_geom && bounce_is_default(b->bg))
-        launch_bounce_search<DefaultBounceGeom, 1, POLICY, FOREST>(b, DefaultBounceGeom{}, a);
+        launch_bounce_search<DefaultBounceGeom, 1, POLICY, FOREST, PROVE>(b, DefaultBounceGeom{}, a);
     else if (b->bg.w <= 8)
-        launch_bounce_search<BounceGeom, 1, POLICY, FOREST>(b, b->bg, a);
+        launch_bounce_search<BounceGeom, 1, POLICY, FOREST, PROVE>(b, b->bg, a);
     else
-        launch_bounce_search<BounceGeom, 3, POLICY, FOREST>(b, b->bg, a);
+        launch_bounce_search<BounceGeom, 3, POLICY, FOREST, PROVE>(b, b->bg, a);
 }
 
-template <bool FOREST>
+template <bool FOREST, bool PROVE = false>
 static void bounce_search_any(const bgs_batch* b, int policy, BounceSearchArgs a) {
     if (a.max_plies > kBounceMaxPlies) a.max_plies = kBounceMaxPlies;   // plies are stored as uint16
     if (policy == BGS_POLICY_DECISIVE)
-        bounce_search_policy<BGS_POLICY_DECISIVE, FOREST>(b, a);
+        bounce_search_policy<BGS_POLICY_DECISIVE, FOREST, PROVE>(b, a);
     else
-        bounce_search_policy<BGS_POLICY_UNIFORM, FOREST>(b, a);
+        bounce_search_policy<BGS_POLICY_UNIFORM, FOREST, PROVE>(b, a);
 }
 
 void bounce_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
@@ -3283,6 +3415,14 @@ void bounce_search(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_
     bounce_search_any<false>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore, (uint32_t)max_plies,
                                          (uint32_t)iterations + 1u, (uint32_t)edges, 1u, d_counts, d_visits, d_best, d_nodes, d_used,
                                          nullptr, d_workspace});
+}
+
+void bounce_search_proving(const bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
+                           int32_t max_plies, int policy, int32_t edges, int32_t* d_counts, int32_t* d_visits, int32_t* d_best,
+                           int32_t* d_nodes, int32_t* d_used, int8_t* d_proved, int32_t* d_done, void* d_workspace) {
+    bounce_search_any<false, true>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore,
+                                               (uint32_t)max_plies, (uint32_t)iterations + 1u, (uint32_t)edges, 1u, d_counts, d_visits,
+                                               d_best, d_nodes, d_used, nullptr, d_workspace, d_proved, d_done});
 }
 
 uint64_t bounce_forest_tree_bytes(int32_t capacity, int32_t edges) {

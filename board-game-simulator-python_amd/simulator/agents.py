@@ -529,14 +529,24 @@ class BounceTreeSearchAgent:
     -- the nodes every tree started with -- as a sixth element.  ``capacity`` is the room of a tree in nodes; None: ``2 *
     iterations + 1``, the nodes one search can make plus as many carried ones; the pool is ``edges`` or the default pool
     of ``capacity - 1`` iterations.  Both are allowances and not measurements: a tree that is full stops growing until
-    the next advance frees room.  Without ``reuse`` the agent is what it was, code path included."""
+    the next advance frees room.  Without ``reuse`` the agent is what it was, code path included.
+
+    ``prove=True`` searches with ``BounceBatch.search_moves_proving``: game-end facts are kept on the edges and backed up
+    by minimax, a root whose value is proved stops iterating, and ``search`` returns (counts, visits, best, nodes, used,
+    proved, done).  ``choose`` follows that launch's ``best`` (a proved win, else the most visited move among those not
+    proved lost).  ``predict`` gives a proved win 1.0 and every other move 0; otherwise the moves proved lost get 0 and
+    the rest are renormalised, and where every move is proved lost the shares are what the visits give.  The forest does
+    not prove: ``prove=True`` with ``reuse=True`` raises ValueError.  Without ``prove`` the code path is what it was."""
 
     def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
                  seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, edges: Optional[int] = None,
-                 reuse: bool = False, capacity: Optional[int] = None):
+                 prove: bool = False, reuse: bool = False, capacity: Optional[int] = None):
         playout_policy(policy)
+        if prove and reuse:
+            raise ValueError("prove=True with reuse=True: the forest does not prove")
         if capacity is not None and capacity < 2:
             raise ValueError("capacity must be >= 2")
+        self.prove = bool(prove)
         self.reuse = bool(reuse)
         self.capacity = 2 * int(iterations) + 1 if capacity is None else int(capacity)
         self._forests: Dict[tuple, list] = {}   # key -> [MovesForest, grids last searched, their movers, their plies, searches so far]
@@ -558,7 +568,7 @@ class BounceTreeSearchAgent:
 
     def search(self, states: Sequence, first_game: int = 0):
         """(counts, visits, best, nodes, used) of the launch over `states` (Bounce states that share one Config); with `reuse`
-        (counts, visits, best, nodes, used, carried)"""
+        (counts, visits, best, nodes, used, carried), with `prove` (counts, visits, best, nodes, used, proved, done)"""
         if isinstance(states[0], connect.State):
             raise ValueError("BounceTreeSearchAgent: Bounce states only; Connect states: TreeSearchAgent")
         if not isinstance(states[0], bounce.State):
@@ -581,6 +591,9 @@ class BounceTreeSearchAgent:
         cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
         if self.reuse:
             return self._search_on(key, b, boards, player, plies, cap)
+        if self.prove:
+            return b.search_moves_proving(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts,
+                                          explore=self.explore, max_plies=cap, policy=self.policy, edges=self.edges)
         return b.search_moves(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore,
                               max_plies=cap, policy=self.policy, edges=self.edges)
 
@@ -650,6 +663,8 @@ class BounceTreeSearchAgent:
         """`predict` of every state, searched in one launch"""
         if not states:
             return []
+        if self.prove:
+            return self._predict_proved(states, first_game)
         visits = self.search(states, first_game)[1]
         w = visits.shape[1]
         if self.reuse:      # the root's visits include the carried ones
@@ -658,6 +673,23 @@ class BounceTreeSearchAgent:
         total = self.iterations * self.leaf_playouts
         return [{a: float(visits[k, a._source[0], a._target[1] * w + a._target[0]]) / total for a in s.actions}
                 for k, s in enumerate(states)]
+
+    def _predict_proved(self, states: Sequence, first_game: int) -> List[Dict[bounce.Action, float]]:
+        """`predict_many` of `prove`: a proved win takes everything, moves proved lost nothing (unless all are)"""
+        out = self.search(states, first_game)
+        visits, proved = out[1], out[5]
+        w = visits.shape[1]
+        shares = []
+        for k, s in enumerate(states):
+            at = {a: (a._source[0], a._target[1] * w + a._target[0]) for a in s.actions}
+            share = {a: float(visits[k][at[a]]) for a in s.actions}
+            if any(proved[k][at[a]] == SOLVE_WIN for a in s.actions):
+                share = {a: 1.0 if proved[k][at[a]] == SOLVE_WIN else 0.0 for a in s.actions}
+            elif any(proved[k][at[a]] != SOLVE_LOSS for a in s.actions):
+                share = {a: 0.0 if proved[k][at[a]] == SOLVE_LOSS else share[a] for a in s.actions}
+            total = sum(share.values())
+            shares.append({a: share[a] / total for a in s.actions})
+        return shares
 
     def predict(self, state, game: int = 0) -> Dict[bounce.Action, float]:
         """{action: share of the visits} for every action in ``state.actions`` (the keys are those Action objects)"""

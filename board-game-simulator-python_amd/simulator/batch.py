@@ -1070,6 +1070,12 @@ class ConnectBatch(_Batch):
 
     search_moves_tensor = search_moves_workspace_bytes = search_moves
 
+    def search_moves_proving(self, *args, **kwargs):
+        """Not available for Connect: search_moves_proving is the Bounce proving search; Connect has `search_actions_proving`."""
+        raise ValueError("search_moves_proving: Bounce batches only (Connect boards: search_actions_proving)")
+
+    search_moves_proving_tensor = search_moves_proving
+
     @property
     def legal(self) -> np.ndarray:
         out = np.empty((self.n, self.width), dtype=np.uint8)
@@ -1267,8 +1273,8 @@ class BounceBatch(_Batch):
     search_actions_tensor = search_workspace_bytes = search_actions
 
     def search_actions_proving(self, *args, **kwargs):
-        """Not available for Bounce: the proving tree search covers bit-packed Connect boards; Bounce has `search_moves`."""
-        raise ValueError("search_actions_proving: Connect batches only (Bounce boards: search_moves)")
+        """Not available for Bounce: search_actions_proving is the Connect proving search; Bounce has `search_moves_proving`."""
+        raise ValueError("search_actions_proving: Connect batches only (Bounce boards: search_moves_proving)")
 
     search_actions_proving_tensor = search_actions_proving
 
@@ -1461,6 +1467,72 @@ class BounceBatch(_Batch):
             ctypes.c_void_p(outs["nodes"].data_ptr()), ctypes.c_void_p(outs["used"].data_ptr()),
             ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
         return outs["counts"], outs["visits"], outs["best"], outs["nodes"], outs["used"]
+
+    def search_moves_proving(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
+                             explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1, policy: str = "uniform",
+                             edges: Optional[int] = None):
+        """`search_moves` that keeps the game-end facts it meets (bgs_bounce_search_moves_proving; MCTS-Solver), one launch:
+        (counts, visits, best, nodes, used, proved int8[n, W, H * W], done int32[n]).  An edge that ends the game -- a move
+        into the goal row, a blocked side -- is tagged a win or a draw, the tags are backed up by minimax beside the
+        averages, a tagged edge is never descended again, and a root whose value is proved stops iterating.  `proved`
+        holds the root's tags by slot in the solver's codes: SOLVE_WIN / SOLVE_DRAW / SOLVE_LOSS for a proved move,
+        SOLVE_UNKNOWN for a legal move still open, SOLVE_NONE for an illegal slot and for a board that has ended or has no
+        move.  `done` is the number of iterations run (`iterations` for a root left undecided, 0 for a board without
+        moves).  `best` is the proved win if there is one, else the most visited move among those not proved lost.  A
+        move whose position holds the cap proves nothing.  A root whose search plays no move that ends the game returns
+        what `search_moves` returns.  The workspace and `edges` are `search_moves`'s."""
+        code = playout_policy(policy)
+        edges = self.search_default_edges(iterations) if edges is None else int(edges)
+        shape = (self.n, self.width, self.height * self.width)
+        counts = np.empty(shape + (3,), dtype=np.int32)
+        visits = np.empty(shape, dtype=np.int32)
+        best, nodes, used, done = (np.empty(self.n, dtype=np.int32) for _ in range(4))
+        proved = np.empty(shape, dtype=np.int8)
+        _abi.check(_abi.lib().bgs_bounce_search_moves_proving(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
+            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), ctypes.c_void_p(counts.ctypes.data),
+            ctypes.c_void_p(visits.ctypes.data), ctypes.c_void_p(best.ctypes.data), ctypes.c_void_p(nodes.ctypes.data),
+            ctypes.c_void_p(used.ctypes.data), ctypes.c_void_p(proved.ctypes.data), ctypes.c_void_p(done.ctypes.data), None, 0, 0))
+        return counts, visits, best, nodes, used, proved, done
+
+    def search_moves_proving_tensor(self, counts=None, visits=None, best=None, nodes=None, used=None, proved=None, done=None,
+                                    seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
+                                    explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1, policy: str = "uniform",
+                                    edges: Optional[int] = None, workspace=None):
+        """`search_moves_proving` into device tensors (allocated when None; `proved` is int8[n, W, H * W], the others int32
+        as in `search_moves_tensor`), enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes,
+        used, proved, done).  Every entry is written.  `workspace` is `search_moves_tensor`'s, and the batch's own cached
+        workspace serves both."""
+        code = playout_policy(policy)
+        t = self._need_torch("search_moves_proving_tensor")
+        edges = self.search_default_edges(iterations) if edges is None else int(edges)
+        slots = (self.n, self.width, self.height * self.width)
+        shapes = {"counts": slots + (3,), "visits": slots, "best": (self.n,), "nodes": (self.n,), "used": (self.n,), "proved": slots,
+                  "done": (self.n,)}
+        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "used": used, "proved": proved, "done": done}
+        for name, shape in shapes.items():
+            dtype = t.int8 if name == "proved" else t.int32
+            x = outs[name]
+            if x is None:
+                x = outs[name] = t.empty(shape, dtype=dtype, device=f"cuda:{self.device}")
+            if not (x.is_cuda and x.dtype == dtype and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
+                raise TypeError(f"{name} must be a contiguous, 16-byte aligned {str(dtype).split('.')[-1]} device tensor of shape {shape}")
+        if workspace is None:
+            need = self.search_moves_workspace_bytes(iterations, edges)   # (refuses bad arguments before anything is allocated)
+            key = (int(iterations), edges)
+            workspace = self._search_workspaces.get(key)
+            if workspace is None:
+                workspace = self._search_workspaces[key] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
+        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        _abi.check(_abi.lib().bgs_bounce_search_moves_proving(
+            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
+            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), ctypes.c_void_p(outs["counts"].data_ptr()),
+            ctypes.c_void_p(outs["visits"].data_ptr()), ctypes.c_void_p(outs["best"].data_ptr()),
+            ctypes.c_void_p(outs["nodes"].data_ptr()), ctypes.c_void_p(outs["used"].data_ptr()),
+            ctypes.c_void_p(outs["proved"].data_ptr()), ctypes.c_void_p(outs["done"].data_ptr()),
+            ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
+        return tuple(outs[name] for name in shapes)
 
     def moves_forest_bytes(self, nodes: int, edges: Optional[int] = None) -> int:
         """bytes of device memory a forest of this batch takes at `nodes` nodes and `edges` pool edges a tree (None: the

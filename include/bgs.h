@@ -303,7 +303,8 @@ BGS_API int bgs_connect_search_actions(bgs_batch* b, uint64_t seed, int32_t iter
  * Equal to the plain search.  While no edge of a root's tree has been tagged, that root's state is the plain search's,
  * bit for bit: a root whose search tags nothing returns the outputs of bgs_connect_search_actions, and done = T.
  * Known weakness: a column proved DRAW stops collecting visits, so an undecided root can prefer an OPEN column whose Q
- * is below a draw's.  The forest (bgs_connect_forest_search) and Bounce do not prove. */
+ * is below a draw's.  The forests (bgs_connect_forest_search, bgs_bounce_forest_search) do not prove; Bounce proves
+ * with bgs_bounce_search_moves_proving. */
 BGS_API int bgs_connect_search_actions_proving(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts,
                                                int32_t explore, int32_t max_plies, int policy, int32_t* counts,
                                                int32_t* visits, int32_t* best, int32_t* nodes, int8_t* proved, int32_t* done,
@@ -490,6 +491,53 @@ BGS_API int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterati
                                     int32_t max_plies, int policy, int32_t edges, int32_t* counts, int32_t* visits,
                                     int32_t* best, int32_t* nodes, int32_t* used, void* workspace, size_t workspace_bytes,
                                     int on_device);
+/* The same search, proving wins, draws and losses in its tree (MCTS-Solver: Winands, Bjornsson and Saito 2008; Bounce,
+ * bit-packed boards only), one launch: the sibling of bgs_connect_search_actions_proving.  What stays as in
+ * bgs_bounce_search_moves: the workspace and its size (bgs_bounce_search_workspace_bytes serves both entry points), the
+ * pool of E edges and the rule that an edge whose node did not fit is tried again, the cap rule, the game ids G =
+ * ((first_game + i) * T + t) * P + j with the T that was asked for, the policies, bgs_steps, sharding by first_game, the
+ * refusals, and the on_device rules (proved and done are 16-byte aligned device pointers then).  proved and done may be
+ * NULL, like visits, best, nodes and used.
+ * Tags.  Every edge (v, a) has a tag, seen from the player to move at v: OPEN, WIN, DRAW or LOSS.  An arm that was never
+ * played is OPEN.  An arm whose position runs and holds the cap is OPEN and stays OPEN: it is selectable and its
+ * playouts score 0, exactly as in bgs_bounce_search_moves.  An edge whose node did not fit the pool is OPEN.  The value
+ * of a node is WIN if an arm is tagged WIN; otherwise OPEN if an arm is OPEN; otherwise DRAW if an arm is tagged DRAW;
+ * otherwise LOSS.
+ * Iteration t (t = 0 .. T-1):
+ *   0. if the root's value is not OPEN, this root's search is over: done[i] = t, and the remaining iterations and their
+ *      game ids are not used;
+ *   1.-3. the selection of bgs_bounce_search_moves, word for word, over the arms of p whose tag is OPEN: the lowest such
+ *      arm with n[a] = 0 if there is one, otherwise the largest U(a), ties to the lowest arm; N is the sum of n[a] over
+ *      the OPEN arms alone.  (A tagged arm has n[a] > 0.)  A node the descent stands on always has an OPEN arm: that is
+ *      the invariant of step 7;
+ *   4. as there.  In addition, an edge that ends the game is tagged: WIN if the mover won -- the target lies in its goal
+ *      row, or the side to move at p' has no move while the mover has one -- and DRAW if neither side has a move.  All P
+ *      playouts of the iteration still carry that outcome.  A position that runs and holds the cap is not an end and
+ *      tags nothing;
+ *   5.-6. as there;
+ *   7. only after an iteration whose last edge was tagged in step 4: go up the path, for k = depth-1 down to 0 (edge k
+ *      leaves path_node[k]; path_node[0] is the root).  If the value of path_node[k] is OPEN, stop.  If k = 0, the root
+ *      is decided.  Otherwise edge k-1 of the path is tagged with the negation of that value: a WIN node makes its
+ *      parent's edge LOSS, a LOSS node makes it WIN, DRAW stays DRAW.  A decided node is therefore never entered again.
+ * Outputs.  counts, visits, nodes and used mean what they mean there; the nodes under a tagged edge stay counted and keep
+ * their pool edges.  proved int8[n][width][height * width] (may be NULL), by slot: BGS_SOLVE_WIN, BGS_SOLVE_DRAW or
+ * BGS_SOLVE_LOSS for a tagged root arm, BGS_SOLVE_UNKNOWN for a legal OPEN arm, BGS_SOLVE_NONE for an illegal slot and
+ * for every slot of a board that has ended, has no move or holds 65535 plies.  done int32[n] (may be NULL) = the
+ * iterations run: T for a root still OPEN after T iterations and for one decided by the T-th, 0 for a board without arms.
+ * best: if a root arm is tagged WIN, its slot (there is at most one: the search stops at the first); otherwise the rule
+ * of bgs_bounce_search_moves (the most visits, then the larger s, then the lower slot, n > 0) over the arms not tagged
+ * LOSS; if every arm is tagged LOSS, that rule over all arms; -1 for a board without arms.
+ * Equal to the plain search.  While no edge of a root's tree has been tagged, that root's state is the plain search's,
+ * bit for bit: a root whose search plays no edge that ends the game returns the outputs of bgs_bounce_search_moves,
+ * done = T and proved = BGS_SOLVE_UNKNOWN on its legal slots.
+ * Soundness.  The tree is a tree of lines, and every tagged line ends in a true end of the game below the cap, so a tag
+ * is a statement about the game without the cap and needs no repetition rule.
+ * Known weakness: as for Connect, an arm proved DRAW stops collecting visits, so an undecided root can prefer an OPEN arm
+ * whose Q is below a draw's.  The forest (bgs_bounce_forest_search) does not prove. */
+BGS_API int bgs_bounce_search_moves_proving(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts,
+                                            int32_t explore, int32_t max_plies, int policy, int32_t edges, int32_t* counts,
+                                            int32_t* visits, int32_t* best, int32_t* nodes, int32_t* used, int8_t* proved,
+                                            int32_t* done, void* workspace, size_t workspace_bytes, int on_device);
 /* The same search on trees that outlive a launch (Bounce, bit-packed boards only), the sibling of
  * bgs_connect_forest_*: a FOREST is caller-owned device memory that holds one tree per board of the batch, each with room
  * for `nodes_cap` (C) nodes, the root included, and `edges` (E) pool edges, and persists from launch to launch.  An agent
