@@ -17,6 +17,7 @@
 #include "bgs_capi_util.h"
 #include "bgs_common.h"
 #include "bgs_internal.h"
+#include "output_plan.h"
 
 // every kernel translation unit carries the hash of its own source, headers and compile flags (csrc/Makefile: -DBGS_TU_ID)
 extern "C" const char bgs_tu_id_connect[];
@@ -273,6 +274,112 @@ int to_host(bgs_batch* b, T* host, const T* dev, size_t count) {
 template <class T>
 int to_device(const bgs_batch* b, T* dev, const T* host, size_t count) {
     HIP_TRY(hipMemcpyAsync(dev, host, count * sizeof(T), hipMemcpyHostToDevice, b->stream));
+    return BGS_OK;
+}
+
+// the tree memory of a search call: the caller's (`ptr`, `bytes`) or, where ptr may be NULL, the library's own;
+// `sizing` is the function that says how large (`need` is its answer)
+struct Workspace {
+    void* ptr;
+    size_t bytes, need;
+    const char* sizing;
+};
+
+int workspace_check(const Workspace& w, bool on_device) {
+    NEED(!on_device || w.ptr != nullptr, "workspace is NULL (on_device: the caller owns it; %s says how large)", w.sizing);
+    if (!w.ptr) return BGS_OK;
+    NEED((reinterpret_cast<uintptr_t>(w.ptr) & 255u) == 0, "the workspace must be 256-byte aligned");
+    NEED(w.bytes >= w.need, "the workspace is too small: %zu bytes, %zu needed", w.bytes, w.need);
+    return BGS_OK;
+}
+
+// One analysis call through its output plan (output_plan.h; DESIGN.md, "Outputs of an analysis call").  launch(d, tree):
+// d[i] is the device pointer of output i, nullptr for an absent optional one; tree is the workspace (nullptr without ws).
+// on_device: the caller's pointers, after the alignment checks in declaration order and the workspace's.  Otherwise one
+// stream-ordered allocation holds a slice per present output and, without a caller's workspace, the library's own; the
+// present outputs are copied back in order, and the buffer is freed whatever happened (an earlier error wins over the
+// free's).
+template <class Launch>
+int run_outputs(bgs_batch* b, const bgs::OutputPlan& plan, bool on_device, const Workspace* ws, Launch&& launch) {
+    NEED(plan.ok, "internal: the output plan does not hold this call");
+    void* d[bgs::OutputPlan::kMax] = {};
+    int rc = BGS_OK;
+    if (on_device) {
+        const int bad = plan.misaligned();
+        NEED(bad < 0, "device %s must be %zu-byte aligned", plan.out[bad].name, plan.out[bad].align);
+        if (ws && (rc = workspace_check(*ws, true))) return rc;
+        for (int i = 0; i < plan.count; ++i) d[i] = plan.out[i].ptr;
+        launch(d, ws ? ws->ptr : nullptr);
+        return finish_launch();
+    }
+    if (ws && (rc = workspace_check(*ws, false))) return rc;
+    const bool own = ws && !ws->ptr;
+    uint8_t* base = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&base), plan.end + (own ? plan.workspace_room(ws->need) : 0), b->stream));
+    for (int i = 0; i < plan.count; ++i)
+        if (plan.out[i].ptr) d[i] = base + plan.out[i].offset;
+    launch(d, own ? base + plan.workspace_offset(reinterpret_cast<uintptr_t>(base)) : ws ? ws->ptr : nullptr);
+    rc = finish_launch();
+    for (int i = 0; i < plan.count && rc == BGS_OK; ++i)
+        if (plan.out[i].ptr) rc = copy_to_host(b, plan.out[i].ptr, d[i], plan.out[i].bytes);
+    const hipError_t e = hipFreeAsync(base, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
+    return BGS_OK;
+}
+
+inline int32_t* i32(void* p) { return static_cast<int32_t*>(p); }
+
+int policy_check(const char* entry, int policy) {
+    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
+         "%s: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", entry, policy, BGS_POLICY_UNIFORM,
+         BGS_POLICY_DECISIVE);
+    return BGS_OK;
+}
+
+// `sizing`: the function that says how large the forest is
+int forest_pointer(const void* forest, size_t forest_bytes, size_t need, const char* sizing) {
+    NEED(forest != nullptr, "forest is NULL (the caller owns it; %s says how large)", sizing);
+    NEED((reinterpret_cast<uintptr_t>(forest) & 255u) == 0, "the forest must be 256-byte aligned");
+    NEED(forest_bytes >= need, "the forest is too small: %zu bytes, %zu needed", forest_bytes, need);
+    return BGS_OK;
+}
+
+// scratch of the Bounce evaluation and solver: the boards' legal-move prefix and the workgroups' totals, in the staging
+// region (ordered on the stream)
+int bounce_move_scratch(const bgs_batch* b, uint64_t** d_ends, uint64_t** d_totals) {
+    Stage st(b);
+    *d_ends = st.take<uint64_t>((size_t)b->n);
+    *d_totals = st.take<uint64_t>((size_t)(b->n + BGS_BLOCK - 1) / BGS_BLOCK);
+    NEED(*d_ends && *d_totals, "staging region too small");
+    return BGS_OK;
+}
+
+// The body of both *_forest_advance entry points behind their checks: `moves` (named `name` in the messages) goes up
+// and `kept`, when asked for, comes back.  advance(d_moves, d_kept) launches.
+template <class Advance>
+int forest_advance(bgs_batch* b, const int32_t* moves, const char* name, int32_t* kept, bool on_device, Advance&& advance) {
+    if (on_device) {
+        NEED((reinterpret_cast<uintptr_t>(moves) & 3u) == 0, "device %s must be 4-byte aligned", name);
+        NEED((reinterpret_cast<uintptr_t>(kept) & 3u) == 0, "device kept must be 4-byte aligned");
+        advance(moves, kept);
+        return finish_launch();
+    }
+    // one device buffer: moves, kept
+    const size_t board_bytes = (size_t)b->n * sizeof(int32_t);
+    int32_t* d = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), 2 * board_bytes, b->stream));
+    int rc = to_device(b, d, moves, (size_t)b->n);
+    if (rc == BGS_OK) {
+        advance(d, kept ? d + b->n : nullptr);
+        rc = finish_launch();
+    }
+    if (rc == BGS_OK && kept) rc = copy_to_host(b, kept, d + b->n, board_bytes);
+    // (without kept no copy back waits for the stream, and the caller's `moves` must have been read when the call returns)
+    if (rc == BGS_OK && !kept && hipStreamSynchronize(b->stream) != hipSuccess) rc = bgs::fail(BGS_ERR_RUNTIME, "hipStreamSynchronize failed");
+    const hipError_t e = hipFreeAsync(d, b->stream);
+    if (rc) return rc;
+    HIP_TRY(e);
     return BGS_OK;
 }
 
@@ -1002,6 +1109,18 @@ int bgs_rollout(bgs_batch* b, uint64_t seed, int32_t max_plies, uint32_t flags) 
     return finish_launch();
 }
 
+// ---- the analysis calls: evaluation, tree search, forest, solver.  Each declares its outputs in an OutputPlan and
+// goes through run_outputs() ("Outputs of an analysis call"); d[i] below is output i in declaration order.
+
+// the outputs the four tree searches of a game share; cells: root moves of the batch (n x width, n x W x H x W)
+static void add_search_outputs(bgs::OutputPlan& plan, const bgs_batch* b, size_t cells, int32_t* counts, int32_t* visits,
+                               int32_t* best, int32_t* nodes) {
+    plan.add("counts", counts, cells * 3 * sizeof(int32_t), false);
+    plan.add("visits", visits, cells * sizeof(int32_t));
+    plan.add("best", best, (size_t)b->n * sizeof(int32_t));
+    plan.add("nodes", nodes, (size_t)b->n * sizeof(int32_t));
+}
+
 // the body of both evaluate_actions entry points (the caller has entered the batch's device)
 static int connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy, int32_t* counts,
                                     int counts_on_device) {
@@ -1011,23 +1130,14 @@ static int connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playout
          64 * BGS_CONNECT_MAX_WORDS, b->cg.h, b->cg.w);
     NEED(playouts >= 1, "playouts must be >= 1 (got %d)", playouts);
     NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    NEED(!counts_on_device || (reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
+    bgs::OutputPlan plan;
+    plan.add("counts", counts, (size_t)b->n * b->cg.w * 3 * sizeof(int32_t), false);
+    // (this entry point reports a misaligned device pointer before the overflow)
+    NEED(!counts_on_device || plan.misaligned() < 0, "device counts must be 16-byte aligned");
     NEED(b->n <= INT64_MAX / b->cg.w / playouts, "n * width * playouts overflows int64 (%lld x %d x %d)", (long long)b->n,
          b->cg.w, playouts);
-    const size_t bytes = (size_t)b->n * b->cg.w * 3 * sizeof(int32_t);
-    if (counts_on_device) {
-        bgs::connect_evaluate(b, seed, playouts, max_plies, counts, policy);
-        return finish_launch();
-    }
-    int32_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
-    bgs::connect_evaluate(b, seed, playouts, max_plies, d, policy);
-    int rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, bytes);
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    return run_outputs(b, plan, counts_on_device, nullptr,
+                       [&](void* const* d, void*) { bgs::connect_evaluate(b, seed, playouts, max_plies, i32(d[0]), policy); });
 }
 
 int bgs_connect_evaluate_actions(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
@@ -1041,9 +1151,8 @@ int bgs_connect_evaluate_actions_policy(bgs_batch* b, uint64_t seed, int32_t pla
                                         int counts_on_device) {
     int rc = enter(b);
     if (rc) return rc;
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "evaluate_actions: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
+    rc = policy_check("evaluate_actions", policy);
+    if (rc) return rc;
     return connect_evaluate_actions(b, seed, playouts, max_plies, policy, counts, counts_on_device);
 }
 
@@ -1055,38 +1164,21 @@ int bgs_connect_evaluate_actions_halving(bgs_batch* b, uint64_t seed, int32_t bu
     NEED(b->game == BGS_GAME_CONNECT, "evaluate_actions_halving: Connect batches only");
     NEED(!b->generic, "evaluate_actions_halving: bit-packed Connect boards only (up to %d bits a plane); %dx%d boards are generic",
          64 * BGS_CONNECT_MAX_WORDS, b->cg.h, b->cg.w);
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "evaluate_actions_halving: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
+    rc = policy_check("evaluate_actions_halving", policy);
+    if (rc) return rc;
     NEED(budget >= bgs::connect_halving_min_budget(b->cg.w),
          "budget must be >= width * max(1, ceil(log2 width)) = %d, the least that gives every round a playout a column (got %d)",
          bgs::connect_halving_min_budget(b->cg.w), budget);
     NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
     NEED(b->n <= INT64_MAX / b->cg.w / budget, "n * width * budget overflows int64 (%lld x %d x %d)", (long long)b->n, b->cg.w, budget);
     const size_t cells = (size_t)b->n * b->cg.w;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(given) & 15u) == 0, "device given must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
-        bgs::connect_evaluate_halving(b, seed, budget, max_plies, policy, counts, given, best);
-        return finish_launch();
-    }
-    // one device buffer: counts, given, best -- each 16-byte aligned
-    const size_t counts_bytes = cells * 3 * sizeof(int32_t), given_bytes = cells * sizeof(int32_t), best_bytes = (size_t)b->n * sizeof(int32_t);
-    const size_t given_off = (counts_bytes + 15) & ~(size_t)15, best_off = given_off + ((given_bytes + 15) & ~(size_t)15);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), best_off + best_bytes, b->stream));
-    bgs::connect_evaluate_halving(b, seed, budget, max_plies, policy, reinterpret_cast<int32_t*>(d),
-                                  given ? reinterpret_cast<int32_t*>(d + given_off) : nullptr,
-                                  best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr);
-    rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
-    if (rc == BGS_OK && given) rc = copy_to_host(b, given, d + given_off, given_bytes);
-    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, best_bytes);
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    bgs::OutputPlan plan;
+    plan.add("counts", counts, cells * 3 * sizeof(int32_t), false);
+    plan.add("given", given, cells * sizeof(int32_t));
+    plan.add("best", best, (size_t)b->n * sizeof(int32_t));
+    return run_outputs(b, plan, on_device, nullptr, [&](void* const* d, void*) {
+        bgs::connect_evaluate_halving(b, seed, budget, max_plies, policy, i32(d[0]), i32(d[1]), i32(d[2]));
+    });
 }
 
 // the checks of the search parameters, the same in the four search entry points; `entry` names the caller in the messages
@@ -1100,9 +1192,8 @@ static int search_params_check(const char* entry, const bgs_batch* b, int32_t it
          "iterations * leaf_playouts must be <= 2^29, so that scores stay in int32 (got %d x %d)", iterations, leaf_playouts);
     NEED(explore >= 0 && explore <= (1 << 18), "explore must be 0 .. 2^18 = 262144 (got %d)", explore);
     NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "%s: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", entry, policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
+    const int rc = policy_check(entry, policy);
+    if (rc) return rc;
     NEED(b->n <= INT64_MAX / iterations / leaf_playouts, "n * iterations * leaf_playouts overflows int64 (%lld x %d x %d)",
          (long long)b->n, iterations, leaf_playouts);
     return BGS_OK;
@@ -1127,8 +1218,8 @@ int bgs_connect_search_workspace_bytes(const bgs_batch* b, int32_t iterations, s
     return connect_search_check(b, iterations, bytes);
 }
 
-// bgs_connect_search_actions and bgs_connect_search_actions_proving: the same checks, workspace and buffer plan; `entry`
-// names the caller in the messages, and the plain entry point has neither proved nor done
+// bgs_connect_search_actions and bgs_connect_search_actions_proving: the same checks and workspace; `entry` names the
+// caller in the messages, and the proving entry point declares two more outputs
 static int connect_search_entry(const char* entry, bool proving, bgs_batch* b, uint64_t seed, int32_t iterations,
                                 int32_t leaf_playouts, int32_t explore, int32_t max_plies, int policy, int32_t* counts,
                                 int32_t* visits, int32_t* best, int32_t* nodes, int8_t* proved, int32_t* done, void* workspace,
@@ -1141,62 +1232,23 @@ static int connect_search_entry(const char* entry, bool proving, bgs_batch* b, u
     if (rc) return rc;
     rc = search_params_check(entry, b, iterations, leaf_playouts, explore, max_plies, policy);
     if (rc) return rc;
-    const auto launch = [&](int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int8_t* d_proved, int32_t* d_done,
-                            void* d_workspace) {
-        if (proving) {
-            bgs::connect_search_proving(b, seed, iterations, leaf_playouts, explore, max_plies, policy, d_counts, d_visits, d_best,
-                                        d_nodes, d_proved, d_done, d_workspace);
-        } else {
-            bgs::connect_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, d_counts, d_visits, d_best, d_nodes,
-                                d_workspace);
-        }
-    };
     const size_t cells = (size_t)b->n * b->cg.w;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(visits) & 15u) == 0, "device visits must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(nodes) & 15u) == 0, "device nodes must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(proved) & 15u) == 0, "device proved must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(done) & 15u) == 0, "device done must be 16-byte aligned");
-        NEED(workspace != nullptr, "workspace is NULL (on_device: the caller owns it; bgs_connect_search_workspace_bytes says how large)");
-        NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
-        NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
-        launch(counts, visits, best, nodes, proved, done, workspace);
-        return finish_launch();
+    bgs::OutputPlan plan;
+    add_search_outputs(plan, b, cells, counts, visits, best, nodes);
+    if (proving) {
+        plan.add("proved", proved, cells * sizeof(int8_t));
+        plan.add("done", done, (size_t)b->n * sizeof(int32_t));
     }
-    if (workspace != nullptr) {
-        NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
-        NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
-    }
-    // one device buffer: counts, visits, best, nodes (proving: and done, proved) -- each 16-byte aligned -- and the workspace
-    // when the caller gave none
-    const auto up = [](size_t x, size_t a) { return (x + a - 1) & ~(a - 1); };
-    const size_t counts_bytes = cells * 3 * sizeof(int32_t), visits_bytes = cells * sizeof(int32_t), board_bytes = (size_t)b->n * sizeof(int32_t);
-    const size_t proved_bytes = cells * sizeof(int8_t);
-    const size_t visits_off = up(counts_bytes, 16), best_off = visits_off + up(visits_bytes, 16), nodes_off = best_off + up(board_bytes, 16);
-    const size_t done_off = nodes_off + up(board_bytes, 16), proved_off = done_off + up(board_bytes, 16);
-    const size_t outputs_end = proving ? proved_off + proved_bytes : nodes_off + board_bytes;
-    // the library's own workspace starts at the first 256-byte boundary behind the outputs, wherever the pool put `d`
-    const size_t tree_room = workspace ? 0 : need + 256;
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), outputs_end + tree_room, b->stream));
-    uint8_t* const own = reinterpret_cast<uint8_t*>(up(reinterpret_cast<uintptr_t>(d + outputs_end), 256));
-    launch(reinterpret_cast<int32_t*>(d), visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
-           best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr, nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr,
-           proved ? reinterpret_cast<int8_t*>(d + proved_off) : nullptr, done ? reinterpret_cast<int32_t*>(d + done_off) : nullptr,
-           workspace ? workspace : own);
-    rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
-    if (rc == BGS_OK && visits) rc = copy_to_host(b, visits, d + visits_off, visits_bytes);
-    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, board_bytes);
-    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d + nodes_off, board_bytes);
-    if (rc == BGS_OK && proved) rc = copy_to_host(b, proved, d + proved_off, proved_bytes);
-    if (rc == BGS_OK && done) rc = copy_to_host(b, done, d + done_off, board_bytes);
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    const Workspace ws{workspace, workspace_bytes, need, "bgs_connect_search_workspace_bytes"};
+    return run_outputs(b, plan, on_device, &ws, [&](void* const* d, void* tree) {
+        if (proving) {
+            bgs::connect_search_proving(b, seed, iterations, leaf_playouts, explore, max_plies, policy, i32(d[0]), i32(d[1]), i32(d[2]),
+                                        i32(d[3]), static_cast<int8_t*>(d[4]), i32(d[5]), tree);
+        } else {
+            bgs::connect_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, i32(d[0]), i32(d[1]), i32(d[2]),
+                                i32(d[3]), tree);
+        }
+    });
 }
 
 int bgs_connect_search_actions(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore,
@@ -1228,13 +1280,6 @@ static int connect_forest_check(const bgs_batch* b, int32_t capacity, size_t* by
     return BGS_OK;
 }
 
-static int connect_forest_pointer(const void* forest, size_t forest_bytes, size_t need) {
-    NEED(forest != nullptr, "forest is NULL (the caller owns it; bgs_connect_forest_bytes says how large)");
-    NEED((reinterpret_cast<uintptr_t>(forest) & 255u) == 0, "the forest must be 256-byte aligned");
-    NEED(forest_bytes >= need, "the forest is too small: %zu bytes, %zu needed", forest_bytes, need);
-    return BGS_OK;
-}
-
 int bgs_connect_forest_bytes(const bgs_batch* b, int32_t capacity, size_t* bytes) {
     NEED(b != nullptr, "batch is NULL");
     NEED(bytes != nullptr, "bytes is NULL");
@@ -1252,41 +1297,15 @@ int bgs_connect_forest_search(bgs_batch* b, uint64_t seed, int32_t iterations, i
     if (rc) return rc;
     rc = search_params_check("forest_search", b, iterations, leaf_playouts, explore, max_plies, policy);
     if (rc) return rc;
-    rc = connect_forest_pointer(forest, forest_bytes, need);
+    rc = forest_pointer(forest, forest_bytes, need, "bgs_connect_forest_bytes");
     if (rc) return rc;
-    const size_t cells = (size_t)b->n * b->cg.w;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(visits) & 15u) == 0, "device visits must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(nodes) & 15u) == 0, "device nodes must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(carried) & 15u) == 0, "device carried must be 16-byte aligned");
-        bgs::connect_forest_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, capacity, restart, counts, visits,
-                                   best, nodes, carried, forest);
-        return finish_launch();
-    }
-    // one device buffer: counts, visits, best, nodes, carried -- each 16-byte aligned
-    const auto up = [](size_t x, size_t a) { return (x + a - 1) & ~(a - 1); };
-    const size_t counts_bytes = cells * 3 * sizeof(int32_t), visits_bytes = cells * sizeof(int32_t), board_bytes = (size_t)b->n * sizeof(int32_t);
-    const size_t visits_off = up(counts_bytes, 16), best_off = visits_off + up(visits_bytes, 16), nodes_off = best_off + up(board_bytes, 16);
-    const size_t carried_off = nodes_off + up(board_bytes, 16);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), carried_off + board_bytes, b->stream));
-    bgs::connect_forest_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, capacity, restart,
-                               reinterpret_cast<int32_t*>(d), visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
-                               best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr,
-                               nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr,
-                               carried ? reinterpret_cast<int32_t*>(d + carried_off) : nullptr, forest);
-    rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
-    if (rc == BGS_OK && visits) rc = copy_to_host(b, visits, d + visits_off, visits_bytes);
-    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, board_bytes);
-    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d + nodes_off, board_bytes);
-    if (rc == BGS_OK && carried) rc = copy_to_host(b, carried, d + carried_off, board_bytes);
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    bgs::OutputPlan plan;
+    add_search_outputs(plan, b, (size_t)b->n * b->cg.w, counts, visits, best, nodes);
+    plan.add("carried", carried, (size_t)b->n * sizeof(int32_t));
+    return run_outputs(b, plan, on_device, nullptr, [&](void* const* d, void*) {
+        bgs::connect_forest_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, capacity, restart, i32(d[0]),
+                                   i32(d[1]), i32(d[2]), i32(d[3]), i32(d[4]), forest);
+    });
 }
 
 int bgs_connect_forest_advance(bgs_batch* b, const int32_t* columns, int32_t capacity, int32_t* kept, void* forest,
@@ -1297,30 +1316,22 @@ int bgs_connect_forest_advance(bgs_batch* b, const int32_t* columns, int32_t cap
     size_t need = 0;
     rc = connect_forest_check(b, capacity, &need);
     if (rc) return rc;
-    rc = connect_forest_pointer(forest, forest_bytes, need);
+    rc = forest_pointer(forest, forest_bytes, need, "bgs_connect_forest_bytes");
     if (rc) return rc;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(columns) & 3u) == 0, "device columns must be 4-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(kept) & 3u) == 0, "device kept must be 4-byte aligned");
-        bgs::connect_forest_advance(b, columns, capacity, kept, forest);
-        return finish_launch();
-    }
-    // one device buffer: columns, kept
-    const size_t board_bytes = (size_t)b->n * sizeof(int32_t);
-    int32_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), 2 * board_bytes, b->stream));
-    rc = to_device(b, d, columns, (size_t)b->n);
-    if (rc == BGS_OK) {
-        bgs::connect_forest_advance(b, d, capacity, kept ? d + b->n : nullptr, forest);
-        rc = finish_launch();
-    }
-    if (rc == BGS_OK && kept) rc = copy_to_host(b, kept, d + b->n, board_bytes);
-    // (without kept no copy back waits for the stream, and the caller's `columns` must have been read when the call returns)
-    if (rc == BGS_OK && !kept && hipStreamSynchronize(b->stream) != hipSuccess) rc = bgs::fail(BGS_ERR_RUNTIME, "hipStreamSynchronize failed");
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    return forest_advance(b, columns, "columns", kept, on_device, [&](const int32_t* d_columns, int32_t* d_kept) {
+        bgs::connect_forest_advance(b, d_columns, capacity, d_kept, forest);
+    });
+}
+
+// the outputs of both solvers; d[2], the node counter, keeps its 8-byte rule, and without a caller's counter the total
+// goes to the batch's own scratch word (behind the work-queue head)
+static void add_solve_outputs(bgs::OutputPlan& plan, size_t cells, int8_t* codes, int16_t* plies, uint64_t* nodes) {
+    plan.add("codes", codes, cells * sizeof(int8_t), false);
+    plan.add("plies", plies, cells * sizeof(int16_t));
+    plan.add("nodes", nodes, sizeof(uint64_t), true, 8);
+}
+static unsigned long long* solve_counter(const bgs_batch* b, void* d_nodes) {
+    return d_nodes ? static_cast<unsigned long long*>(d_nodes) : reinterpret_cast<unsigned long long*>(b->d_work_count) + 1;
 }
 
 int bgs_connect_solve_actions(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
@@ -1333,33 +1344,14 @@ int bgs_connect_solve_actions(bgs_batch* b, int32_t depth, int64_t max_nodes, in
          64 * BGS_CONNECT_MAX_WORDS, b->cg.h, b->cg.w);
     NEED(depth >= 1, "depth must be >= 1 (got %d)", depth);
     NEED(max_nodes >= 1, "max_nodes must be >= 1 (got %lld)", (long long)max_nodes);
-    const size_t cells = (size_t)b->n * b->cg.w;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(codes) & 15u) == 0, "device codes must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(plies) & 15u) == 0, "device plies must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(nodes) & 7u) == 0, "device nodes must be 8-byte aligned");
-        // without a caller's counter the total goes to the batch's own scratch word (behind the work-queue head)
-        unsigned long long* d_nodes = nodes ? reinterpret_cast<unsigned long long*>(nodes)
-                                            : reinterpret_cast<unsigned long long*>(b->d_work_count) + 1;
-        bgs::connect_solve(b, depth, max_nodes, codes, plies, d_nodes);
-        return finish_launch();
-    }
-    // one device buffer: nodes (8 bytes), codes, plies -- each 16-byte aligned
-    const size_t codes_off = 16, plies_off = codes_off + ((cells + 15) & ~(size_t)15);
-    const size_t bytes = plies_off + cells * sizeof(int16_t);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
-    bgs::connect_solve(b, depth, max_nodes, reinterpret_cast<int8_t*>(d + codes_off),
-                       plies ? reinterpret_cast<int16_t*>(d + plies_off) : nullptr, reinterpret_cast<unsigned long long*>(d));
-    rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, codes, d + codes_off, cells);
-    if (rc == BGS_OK && plies) rc = copy_to_host(b, plies, d + plies_off, cells * sizeof(int16_t));
-    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d, sizeof(uint64_t));
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    bgs::OutputPlan plan;
+    add_solve_outputs(plan, (size_t)b->n * b->cg.w, codes, plies, nodes);
+    return run_outputs(b, plan, on_device, nullptr, [&](void* const* d, void*) {
+        bgs::connect_solve(b, depth, max_nodes, static_cast<int8_t*>(d[0]), static_cast<int16_t*>(d[1]), solve_counter(b, d[2]));
+    });
 }
+
+static size_t bounce_slots(const bgs_batch* b) { return (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w; }
 
 // bgs_bounce_evaluate_moves and bgs_bounce_evaluate_moves_policy behind their entry checks (enter(b), the policy's range)
 static int bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int policy, int32_t* counts,
@@ -1370,29 +1362,19 @@ static int bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, 
          BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
     NEED(playouts >= 1, "playouts must be >= 1 (got %d)", playouts);
     NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    NEED(!counts_on_device || (reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
-    const int64_t slots = (int64_t)b->bg.w * b->bg.h * b->bg.w;
+    const int64_t slots = (int64_t)bounce_slots(b);
+    bgs::OutputPlan plan;
+    plan.add("counts", counts, (size_t)b->n * (size_t)slots * 3 * sizeof(int32_t), false);
+    // (this entry point reports a misaligned device pointer before the overflow)
+    NEED(!counts_on_device || plan.misaligned() < 0, "device counts must be 16-byte aligned");
     NEED(b->n <= INT64_MAX / slots / playouts, "n * width * height * width * playouts overflows int64 (%lld x %lld x %d)",
          (long long)b->n, (long long)slots, playouts);
-    // scratch: the roots' legal-move prefix and the workgroups' totals, in the staging region (ordered on the stream)
-    Stage st(b);
-    uint64_t* d_ends = st.take<uint64_t>((size_t)b->n);
-    uint64_t* d_totals = st.take<uint64_t>((size_t)(b->n + BGS_BLOCK - 1) / BGS_BLOCK);
-    NEED(d_ends && d_totals, "staging region too small");
-    const size_t bytes = (size_t)b->n * (size_t)slots * 3 * sizeof(int32_t);
-    if (counts_on_device) {
-        bgs::bounce_evaluate(b, seed, playouts, max_plies, counts, d_ends, d_totals, policy);
-        return finish_launch();
-    }
-    int32_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
-    bgs::bounce_evaluate(b, seed, playouts, max_plies, d, d_ends, d_totals, policy);
-    int rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, bytes);
-    const hipError_t e = hipFreeAsync(d, b->stream);
+    uint64_t *d_ends, *d_totals;
+    const int rc = bounce_move_scratch(b, &d_ends, &d_totals);
     if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    return run_outputs(b, plan, counts_on_device, nullptr, [&](void* const* d, void*) {
+        bgs::bounce_evaluate(b, seed, playouts, max_plies, i32(d[0]), d_ends, d_totals, policy);
+    });
 }
 
 int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies, int32_t* counts,
@@ -1406,9 +1388,8 @@ int bgs_bounce_evaluate_moves_policy(bgs_batch* b, uint64_t seed, int32_t playou
                                      int counts_on_device) {
     int rc = enter(b);
     if (rc) return rc;
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "evaluate_moves: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
+    rc = policy_check("evaluate_moves", policy);
+    if (rc) return rc;
     return bounce_evaluate_moves(b, seed, playouts, max_plies, policy, counts, counts_on_device);
 }
 
@@ -1421,38 +1402,21 @@ int bgs_bounce_evaluate_moves_halving(bgs_batch* b, uint64_t seed, int32_t budge
     NEED(!b->generic,
          "evaluate_moves_halving: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
          BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
-    NEED(policy == BGS_POLICY_UNIFORM || policy == BGS_POLICY_DECISIVE,
-         "evaluate_moves_halving: unknown policy %d (BGS_POLICY_UNIFORM %d, BGS_POLICY_DECISIVE %d)", policy, BGS_POLICY_UNIFORM,
-         BGS_POLICY_DECISIVE);
+    rc = policy_check("evaluate_moves_halving", policy);
+    if (rc) return rc;
     NEED(budget >= 1, "budget must be >= 1 (got %d)", budget);
     NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    const int64_t slots = (int64_t)b->bg.w * b->bg.h * b->bg.w;
+    const int64_t slots = (int64_t)bounce_slots(b);
     NEED(b->n <= INT64_MAX / slots / budget, "n * width * height * width * budget overflows int64 (%lld x %lld x %d)", (long long)b->n,
          (long long)slots, budget);
     const size_t cells = (size_t)b->n * (size_t)slots;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(given) & 15u) == 0, "device given must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
-        bgs::bounce_evaluate_halving(b, seed, budget, max_plies, policy, counts, given, best);
-        return finish_launch();
-    }
-    // one device buffer: counts, given, best -- each 16-byte aligned
-    const size_t counts_bytes = cells * 3 * sizeof(int32_t), given_bytes = cells * sizeof(int32_t), best_bytes = (size_t)b->n * sizeof(int32_t);
-    const size_t given_off = (counts_bytes + 15) & ~(size_t)15, best_off = given_off + ((given_bytes + 15) & ~(size_t)15);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), best_off + best_bytes, b->stream));
-    bgs::bounce_evaluate_halving(b, seed, budget, max_plies, policy, reinterpret_cast<int32_t*>(d),
-                                 given ? reinterpret_cast<int32_t*>(d + given_off) : nullptr,
-                                 best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr);
-    rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
-    if (rc == BGS_OK && given) rc = copy_to_host(b, given, d + given_off, given_bytes);
-    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, best_bytes);
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    bgs::OutputPlan plan;
+    plan.add("counts", counts, cells * 3 * sizeof(int32_t), false);
+    plan.add("given", given, cells * sizeof(int32_t));
+    plan.add("best", best, (size_t)b->n * sizeof(int32_t));
+    return run_outputs(b, plan, on_device, nullptr, [&](void* const* d, void*) {
+        bgs::bounce_evaluate_halving(b, seed, budget, max_plies, policy, i32(d[0]), i32(d[1]), i32(d[2]));
+    });
 }
 
 // the checks of both Bounce search entry points that need no device; *bytes: the workspace of the batch
@@ -1477,8 +1441,8 @@ int bgs_bounce_search_workspace_bytes(const bgs_batch* b, int32_t iterations, in
     return bounce_search_check(b, iterations, edges, bytes);
 }
 
-// bgs_bounce_search_moves and bgs_bounce_search_moves_proving: the same checks, workspace and buffer plan; `entry` names
-// the caller in the messages, and the plain entry point has neither proved nor done
+// bgs_bounce_search_moves and bgs_bounce_search_moves_proving: the same checks and workspace; `entry` names the caller
+// in the messages, and the proving entry point declares two more outputs
 static int bounce_search_entry(const char* entry, bool proving, bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts,
                                int32_t explore, int32_t max_plies, int policy, int32_t edges, int32_t* counts, int32_t* visits,
                                int32_t* best, int32_t* nodes, int32_t* used, int8_t* proved, int32_t* done, void* workspace,
@@ -1491,65 +1455,24 @@ static int bounce_search_entry(const char* entry, bool proving, bgs_batch* b, ui
     if (rc) return rc;
     rc = search_params_check(entry, b, iterations, leaf_playouts, explore, max_plies, policy);
     if (rc) return rc;
-    const auto launch = [&](int32_t* d_counts, int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int8_t* d_proved,
-                            int32_t* d_done, void* d_workspace) {
+    const size_t cells = (size_t)b->n * bounce_slots(b);
+    bgs::OutputPlan plan;
+    add_search_outputs(plan, b, cells, counts, visits, best, nodes);
+    plan.add("used", used, (size_t)b->n * sizeof(int32_t));
+    if (proving) {
+        plan.add("proved", proved, cells * sizeof(int8_t));
+        plan.add("done", done, (size_t)b->n * sizeof(int32_t));
+    }
+    const Workspace ws{workspace, workspace_bytes, need, "bgs_bounce_search_workspace_bytes"};
+    return run_outputs(b, plan, on_device, &ws, [&](void* const* d, void* tree) {
         if (proving) {
-            bgs::bounce_search_proving(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, d_counts, d_visits, d_best,
-                                       d_nodes, d_used, d_proved, d_done, d_workspace);
+            bgs::bounce_search_proving(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, i32(d[0]), i32(d[1]),
+                                       i32(d[2]), i32(d[3]), i32(d[4]), static_cast<int8_t*>(d[5]), i32(d[6]), tree);
         } else {
-            bgs::bounce_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, d_counts, d_visits, d_best, d_nodes,
-                               d_used, d_workspace);
+            bgs::bounce_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, edges, i32(d[0]), i32(d[1]), i32(d[2]),
+                               i32(d[3]), i32(d[4]), tree);
         }
-    };
-    const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(visits) & 15u) == 0, "device visits must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(nodes) & 15u) == 0, "device nodes must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(used) & 15u) == 0, "device used must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(proved) & 15u) == 0, "device proved must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(done) & 15u) == 0, "device done must be 16-byte aligned");
-        NEED(workspace != nullptr, "workspace is NULL (on_device: the caller owns it; bgs_bounce_search_workspace_bytes says how large)");
-        NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
-        NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
-        launch(counts, visits, best, nodes, used, proved, done, workspace);
-        return finish_launch();
-    }
-    if (workspace != nullptr) {
-        NEED((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "the workspace must be 256-byte aligned");
-        NEED(workspace_bytes >= need, "the workspace is too small: %zu bytes, %zu needed", workspace_bytes, need);
-    }
-    // one device buffer: counts, visits, best, nodes, used (proving: and done, proved) -- each 16-byte aligned -- and the
-    // workspace when the caller gave none
-    const auto up = [](size_t x, size_t a) { return (x + a - 1) & ~(a - 1); };
-    const size_t counts_bytes = cells * 3 * sizeof(int32_t), visits_bytes = cells * sizeof(int32_t), board_bytes = (size_t)b->n * sizeof(int32_t);
-    const size_t proved_bytes = cells * sizeof(int8_t);
-    const size_t visits_off = up(counts_bytes, 16), best_off = visits_off + up(visits_bytes, 16), nodes_off = best_off + up(board_bytes, 16);
-    const size_t used_off = nodes_off + up(board_bytes, 16);
-    const size_t done_off = used_off + up(board_bytes, 16), proved_off = done_off + up(board_bytes, 16);
-    const size_t outputs_end = proving ? proved_off + proved_bytes : used_off + board_bytes;
-    // the library's own workspace starts at the first 256-byte boundary behind the outputs, wherever the pool put `d`
-    const size_t tree_room = workspace ? 0 : need + 256;
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), outputs_end + tree_room, b->stream));
-    uint8_t* const own = reinterpret_cast<uint8_t*>(up(reinterpret_cast<uintptr_t>(d + outputs_end), 256));
-    launch(reinterpret_cast<int32_t*>(d), visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
-           best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr, nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr,
-           used ? reinterpret_cast<int32_t*>(d + used_off) : nullptr, proved ? reinterpret_cast<int8_t*>(d + proved_off) : nullptr,
-           done ? reinterpret_cast<int32_t*>(d + done_off) : nullptr, workspace ? workspace : own);
-    rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
-    if (rc == BGS_OK && visits) rc = copy_to_host(b, visits, d + visits_off, visits_bytes);
-    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, board_bytes);
-    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d + nodes_off, board_bytes);
-    if (rc == BGS_OK && used) rc = copy_to_host(b, used, d + used_off, board_bytes);
-    if (rc == BGS_OK && proved) rc = copy_to_host(b, proved, d + proved_off, proved_bytes);
-    if (rc == BGS_OK && done) rc = copy_to_host(b, done, d + done_off, board_bytes);
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    });
 }
 
 int bgs_bounce_search_moves(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
@@ -1585,21 +1508,10 @@ static int bounce_forest_check(const bgs_batch* b, int32_t nodes_cap, int32_t ed
     return BGS_OK;
 }
 
-static int bounce_forest_pointer(const void* forest, size_t forest_bytes, size_t need) {
-    NEED(forest != nullptr, "forest is NULL (the caller owns it; bgs_bounce_forest_bytes says how large)");
-    NEED((reinterpret_cast<uintptr_t>(forest) & 255u) == 0, "the forest must be 256-byte aligned");
-    NEED(forest_bytes >= need, "the forest is too small: %zu bytes, %zu needed", forest_bytes, need);
-    return BGS_OK;
-}
-
 int bgs_bounce_forest_bytes(const bgs_batch* b, int32_t nodes, int32_t edges, size_t* bytes) {
     NEED(b != nullptr, "batch is NULL");
     NEED(bytes != nullptr, "bytes is NULL");
-    size_t need = 0;
-    const int rc = bounce_forest_check(b, nodes, edges, &need);
-    if (rc) return rc;
-    *bytes = need;
-    return BGS_OK;
+    return bounce_forest_check(b, nodes, edges, bytes);
 }
 
 int bgs_bounce_forest_search(bgs_batch* b, uint64_t seed, int32_t iterations, int32_t leaf_playouts, int32_t explore, int32_t max_plies,
@@ -1613,44 +1525,16 @@ int bgs_bounce_forest_search(bgs_batch* b, uint64_t seed, int32_t iterations, in
     if (rc) return rc;
     rc = search_params_check("bounce_forest_search", b, iterations, leaf_playouts, explore, max_plies, policy);
     if (rc) return rc;
-    rc = bounce_forest_pointer(forest, forest_bytes, need);
+    rc = forest_pointer(forest, forest_bytes, need, "bgs_bounce_forest_bytes");
     if (rc) return rc;
-    const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(counts) & 15u) == 0, "device counts must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(visits) & 15u) == 0, "device visits must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(best) & 15u) == 0, "device best must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(nodes) & 15u) == 0, "device nodes must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(used) & 15u) == 0, "device used must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(carried) & 15u) == 0, "device carried must be 16-byte aligned");
-        bgs::bounce_forest_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, nodes_cap, edges, restart, counts,
-                                  visits, best, nodes, used, carried, forest);
-        return finish_launch();
-    }
-    // one device buffer: counts, visits, best, nodes, used, carried -- each 16-byte aligned
-    const auto up = [](size_t x, size_t a) { return (x + a - 1) & ~(a - 1); };
-    const size_t counts_bytes = cells * 3 * sizeof(int32_t), visits_bytes = cells * sizeof(int32_t), board_bytes = (size_t)b->n * sizeof(int32_t);
-    const size_t visits_off = up(counts_bytes, 16), best_off = visits_off + up(visits_bytes, 16), nodes_off = best_off + up(board_bytes, 16);
-    const size_t used_off = nodes_off + up(board_bytes, 16), carried_off = used_off + up(board_bytes, 16);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), carried_off + board_bytes, b->stream));
-    bgs::bounce_forest_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, nodes_cap, edges, restart,
-                              reinterpret_cast<int32_t*>(d), visits ? reinterpret_cast<int32_t*>(d + visits_off) : nullptr,
-                              best ? reinterpret_cast<int32_t*>(d + best_off) : nullptr,
-                              nodes ? reinterpret_cast<int32_t*>(d + nodes_off) : nullptr,
-                              used ? reinterpret_cast<int32_t*>(d + used_off) : nullptr,
-                              carried ? reinterpret_cast<int32_t*>(d + carried_off) : nullptr, forest);
-    rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, counts, d, counts_bytes);
-    if (rc == BGS_OK && visits) rc = copy_to_host(b, visits, d + visits_off, visits_bytes);
-    if (rc == BGS_OK && best) rc = copy_to_host(b, best, d + best_off, board_bytes);
-    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d + nodes_off, board_bytes);
-    if (rc == BGS_OK && used) rc = copy_to_host(b, used, d + used_off, board_bytes);
-    if (rc == BGS_OK && carried) rc = copy_to_host(b, carried, d + carried_off, board_bytes);
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    bgs::OutputPlan plan;
+    add_search_outputs(plan, b, (size_t)b->n * bounce_slots(b), counts, visits, best, nodes);
+    plan.add("used", used, (size_t)b->n * sizeof(int32_t));
+    plan.add("carried", carried, (size_t)b->n * sizeof(int32_t));
+    return run_outputs(b, plan, on_device, nullptr, [&](void* const* d, void*) {
+        bgs::bounce_forest_search(b, seed, iterations, leaf_playouts, explore, max_plies, policy, nodes_cap, edges, restart, i32(d[0]),
+                                  i32(d[1]), i32(d[2]), i32(d[3]), i32(d[4]), i32(d[5]), forest);
+    });
 }
 
 int bgs_bounce_forest_advance(bgs_batch* b, const int32_t* slots, int32_t nodes_cap, int32_t edges, int32_t* kept, void* forest,
@@ -1661,30 +1545,11 @@ int bgs_bounce_forest_advance(bgs_batch* b, const int32_t* slots, int32_t nodes_
     size_t need = 0;
     rc = bounce_forest_check(b, nodes_cap, edges, &need);
     if (rc) return rc;
-    rc = bounce_forest_pointer(forest, forest_bytes, need);
+    rc = forest_pointer(forest, forest_bytes, need, "bgs_bounce_forest_bytes");
     if (rc) return rc;
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(slots) & 3u) == 0, "device slots must be 4-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(kept) & 3u) == 0, "device kept must be 4-byte aligned");
-        bgs::bounce_forest_advance(b, slots, nodes_cap, edges, kept, forest);
-        return finish_launch();
-    }
-    // one device buffer: slots, kept
-    const size_t board_bytes = (size_t)b->n * sizeof(int32_t);
-    int32_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), 2 * board_bytes, b->stream));
-    rc = to_device(b, d, slots, (size_t)b->n);
-    if (rc == BGS_OK) {
-        bgs::bounce_forest_advance(b, d, nodes_cap, edges, kept ? d + b->n : nullptr, forest);
-        rc = finish_launch();
-    }
-    if (rc == BGS_OK && kept) rc = copy_to_host(b, kept, d + b->n, board_bytes);
-    // (without kept no copy back waits for the stream, and the caller's `slots` must have been read when the call returns)
-    if (rc == BGS_OK && !kept && hipStreamSynchronize(b->stream) != hipSuccess) rc = bgs::fail(BGS_ERR_RUNTIME, "hipStreamSynchronize failed");
-    const hipError_t e = hipFreeAsync(d, b->stream);
-    if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    return forest_advance(b, slots, "slots", kept, on_device, [&](const int32_t* d_slots, int32_t* d_kept) {
+        bgs::bounce_forest_advance(b, d_slots, nodes_cap, edges, d_kept, forest);
+    });
 }
 
 int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
@@ -1699,38 +1564,15 @@ int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_
     NEED(depth <= BGS_BOUNCE_SOLVE_MAX_DEPTH, "depth %d is beyond the maximum of %d plies the search stack is sized for", depth,
          BGS_BOUNCE_SOLVE_MAX_DEPTH);
     NEED(max_nodes >= 1, "max_nodes must be >= 1 (got %lld)", (long long)max_nodes);
-    const size_t cells = (size_t)b->n * (size_t)b->bg.w * (size_t)b->bg.h * (size_t)b->bg.w;
-    // scratch: the boards' legal-move prefix and the workgroups' totals, in the staging region (ordered on the stream)
-    Stage st(b);
-    uint64_t* d_ends = st.take<uint64_t>((size_t)b->n);
-    uint64_t* d_totals = st.take<uint64_t>((size_t)(b->n + BGS_BLOCK - 1) / BGS_BLOCK);
-    NEED(d_ends && d_totals, "staging region too small");
-    if (on_device) {
-        NEED((reinterpret_cast<uintptr_t>(codes) & 15u) == 0, "device codes must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(plies) & 15u) == 0, "device plies must be 16-byte aligned");
-        NEED((reinterpret_cast<uintptr_t>(nodes) & 7u) == 0, "device nodes must be 8-byte aligned");
-        // without a caller's counter the total goes to the batch's own scratch word (behind the work-queue head)
-        unsigned long long* d_nodes = nodes ? reinterpret_cast<unsigned long long*>(nodes)
-                                            : reinterpret_cast<unsigned long long*>(b->d_work_count) + 1;
-        bgs::bounce_solve(b, depth, max_nodes, codes, plies, d_nodes, d_ends, d_totals);
-        return finish_launch();
-    }
-    // one device buffer: nodes (8 bytes), codes, plies -- each 16-byte aligned
-    const size_t codes_off = 16, plies_off = codes_off + ((cells + 15) & ~(size_t)15);
-    const size_t bytes = plies_off + cells * sizeof(int16_t);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, b->stream));
-    bgs::bounce_solve(b, depth, max_nodes, reinterpret_cast<int8_t*>(d + codes_off),
-                      plies ? reinterpret_cast<int16_t*>(d + plies_off) : nullptr, reinterpret_cast<unsigned long long*>(d), d_ends,
-                      d_totals);
-    rc = finish_launch();
-    if (rc == BGS_OK) rc = copy_to_host(b, codes, d + codes_off, cells);
-    if (rc == BGS_OK && plies) rc = copy_to_host(b, plies, d + plies_off, cells * sizeof(int16_t));
-    if (rc == BGS_OK && nodes) rc = copy_to_host(b, nodes, d, sizeof(uint64_t));
-    const hipError_t e = hipFreeAsync(d, b->stream);
+    uint64_t *d_ends, *d_totals;
+    rc = bounce_move_scratch(b, &d_ends, &d_totals);
     if (rc) return rc;
-    HIP_TRY(e);
-    return BGS_OK;
+    bgs::OutputPlan plan;
+    add_solve_outputs(plan, (size_t)b->n * bounce_slots(b), codes, plies, nodes);
+    return run_outputs(b, plan, on_device, nullptr, [&](void* const* d, void*) {
+        bgs::bounce_solve(b, depth, max_nodes, static_cast<int8_t*>(d[0]), static_cast<int16_t*>(d[1]), solve_counter(b, d[2]), d_ends,
+                          d_totals);
+    });
 }
 
 int bgs_steps(bgs_batch* b, uint64_t* steps) {

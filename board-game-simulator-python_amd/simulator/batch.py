@@ -683,6 +683,38 @@ class _Batch:
             raise RuntimeError(f"{who} needs torch with a GPU")
         return self._torch
 
+    def _device_tensors(self, who: str, specs, align: int = 16):
+        """The device tensors of a `*_tensor` call, in order: specs are (name, tensor or None, shape[, dtype name[,
+        optional]]), the dtype "int32" and not optional unless given.  A tensor that is None is allocated unless it is
+        optional; one that is there must be a contiguous device tensor of that dtype and shape whose address is a
+        multiple of `align`, else TypeError names the argument."""
+        t = self._need_torch(who)
+        rule = f", {align}-byte aligned" if align > 1 else ""
+        tensors = []
+        for name, x, shape, *rest in specs:
+            dtype, optional = rest + ["int32", False][len(rest):]
+            if x is None and not optional:
+                x = t.empty(shape, dtype=getattr(t, dtype), device=f"cuda:{self.device}")
+            if x is not None and not (x.is_cuda and x.dtype == getattr(t, dtype) and tuple(x.shape) == shape and x.is_contiguous()
+                                      and x.data_ptr() % align == 0):
+                raise TypeError(f"{name} must be a contiguous{rule} {dtype} device tensor of shape {shape}")
+            tensors.append(x)
+        return tensors
+
+    def _search_workspace(self, who: str, workspace, size_query, cache_key):
+        """The workspace of a `search_*_tensor` call: the caller's, or when None the batch's own for cache_key(),
+        allocated on first use.  size_query() runs on every call without a workspace, before the key is made: it refuses
+        bad arguments (ValueError) before anything is allocated for them."""
+        t = self._need_torch(who)
+        if workspace is None:
+            need, key = size_query(), cache_key()
+            workspace = self._search_workspaces.get(key)
+            if workspace is None:
+                workspace = self._search_workspaces[key] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
+        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        return workspace
+
     # ---- snapshot / restore in the reference's wire format (State.to_json / State.from_json) -------------------
     def to_json_states(self) -> list:
         """The batch as a list of reference-shaped State JSON dicts {"grid", "player", "winner"}
@@ -832,13 +864,7 @@ class ConnectBatch(_Batch):
         """`evaluate_actions` into a device tensor int32[n, width, 3] (allocated when None), enqueued on the batch's stream
         with no synchronisation.  Every entry is written."""
         playout_policy(policy)
-        t = self._need_torch("evaluate_actions_tensor")
-        shape = (self.n, self.width, 3)
-        if out is None:
-            out = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
-        if not (out.is_cuda and out.dtype == t.int32 and tuple(out.shape) == shape and out.is_contiguous()
-                and out.data_ptr() % 16 == 0):
-            raise TypeError(f"out must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        out, = self._device_tensors("evaluate_actions_tensor", [("out", out, (self.n, self.width, 3))])
         self._evaluate(seed, playouts, max_plies, policy, out.data_ptr(), 1)
         return out
 
@@ -871,20 +897,12 @@ class ConnectBatch(_Batch):
         """`evaluate_actions_halving` into device tensors int32[n, width, 3], int32[n, width] and int32[n] (allocated when
         None), enqueued on the batch's stream with no synchronisation: (counts, given, best).  Every entry is written."""
         code = playout_policy(policy)
-        t = self._need_torch("evaluate_actions_halving_tensor")
-        shapes = {"counts": (self.n, self.width, 3), "given": (self.n, self.width), "best": (self.n,)}
-        outs = {"counts": counts, "given": given, "best": best}
-        for name, shape in shapes.items():
-            x = outs[name]
-            if x is None:
-                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
-            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        outs = self._device_tensors("evaluate_actions_halving_tensor", [
+            ("counts", counts, (self.n, self.width, 3)), ("given", given, (self.n, self.width)), ("best", best, (self.n,))])
         _abi.check(_abi.lib().bgs_connect_evaluate_actions_halving(
             self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
-            ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["given"].data_ptr()),
-            ctypes.c_void_p(outs["best"].data_ptr()), 1))
-        return outs["counts"], outs["given"], outs["best"]
+            *(ctypes.c_void_p(x.data_ptr()) for x in outs), 1))
+        return tuple(outs)
 
     def search_workspace_bytes(self, iterations: int = 256) -> int:
         """bytes of device memory `search_actions` needs for its trees at `iterations` (bgs_connect_search_workspace_bytes)"""
@@ -923,28 +941,19 @@ class ConnectBatch(_Batch):
         `search_workspace_bytes(iterations)` bytes; None: a tensor of the batch's own, allocated on first use and kept per
         `iterations`.  The workspace needs no preparation, and calls on one stream may share it."""
         code = playout_policy(policy)
-        t = self._need_torch("search_actions_tensor")
-        shapes = {"counts": (self.n, self.width, 3), "visits": (self.n, self.width), "best": (self.n,), "nodes": (self.n,)}
-        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes}
-        for name, shape in shapes.items():
-            x = outs[name]
-            if x is None:
-                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
-            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
-        if workspace is None:
-            need = self.search_workspace_bytes(iterations)     # (refuses iterations < 1 before anything is allocated)
-            workspace = self._search_workspaces.get(int(iterations))
-            if workspace is None:
-                workspace = self._search_workspaces[int(iterations)] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
-        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
-            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        outs = self._device_tensors("search_actions_tensor", self._search_specs(counts, visits, best, nodes))
+        workspace = self._search_workspace("search_actions_tensor", workspace, lambda: self.search_workspace_bytes(iterations),
+                                           lambda: int(iterations))
         _abi.check(_abi.lib().bgs_connect_search_actions(
             self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["visits"].data_ptr()),
-            ctypes.c_void_p(outs["best"].data_ptr()), ctypes.c_void_p(outs["nodes"].data_ptr()),
+            ctypes.c_int32(max_plies), code, *(ctypes.c_void_p(x.data_ptr()) for x in outs),
             ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
-        return outs["counts"], outs["visits"], outs["best"], outs["nodes"]
+        return tuple(outs)
+
+    def _search_specs(self, counts, visits, best, nodes):
+        """the four outputs every tree search of this batch has, as `_device_tensors` takes them"""
+        return [("counts", counts, (self.n, self.width, 3)), ("visits", visits, (self.n, self.width)), ("best", best, (self.n,)),
+                ("nodes", nodes, (self.n,))]
 
     def search_actions_proving(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
                                explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1, policy: str = "uniform"):
@@ -980,31 +989,15 @@ class ConnectBatch(_Batch):
         nodes, proved, done).  Every entry is written.  `workspace` is `search_actions_tensor`'s, and the batch's own
         cached workspace serves both."""
         code = playout_policy(policy)
-        t = self._need_torch("search_actions_proving_tensor")
-        shapes = {"counts": (self.n, self.width, 3), "visits": (self.n, self.width), "best": (self.n,), "nodes": (self.n,),
-                  "proved": (self.n, self.width), "done": (self.n,)}
-        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "proved": proved, "done": done}
-        for name, shape in shapes.items():
-            dtype = t.int8 if name == "proved" else t.int32
-            x = outs[name]
-            if x is None:
-                x = outs[name] = t.empty(shape, dtype=dtype, device=f"cuda:{self.device}")
-            if not (x.is_cuda and x.dtype == dtype and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned {str(dtype).split('.')[-1]} device tensor of shape {shape}")
-        if workspace is None:
-            need = self.search_workspace_bytes(iterations)     # (refuses iterations < 1 before anything is allocated)
-            workspace = self._search_workspaces.get(int(iterations))
-            if workspace is None:
-                workspace = self._search_workspaces[int(iterations)] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
-        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
-            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        outs = self._device_tensors("search_actions_proving_tensor", self._search_specs(counts, visits, best, nodes) + [
+            ("proved", proved, (self.n, self.width), "int8"), ("done", done, (self.n,))])
+        workspace = self._search_workspace("search_actions_proving_tensor", workspace,
+                                           lambda: self.search_workspace_bytes(iterations), lambda: int(iterations))
         _abi.check(_abi.lib().bgs_connect_search_actions_proving(
             self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["visits"].data_ptr()),
-            ctypes.c_void_p(outs["best"].data_ptr()), ctypes.c_void_p(outs["nodes"].data_ptr()),
-            ctypes.c_void_p(outs["proved"].data_ptr()), ctypes.c_void_p(outs["done"].data_ptr()),
+            ctypes.c_int32(max_plies), code, *(ctypes.c_void_p(x.data_ptr()) for x in outs),
             ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
-        return outs["counts"], outs["visits"], outs["best"], outs["nodes"], outs["proved"], outs["done"]
+        return tuple(outs)
 
     def forest_bytes(self, capacity: int) -> int:
         """bytes of device memory a forest of this batch takes at `capacity` nodes a tree (bgs_connect_forest_bytes)"""
@@ -1036,16 +1029,9 @@ class ConnectBatch(_Batch):
                              with_plies: bool = True):
         """`solve_actions` into device tensors int8[n, width] and int16[n, width] (allocated when None; plies only
         `with_plies` or when given), enqueued on the batch's stream with no synchronisation: (codes, plies or None)."""
-        t = self._need_torch("solve_actions_tensor")
         shape = (self.n, self.width)
-        if codes is None:
-            codes = t.empty(shape, dtype=t.int8, device=f"cuda:{self.device}")
-        if plies is None and with_plies:
-            plies = t.empty(shape, dtype=t.int16, device=f"cuda:{self.device}")
-        for name, x, dt in (("codes", codes, t.int8), ("plies", plies, t.int16)):
-            if x is not None and not (x.is_cuda and x.dtype == dt and tuple(x.shape) == shape and x.is_contiguous()
-                                      and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned {dt} device tensor of shape {shape}")
+        codes, plies = self._device_tensors("solve_actions_tensor", [("codes", codes, shape, "int8"),
+                                                                     ("plies", plies, shape, "int16", not with_plies)])
         depth = self.height * self.width if depth is None else int(depth)
         _abi.check(_abi.lib().bgs_connect_solve_actions(
             self._handle, ctypes.c_int32(depth), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.data_ptr()),
@@ -1146,18 +1132,10 @@ class SearchForest:
                       policy: str = "uniform", restart: bool = False):
         """`search` into device tensors int32[n, width, 3], int32[n, width] and three int32[n] (allocated when None),
         enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes, carried)."""
-        t = self.batch._need_torch("search_tensor")
-        n, w = self.batch.n, self.batch.width
-        shapes = {"counts": (n, w, 3), "visits": (n, w), "best": (n,), "nodes": (n,), "carried": (n,)}
-        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "carried": carried}
-        for name, shape in shapes.items():
-            x = outs[name]
-            if x is None:
-                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.batch.device}")
-            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
-        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [outs[k].data_ptr() for k in shapes], 1)
-        return tuple(outs[k] for k in shapes)
+        outs = self.batch._device_tensors("search_tensor", self.batch._search_specs(counts, visits, best, nodes) + [
+            ("carried", carried, (self.batch.n,))])
+        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [x.data_ptr() for x in outs], 1)
+        return tuple(outs)
 
     def _advance(self, columns: int, kept: int, on_device: int) -> None:
         if self._buffer is None:
@@ -1181,12 +1159,9 @@ class SearchForest:
     def advance_tensor(self, columns, kept=None):
         """`advance` with `columns` and `kept` as int32[n] device tensors (kept allocated when None), enqueued on the
         batch's stream with no synchronisation: kept."""
-        t = self.batch._need_torch("advance_tensor")
-        if kept is None:
-            kept = t.empty((self.batch.n,), dtype=t.int32, device=f"cuda:{self.batch.device}")
-        for name, x in (("columns", columns), ("kept", kept)):
-            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == (self.batch.n,) and x.is_contiguous()):
-                raise TypeError(f"{name} must be a contiguous int32 device tensor of shape ({self.batch.n},)")
+        shape = (self.batch.n,)   # (columns is an input: "optional", so that it is checked and never allocated)
+        columns, kept = self.batch._device_tensors("advance_tensor", [("columns", columns, shape, "int32", True),
+                                                                      ("kept", kept, shape)], align=1)
         self._advance(columns.data_ptr(), kept.data_ptr(), 1)
         return kept
 
@@ -1321,13 +1296,7 @@ class BounceBatch(_Batch):
         """`evaluate_moves` into a device tensor int32[n, W, H * W, 3] (allocated when None), enqueued on the batch's stream
         with no synchronisation.  Every entry is written."""
         playout_policy(policy)
-        t = self._need_torch("evaluate_moves_tensor")
-        shape = (self.n, self.width, self.height * self.width, 3)
-        if out is None:
-            out = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
-        if not (out.is_cuda and out.dtype == t.int32 and tuple(out.shape) == shape and out.is_contiguous()
-                and out.data_ptr() % 16 == 0):
-            raise TypeError(f"out must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        out, = self._device_tensors("evaluate_moves_tensor", [("out", out, (self.n, self.width, self.height * self.width, 3))])
         self._evaluate_moves(seed, playouts, max_plies, policy, out.data_ptr(), 1)
         return out
 
@@ -1367,21 +1336,13 @@ class BounceBatch(_Batch):
         when None), enqueued on the batch's stream with no synchronisation: (counts, given, best).  Every entry is
         written."""
         code = playout_policy(policy)
-        t = self._need_torch("evaluate_moves_halving_tensor")
         slots = (self.n, self.width, self.height * self.width)
-        shapes = {"counts": slots + (3,), "given": slots, "best": (self.n,)}
-        outs = {"counts": counts, "given": given, "best": best}
-        for name, shape in shapes.items():
-            x = outs[name]
-            if x is None:
-                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
-            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
+        outs = self._device_tensors("evaluate_moves_halving_tensor", [
+            ("counts", counts, slots + (3,)), ("given", given, slots), ("best", best, (self.n,))])
         _abi.check(_abi.lib().bgs_bounce_evaluate_moves_halving(
             self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
-            ctypes.c_void_p(outs["counts"].data_ptr()), ctypes.c_void_p(outs["given"].data_ptr()),
-            ctypes.c_void_p(outs["best"].data_ptr()), 1))
-        return outs["counts"], outs["given"], outs["best"]
+            *(ctypes.c_void_p(x.data_ptr()) for x in outs), 1))
+        return tuple(outs)
 
     def search_min_edges(self) -> int:
         """BGS_BOUNCE_SEARCH_MIN_EDGES(H, W): the most arms a position of this geometry can have, W * W * (H - 2)"""
@@ -1441,32 +1402,23 @@ class BounceBatch(_Batch):
         `search_moves_workspace_bytes(iterations, edges)` bytes; None: a tensor of the batch's own, allocated on first use
         and kept per (iterations, edges).  The workspace needs no preparation, and calls on one stream may share it."""
         code = playout_policy(policy)
-        t = self._need_torch("search_moves_tensor")
+        self._need_torch("search_moves_tensor")
         edges = self.search_default_edges(iterations) if edges is None else int(edges)
-        slots = (self.n, self.width, self.height * self.width)
-        shapes = {"counts": slots + (3,), "visits": slots, "best": (self.n,), "nodes": (self.n,), "used": (self.n,)}
-        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "used": used}
-        for name, shape in shapes.items():
-            x = outs[name]
-            if x is None:
-                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.device}")
-            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
-        if workspace is None:
-            need = self.search_moves_workspace_bytes(iterations, edges)   # (refuses bad arguments before anything is allocated)
-            key = (int(iterations), edges)
-            workspace = self._search_workspaces.get(key)
-            if workspace is None:
-                workspace = self._search_workspaces[key] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
-        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
-            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        outs = self._device_tensors("search_moves_tensor", self._search_specs(counts, visits, best, nodes, used))
+        workspace = self._search_workspace("search_moves_tensor", workspace,
+                                           lambda: self.search_moves_workspace_bytes(iterations, edges),
+                                           lambda: (int(iterations), edges))
         _abi.check(_abi.lib().bgs_bounce_search_moves(
             self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), ctypes.c_void_p(outs["counts"].data_ptr()),
-            ctypes.c_void_p(outs["visits"].data_ptr()), ctypes.c_void_p(outs["best"].data_ptr()),
-            ctypes.c_void_p(outs["nodes"].data_ptr()), ctypes.c_void_p(outs["used"].data_ptr()),
+            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), *(ctypes.c_void_p(x.data_ptr()) for x in outs),
             ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
-        return outs["counts"], outs["visits"], outs["best"], outs["nodes"], outs["used"]
+        return tuple(outs)
+
+    def _search_specs(self, counts, visits, best, nodes, used):
+        """the five outputs every tree search of this batch has, as `_device_tensors` takes them"""
+        slots = (self.n, self.width, self.height * self.width)
+        return [("counts", counts, slots + (3,)), ("visits", visits, slots), ("best", best, (self.n,)), ("nodes", nodes, (self.n,)),
+                ("used", used, (self.n,))]
 
     def search_moves_proving(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
                              explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1, policy: str = "uniform",
@@ -1504,35 +1456,18 @@ class BounceBatch(_Batch):
         used, proved, done).  Every entry is written.  `workspace` is `search_moves_tensor`'s, and the batch's own cached
         workspace serves both."""
         code = playout_policy(policy)
-        t = self._need_torch("search_moves_proving_tensor")
+        self._need_torch("search_moves_proving_tensor")
         edges = self.search_default_edges(iterations) if edges is None else int(edges)
-        slots = (self.n, self.width, self.height * self.width)
-        shapes = {"counts": slots + (3,), "visits": slots, "best": (self.n,), "nodes": (self.n,), "used": (self.n,), "proved": slots,
-                  "done": (self.n,)}
-        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "used": used, "proved": proved, "done": done}
-        for name, shape in shapes.items():
-            dtype = t.int8 if name == "proved" else t.int32
-            x = outs[name]
-            if x is None:
-                x = outs[name] = t.empty(shape, dtype=dtype, device=f"cuda:{self.device}")
-            if not (x.is_cuda and x.dtype == dtype and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned {str(dtype).split('.')[-1]} device tensor of shape {shape}")
-        if workspace is None:
-            need = self.search_moves_workspace_bytes(iterations, edges)   # (refuses bad arguments before anything is allocated)
-            key = (int(iterations), edges)
-            workspace = self._search_workspaces.get(key)
-            if workspace is None:
-                workspace = self._search_workspaces[key] = t.empty(need, dtype=t.uint8, device=f"cuda:{self.device}")
-        if not (workspace.is_cuda and workspace.dtype == t.uint8 and workspace.is_contiguous()):
-            raise TypeError("workspace must be a contiguous uint8 device tensor")
+        outs = self._device_tensors("search_moves_proving_tensor", self._search_specs(counts, visits, best, nodes, used) + [
+            ("proved", proved, (self.n, self.width, self.height * self.width), "int8"), ("done", done, (self.n,))])
+        workspace = self._search_workspace("search_moves_proving_tensor", workspace,
+                                           lambda: self.search_moves_workspace_bytes(iterations, edges),
+                                           lambda: (int(iterations), edges))
         _abi.check(_abi.lib().bgs_bounce_search_moves_proving(
             self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), ctypes.c_void_p(outs["counts"].data_ptr()),
-            ctypes.c_void_p(outs["visits"].data_ptr()), ctypes.c_void_p(outs["best"].data_ptr()),
-            ctypes.c_void_p(outs["nodes"].data_ptr()), ctypes.c_void_p(outs["used"].data_ptr()),
-            ctypes.c_void_p(outs["proved"].data_ptr()), ctypes.c_void_p(outs["done"].data_ptr()),
+            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), *(ctypes.c_void_p(x.data_ptr()) for x in outs),
             ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
-        return tuple(outs[name] for name in shapes)
+        return tuple(outs)
 
     def moves_forest_bytes(self, nodes: int, edges: Optional[int] = None) -> int:
         """bytes of device memory a forest of this batch takes at `nodes` nodes and `edges` pool edges a tree (None: the
@@ -1602,16 +1537,9 @@ class BounceBatch(_Batch):
                            max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """`solve_moves` into device tensors int8[n, W, H * W] and int16[n, W, H * W] (allocated when None; plies only
         `with_plies` or when given), enqueued on the batch's stream with no synchronisation: (codes, plies or None)."""
-        t = self._need_torch("solve_moves_tensor")
         shape = (self.n, self.width, self.height * self.width)
-        if codes is None:
-            codes = t.empty(shape, dtype=t.int8, device=f"cuda:{self.device}")
-        if plies is None and with_plies:
-            plies = t.empty(shape, dtype=t.int16, device=f"cuda:{self.device}")
-        for name, x, dt in (("codes", codes, t.int8), ("plies", plies, t.int16)):
-            if x is not None and not (x.is_cuda and x.dtype == dt and tuple(x.shape) == shape and x.is_contiguous()
-                                      and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned {dt} device tensor of shape {shape}")
+        codes, plies = self._device_tensors("solve_moves_tensor", [("codes", codes, shape, "int8"),
+                                                                   ("plies", plies, shape, "int16", not with_plies)])
         _abi.check(_abi.lib().bgs_bounce_solve_moves(
             self._handle, ctypes.c_int32(int(depth)), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.data_ptr()),
             None if plies is None else ctypes.c_void_p(plies.data_ptr()), None, 1))
@@ -1700,18 +1628,10 @@ class MovesForest:
                       policy: str = "uniform", restart: bool = False):
         """`search` into device tensors int32[n, W, H * W, 3], int32[n, W, H * W] and four int32[n] (allocated when None),
         enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes, used, carried)."""
-        t = self.batch._need_torch("search_tensor")
-        n, w, hw = self.batch.n, self.batch.width, self.batch.height * self.batch.width
-        shapes = {"counts": (n, w, hw, 3), "visits": (n, w, hw), "best": (n,), "nodes": (n,), "used": (n,), "carried": (n,)}
-        outs = {"counts": counts, "visits": visits, "best": best, "nodes": nodes, "used": used, "carried": carried}
-        for name, shape in shapes.items():
-            x = outs[name]
-            if x is None:
-                x = outs[name] = t.empty(shape, dtype=t.int32, device=f"cuda:{self.batch.device}")
-            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == shape and x.is_contiguous() and x.data_ptr() % 16 == 0):
-                raise TypeError(f"{name} must be a contiguous, 16-byte aligned int32 device tensor of shape {shape}")
-        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [outs[k].data_ptr() for k in shapes], 1)
-        return tuple(outs[k] for k in shapes)
+        outs = self.batch._device_tensors("search_tensor", self.batch._search_specs(counts, visits, best, nodes, used) + [
+            ("carried", carried, (self.batch.n,))])
+        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [x.data_ptr() for x in outs], 1)
+        return tuple(outs)
 
     def _advance(self, slots: int, kept: int, on_device: int) -> None:
         if self._buffer is None:
@@ -1736,11 +1656,8 @@ class MovesForest:
     def advance_tensor(self, slots, kept=None):
         """`advance` with `slots` and `kept` as int32[n] device tensors (kept allocated when None), enqueued on the
         batch's stream with no synchronisation: kept."""
-        t = self.batch._need_torch("advance_tensor")
-        if kept is None:
-            kept = t.empty((self.batch.n,), dtype=t.int32, device=f"cuda:{self.batch.device}")
-        for name, x in (("slots", slots), ("kept", kept)):
-            if not (x.is_cuda and x.dtype == t.int32 and tuple(x.shape) == (self.batch.n,) and x.is_contiguous()):
-                raise TypeError(f"{name} must be a contiguous int32 device tensor of shape ({self.batch.n},)")
+        shape = (self.batch.n,)   # (slots is an input: "optional", so that it is checked and never allocated)
+        slots, kept = self.batch._device_tensors("advance_tensor", [("slots", slots, shape, "int32", True),
+                                                                    ("kept", kept, shape)], align=1)
         self._advance(slots.data_ptr(), kept.data_ptr(), 1)
         return kept
