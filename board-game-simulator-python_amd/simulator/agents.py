@@ -20,6 +20,11 @@ launch) and plays the column with the most visits; with ``reuse=True`` it keeps 
 ``BounceTreeSearchAgent`` grows a UCT tree a Bounce position (``BounceBatch.search_moves``) and plays the move with the
 most visits; with ``reuse=True`` it keeps the trees from call to call (``BounceBatch.search_moves_forest``) as
 ``TreeSearchAgent`` does.
+
+What differs between the two games at this level stands once, in ``_Connect`` and ``_Bounce`` below: the key and the making
+of a batch, the arrays ``write_state`` takes, the default playout cap, and the mapping between an action, its index in a
+per-root output row and its flat slot.  ``_Agent`` owns an agent's batches and loads states into them (``_loaded``), and
+``_TreeSearch`` is the one body of the two tree-search agents, which add their batch calls and their "between" function.
 """
 
 from __future__ import annotations
@@ -37,7 +42,144 @@ from .game import bounce, connect
 BOUNCE_MAX_PLIES = 1024
 
 
-class MonteCarloAgent:
+class _Connect:
+    """Connect, as an agent sees it."""
+
+    name = "Connect"
+    State = connect.State
+    max_plies = 2**31 - 1       # the playout cap of an agent that was given none: Connect games end by themselves
+
+    @staticmethod
+    def key(config: connect.Config, n: int) -> tuple:
+        """of the batch of `n` boards of `config` in an agent's cache"""
+        return ("connect", config.height, config.width, config.count, n)
+
+    @staticmethod
+    def batch(config: connect.Config, n: int, device: int) -> ConnectBatch:
+        return ConnectBatch(config.height, config.width, config.count, n, device=device)
+
+    @staticmethod
+    def arrays(states: Sequence) -> tuple:
+        """(grid, player, winner) of `states`, as `write_state` takes them"""
+        return (np.stack([s.grid for s in states]), np.array([s.player for s in states], dtype=np.int8),
+                np.array([s._winner for s in states], dtype=np.int8))
+
+    @staticmethod
+    def index(action) -> tuple:
+        """where `action` sits in its root's row of a per-column output"""
+        return (action.column,)
+
+    @staticmethod
+    def slot(action) -> int:
+        return action.column
+
+    @staticmethod
+    def action(state, slot):
+        """the action of `state` in column `slot`; None for a negative one (an ended board)"""
+        return state.action_at(int(slot)) if slot >= 0 else None
+
+
+class _Bounce:
+    """Bounce, as an agent sees it.  A move is the piece in column x of the active row going to (tx, ty): entry (x, ty *
+    width + tx) of its root's row of a per-move output, slot x * height * width + ty * width + tx."""
+
+    name = "Bounce"
+    State = bounce.State
+    max_plies = BOUNCE_MAX_PLIES
+
+    @staticmethod
+    def key(config: bounce.Config, n: int) -> tuple:
+        grid = config.grid
+        return ("bounce", grid.shape, grid.tobytes(), n)
+
+    @staticmethod
+    def batch(config: bounce.Config, n: int, device: int) -> BounceBatch:
+        return BounceBatch(config.grid, n, device=device)
+
+    @staticmethod
+    def arrays(states: Sequence) -> tuple:
+        """(grid, player, winner, plies) of `states`, as `write_state` takes them: the plies are the state's own count,
+        because a playout's draws are keyed by the absolute ply"""
+        return (np.stack([s.grid for s in states]), np.array([s.player for s in states], dtype=np.int8),
+                np.array([s._winner for s in states], dtype=np.int8), np.array([s._plies for s in states], dtype=np.int32))
+
+    @staticmethod
+    def index(action) -> tuple:
+        return (action._source[0], action._target[1] * action.state._grid.shape[1] + action._target[0])
+
+    @staticmethod
+    def slot(action) -> int:
+        x, cell = _Bounce.index(action)
+        return x * action.state._grid.size + cell
+
+    @staticmethod
+    def action(state, slot):
+        """the action of `state` with flat slot `slot`; None for a negative one (an ended board)"""
+        return {_Bounce.slot(a): a for a in state.actions}[int(slot)] if slot >= 0 else None
+
+
+def _game_of(state):
+    """the game of a state that is known to be one of the two's"""
+    return _Bounce if isinstance(state, bounce.State) else _Connect
+
+
+def _only(game, state, who: str, elsewhere: str) -> None:
+    """refuse a `state` that is not `game`'s: the other game's with `elsewhere`, anything else by the name of its type"""
+    if isinstance(state, game.State):
+        return
+    if isinstance(state, (connect.State, bounce.State)):
+        raise ValueError(f"{who} {elsewhere}")
+    raise TypeError(f"{who} {game.name} states, not {type(state).__name__}")
+
+
+class _Agent:
+    """What the agents share: the batches an agent holds, one a (game, Config, number of states), the loading of states
+    into them, and the one-state wrappers."""
+
+    def __init__(self, device: int):
+        self.device = int(device)
+        self._batches: Dict[tuple, Union[ConnectBatch, BounceBatch]] = {}
+
+    def _cap(self, game) -> int:
+        """the playout cap of a launch: the agent's own `max_plies`, else the game's default"""
+        return game.max_plies if self.max_plies is None else self.max_plies
+
+    def _loaded(self, states: Sequence, who: str, game=None, shared: Optional[str] = None):
+        """(batch, arrays): the agent's batch of len(states) boards, holding `states`, and the arrays it was given
+        (`game.arrays`).  The states must be `game`'s and share one Config; `who` opens the refusals, and `shared` is the
+        text of that one where it is another.  Without `game` the states must be of one type, and the agent's `_game_for`
+        says, after that check, which game they are."""
+        config = states[0].config
+        kind = type(states[0]) if game is None else game.State
+        if any(not isinstance(s, kind) or s.config != config for s in states):
+            raise ValueError(shared or f"{who} the states must share one Config")
+        if game is None:
+            game = self._game_for(states[0])
+        key = game.key(config, len(states))
+        b = self._batches.get(key)
+        if b is None:
+            b = self._batches[key] = game.batch(config, len(states), self.device)
+        arrays = game.arrays(states)
+        if (b.write_state(*arrays) != 0).any():
+            raise ValueError(f"{who} a state could not be loaded")
+        return b, arrays
+
+    def predict(self, state, game: int = 0) -> Dict:
+        """{action: value} for every action in ``state.actions`` (the keys are those Action objects): `predict_many` of
+        one state, as game `game`"""
+        return self.predict_many([state], first_game=game)[0]
+
+    def choose(self, state, game: int = 0):
+        """`choose_many` of one state"""
+        return self.choose_many([state], first_game=game)[0]
+
+    def close(self) -> None:
+        for b in self._batches.values():
+            b.close()
+        self._batches.clear()
+
+
+class MonteCarloAgent(_Agent):
     """Flat Monte-Carlo evaluation of Connect positions (``simulator.game.connect.State``) and Bounce positions
     (``simulator.game.bounce.State``), dispatched on the state's type.
 
@@ -77,14 +219,13 @@ class MonteCarloAgent:
             raise ValueError("playouts must be >= 1")
         if max_plies is not None and max_plies < 1:
             raise ValueError("max_plies must be >= 1")
+        super().__init__(device)
         self.playouts = int(playouts)
         self.seed = int(seed)
-        self.device = int(device)
         self.max_plies = None if max_plies is None else int(max_plies)
         self.policy = policy
         self.allocation = allocation
         self.budget = None if budget is None else int(budget)
-        self._batches: Dict[tuple, Union[ConnectBatch, BounceBatch]] = {}
         self._policy_game: Optional[str] = None   # the game whose `policy` this agent plays (set by its first states)
 
     def _bind(self, game: str) -> None:
@@ -97,22 +238,16 @@ class MonteCarloAgent:
             raise ValueError(f"MonteCarloAgent: this agent plays {self._policy_game}'s {self.policy!r} playout policy, which is not "
                              f"{game}'s policy of that name: make an agent of its own for {game} states")
 
-    def _batch(self, config: connect.Config, n: int) -> ConnectBatch:
-        key = ("connect", config.height, config.width, config.count, n)
-        b = self._batches.get(key)
-        if b is None:
-            b = ConnectBatch(config.height, config.width, config.count, n, device=self.device)
-            self._batches[key] = b
-        return b
-
-    def _bounce_batch(self, config: bounce.Config, n: int) -> BounceBatch:
-        grid = config.grid
-        key = ("bounce", grid.shape, grid.tobytes(), n)
-        b = self._batches.get(key)
-        if b is None:
-            b = BounceBatch(grid, n, device=self.device)
-            self._batches[key] = b
-        return b
+    def _game_for(self, state):
+        """the game of `state`, once the agent takes it (`_loaded` asks, before it makes a batch)"""
+        if isinstance(state, bounce.State):
+            if self.allocation != "flat":
+                raise ValueError("MonteCarloAgent: Bounce moves are evaluated flat, there is no halving allocation for Bounce states")
+        elif not isinstance(state, connect.State):
+            raise TypeError(f"predict_many: Connect or Bounce states, not {type(state).__name__}")
+        game = _game_of(state)
+        self._bind(game.name)
+        return game
 
     def values(self, batch: ConnectBatch, first_game: int = 0) -> np.ndarray:
         """float64[n, width] for the boards of `batch`: (wins + draws / 2) / playouts of every column for the player to
@@ -121,7 +256,7 @@ class MonteCarloAgent:
         if self.allocation == "halving":
             return self.halving_values(batch, first_game)[0]
         batch.set_first_game(first_game)
-        cap = 2**31 - 1 if self.max_plies is None else self.max_plies
+        cap = self._cap(_Connect)
         counts = batch.evaluate_actions(seed=self.seed, playouts=self.playouts, max_plies=cap, policy=self.policy).astype(np.float64)
         v = (counts[..., 0] + 0.5 * counts[..., 1]) / self.playouts
         v[batch.legal == 0] = np.nan
@@ -132,7 +267,7 @@ class MonteCarloAgent:
         every column (NaN where the column is illegal or the board has ended; a legal column is never given zero
         playouts) and the last surviving column (-1: an ended board).  Sets the batch's first_game to `first_game`."""
         batch.set_first_game(first_game)
-        cap = 2**31 - 1 if self.max_plies is None else self.max_plies
+        cap = self._cap(_Connect)
         budget = self.playouts * batch.width if self.budget is None else self.budget
         counts, given, best = batch.evaluate_actions_halving(seed=self.seed, budget=budget, max_plies=cap, policy=self.policy)
         v = np.full(given.shape, np.nan)
@@ -145,7 +280,7 @@ class MonteCarloAgent:
         the piece in column x of the active row to cell c, for the player to move; NaN where that move is illegal or the
         board has ended.  Sets the batch's first_game to `first_game`; the boards are not modified."""
         batch.set_first_game(first_game)
-        cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
+        cap = self._cap(_Bounce)
         counts = batch.evaluate_moves(seed=self.seed, playouts=self.playouts, max_plies=cap, policy=self.policy).astype(np.float64)
         v = (counts[..., 0] + 0.5 * counts[..., 1]) / self.playouts
         t = batch.targets[:, : batch.width]
@@ -158,55 +293,10 @@ class MonteCarloAgent:
         """`predict` of every state, evaluated in one call (all states must be of one game and share one Config)."""
         if not states:
             return []
-        config = states[0].config
-        if any(type(s) is not type(states[0]) or s.config != config for s in states):
-            raise ValueError("predict_many: the states must share one Config")
-        if isinstance(states[0], bounce.State):
-            self._check_bounce()
-            return self._predict_bounce(states, first_game)
-        b = self._load_connect(states)
-        v = self.values(b, first_game)
-        return [{a: float(v[k, a.column]) for a in s.actions} for k, s in enumerate(states)]
-
-    def _check_bounce(self) -> None:
-        if self.allocation != "flat":
-            raise ValueError("MonteCarloAgent: Bounce moves are evaluated flat, there is no halving allocation for Bounce states")
-
-    def _load_connect(self, states: Sequence) -> ConnectBatch:
-        """the agent's batch of len(states) boards, holding `states`"""
-        if not isinstance(states[0], connect.State):
-            raise TypeError(f"predict_many: Connect or Bounce states, not {type(states[0]).__name__}")
-        self._bind("Connect")
-        b = self._batch(states[0].config, len(states))
-        grid = np.stack([s.grid for s in states])
-        player = np.array([s.player for s in states], dtype=np.int8)
-        winner = np.array([-1 if not s.has_ended else int(s.to_json()["winner"]) for s in states], dtype=np.int8)
-        status = b.write_state(grid, player, winner)
-        if (status != 0).any():
-            raise ValueError("predict_many: a state could not be loaded")
-        return b
-
-    def _predict_bounce(self, states: Sequence[bounce.State], first_game: int) -> List[Dict[bounce.Action, float]]:
-        self._bind("Bounce")
-        b = self._bounce_batch(states[0].config, len(states))
-        grid = np.stack([s.grid for s in states])
-        player = np.array([s.player for s in states], dtype=np.int8)
-        winner = np.array([s.to_json()["winner"] for s in states], dtype=np.int8)
-        # the state's own ply count: a playout's draws are keyed by the absolute ply
-        plies = np.array([s._plies for s in states], dtype=np.int32)
-        status = b.write_state(grid, player, winner, plies)
-        if (status != 0).any():
-            raise ValueError("predict_many: a state could not be loaded")
-        v = self.bounce_values(b, first_game)
-        w = b.width
-        out = []
-        for k, s in enumerate(states):
-            out.append({a: float(v[k, a._source[0], a._target[1] * w + a._target[0]]) for a in s.actions})
-        return out
-
-    def predict(self, state, game: int = 0) -> Dict:
-        """{action: value} for every action in ``state.actions`` (the keys are those Action objects)."""
-        return self.predict_many([state], first_game=game)[0]
+        b, _ = self._loaded(states, "predict_many:")
+        game = _game_of(states[0])
+        v = self.bounce_values(b, first_game) if game is _Bounce else self.values(b, first_game)
+        return [{a: float(v[k][game.index(a)]) for a in s.actions} for k, s in enumerate(states)]
 
     def choose_many(self, states: Sequence, first_game: int = 0) -> List:
         """the action to play in every state (None where it has no action): flat, the best-valued action, the first in
@@ -214,27 +304,124 @@ class MonteCarloAgent:
         if not states:
             return []
         if self.allocation == "halving" and not isinstance(states[0], bounce.State):
-            config = states[0].config
-            if any(type(s) is not type(states[0]) or s.config != config for s in states):
-                raise ValueError("choose_many: the states must share one Config")
-            best = self.halving_values(self._load_connect(states), first_game)[1]
-            return [s.action_at(int(c)) if c >= 0 else None for s, c in zip(states, best)]
+            # (callers match these texts: the refusal of mixed Configs names choose_many, this path's others predict_many)
+            b, _ = self._loaded(states, "predict_many:", shared="choose_many: the states must share one Config")
+            best = self.halving_values(b, first_game)[1]
+            return [_Connect.action(s, c) for s, c in zip(states, best)]
         out = []
         for s, values in zip(states, self.predict_many(states, first_game)):
             out.append(max(s.actions, key=values.get) if s.actions else None)   # (max keeps the first of equal values)
         return out
 
-    def choose(self, state, game: int = 0):
-        """`choose_many` of one state"""
-        return self.choose_many([state], first_game=game)[0]
+
+def _proved_shares(visits, proved, at: Sequence[tuple]) -> List[float]:
+    """The shares `predict` gives the legal moves of one root that was searched with `prove`, in the order of `at`, the
+    moves' indices in the root's rows `visits` and `proved`.  A proved win takes everything (several share it); else the
+    moves proved lost get 0, unless every move is, and the others keep their visits.  The shares sum to 1."""
+    share = [float(visits[i]) for i in at]
+    codes = [proved[i] for i in at]
+    if any(c == SOLVE_WIN for c in codes):
+        share = [1.0 if c == SOLVE_WIN else 0.0 for c in codes]
+    elif any(c != SOLVE_LOSS for c in codes):
+        share = [0.0 if c == SOLVE_LOSS else s for c, s in zip(codes, share)]
+    total = sum(share)
+    return [s / total for s in share]
+
+
+class _TreeSearch(_Agent):
+    """The body of ``TreeSearchAgent`` and ``BounceTreeSearchAgent``.  A subclass names its game (``_game``) and what it
+    says to states that are not that game's (``_who``, ``_elsewhere``) and to ``prove`` with ``reuse`` (``_no_proving_forest``),
+    and makes the batch's calls: ``_launch``, ``_forest``, and ``_between`` for the plies played since the forest's last
+    search.  What a search returns is the batch's tuple, in which ``visits`` and ``best`` are the second and third element
+    and, with ``prove``, ``proved`` and ``done`` the last two."""
+
+    def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
+                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, prove: bool = False,
+                 reuse: bool = False, capacity: Optional[int] = None):
+        playout_policy(policy)
+        if prove and reuse:
+            raise ValueError(f"prove=True with reuse=True: {self._no_proving_forest}")
+        if iterations < 1 or leaf_playouts < 1:
+            raise ValueError("iterations and leaf_playouts must be >= 1")
+        if not 0 <= explore <= 1 << 18:
+            raise ValueError("explore must be 0 .. 2**18")
+        if max_plies is not None and max_plies < 1:
+            raise ValueError("max_plies must be >= 1")
+        if capacity is not None and capacity < 2:
+            raise ValueError("capacity must be >= 2")
+        super().__init__(device)
+        self.prove = bool(prove)
+        self.reuse = bool(reuse)
+        self.capacity = 2 * int(iterations) + 1 if capacity is None else int(capacity)
+        # key of the batch -> [the forest, what was last searched there (grids, movers; for Bounce, ply counts), searches so far]
+        self._forests: Dict[tuple, list] = {}
+        self.iterations = int(iterations)
+        self.leaf_playouts = int(leaf_playouts)
+        self.explore = int(explore)
+        self.policy = policy
+        self.seed = int(seed)
+        self.max_plies = None if max_plies is None else int(max_plies)
+
+    def search(self, states: Sequence, first_game: int = 0):
+        """the launch over `states` (states of the agent's game that share one Config): (counts, visits, best, nodes), for
+        Bounce (counts, visits, best, nodes, used); with `reuse` followed by carried, with `prove` by proved and done"""
+        game = self._game
+        _only(game, states[0], self._who, self._elsewhere)
+        b, arrays = self._loaded(states, self._who, game)
+        b.set_first_game(first_game)
+        arguments = dict(iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore, max_plies=self._cap(game),
+                         policy=self.policy)
+        if not self.reuse:
+            return self._launch(b, seed=self.seed, **arguments)
+        # the search of `reuse`: advance the batch's forest from what it last searched to these states, then search on
+        now = arrays[:2] + arrays[3:]       # grids, movers (, ply counts)
+        key = game.key(states[0].config, len(states))
+        entry = self._forests.get(key)
+        if entry is None:
+            entry = self._forests[key] = [self._forest(b), *[None] * len(now), 0]
+        forest, *last, searches = entry
+        if last[0] is not None:
+            plies = np.array([self._between(last, now, k) for k in range(len(states))], dtype=np.int32)
+            for ply in (plies[:, 0], plies[:, 1]):
+                if (ply >= 0).any():
+                    forest.advance(ply)
+        out = forest.search(seed=(self.seed + searches) % 2**64, **arguments)
+        entry[1:] = [*now, searches + 1]
+        return out
+
+    def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict]:
+        """`predict` of every state, searched in one launch"""
+        if not states:
+            return []
+        out = self.search(states, first_game)
+        visits, index = out[1], self._game.index
+        shares = []
+        for k, s in enumerate(states):
+            actions = s.actions
+            if self.prove:      # a proved win takes everything, moves proved lost nothing (unless all are)
+                shares.append(dict(zip(actions, _proved_shares(visits[k], out[-2][k], [index(a) for a in actions]))))
+                continue
+            # a kept root's visits include the carried ones
+            total = int(visits[k].sum()) if self.reuse else self.iterations * self.leaf_playouts
+            shares.append({a: float(visits[k][index(a)]) / total for a in actions})
+        return shares
+
+    def choose_many(self, states: Sequence, first_game: int = 0) -> List:
+        """the most visited action of every state (with `prove`, the launch's `best`), of the same launch `predict_many`
+        makes (None: no action)"""
+        if not states:
+            return []
+        best = self.search(states, first_game)[2]
+        return [self._game.action(s, slot) for s, slot in zip(states, best)]
 
     def close(self) -> None:
-        for b in self._batches.values():
-            b.close()
-        self._batches.clear()
+        for entry in self._forests.values():
+            entry[0].close()
+        self._forests.clear()
+        super().close()
 
 
-class TreeSearchAgent:
+class TreeSearchAgent(_TreeSearch):
     """UCT tree search over Connect positions (``simulator.game.connect.State``): ``ConnectBatch.search_actions`` with
     ``iterations`` iterations and ``leaf_playouts`` playouts a leaf, ``iterations * leaf_playouts`` playouts a position,
     one launch for all positions of a call.
@@ -266,61 +453,10 @@ class TreeSearchAgent:
     does not prove yet: ``prove=True`` with ``reuse=True`` raises ValueError.  Without ``prove`` the code path is what it
     was."""
 
-    def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
-                 seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, prove: bool = False,
-                 reuse: bool = False, capacity: Optional[int] = None):
-        playout_policy(policy)
-        if prove and reuse:
-            raise ValueError("prove=True with reuse=True: the forest does not prove yet")
-        if iterations < 1 or leaf_playouts < 1:
-            raise ValueError("iterations and leaf_playouts must be >= 1")
-        if not 0 <= explore <= 1 << 18:
-            raise ValueError("explore must be 0 .. 2**18")
-        if max_plies is not None and max_plies < 1:
-            raise ValueError("max_plies must be >= 1")
-        if capacity is not None and capacity < 2:
-            raise ValueError("capacity must be >= 2")
-        self.prove = bool(prove)
-        self.reuse = bool(reuse)
-        self.capacity = 2 * int(iterations) + 1 if capacity is None else int(capacity)
-        self._forests: Dict[tuple, list] = {}   # key -> [SearchForest, grids last searched, their movers, searches so far]
-        self.iterations = int(iterations)
-        self.leaf_playouts = int(leaf_playouts)
-        self.explore = int(explore)
-        self.policy = policy
-        self.seed = int(seed)
-        self.device = int(device)
-        self.max_plies = None if max_plies is None else int(max_plies)
-        self._batches: Dict[tuple, ConnectBatch] = {}
-
-    def search(self, states: Sequence, first_game: int = 0):
-        """(counts, visits, best, nodes) of the launch over `states` (Connect states that share one Config); with `reuse`
-        (counts, visits, best, nodes, carried), with `prove` (counts, visits, best, nodes, proved, done)"""
-        if isinstance(states[0], bounce.State):
-            raise ValueError("TreeSearchAgent: Connect states only; the tree search does not cover Bounce")
-        if not isinstance(states[0], connect.State):
-            raise TypeError(f"TreeSearchAgent: Connect states, not {type(states[0]).__name__}")
-        config = states[0].config
-        if any(type(s) is not type(states[0]) or s.config != config for s in states):
-            raise ValueError("TreeSearchAgent: the states must share one Config")
-        key = (config.height, config.width, config.count, len(states))
-        b = self._batches.get(key)
-        if b is None:
-            b = self._batches[key] = ConnectBatch(config.height, config.width, config.count, len(states), device=self.device)
-        grid = np.stack([s.grid for s in states])
-        player = np.array([s.player for s in states], dtype=np.int8)
-        winner = np.array([-1 if not s.has_ended else int(s.to_json()["winner"]) for s in states], dtype=np.int8)
-        if (b.write_state(grid, player, winner) != 0).any():
-            raise ValueError("TreeSearchAgent: a state could not be loaded")
-        b.set_first_game(first_game)
-        cap = 2**31 - 1 if self.max_plies is None else self.max_plies
-        if self.reuse:
-            return self._search_on(key, b, grid, player, cap)
-        if self.prove:
-            return b.search_actions_proving(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts,
-                                            explore=self.explore, max_plies=cap, policy=self.policy)
-        return b.search_actions(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore,
-                                max_plies=cap, policy=self.policy)
+    _game = _Connect
+    _who = "TreeSearchAgent:"
+    _elsewhere = "Connect states only; the tree search does not cover Bounce"
+    _no_proving_forest = "the forest does not prove yet"
 
     @staticmethod
     def stones_between(old: np.ndarray, mover: int, new: np.ndarray):
@@ -339,75 +475,17 @@ class TreeSearchAgent:
         stones.sort(key=lambda s: s[0] if stacked else s[2] != mover)
         return stones[0][1], stones[1][1]
 
-    def _search_on(self, key, b: ConnectBatch, grid: np.ndarray, player: np.ndarray, cap: int):
-        """the search of `reuse`: advance the forest of `key` from the grids it last searched to `grid`, then search on"""
-        entry = self._forests.get(key)
-        if entry is None:
-            entry = self._forests[key] = [b.search_forest(self.capacity), None, None, 0]
-        forest, last_grid, last_player, searches = entry
-        if last_grid is not None:
-            plies = np.array([self.stones_between(last_grid[k], int(last_player[k]), grid[k]) for k in range(len(grid))],
-                             dtype=np.int32)
-            for columns in (plies[:, 0], plies[:, 1]):
-                if (columns >= 0).any():
-                    forest.advance(columns)
-        out = forest.search(seed=(self.seed + searches) % 2**64, iterations=self.iterations, leaf_playouts=self.leaf_playouts,
-                            explore=self.explore, max_plies=cap, policy=self.policy)
-        entry[1:] = [grid, player, searches + 1]
-        return out
+    def _launch(self, b: ConnectBatch, **arguments):
+        return (b.search_actions_proving if self.prove else b.search_actions)(**arguments)
 
-    def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict]:
-        """`predict` of every state, searched in one launch"""
-        if not states:
-            return []
-        if self.prove:
-            return self._predict_proved(states, first_game)
-        visits = self.search(states, first_game)[1]
-        if self.reuse:      # the root's visits include the carried ones
-            return [{a: float(visits[k, a.column]) / int(visits[k].sum()) for a in s.actions} for k, s in enumerate(states)]
-        total = self.iterations * self.leaf_playouts
-        return [{a: float(visits[k, a.column]) / total for a in s.actions} for k, s in enumerate(states)]
+    def _forest(self, b: ConnectBatch):
+        return b.search_forest(self.capacity)
 
-    def _predict_proved(self, states: Sequence, first_game: int) -> List[Dict]:
-        """`predict_many` of `prove`: a proved win takes everything, columns proved lost nothing (unless all are)"""
-        _, visits, _, _, proved, _ = self.search(states, first_game)
-        out = []
-        for k, s in enumerate(states):
-            columns = [a.column for a in s.actions]
-            share = {c: float(visits[k, c]) for c in columns}
-            if any(proved[k, c] == SOLVE_WIN for c in columns):
-                share = {c: 1.0 if proved[k, c] == SOLVE_WIN else 0.0 for c in columns}
-            elif any(proved[k, c] != SOLVE_LOSS for c in columns):
-                share = {c: 0.0 if proved[k, c] == SOLVE_LOSS else share[c] for c in columns}
-            total = sum(share.values())
-            out.append({a: share[a.column] / total for a in s.actions})
-        return out
-
-    def predict(self, state, game: int = 0) -> Dict:
-        """{action: share of the visits} for every action in ``state.actions`` (the keys are those Action objects)"""
-        return self.predict_many([state], first_game=game)[0]
-
-    def choose_many(self, states: Sequence, first_game: int = 0) -> List:
-        """the column with the most visits of every state, of the same launch `predict_many` makes (None: no action)"""
-        if not states:
-            return []
-        best = self.search(states, first_game)[2]
-        return [s.action_at(int(c)) if c >= 0 else None for s, c in zip(states, best)]
-
-    def choose(self, state, game: int = 0):
-        """`choose_many` of one state"""
-        return self.choose_many([state], first_game=game)[0]
-
-    def close(self) -> None:
-        for entry in self._forests.values():
-            entry[0].close()
-        self._forests.clear()
-        for b in self._batches.values():
-            b.close()
-        self._batches.clear()
+    def _between(self, last, now, k: int):
+        return self.stones_between(last[0][k], int(last[1][k]), now[0][k])
 
 
-class BounceHalvingAgent:
+class BounceHalvingAgent(_Agent):
     """Sequential halving over the moves of Bounce positions (``simulator.game.bounce.State``):
     ``BounceBatch.evaluate_moves_halving`` with ``budget`` playouts a position, one launch for all positions of a call.
 
@@ -429,83 +507,48 @@ class BounceHalvingAgent:
             raise ValueError("budget must be >= 1")
         if max_plies is not None and max_plies < 1:
             raise ValueError("max_plies must be >= 1")
+        super().__init__(device)
         self.budget = int(budget)
         self.seed = int(seed)
-        self.device = int(device)
         self.max_plies = None if max_plies is None else int(max_plies)
         self.policy = policy
-        self._batches: Dict[tuple, BounceBatch] = {}
 
     def _evaluate(self, states: Sequence, first_game: int):
-        """(counts, given, best, width) of the launch over `states`"""
-        if isinstance(states[0], connect.State):
-            raise ValueError('BounceHalvingAgent: Bounce states only; Connect states: MonteCarloAgent(allocation="halving")')
-        if not isinstance(states[0], bounce.State):
-            raise TypeError(f"BounceHalvingAgent: Bounce states, not {type(states[0]).__name__}")
-        config = states[0].config
-        if any(type(s) is not type(states[0]) or s.config != config for s in states):
-            raise ValueError("BounceHalvingAgent: the states must share one Config")
-        grid = config.grid
-        key = (grid.shape, grid.tobytes(), len(states))
-        b = self._batches.get(key)
-        if b is None:
-            b = self._batches[key] = BounceBatch(grid, len(states), device=self.device)
-        boards = np.stack([s.grid for s in states])
-        player = np.array([s.player for s in states], dtype=np.int8)
-        winner = np.array([s.to_json()["winner"] for s in states], dtype=np.int8)
-        plies = np.array([s._plies for s in states], dtype=np.int32)   # a playout's draws are keyed by the absolute ply
-        if (b.write_state(boards, player, winner, plies) != 0).any():
-            raise ValueError("BounceHalvingAgent: a state could not be loaded")
+        """(counts, given, best) of the launch over `states`"""
+        _only(_Bounce, states[0], "BounceHalvingAgent:", 'Bounce states only; Connect states: MonteCarloAgent(allocation="halving")')
+        b, _ = self._loaded(states, "BounceHalvingAgent:", _Bounce)
         b.set_first_game(first_game)
-        cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
-        counts, given, best = b.evaluate_moves_halving(seed=self.seed, budget=self.budget, max_plies=cap, policy=self.policy)
+        counts, given, best = b.evaluate_moves_halving(seed=self.seed, budget=self.budget, max_plies=self._cap(_Bounce),
+                                                       policy=self.policy)
         for k in np.flatnonzero(best == HALVING_SHORT):
             moves = len(states[k].actions)
             raise ValueError(f"BounceHalvingAgent: state {k} has {moves} legal moves and needs a budget of "
                              f"{BounceBatch.halving_min_budget(moves)} playouts, this agent's is {self.budget}")
-        return counts, given, best, b.width
+        return counts, given, best
 
     def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict[bounce.Action, float]]:
         """`predict` of every state, evaluated in one launch (the states must share one Config)"""
         if not states:
             return []
-        counts, given, _, w = self._evaluate(states, first_game)
+        counts, given, _ = self._evaluate(states, first_game)
         out = []
         for k, s in enumerate(states):
             values = {}
             for a in s.actions:
-                at = (k, a._source[0], a._target[1] * w + a._target[0])
+                at = (k,) + _Bounce.index(a)
                 values[a] = float((counts[at][0] + 0.5 * counts[at][1]) / given[at]) if given[at] else 0.0
             out.append(values)
         return out
-
-    def predict(self, state, game: int = 0) -> Dict[bounce.Action, float]:
-        """{action: value} for every action in ``state.actions`` (the keys are those Action objects)"""
-        return self.predict_many([state], first_game=game)[0]
 
     def choose_many(self, states: Sequence, first_game: int = 0) -> List:
         """the last surviving move of every state, of the same launch `predict_many` makes (None: no action)"""
         if not states:
             return []
-        _, _, best, w = self._evaluate(states, first_game)
-        out = []
-        for s, slot in zip(states, best):
-            hw = s.grid.shape[0] * w
-            by_slot = {a._source[0] * hw + a._target[1] * w + a._target[0]: a for a in s.actions}
-            out.append(by_slot[int(slot)] if slot >= 0 else None)
-        return out
-
-    def choose(self, state, game: int = 0):
-        """`choose_many` of one state"""
-        return self.choose_many([state], first_game=game)[0]
-
-    def close(self) -> None:
-        for b in self._batches.values():
-            b.close()
-        self._batches.clear()
+        best = self._evaluate(states, first_game)[2]
+        return [_Bounce.action(s, slot) for s, slot in zip(states, best)]
 
 
-class BounceTreeSearchAgent:
+class BounceTreeSearchAgent(_TreeSearch):
     """UCT tree search over Bounce positions (``simulator.game.bounce.State``): ``BounceBatch.search_moves`` with
     ``iterations`` iterations and ``leaf_playouts`` playouts a leaf, ``iterations * leaf_playouts`` playouts a position,
     one launch for all positions of a call.  The sibling of ``BounceHalvingAgent``, which spends the same playouts on one
@@ -538,64 +581,16 @@ class BounceTreeSearchAgent:
     the rest are renormalised, and where every move is proved lost the shares are what the visits give.  The forest does
     not prove: ``prove=True`` with ``reuse=True`` raises ValueError.  Without ``prove`` the code path is what it was."""
 
+    _game = _Bounce
+    _who = "BounceTreeSearchAgent:"
+    _elsewhere = "Bounce states only; Connect states: TreeSearchAgent"
+    _no_proving_forest = "the forest does not prove"
+
     def __init__(self, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, policy: str = "uniform",
                  seed: int = DEFAULT_SEED, device: int = 0, max_plies: Optional[int] = None, edges: Optional[int] = None,
                  prove: bool = False, reuse: bool = False, capacity: Optional[int] = None):
-        playout_policy(policy)
-        if prove and reuse:
-            raise ValueError("prove=True with reuse=True: the forest does not prove")
-        if capacity is not None and capacity < 2:
-            raise ValueError("capacity must be >= 2")
-        self.prove = bool(prove)
-        self.reuse = bool(reuse)
-        self.capacity = 2 * int(iterations) + 1 if capacity is None else int(capacity)
-        self._forests: Dict[tuple, list] = {}   # key -> [MovesForest, grids last searched, their movers, their plies, searches so far]
-        if iterations < 1 or leaf_playouts < 1:
-            raise ValueError("iterations and leaf_playouts must be >= 1")
-        if not 0 <= explore <= 1 << 18:
-            raise ValueError("explore must be 0 .. 2**18")
-        if max_plies is not None and max_plies < 1:
-            raise ValueError("max_plies must be >= 1")
-        self.iterations = int(iterations)
-        self.leaf_playouts = int(leaf_playouts)
-        self.explore = int(explore)
-        self.policy = policy
-        self.seed = int(seed)
-        self.device = int(device)
-        self.max_plies = None if max_plies is None else int(max_plies)
+        super().__init__(iterations, leaf_playouts, explore, policy, seed, device, max_plies, prove, reuse, capacity)
         self.edges = None if edges is None else int(edges)
-        self._batches: Dict[tuple, BounceBatch] = {}
-
-    def search(self, states: Sequence, first_game: int = 0):
-        """(counts, visits, best, nodes, used) of the launch over `states` (Bounce states that share one Config); with `reuse`
-        (counts, visits, best, nodes, used, carried), with `prove` (counts, visits, best, nodes, used, proved, done)"""
-        if isinstance(states[0], connect.State):
-            raise ValueError("BounceTreeSearchAgent: Bounce states only; Connect states: TreeSearchAgent")
-        if not isinstance(states[0], bounce.State):
-            raise TypeError(f"BounceTreeSearchAgent: Bounce states, not {type(states[0]).__name__}")
-        config = states[0].config
-        if any(type(s) is not type(states[0]) or s.config != config for s in states):
-            raise ValueError("BounceTreeSearchAgent: the states must share one Config")
-        grid = config.grid
-        key = (grid.shape, grid.tobytes(), len(states))
-        b = self._batches.get(key)
-        if b is None:
-            b = self._batches[key] = BounceBatch(grid, len(states), device=self.device)
-        boards = np.stack([s.grid for s in states])
-        player = np.array([s.player for s in states], dtype=np.int8)
-        winner = np.array([s.to_json()["winner"] for s in states], dtype=np.int8)
-        plies = np.array([s._plies for s in states], dtype=np.int32)   # a playout's draws are keyed by the absolute ply
-        if (b.write_state(boards, player, winner, plies) != 0).any():
-            raise ValueError("BounceTreeSearchAgent: a state could not be loaded")
-        b.set_first_game(first_game)
-        cap = BOUNCE_MAX_PLIES if self.max_plies is None else self.max_plies
-        if self.reuse:
-            return self._search_on(key, b, boards, player, plies, cap)
-        if self.prove:
-            return b.search_moves_proving(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts,
-                                          explore=self.explore, max_plies=cap, policy=self.policy, edges=self.edges)
-        return b.search_moves(seed=self.seed, iterations=self.iterations, leaf_playouts=self.leaf_playouts, explore=self.explore,
-                              max_plies=cap, policy=self.policy, edges=self.edges)
 
     @staticmethod
     def moves_between(old: np.ndarray, mover: int, new: np.ndarray, plies: int):
@@ -642,86 +637,17 @@ class BounceTreeSearchAgent:
         targets = pairings[0][1]
         return slot(gone[0], targets[0]), slot(gone[1], targets[1])
 
-    def _search_on(self, key, b: BounceBatch, grid: np.ndarray, player: np.ndarray, plies: np.ndarray, cap: int):
-        """the search of `reuse`: advance the forest of `key` from the grids it last searched to `grid`, then search on"""
-        entry = self._forests.get(key)
-        if entry is None:
-            entry = self._forests[key] = [b.search_moves_forest(self.capacity, self.edges), None, None, None, 0]
-        forest, last_grid, last_player, last_plies, searches = entry
-        if last_grid is not None:
-            slots = np.array([self.moves_between(last_grid[k], int(last_player[k]), grid[k], int(plies[k]) - int(last_plies[k]))
-                              for k in range(len(grid))], dtype=np.int32)
-            for ply in (slots[:, 0], slots[:, 1]):
-                if (ply >= 0).any():
-                    forest.advance(ply)
-        out = forest.search(seed=(self.seed + searches) % 2**64, iterations=self.iterations, leaf_playouts=self.leaf_playouts,
-                            explore=self.explore, max_plies=cap, policy=self.policy)
-        entry[1:] = [grid, player, plies, searches + 1]
-        return out
+    def _launch(self, b: BounceBatch, **arguments):
+        return (b.search_moves_proving if self.prove else b.search_moves)(edges=self.edges, **arguments)
 
-    def predict_many(self, states: Sequence, first_game: int = 0) -> List[Dict[bounce.Action, float]]:
-        """`predict` of every state, searched in one launch"""
-        if not states:
-            return []
-        if self.prove:
-            return self._predict_proved(states, first_game)
-        visits = self.search(states, first_game)[1]
-        w = visits.shape[1]
-        if self.reuse:      # the root's visits include the carried ones
-            return [{a: float(visits[k, a._source[0], a._target[1] * w + a._target[0]]) / int(visits[k].sum()) for a in s.actions}
-                    for k, s in enumerate(states)]
-        total = self.iterations * self.leaf_playouts
-        return [{a: float(visits[k, a._source[0], a._target[1] * w + a._target[0]]) / total for a in s.actions}
-                for k, s in enumerate(states)]
+    def _forest(self, b: BounceBatch):
+        return b.search_moves_forest(self.capacity, self.edges)
 
-    def _predict_proved(self, states: Sequence, first_game: int) -> List[Dict[bounce.Action, float]]:
-        """`predict_many` of `prove`: a proved win takes everything, moves proved lost nothing (unless all are)"""
-        out = self.search(states, first_game)
-        visits, proved = out[1], out[5]
-        w = visits.shape[1]
-        shares = []
-        for k, s in enumerate(states):
-            at = {a: (a._source[0], a._target[1] * w + a._target[0]) for a in s.actions}
-            share = {a: float(visits[k][at[a]]) for a in s.actions}
-            if any(proved[k][at[a]] == SOLVE_WIN for a in s.actions):
-                share = {a: 1.0 if proved[k][at[a]] == SOLVE_WIN else 0.0 for a in s.actions}
-            elif any(proved[k][at[a]] != SOLVE_LOSS for a in s.actions):
-                share = {a: 0.0 if proved[k][at[a]] == SOLVE_LOSS else share[a] for a in s.actions}
-            total = sum(share.values())
-            shares.append({a: share[a] / total for a in s.actions})
-        return shares
-
-    def predict(self, state, game: int = 0) -> Dict[bounce.Action, float]:
-        """{action: share of the visits} for every action in ``state.actions`` (the keys are those Action objects)"""
-        return self.predict_many([state], first_game=game)[0]
-
-    def choose_many(self, states: Sequence, first_game: int = 0) -> List:
-        """the move with the most visits of every state, of the same launch `predict_many` makes (None: no action)"""
-        if not states:
-            return []
-        out = self.search(states, first_game)
-        best, w = out[2], out[1].shape[1]
-        chosen = []
-        for s, slot in zip(states, best):
-            hw = s.grid.shape[0] * w
-            by_slot = {a._source[0] * hw + a._target[1] * w + a._target[0]: a for a in s.actions}
-            chosen.append(by_slot[int(slot)] if slot >= 0 else None)
-        return chosen
-
-    def choose(self, state, game: int = 0):
-        """`choose_many` of one state"""
-        return self.choose_many([state], first_game=game)[0]
-
-    def close(self) -> None:
-        for entry in self._forests.values():
-            entry[0].close()
-        self._forests.clear()
-        for b in self._batches.values():
-            b.close()
-        self._batches.clear()
+    def _between(self, last, now, k: int):
+        return self.moves_between(last[0][k], int(last[1][k]), now[0][k], int(now[2][k]) - int(last[2][k]))
 
 
-class SolverAgent:
+class SolverAgent(_Agent):
     """Exact values of Connect positions (``simulator.game.connect.State``) and Bounce positions
     (``simulator.game.bounce.State``) by the batched alpha-beta solvers, dispatched on the state's type.
 
@@ -744,58 +670,15 @@ class SolverAgent:
         self.depth = None if depth is None else int(depth)
         self.max_nodes = int(max_nodes)
         self.fallback = fallback
-        self.device = int(device)
-        self._batches: Dict[tuple, Union[ConnectBatch, BounceBatch]] = {}
-
-    def _batch(self, config: connect.Config, n: int) -> ConnectBatch:
-        key = (config.height, config.width, config.count, n)
-        b = self._batches.get(key)
-        if b is None:
-            b = ConnectBatch(config.height, config.width, config.count, n, device=self.device)
-            self._batches[key] = b
-        return b
-
-    def _bounce_batch(self, config: bounce.Config, n: int) -> BounceBatch:
-        grid = config.grid
-        key = ("bounce", grid.shape, grid.tobytes(), n)
-        b = self._batches.get(key)
-        if b is None:
-            b = BounceBatch(grid, n, device=self.device)
-            self._batches[key] = b
-        return b
-
-    @staticmethod
-    def _slot(state, action) -> tuple:
-        """the index of `action` in a row of solver codes"""
-        if isinstance(state, bounce.State):
-            (sx, _), (tx, ty) = action.source.tolist(), action.target.tolist()
-            return (sx, ty * state.grid.shape[1] + tx)
-        return (action.column,)
+        super().__init__(device)
 
     def solve_many(self, states: Sequence):
         """(codes, plies) of `states` (states of one game sharing one Config): int8 / int16 [n, width] for Connect,
         [n, width, height * width] for Bounce"""
-        config = states[0].config
-        if isinstance(states[0], bounce.State):
-            if any(not isinstance(s, bounce.State) or s.config != config for s in states):
-                raise ValueError("SolverAgent: Bounce states that share one Config")
-            b = self._bounce_batch(config, len(states))
-            grid = np.stack([s.grid for s in states])
-            player = np.array([s.player for s in states], dtype=np.int8)
-            winner = np.array([s.to_json()["winner"] for s in states], dtype=np.int8)
-            plies = np.array([s._plies for s in states], dtype=np.int32)
-            if (b.write_state(grid, player, winner, plies) != 0).any():
-                raise ValueError("SolverAgent: a state could not be loaded")
-            depth = DEFAULT_BOUNCE_SOLVE_DEPTH if self.depth is None else self.depth
-            return b.solve_moves(depth=depth, max_nodes=self.max_nodes)
-        if any(not isinstance(s, connect.State) or s.config != config for s in states):
-            raise ValueError("SolverAgent: Connect states that share one Config")
-        b = self._batch(config, len(states))
-        grid = np.stack([s.grid for s in states])
-        player = np.array([s.player for s in states], dtype=np.int8)
-        winner = np.array([-1 if not s.has_ended else int(s.to_json()["winner"]) for s in states], dtype=np.int8)
-        if (b.write_state(grid, player, winner) != 0).any():
-            raise ValueError("SolverAgent: a state could not be loaded")
+        game = _game_of(states[0])
+        b, _ = self._loaded(states, "SolverAgent:", game, shared=f"SolverAgent: {game.name} states that share one Config")
+        if game is _Bounce:
+            return b.solve_moves(depth=DEFAULT_BOUNCE_SOLVE_DEPTH if self.depth is None else self.depth, max_nodes=self.max_nodes)
         return b.solve_actions(depth=self.depth, max_nodes=self.max_nodes)
 
     def _values(self, states: Sequence, codes: np.ndarray) -> List[Dict]:
@@ -806,11 +689,12 @@ class SolverAgent:
         if self.fallback is not None and open_.any():
             fill = self.fallback.predict_many(list(states))
         exact = {SOLVE_WIN: 1.0, SOLVE_DRAW: 0.5, SOLVE_LOSS: 0.0}
+        index = _game_of(states[0]).index
         out = []
         for k, s in enumerate(states):
             v = {}
             for a in s.actions:
-                c = int(codes[(k,) + self._slot(s, a)])
+                c = int(codes[(k,) + index(a)])
                 v[a] = exact[c] if c in exact else (float(fill[k][a]) if fill is not None else 0.5)
             out.append(v)
         return out
@@ -832,7 +716,7 @@ class SolverAgent:
         values = self._values([state], codes)[0]
         best, best_key = None, None
         for a in state.actions:
-            at = (0,) + self._slot(state, a)
+            at = (0,) + _game_of(state).index(a)
             c, p = int(codes[at]), int(plies[at])
             if c == SOLVE_WIN:
                 key = (2, -p)
@@ -843,8 +727,3 @@ class SolverAgent:
             if best_key is None or key > best_key:
                 best, best_key = a, key
         return best
-
-    def close(self) -> None:
-        for b in self._batches.values():
-            b.close()
-        self._batches.clear()
