@@ -11,7 +11,10 @@ The boards are written into batches with write_state.  On every position set:
      under the default plan and under each forced family that accepts loaded boards;
   e. the object API: transition, 64 boards a call and one board a call, with transition_wave on and off (Bounce:
      also on the generic kernels);
-  f. flat Monte-Carlo: evaluate_actions / evaluate_moves with P = 1 and P = 7, one of them at a first game id >= 2^32.
+  f. flat Monte-Carlo: evaluate_actions / evaluate_moves with P = 1 and P = 7, one of them at a first game id >= 2^32;
+  g. the decisive playout policy: evaluate_actions / evaluate_moves with policy="decisive", P = 2, uncapped (Bounce: 4096
+     plies), twice, one of the runs at a first game id >= 2^32, against tests/policy_expected.py and
+     tests/bounce_policy_expected.py.
 
 Position sets (positions; moves of check a = positions x (W + 2) for Connect):
   Connect full trees: 2x3 k2 45, 3x3 k3 694, 3x4 k3 7 157, 4x3 k3 2 715, 4x4 k3 41 750, 4x4 k4 161 029.
@@ -23,7 +26,10 @@ Position sets (positions; moves of check a = positions x (W + 2) for Connect):
   Bounce full graphs: narrow 2, blocked_start 1, three_next_to_goal 1 476; small to depth 6: 11 267; the default 9x6
   board to depth 3: 9 670.
 Check f runs on every position of the full Connect trees up to 4x4 k3 and on a fixed sample elsewhere (it replicates
-each root W x P times, H x W x W x P for Bounce).  Generic Connect boards (4x20) refuse env_step's auto-reset and
+each root W x P times, H x W x W x P for Bounce).  Check g runs on every position of the full Connect trees while
+positions x W x P stays under 60 000 boards (2x3 k2, 3x3 k3, 4x3 k3, 3x4 k3) and on a fixed sample of 2000 elsewhere --
+1000 on 8x8 k5 and 6x12 k4, 300 on 12x13 k5, where the CPU reference's long games set the size; Bounce: up to 1024
+positions, 128 of the default board.  Generic Connect boards (4x20) refuse env_step's auto-reset and
 evaluate_actions by design: there the tests assert the refusal.  The counts are printed (pytest -s).
 """
 
@@ -34,8 +40,10 @@ import pytest
 
 from oracle import oracle
 from tests import game_trees as gt
+from tests.bounce_policy_expected import bounce_policy_expected
 from tests.knobs import knobs
 from tests.mc_expected import connect_expected
+from tests.policy_expected import connect_policy_expected
 from tests.test_gpu_evaluate_bounce import expected as bounce_expected
 from tests.test_gpu_parity import DEFAULT_BOUNCE, assert_bounce_actions, assert_same
 from tests.test_spec_exhaustive import BOUNCE_CONFIGS
@@ -319,6 +327,36 @@ def test_connect_evaluate_on_every_position(bm, geom):
         b.close()
 
 
+# the roots of check g where the tree is not walked in full: 2000, fewer where the games are long (the lock-step reference
+# costs about 26 us a playout ply; both runs of a geometry together stay under about 10 s on the host)
+DECISIVE_BOARDS = 60_000
+DECISIVE_SAMPLE = {(8, 8, 5): 1000, (6, 12, 4): 1000, (12, 13, 5): 300}
+
+
+@pytest.mark.parametrize("geom", ALL_CONNECT, ids=geom_id)
+def test_connect_decisive_evaluate_on_every_position(bm, geom):
+    """g: the decisive policy's counts and env-steps, P = 2, uncapped, one of the two runs at a first game above 2^32"""
+    h, w, k = geom
+    pos = connect_positions(h, w, k)
+    playouts = 2
+    full = geom in CONNECT_FULL and pos[0].shape[0] * w * playouts <= DECISIVE_BOARDS
+    roots = pos if full else take(pos, sample(pos[0].shape[0], DECISIVE_SAMPLE.get(geom, 2000), w))
+    for first in (3, BIG_GAME):
+        b = loaded(bm.ConnectBatch(h, w, k, roots[0].shape[0]), roots)
+        b.set_first_game(first)
+        if b.generic:   # bit-packed boards only: a generic geometry is refused, not served by a fall-back
+            with pytest.raises(ValueError, match="bit-packed Connect boards only"):
+                b.evaluate_actions(seed=SEED, playouts=playouts, policy="decisive")
+            b.close()
+            continue
+        got = b.evaluate_actions(seed=SEED, playouts=playouts, policy="decisive")
+        want, steps, seen = connect_policy_expected(h, w, k, roots, SEED, first, playouts, 2**31 - 1, False)
+        np.testing.assert_array_equal(got, want, err_msg=f"{geom} decisive first game {first}")
+        assert b.steps == steps
+        print(f"Connect {geom} decisive: {roots[0].shape[0]} roots{' (every position)' if full else ''}, {steps} env-steps, plies {seen}")
+        b.close()
+
+
 # ------------------------------------------------------------------------------------------------ Bounce
 
 
@@ -485,4 +523,21 @@ def test_bounce_evaluate_on_the_positions(bm, name):
         want, steps = bounce_expected(cfg, roots, SEED, first, playouts, BOUNCE_CAP)
         np.testing.assert_array_equal(got, want, err_msg=f"{name} P={playouts}")
         assert b.steps == steps
+        b.close()
+
+
+@pytest.mark.parametrize("name", list(BOUNCE_WALKS))
+def test_bounce_decisive_evaluate_on_the_positions(bm, name):
+    """g: the decisive policy's counts and env-steps, P = 2, one of the two runs at a first game above 2^32, on up to 1024
+    positions (128 of the default board, whose games are long)"""
+    cfg, pos, acts = bounce_positions(name)
+    roots = take(pos, sample(pos[0].shape[0], 128 if name == "default" else 1024, 5))
+    for first in (0, BIG_GAME):
+        b = loaded(bm.BounceBatch(cfg, roots[0].shape[0]), roots)
+        b.set_first_game(first)
+        got = b.evaluate_moves(seed=SEED, playouts=2, max_plies=BOUNCE_CAP, policy="decisive")
+        want, steps, seen = bounce_policy_expected(cfg, roots, SEED, first, 2, BOUNCE_CAP)
+        np.testing.assert_array_equal(got, want, err_msg=f"{name} decisive first game {first}")
+        assert b.steps == steps
+        print(f"Bounce {name} decisive: {roots[0].shape[0]} roots, {steps} env-steps, plies {seen}")
         b.close()
