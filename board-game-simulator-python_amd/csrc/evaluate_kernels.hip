@@ -1236,6 +1236,14 @@ k_bounce_eval_add_totals(uint64_t* __restrict__ ends, const uint64_t* __restrict
     if (i < n && blockIdx.x) ends[i] += totals[blockIdx.x];
 }
 
+// one more finished game on a W/D/L triple, seen from the root's mover.  s is the game's status, 1 / 2 (the winner + 1)
+// or BGS_ST_DRAW; a capped game (s = 0) is counted nowhere
+__device__ __forceinline__ void wdl_count(uint32_t s, uint32_t root_mover, uint32_t& wins, uint32_t& draws, uint32_t& losses) {
+    wins += (s != 0u && s != BGS_ST_DRAW && s - 1u == root_mover) ? 1u : 0u;
+    losses += (s != 0u && s != BGS_ST_DRAW && s - 1u != root_mover) ? 1u : 0u;
+    draws += s == BGS_ST_DRAW ? 1u : 0u;
+}
+
 // BGS_POLICY_DECISIVE for Bounce (include/bgs.h): the candidate list of a ply is W, the actions whose target lies in the
 // mover's goal row, when W is not empty.  Every element of W ends the game for the mover and the outputs are counts and
 // steps alone, so such a ply neither draws nor moves: the lanes that have just searched fold their sources' LDS masks
@@ -1252,6 +1260,80 @@ __device__ __forceinline__ bool b_can_win(const FlatMoves<NC>& m, const uint32_t
         hit |= cnt ? (lo | hi) : 0u;
     }
     return hit != 0u;
+}
+
+template <int NC>
+__device__ __forceinline__ FlatMoves<NC> no_moves() {
+    FlatMoves<NC> m;
+#pragma unroll
+    for (int k = 0; k < NC; ++k) m.counts[k] = 0;
+    m.n = 0;
+    m.row_base = 0;
+    return m;
+}
+
+// The Bounce playout step of the flat evaluation (k_bounce_evaluate) and of the tree searches (k_bounce_search: plain,
+// forest, proving); k_bounce_evaluate_halving plays the same ply from a copy of its own, which says why.  The wave plays
+// one ply of every lane's game.  A lane's game is its kernel's own locals, taken by reference:
+// the board b with `plies` plies and the status st (BGS_ST_RUNNING, or how the game ended: 1 / 2 the winner + 1,
+// BGS_ST_DRAW), the global game id, the mover's action list mv, and the flags `has` (the lane holds a
+// game), `search` (b has just moved: its list is not made yet), have_block (blk holds the draws of the 4-ply block of
+// `plies`) and, for BGS_POLICY_DECISIVE, can_win (the list has a target in the mover's goal row).  A lane that takes a new
+// game sets has, search = "st is running" (a blocked side to move is settled by the search, also at the cap) and clears
+// have_block.
+//   * The action lists of the boards that have just moved, into the lane's LDS column.  A side to move without an action
+//     settles the game: the other side wins if IT could move, else a draw.
+//   * A game that has ended, or runs and holds the cap (st = BGS_ST_RUNNING = 0: counted nowhere), leaves the lane, and
+//     the function returns true for it: nothing below touches its st, so the caller finds there how it ended.  What a
+//     kernel does with a finished game is all the kernels differ in here, and stays in the kernel.
+//   * One ply on every running board.  BGS_POLICY_DECISIVE: when the list has a target in the mover's goal row every
+//     candidate ends the game for the mover, so the ply is one transition and the mover's win, nothing drawn or moved.
+//     Else the draw of DESIGN.md §3 ("RNG contract") at the game's absolute ply -- word plies & 3 of
+//     philox4x32_10(seed, game, plies >> 2), one call a four plies and for a new game -- indexes the list.
+// `stepped` grows by the transitions the lane made.
+template <int NC, int POLICY, class GEO>
+__device__ __forceinline__ bool bounce_playout_ply(const GEO& g, uint64_t seed, uint32_t max_plies, uint32_t* column, Board& b,
+                                                   FlatMoves<NC>& mv, uint32_t& st, uint32_t& plies, uint64_t game, bool& has,
+                                                   bool& search, bool& have_block, bool& can_win, Philox4& blk, uint32_t& stepped) {
+    if (__builtin_amdgcn_ballot_w64(search)) {
+        const uint64_t occ = occupancy(b);
+        enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
+        const bool blocked = search && mv.n == 0u;
+        if (__builtin_amdgcn_ballot_w64(blocked)) {
+            FlatMoves<NC> other = no_moves<NC>();
+            enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
+            if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
+        }
+        if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+            if (search) can_win = st == BGS_ST_RUNNING && b_can_win<NC>(mv, column, (plies & 1u) ? g.goal_bottom : g.goal_top);
+        }
+        search = false;
+    }
+    const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
+    const bool finished = has && !run;
+    has = has && run;
+    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+        if (run && can_win) {
+            st = (plies & 1u) + 1u;
+            ++plies;
+            stepped += 1u;
+        }
+    }
+    if (POLICY == BGS_POLICY_DECISIVE ? run && !can_win : run) {
+        if (!have_block || (plies & 3u) == 0u) {
+            blk = philox4x32_10(seed, game, plies >> 2);
+            have_block = true;
+        }
+        const uint32_t mover = plies & 1u;
+        int s, t;
+        pick_flat<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, t);
+        move_piece(b, s, t);
+        ++plies;
+        stepped += 1u;
+        if ((1ull << t) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
+        else search = true;
+    }
+    return finished;
 }
 
 template <class GEO, int NC, int POLICY = BGS_POLICY_UNIFORM>
@@ -1278,11 +1360,7 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
     Board b, cb;                     // the lane's game; the board after its segment's first move
 #pragma unroll
     for (int j = 0; j < 4; ++j) b.v[j] = cb.v[j] = 0;
-    FlatMoves<NC> mv;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) mv.counts[k] = 0;
-    mv.n = 0;
-    mv.row_base = 0;
+    FlatMoves<NC> mv = no_moves<NC>();
     uint32_t st = 0, plies = 0, child_st = 0, child_ply = 0, root_mover = 0, stepped = 0;
     uint32_t wins = 0, draws = 0, losses = 0;
     uint64_t cur_seg = ~0ull, cur_where = 0, game = 0;
@@ -1290,11 +1368,6 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
     Philox4 blk;
     blk.v[0] = blk.v[1] = blk.v[2] = blk.v[3] = 0;
 
-    auto count = [&](uint32_t s) {   // s: status of a finished game (0: capped, counted nowhere)
-        wins += (s != 0u && s != BGS_ST_DRAW && s - 1u == root_mover) ? 1u : 0u;
-        losses += (s != 0u && s != BGS_ST_DRAW && s - 1u != root_mover) ? 1u : 0u;
-        draws += s == BGS_ST_DRAW ? 1u : 0u;
-    };
     auto flush = [&]() {   // this lane's counts of cur_seg -> the window, or global memory
         if (wins | draws | losses) {
             const uint64_t k = cur_seg - win_base;
@@ -1410,52 +1483,8 @@ k_bounce_evaluate(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __r
         }
         if (!__builtin_amdgcn_ballot_w64(has)) break;
 
-        // ---- the action lists of the boards that have just moved; a side to move without an action settles the game:
-        // the other side wins if IT could move, else a draw
-        if (__builtin_amdgcn_ballot_w64(search)) {
-            const uint64_t occ = occupancy(b);
-            enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
-            const bool blocked = search && mv.n == 0u;
-            if (__builtin_amdgcn_ballot_w64(blocked)) {
-                FlatMoves<NC> other;
-#pragma unroll
-                for (int k = 0; k < NC; ++k) other.counts[k] = 0;
-                other.n = 0;
-                other.row_base = 0;
-                enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
-                if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
-            }
-            if constexpr (POLICY == BGS_POLICY_DECISIVE) {
-                if (search) can_win = st == BGS_ST_RUNNING && b_can_win<NC>(mv, column, (plies & 1u) ? g.goal_bottom : g.goal_top);
-            }
-            search = false;
-        }
-        const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
-        if (has && !run) {
-            count(st);
-            has = false;
-        }
-        // ---- one ply on every running board
-        if constexpr (POLICY == BGS_POLICY_DECISIVE) {
-            if (run && can_win) {   // every candidate ends the game for the mover: one transition, nothing drawn or moved
-                st = (plies & 1u) + 1u;
-                ++plies;
-                stepped += 1u;
-            }
-        }
-        if (POLICY == BGS_POLICY_DECISIVE ? run && !can_win : run) {
-            if (!have_block || (plies & 3u) == 0u) {
-                blk = philox4x32_10(seed, game, plies >> 2);
-                have_block = true;
-            }
-            const uint32_t mover = plies & 1u;
-            int s, t;
-            pick_flat<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, t);
-            move_piece(b, s, t);
-            ++plies;
-            stepped += 1u;
-            if ((1ull << t) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
-            else search = true;
+        if (bounce_playout_ply<NC, POLICY>(g, seed, max_plies, column, b, mv, st, plies, game, has, search, have_block, can_win, blk, stepped)) {
+            wdl_count(st, root_mover, wins, draws, losses);
         }
     }
     flush();
@@ -1499,8 +1528,8 @@ void launch_bounce_evaluate(const bgs_batch* b, const GEO& g, uint64_t seed, uin
 // searched by lane x (reach), the masks go to LDS, and every lane of the team fills its share of the arm table (source
 // cell, target cell).  The root board stays in registers: a lane that takes a playout applies its arm's move to it.  A
 // round's items are |S_r| * q_r playouts in (arm ascending, p) order; the waves draw them from a counter in LDS and refill
-// their idle lanes at ply boundaries; the ply is k_bounce_evaluate's (the search into the lane's LDS column, the
-// blocked-side settlement, the decisive short-cut, a philox call per four plies).  A finished playout is one LDS atomic
+// their idle lanes at ply boundaries; the ply is this kernel's own copy of bounce_playout_ply (the search into the lane's
+// LDS column, the blocked-side settlement, the decisive short-cut, a philox call per four plies).  A finished playout is one LDS atomic
 // into the tally [arm][3], so the result does not depend on which lane played what.  A barrier ends the round.  Selection
 // is by rank: lanes take the survivors tid, tid + BGS_BLOCK, ... and count those that beat each one on (score descending,
 // arm ascending); an arm that leaves -- in the last round every arm -- stores its counts and its playouts.  The kept arms
@@ -1639,8 +1668,9 @@ k_bounce_evaluate_halving(GEO g, const uint64_t* __restrict__ planes, const uint
             }
             if (!__builtin_amdgcn_ballot_w64(has)) continue;
 
-            // ---- the ply of k_bounce_evaluate: the action lists of the boards that have just moved (a side to move
-            // without an action settles the game), the cap, one move
+            // ---- this kernel's own copy of bounce_playout_ply, kept equal by eye: the same draws, the same ply code.  With
+            // the shared call its registers, LDS and waves were the same and its uniform launches some 4 % slower at 64 and 256
+            // roots (docs/EXPERIMENTS.md §36)
             if (__builtin_amdgcn_ballot_w64(search)) {
                 const uint64_t occ = occupancy(b);
                 enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
@@ -1787,7 +1817,7 @@ void launch_bounce_evaluate_halving(const bgs_batch* b, const GEO& g, uint64_t s
 // (U << 9 | 511 - arm) + 1 the same way (U < 2^17).  The reduction words are double-buffered by the parity of the depth:
 // every step has at least one barrier, so a wave cannot write a buffer that another wave still reads.
 //
-// The leaf's P playouts are the halving kernel's refill loop and ply, unchanged in their draws: the waves draw playouts
+// The leaf's P playouts are the halving kernel's refill loop and bounce_playout_ply: the waves draw playouts
 // from a counter in LDS, refill idle lanes at ply boundaries, count W/D/L of the root's mover in registers and add them
 // to an LDS tally when the leaf is played out.  Lane k then updates edge k of the path.
 //
@@ -2031,11 +2061,7 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
     Board b;                         // the lane's game
 #pragma unroll
     for (int j = 0; j < 4; ++j) b.v[j] = 0;
-    FlatMoves<NC> mv;
-#pragma unroll
-    for (int k = 0; k < NC; ++k) mv.counts[k] = 0;
-    mv.n = 0;
-    mv.row_base = 0;
+    FlatMoves<NC> mv = no_moves<NC>();
     uint32_t st = 0, plies = 0, stepped = 0;
     uint64_t game = 0;
     bool has = false, search = false, have_block = false;
@@ -2175,7 +2201,7 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
             break;
         }
 
-        // ---- the leaf's playouts: the halving kernel's refill loop and ply from p'
+        // ---- the leaf's playouts: the halving kernel's refill loop, from p'
         const bool play = leaf == BGS_ST_RUNNING && !capped;
         if (tid < 3u) tally[tid] = 0;
         if (tid == 0) next_item = 0;
@@ -2210,51 +2236,8 @@ k_bounce_search(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __res
                 }
                 if (!__builtin_amdgcn_ballot_w64(has)) continue;
 
-                if (__builtin_amdgcn_ballot_w64(search)) {
-                    const uint64_t occ = occupancy(b);
-                    enumerate_flat<NC, true>(g, b, occ, plies & 1u, search, column, mv);
-                    const bool blocked = search && mv.n == 0u;
-                    if (__builtin_amdgcn_ballot_w64(blocked)) {
-                        FlatMoves<NC> other;
-#pragma unroll
-                        for (int k = 0; k < NC; ++k) other.counts[k] = 0;
-                        other.n = 0;
-                        other.row_base = 0;
-                        enumerate_flat<NC, true>(g, b, occ, 1u - (plies & 1u), blocked, column, other);
-                        if (blocked) st = other.n ? (1u - (plies & 1u)) + 1u : BGS_ST_DRAW;
-                    }
-                    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
-                        if (search) can_win = st == BGS_ST_RUNNING && b_can_win<NC>(mv, column, (plies & 1u) ? g.goal_bottom : g.goal_top);
-                    }
-                    search = false;
-                }
-                const bool run = has && st == BGS_ST_RUNNING && plies < max_plies;
-                if (has && !run) {       // finished (a capped game, st 0, is counted nowhere)
-                    wins += (st != 0u && st != BGS_ST_DRAW && st - 1u == root_mover) ? 1u : 0u;
-                    losses += (st != 0u && st != BGS_ST_DRAW && st - 1u != root_mover) ? 1u : 0u;
-                    draws += st == BGS_ST_DRAW ? 1u : 0u;
-                    has = false;
-                }
-                if constexpr (POLICY == BGS_POLICY_DECISIVE) {
-                    if (run && can_win) {   // every candidate ends the game for the mover: one transition, nothing drawn or moved
-                        st = (plies & 1u) + 1u;
-                        ++plies;
-                        stepped += 1u;
-                    }
-                }
-                if (POLICY == BGS_POLICY_DECISIVE ? run && !can_win : run) {
-                    if (!have_block || (plies & 3u) == 0u) {
-                        blk = philox4x32_10(seed, game, plies >> 2);
-                        have_block = true;
-                    }
-                    const uint32_t mover = plies & 1u;
-                    int s, tc;
-                    pick_flat<NC>(mv, column, sample_index(philox_word(blk, plies), mv.n), s, tc);
-                    move_piece(b, s, tc);
-                    ++plies;
-                    stepped += 1u;
-                    if ((1ull << tc) & (g.goal_top | g.goal_bottom)) st = mover + 1u;
-                    else search = true;
+                if (bounce_playout_ply<NC, POLICY>(g, seed, max_plies, column, b, mv, st, plies, game, has, search, have_block, can_win, blk, stepped)) {
+                    wdl_count(st, root_mover, wins, draws, losses);
                 }
             }
             if (wins) atomicAdd(tally + 0, wins);

@@ -240,6 +240,9 @@ CHAINS = (
     Chain("ids", "small", 8, 6, 49, None, E0, None, "uniform", 2**33, _moves(1000, (24, 8, "best"), (24, 8, "best2"), (24, 8, "best"))),
     # trees of several hundred nodes on two roots: a re-rooting over many chunks that keeps more than 256 nodes
     Chain("large", "default", 2, 5, 2048, None, 0, None, "uniform", 0, _moves(1100, (1000, 1, "best"), (100, 1, "best"), (100, 1, "best"))),
+    # the decisive playout policy in a kept tree off the default grid: 12 columns (three count words) and a grid of run-time geometry
+    Chain("wide_decisive", "wide", 4, 3, 129, None, E0, None, "decisive", 3, _moves(1200, (100, 2, "deep"), (40, 2, "deep"), (40, 2, "best"))),
+    Chain("small_decisive", "small", 4, 6, 33, None, E0, None, "decisive", 1, _moves(1300, (16, 4, "best"), (16, 4, "best"), (16, 4, "best"))),
 )
 BY_NAME = {c.name: c for c in CHAINS}
 # the game of BounceTreeSearchAgent(reuse=True) against a scripted reply (the most visited arm of its tree): seeds SEED, SEED + 1, ...,
