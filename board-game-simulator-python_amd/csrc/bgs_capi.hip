@@ -24,6 +24,8 @@ extern "C" const char bgs_tu_id_connect[];
 extern "C" const char bgs_tu_id_bounce[];
 extern "C" const char bgs_tu_id_generic[];
 extern "C" const char bgs_tu_id_evaluate[];
+extern "C" const char bgs_tu_id_search[];
+extern "C" const char bgs_tu_id_solve[];
 
 namespace {
 thread_local char g_error[512] = "";
@@ -740,14 +742,14 @@ extern "C" {
 
 int bgs_version(void) { return 200; }
 
-// The identity of the kernels this library was LINKED with: the four units' own ids folded into 16 hex digits (the same
+// The identity of the kernels this library was LINKED with: the six units' own ids folded into 16 hex digits (the same
 // fold as `make print-id`: h = id_0; h = h * 0x100000001b3 ^ id_k, 64-bit wrap-around).  "unknown..." when a unit was
 // compiled outside the Makefile.
 const char* bgs_build_id(void) {
     static const std::string id = [] {
         uint64_t h = 0;
         bool first = true;
-        for (const char* tu : {bgs_tu_id_connect, bgs_tu_id_bounce, bgs_tu_id_generic, bgs_tu_id_evaluate}) {
+        for (const char* tu : {bgs_tu_id_connect, bgs_tu_id_bounce, bgs_tu_id_generic, bgs_tu_id_evaluate, bgs_tu_id_search, bgs_tu_id_solve}) {
             char* end = nullptr;
             const uint64_t v = strtoull(tu, &end, 16);
             if (end == tu || *end != 0) return std::string("unknown");
@@ -767,6 +769,8 @@ const char* bgs_kernel_unit_id(int unit) {
         case 1: return bgs_tu_id_bounce;
         case 2: return bgs_tu_id_generic;
         case 3: return bgs_tu_id_evaluate;
+        case 4: return bgs_tu_id_search;
+        case 5: return bgs_tu_id_solve;
         default: return nullptr;
     }
 }

@@ -135,7 +135,7 @@ void connect_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32
 int32_t connect_halving_min_budget(int width);
 void connect_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* d_counts,
                               int32_t* d_given, int32_t* d_best);
-// UCT tree search over packed Connect boards (bgs_connect_search_actions): counts int32[n][w][3], visits int32[n][w],
+// UCT tree search over packed Connect boards (bgs_connect_search_actions; search_kernels.hip): counts int32[n][w][3], visits int32[n][w],
 // best int32[n] and nodes int32[n] (the last three may be NULL) on the device, every entry written; d_workspace: n *
 // connect_search_root_bytes(w, iterations) bytes, 256-byte aligned, no preparation needed; enqueued on the batch's stream
 uint64_t connect_search_root_bytes(int width, int32_t iterations);
@@ -154,7 +154,7 @@ void connect_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations
                            int32_t max_plies, int policy, int32_t capacity, int restart, int32_t* d_counts, int32_t* d_visits,
                            int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest);
 void connect_forest_advance(const bgs_batch* b, const int32_t* d_columns, int32_t capacity, int32_t* d_kept, void* d_forest);
-// exact alpha-beta solve of every column of packed Connect boards (bgs_connect_solve_actions): codes int8[n][w], plies
+// exact alpha-beta solve of every column of packed Connect boards (bgs_connect_solve_actions; solve_kernels.hip): codes int8[n][w], plies
 // int16[n][w] (may be NULL), *d_nodes = positions visited; device pointers, enqueued on the batch's stream
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,
                    unsigned long long* d_nodes);
@@ -168,7 +168,7 @@ void bounce_evaluate(const bgs_batch* b, uint64_t seed, int32_t playouts, int32_
 // given are zeroed here, best is written for every board; no scratch; enqueued on the batch's stream
 void bounce_evaluate_halving(const bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy, int32_t* d_counts,
                              int32_t* d_given, int32_t* d_best);
-// UCT tree search over packed Bounce boards (bgs_bounce_search_moves): counts int32[n][w][h * w][3], visits
+// UCT tree search over packed Bounce boards (bgs_bounce_search_moves; search_kernels.hip): counts int32[n][w][h * w][3], visits
 // int32[n][w][h * w], best, nodes and used int32[n] (all but counts may be NULL) on the device; counts and visits are
 // zeroed here, the per-board outputs are written for every board; edges >= BGS_BOUNCE_SEARCH_MIN_EDGES(h, w);
 // d_workspace: n * bounce_search_root_bytes(iterations, edges) bytes, 256-byte aligned, no preparation needed; enqueued
@@ -190,7 +190,7 @@ void bounce_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations,
                           int32_t max_plies, int policy, int32_t capacity, int32_t edges, int restart, int32_t* d_counts,
                           int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int32_t* d_carried, void* d_forest);
 void bounce_forest_advance(const bgs_batch* b, const int32_t* d_slots, int32_t capacity, int32_t edges, int32_t* d_kept, void* d_forest);
-// exact horizon search of every legal move of packed Bounce boards (bgs_bounce_solve_moves): codes int8[n][w][h * w] and
+// exact horizon search of every legal move of packed Bounce boards (bgs_bounce_solve_moves; solve_kernels.hip): codes int8[n][w][h * w] and
 // plies int16[n][w][h * w] (may be NULL) are filled here (illegal slots NONE / 0), *d_nodes = positions visited; scratch
 // as bounce_evaluate; depth 1 .. BGS_BOUNCE_SOLVE_MAX_DEPTH; device pointers, enqueued on the batch's stream
 void bounce_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies, unsigned long long* d_nodes,

@@ -395,11 +395,11 @@ def unit_ids() -> dict:
 
 
 # kernel units beyond UNITS (bench.py records UNITS alone, and its line stays as it was): index -> name
-EXTRA_UNITS = {3: "evaluate"}
+EXTRA_UNITS = {3: "evaluate", 4: "search", 5: "solve"}
 
 
 def extra_unit_ids() -> dict:
-    """{"evaluate": id}: the ids of the kernel units that are not in UNITS (bgs_kernel_unit_id(3) on)."""
+    """{"evaluate": id, "search": id, "solve": id}: the ids of the kernel units that are not in UNITS (bgs_kernel_unit_id(3) on)."""
     return {name: (lib().bgs_kernel_unit_id(k) or b"unknown").decode("ascii") for k, name in EXTRA_UNITS.items()}
 
 

@@ -92,12 +92,12 @@ BGS_API int bgs_version(void);
 BGS_API const char* bgs_last_error(void);
 BGS_API int bgs_device_count(int* count);
 /* identity of the kernels this library was LINKED with (16 hex digits): every kernel translation unit embeds the hash of
- * its own source, the kernel headers and the compile flags when it is compiled, and this folds the four.  Measurement
+ * its own source, the kernel headers and the compile flags when it is compiled, and this folds the six.  Measurement
  * files under profiles/ carry the id of the build they were taken on, and bench.py refuses to quote instruction counts
  * of another build.  `make -C csrc print-id` gives the id the sources in the tree would produce. */
 BGS_API const char* bgs_build_id(void);
-/* the id one kernel unit was compiled with: 0 connect_kernels, 1 bounce_kernels, 2 generic_kernels, 3 evaluate_kernels;
- * NULL otherwise */
+/* the id one kernel unit was compiled with: 0 connect_kernels, 1 bounce_kernels, 2 generic_kernels, 3 evaluate_kernels,
+ * 4 search_kernels, 5 solve_kernels; NULL otherwise */
 BGS_API const char* bgs_kernel_unit_id(int unit);
 
 /* ---- configuration + batch lifetime ------------------------------------------------------------- */

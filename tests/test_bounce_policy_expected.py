@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests import bounce_policy_expected as be
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, ROOT, TEST_LIB
 from tests.mc_expected import expected
 
@@ -105,9 +106,8 @@ def test_python_signatures_show_the_policy():
         playout_policy("greedy")
 
 
-def test_both_libraries_export_it_from_four_kernel_units():
+def test_both_libraries_export_it_from_six_kernel_units():
     for path in (PRODUCT_LIB, TEST_LIB):
         out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
         assert SYMBOL in {line.split()[-1] for line in out.splitlines() if line.strip()}, path
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", os.path.join(PKG, "csrc"), "print-unit-ids"], text=True)
-    assert [line.split()[0] for line in out.splitlines()] == ["connect", "bounce", "generic", "evaluate"]
+    kernel_units.check_six_distinct_ids()

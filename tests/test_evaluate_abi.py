@@ -1,10 +1,12 @@
 """CPU-only checks of the flat Monte-Carlo evaluation's plumbing: both libraries export bgs_connect_evaluate_actions, its
-kernels are a fourth kernel unit of their own, and bench.py's three units are untouched by it."""
+kernels are a fourth kernel unit of their own (of six: the searches and the solvers follow it), and bench.py's three units
+are untouched by it."""
 
 import os
 import subprocess
 import sys
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -21,10 +23,8 @@ def test_both_libraries_export_the_evaluation():
 
 
 def test_the_evaluation_is_a_fourth_kernel_unit():
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    units = dict(line.split() for line in out.splitlines())
-    assert list(units) == ["connect", "bounce", "generic", "evaluate"]
-    assert len(set(units.values())) == 4 and all(len(v) == 16 for v in units.values())
+    units = kernel_units.check_six_distinct_ids()
+    assert list(units)[3] == "evaluate" and kernel_units.units_defining("k_connect_evaluate<") == ["evaluate"]
 
 
 def test_loaded_library_reports_the_fourth_unit_and_bench_keeps_three():
@@ -35,6 +35,5 @@ def test_loaded_library_reports_the_fourth_unit_and_bench_keeps_three():
     env = dict(os.environ, BGS_LIBRARY=PRODUCT_LIB)
     out = subprocess.check_output([sys.executable, "-c", code, PKG], text=True, env=env).splitlines()
     assert out[0].split() == ["connect", "bounce", "generic"]
-    made = dict(line.split() for line in subprocess.check_output(
-        ["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True).splitlines())
+    made = kernel_units.made_unit_ids()
     assert out[1].split() == [made["connect"], made["evaluate"]]

@@ -4,6 +4,7 @@ the header declares it, and its kernels live in the existing evaluate unit (stil
 import os
 import subprocess
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, ROOT, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -25,10 +26,9 @@ def test_the_header_declares_it():
     assert "BGS_API int bgs_bounce_evaluate_moves(bgs_batch* b, uint64_t seed, int32_t playouts, int32_t max_plies," in text
 
 
-def test_still_four_kernel_units():
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    units = dict(line.split() for line in out.splitlines())
-    assert list(units) == ["connect", "bounce", "generic", "evaluate"]
+def test_the_kernel_lives_in_the_evaluate_unit_of_six():
+    kernel_units.check_six_distinct_ids()
+    assert kernel_units.units_defining("k_bounce_evaluate<") == ["evaluate"]
 
 
 def test_python_binding_is_declared():

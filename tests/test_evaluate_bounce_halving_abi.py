@@ -1,11 +1,12 @@
 """CPU-only checks of the Bounce sequential-halving evaluation's plumbing: both libraries export
 bgs_bounce_evaluate_moves_halving, the ctypes binding table has it with the header's nine arguments, and its kernel lives
-in the evaluate unit: `make print-unit-ids` still lists four units."""
+in the evaluate unit, one of the six `make print-unit-ids` lists."""
 
 import ctypes
 import os
 import subprocess
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -51,8 +52,6 @@ def test_the_python_layer_has_the_methods_and_the_agent():
     assert agent.predict_many([]) == [] and agent.choose_many([]) == []
 
 
-def test_there_are_still_four_kernel_units():
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    units = dict(line.split() for line in out.splitlines())
-    assert list(units) == ["connect", "bounce", "generic", "evaluate"]
-    assert len(set(units.values())) == 4
+def test_the_kernel_lives_in_the_evaluate_unit_of_six():
+    kernel_units.check_six_distinct_ids()
+    assert kernel_units.units_defining("k_bounce_evaluate_halving") == ["evaluate"]

@@ -1,11 +1,12 @@
 """CPU-only checks of the sequential-halving evaluation's plumbing: both libraries export
 bgs_connect_evaluate_actions_halving, the ctypes binding table has it with the header's nine arguments, and its kernel
-lives in the evaluate unit: `make print-unit-ids` still lists four units."""
+lives in the evaluate unit, one of the six `make print-unit-ids` lists."""
 
 import ctypes
 import os
 import subprocess
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -37,8 +38,6 @@ def test_the_header_declares_it():
     assert f"BGS_API int {SYMBOL}(bgs_batch* b, uint64_t seed, int32_t budget, int32_t max_plies, int policy," in text
 
 
-def test_there_are_still_four_kernel_units():
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    units = dict(line.split() for line in out.splitlines())
-    assert list(units) == ["connect", "bounce", "generic", "evaluate"]
-    assert len(set(units.values())) == 4
+def test_the_kernel_lives_in_the_evaluate_unit_of_six():
+    kernel_units.check_six_distinct_ids()
+    assert kernel_units.units_defining("k_connect_evaluate_halving") == ["evaluate"]

@@ -2,7 +2,7 @@
 bgs_connect_search_workspace_bytes, the header declares them, the version script lets them out, the ctypes binding table
 has them with the header's arguments, a NULL batch is refused with BGS_ERR_ARG and a message (the one refusal that can be
 reached without a device: every other argument check needs a batch and is made in tests/test_gpu_search.py), the Python
-surface is there, and only the evaluate unit's id moved: `make print-unit-ids` still lists four units."""
+surface is there, and the kernel lives in the search unit, one of the six `make print-unit-ids` lists."""
 
 import ctypes
 import fnmatch
@@ -13,6 +13,7 @@ import subprocess
 
 import pytest
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -98,8 +99,6 @@ def test_the_python_surface():
         agents.TreeSearchAgent(explore=(1 << 18) + 1)
 
 
-def test_there_are_still_four_kernel_units():
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    units = dict(line.split() for line in out.splitlines())
-    assert list(units) == ["connect", "bounce", "generic", "evaluate"]
-    assert len(set(units.values())) == 4
+def test_the_kernel_lives_in_the_search_unit_of_six():
+    kernel_units.check_six_distinct_ids()
+    assert kernel_units.units_defining("k_connect_search") == ["search"]

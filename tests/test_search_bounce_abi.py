@@ -2,8 +2,8 @@
 bgs_bounce_search_workspace_bytes, the header declares them verbatim, the version script lets them out, the ctypes binding
 table has them with the header's argument counts, a NULL batch is refused with BGS_ERR_ARG and a message (the one refusal
 that can be reached without a device: every other argument check needs a batch and is made in
-tests/test_gpu_search_bounce.py), the Python surface is there, and the kernel lives in the evaluate unit: `make
-print-unit-ids` still lists four units."""
+tests/test_gpu_search_bounce.py), the Python surface is there, and the kernel lives in the search unit, one of the six `make
+print-unit-ids` lists."""
 
 import ctypes
 import fnmatch
@@ -14,6 +14,7 @@ import subprocess
 
 import pytest
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -120,13 +121,8 @@ def test_the_python_surface():
         agents.BounceTreeSearchAgent(iterations=0)
 
 
-def test_the_kernel_lives_in_the_evaluate_unit():
-    with open(os.path.join(CSRC, "evaluate_kernels.hip")) as f:
+def test_the_kernel_lives_in_the_search_unit():
+    with open(kernel_units.source("search")) as f:
         assert "k_bounce_search(" in f.read()
-    for unit in ("connect", "bounce", "generic", "evaluate"):
-        symbols = subprocess.check_output(["nm", "-C", os.path.join(CSRC, f"{unit}_kernels.o")], text=True)
-        assert ("k_bounce_search" in symbols) == (unit == "evaluate"), unit
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    units = dict(line.split() for line in out.splitlines())
-    assert list(units) == ["connect", "bounce", "generic", "evaluate"]
-    assert len(set(units.values())) == 4
+    assert kernel_units.units_defining("k_bounce_search") == ["search"]   # that unit's object and no other
+    kernel_units.check_six_distinct_ids()

@@ -14,6 +14,7 @@ import subprocess
 
 import pytest
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -104,11 +105,11 @@ def test_the_python_surface():
 
 
 def test_the_proving_search_is_a_form_of_the_search_kernel():
-    with open(os.path.join(CSRC, "evaluate_kernels.hip")) as f:
+    with open(kernel_units.source("search")) as f:
         text = f.read()
     kernel = text[text.index("k_bounce_search(GEO g"):text.index("struct BounceSearchArgs")]
     assert "template <class GEO, int NC, int POLICY, bool FOREST, bool PROVE = false>" in text
     assert "static_assert(!(PROVE && FOREST)" in kernel and "if constexpr (PROVE)" in kernel
     assert "bounce_search_proving" in text
-    assert sorted(name for name in os.listdir(CSRC) if name.endswith("_kernels.hip")) == [
-        "bounce_kernels.hip", "connect_kernels.hip", "evaluate_kernels.hip", "generic_kernels.hip"]
+    assert kernel_units.kernel_files() == sorted(f"{unit}_kernels.hip" for unit in kernel_units.UNITS)
+    assert not [name for name in os.listdir(CSRC) if "prov" in name]

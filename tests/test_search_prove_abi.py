@@ -2,7 +2,7 @@
 header declares it with its contract, the version script lets it out, the ctypes binding table has it with the header's
 arguments, a NULL batch is refused with BGS_ERR_ARG and a message (the one refusal that can be reached without a device:
 every other argument check needs a batch and is made in tests/test_gpu_search_prove.py), the Python surface is there --
-the Bounce refusal and the `prove` with `reuse` refusal included --, and `make print-unit-ids` still lists four units."""
+the Bounce refusal and the `prove` with `reuse` refusal included --, and `make print-unit-ids` lists the six units, none of them the proving search's own."""
 
 import ctypes
 import fnmatch
@@ -13,6 +13,7 @@ import subprocess
 
 import pytest
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -101,14 +102,11 @@ def test_the_python_surface():
         agents.TreeSearchAgent(prove=True, reuse=True)
 
 
-def test_there_are_still_four_kernel_units():
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    units = dict(line.split() for line in out.splitlines())
-    assert list(units) == ["connect", "bounce", "generic", "evaluate"]
-    assert len(set(units.values())) == 4
-    # the proving search is a form of k_connect_search in the evaluate unit, not a kernel file of its own
-    with open(os.path.join(CSRC, "evaluate_kernels.hip")) as f:
+def test_the_proving_search_has_no_kernel_unit_of_its_own():
+    kernel_units.check_six_distinct_ids()
+    # the proving search is a form of k_connect_search in the search unit, not a kernel file of its own
+    with open(kernel_units.source("search")) as f:
         text = f.read()
     assert "bool PROVE" in text and "connect_search_proving" in text
-    assert sorted(name for name in os.listdir(CSRC) if name.endswith("_kernels.hip")) == [
-        "bounce_kernels.hip", "connect_kernels.hip", "evaluate_kernels.hip", "generic_kernels.hip"]
+    assert kernel_units.kernel_files() == sorted(f"{unit}_kernels.hip" for unit in kernel_units.UNITS)
+    assert not [name for name in os.listdir(CSRC) if "prov" in name]

@@ -1,11 +1,12 @@
 """CPU-only checks of the exact solver's plumbing: both libraries export bgs_connect_solve_actions, the header declares
-it and its codes, the solver lives in the evaluate unit (still four kernel units), and bench.py's units are untouched."""
+it and its codes, the solver lives in the solve unit (one of six kernel units), and bench.py's units are untouched."""
 
 import os
 import re
 import subprocess
 import sys
 
+from tests import kernel_units
 from tests.conftest import PKG, PRODUCT_LIB, ROOT, TEST_LIB
 
 CSRC = os.path.join(PKG, "csrc")
@@ -35,10 +36,9 @@ def test_header_declares_the_solver_and_its_codes():
         (-2, -1, 0, 1, 2, 3)
 
 
-def test_still_four_kernel_units():
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    units = dict(line.split() for line in out.splitlines())
-    assert list(units) == ["connect", "bounce", "generic", "evaluate"]
+def test_the_solver_lives_in_the_solve_unit_of_six():
+    kernel_units.check_six_distinct_ids()
+    assert kernel_units.units_defining("k_connect_solve") == ["solve"] and kernel_units.units_defining("bgs::connect_solve(") == ["solve"]
 
 
 def test_abi_units_unchanged():

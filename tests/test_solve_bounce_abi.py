@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 
 from tests import game_trees as gt
+from tests import kernel_units
 from tests import solve_reference_bounce as ref
 from tests import spec_rules as spec
 from tests.conftest import PKG, PRODUCT_LIB, ROOT, TEST_LIB
@@ -35,8 +36,8 @@ def test_symbol_in_header_map_and_binding():
     assert "bgs_bounce_solve_moves" in _abi.SIGNATURES
     assert _abi.SIGNATURES["bgs_bounce_solve_moves"] == _abi.SIGNATURES["bgs_connect_solve_actions"]
     assert batch.BOUNCE_SOLVE_MAX_DEPTH == 16 and batch.DEFAULT_BOUNCE_SOLVE_DEPTH == 3
-    out = subprocess.check_output(["make", "-s", "--no-print-directory", "-C", CSRC, "print-unit-ids"], text=True)
-    assert [line.split()[0] for line in out.splitlines()] == ["connect", "bounce", "generic", "evaluate"]
+    kernel_units.check_six_distinct_ids()
+    assert kernel_units.units_defining("k_bounce_solve") == ["solve"] and kernel_units.units_defining("bgs::bounce_solve(") == ["solve"]
 
 
 def one_root(grid, player=0):

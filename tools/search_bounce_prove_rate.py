@@ -148,7 +148,8 @@ def against_parent(parent_tree, ab_rounds, res):
                     if step is None:
                         return rows     # nothing more is started on the GPU after a step that failed
                     row[key].append(step["search"]["device_ms"])
-                    row[key.replace("_ms", "_evaluate_unit")] = step["unit_ids"].get("evaluate")
+                    # (a parent tree from before the search unit was split off holds k_bounce_search in its evaluate unit)
+                    row[key.replace("_ms", "_search_unit")] = step["unit_ids"].get("search", step["unit_ids"].get("evaluate"))
             row["this_inside_parent_range"] = min(row["parent_ms"]) <= statistics.median(row["this_ms"]) <= max(row["parent_ms"])
             rows.append(row)
     return rows
