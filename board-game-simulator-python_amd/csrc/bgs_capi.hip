@@ -1327,6 +1327,58 @@ int bgs_connect_forest_advance(bgs_batch* b, const int32_t* columns, int32_t cap
     });
 }
 
+// the checks of both guided entry points that need no device; *bytes: the trees of the batch
+static int connect_guided_check(const bgs_batch* b, int32_t capacity, size_t* bytes) {
+    NEED(b->game == BGS_GAME_CONNECT, "guided: Connect batches only");
+    NEED(!b->generic, "guided: bit-packed Connect boards only (up to %d bits a plane); %dx%d boards are generic",
+         64 * BGS_CONNECT_MAX_WORDS, b->cg.h, b->cg.w);
+    NEED(capacity >= 2 && capacity <= BGS_GUIDED_MAX_CAPACITY, "capacity must be 2 .. %d nodes a tree (got %d)",
+         BGS_GUIDED_MAX_CAPACITY, capacity);
+    const uint64_t tree = bgs::connect_guided_tree_bytes(b->cg.h, b->cg.w, capacity);
+    NEED((uint64_t)b->n <= (uint64_t)(SIZE_MAX / 2) / tree, "the trees of %lld boards x %d nodes overflow size_t", (long long)b->n,
+         capacity);
+    *bytes = (size_t)((uint64_t)b->n * tree);
+    return BGS_OK;
+}
+
+int bgs_connect_guided_bytes(const bgs_batch* b, int32_t capacity, size_t* bytes) {
+    NEED(b != nullptr, "batch is NULL");
+    NEED(bytes != nullptr, "bytes is NULL");
+    return connect_guided_check(b, capacity, bytes);
+}
+
+int bgs_connect_guided_step(bgs_batch* b, int32_t capacity, int32_t cpuct, uint32_t flags, const float* priors, const float* values,
+                            int8_t* leaf_grid, int8_t* leaf_player, int32_t* leaf_kind, int32_t* visits, int32_t* scores,
+                            int32_t* best, int32_t* nodes, void* trees, size_t trees_bytes) {
+    int rc = enter(b);
+    if (rc) return rc;
+    size_t need = 0;
+    rc = connect_guided_check(b, capacity, &need);
+    if (rc) return rc;
+    NEED(cpuct >= 0 && cpuct <= 4096, "cpuct must be 0 .. 4096, c_puct in Q8 (got %d)", cpuct);
+    NEED((flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH)) == 0u, "unknown flag bits 0x%x (BGS_GUIDED_RESTART 0x%x, BGS_GUIDED_FINISH 0x%x)",
+         flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH), BGS_GUIDED_RESTART, BGS_GUIDED_FINISH);
+    NEED((flags & BGS_GUIDED_RESTART) == 0u || (flags & BGS_GUIDED_FINISH) == 0u,
+         "BGS_GUIDED_RESTART with BGS_GUIDED_FINISH: a restarted tree has nothing to finish");
+    NEED(trees != nullptr, "trees is NULL (the caller owns them; bgs_connect_guided_bytes says how large)");
+    NEED(leaf_grid != nullptr, "leaf_grid is NULL");
+    NEED(leaf_player != nullptr, "leaf_player is NULL");
+    NEED(leaf_kind != nullptr, "leaf_kind is NULL");
+    NEED((flags & BGS_GUIDED_RESTART) != 0u || priors != nullptr, "priors is NULL (allowed with BGS_GUIDED_RESTART only)");
+    NEED((flags & BGS_GUIDED_RESTART) != 0u || values != nullptr, "values is NULL (allowed with BGS_GUIDED_RESTART only)");
+    NEED((reinterpret_cast<uintptr_t>(trees) & 255u) == 0, "trees must be 256-byte aligned");
+    const struct {
+        const char* name;
+        const void* ptr;
+    } rest[] = {{"priors", priors},   {"values", values}, {"leaf_grid", leaf_grid}, {"leaf_player", leaf_player}, {"leaf_kind", leaf_kind},
+                {"visits", visits},   {"scores", scores}, {"best", best},           {"nodes", nodes}};
+    for (const auto& p : rest) NEED((reinterpret_cast<uintptr_t>(p.ptr) & 15u) == 0, "device %s must be 16-byte aligned", p.name);
+    NEED(trees_bytes >= need, "the trees are too small: %zu bytes, %zu needed", trees_bytes, need);
+    bgs::connect_guided_step(b, capacity, cpuct, flags, priors, values, leaf_grid, leaf_player, leaf_kind, visits, scores, best, nodes,
+                             trees);
+    return finish_launch();
+}
+
 // the outputs of both solvers; d[2], the node counter, keeps its 8-byte rule, and without a caller's counter the total
 // goes to the batch's own scratch word (behind the work-queue head)
 static void add_solve_outputs(bgs::OutputPlan& plan, size_t cells, int8_t* codes, int16_t* plies, uint64_t* nodes) {

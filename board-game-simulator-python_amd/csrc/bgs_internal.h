@@ -154,6 +154,14 @@ void connect_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations
                            int32_t max_plies, int policy, int32_t capacity, int restart, int32_t* d_counts, int32_t* d_visits,
                            int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest);
 void connect_forest_advance(const bgs_batch* b, const int32_t* d_columns, int32_t capacity, int32_t* d_kept, void* d_forest);
+// one simulation of the PUCT search whose leaves the caller evaluates (bgs_connect_guided_step): d_trees holds n *
+// connect_guided_tree_bytes(h, w, capacity) bytes, 256-byte aligned; d_priors float[n][w] and d_values float[n] are read
+// for trees with a pending EVALUATE leaf only; d_visits, d_scores, d_best and d_nodes may be NULL; every pointer is a
+// device pointer; enqueued on the batch's stream, the boards are not touched
+uint64_t connect_guided_tree_bytes(int height, int width, int32_t capacity);
+void connect_guided_step(const bgs_batch* b, int32_t capacity, int32_t cpuct, uint32_t flags, const float* d_priors,
+                         const float* d_values, int8_t* d_leaf_grid, int8_t* d_leaf_player, int32_t* d_leaf_kind, int32_t* d_visits,
+                         int32_t* d_scores, int32_t* d_best, int32_t* d_nodes, void* d_trees);
 // exact alpha-beta solve of every column of packed Connect boards (bgs_connect_solve_actions; solve_kernels.hip): codes int8[n][w], plies
 // int16[n][w] (may be NULL), *d_nodes = positions visited; device pointers, enqueued on the batch's stream
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,

@@ -2,7 +2,9 @@
 // bgs_connect_forest_search / bgs_connect_forest_advance, the proving search bgs_connect_search_actions_proving) in the
 // first half of this file, Bounce (bgs_bounce_search_moves and its forest and proving forms) in the second.  A search is
 // one kernel a game, k_connect_search / k_bounce_search; the forest and the proving search are template parameters of it
-// (FOREST, PROVE), and the re-rooting of a forest is a kernel of its own.  The section comments below describe each.
+// (FOREST, PROVE), and the re-rooting of a forest is a kernel of its own.  The PUCT search whose leaves the caller
+// evaluates (bgs_connect_guided_step, k_connect_search_guided) follows the Connect forest.  The section comments below
+// describe each.
 //
 // A unit of its own (bgs_kernel_unit_id(4)).  The leaves' playouts are the evaluation unit's (evaluate_kernels.hip): the
 // Connect 4-ply block is written out in k_connect_search, the Bounce ply is bounce_playout_ply of playout.h, which also
@@ -605,6 +607,286 @@ k_connect_forest_advance(uint32_t height, uint32_t width, uint32_t nw, const int
         head[0] = total;
         head[2u + ((stones & 1u) ? plane_words : 0u) + (bit >> 5)] |= 1u << (bit & 31u);
         if (kept) kept[i] = (int32_t)(total - 1u);
+    }
+}
+
+// ================================================================================================================
+// PUCT tree search with caller-evaluated leaves (bgs_connect_guided_step, include/bgs.h): one launch is one simulation
+// of every tree -- the caller's (priors, value) of the pending leaf go into the tree, the root's statistics come out,
+// and a descent finds the next leaf, whose position goes out for the caller's evaluator.  No playouts, no RNG.
+//
+// Shape: k_connect_search's.  One wave owns one tree; the descent is wave-uniform and rebuilds the position from the
+// root; lane c holds n, s, the child and P of column c of the node at hand and computes U(c); N and the arg-max key
+// are reduced over the lanes with readlane.  What differs is where the state between two simulations lives: the
+// launch ends at the leaf, so the path and the leaf's kind are in the tree's share, not in LDS.
+//
+// A node is 4 * width words: n[c], s[c], child[c] (0: none), P[c].  A tree's share, in 32-bit words, rounded up to 256
+// bytes:
+//     word 0         the nodes in use, the root counted (0: an emptied tree)
+//     word 1         the pending leaf: bits 7:0 its kind (kGuidedNone, kGuidedEvaluate, kGuidedWon, kGuidedFull), bits
+//                    31:16 the legal columns of an EVALUATE leaf, a bit a column (the priors are read for those alone)
+//     word 2         the edges of the pending path
+//     word 3         1 once the root has its P
+//     words 4 ..     the position the root stands for: the 2 * NW plane words of the batch, 64 bits each
+//     words 16 ..    the path: h * w words, edge k leaves node (word >> 4) by column (word & 15)
+//     then           `capacity` nodes
+// Every word read back from the share is used only within its bounds (a path no longer than h * w, a node below the
+// count, a column below the width): memory that passes the check by accident gives a wrong tree, never a wild store.
+//
+// Ordering: the tree is written by some lanes (lane k of the back-propagation, the lanes that fill a new node, lane 0
+// for the path) and read by others; a __syncthreads() of the one-wave workgroup stands between the application and
+// the report, the only such pair of a launch (the descent reads nodes the application wrote, behind the same barrier,
+// and the path it writes is read by the next launch).
+// ================================================================================================================
+constexpr uint32_t kGuidedHeaderWords = 16;
+constexpr uint32_t kGuidedNone = 0u, kGuidedEvaluate = 1u, kGuidedWon = 2u, kGuidedFull = 3u;
+static_assert(BGS_GUIDED_MAX_CAPACITY <= (1 << 28), "a path word holds node << 4 | column");
+static_assert(((uint64_t)BGS_GUIDED_MAX_VISITS + 1u) << 12 < ((uint64_t)1 << 32), "(N + 1) << 12 fits 32 bits");
+
+// words of a tree's share: the header, the path and `capacity` nodes, rounded up to 256 bytes (below 2^32)
+__host__ __device__ __forceinline__ uint64_t guided_tree_words(uint32_t height, uint32_t width, uint32_t capacity) {
+    return (kGuidedHeaderWords + (uint64_t)height * width + (uint64_t)capacity * width * 4u + 63u) & ~(uint64_t)63u;
+}
+
+// floor(num / den), den >= 1, num < 2^34: the double quotient of two such integers is within one of it
+__device__ __forceinline__ uint32_t guided_quotient(uint64_t num, uint32_t den) {
+    uint32_t q = (uint32_t)((double)num / (double)den);
+    while ((uint64_t)q * den > num) --q;
+    while ((uint64_t)(q + 1u) * den <= num) ++q;
+    return q;
+}
+
+template <int NW>
+__global__ void __launch_bounds__(BGS_WAVE)
+k_connect_search_guided(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, int64_t n,
+                        int64_t root_base, uint32_t capacity, uint32_t cpuct, uint32_t flags, const float* __restrict__ priors,
+                        const float* __restrict__ values, int8_t* __restrict__ leaf_grid, int8_t* __restrict__ leaf_player,
+                        int32_t* __restrict__ leaf_kind, int32_t* __restrict__ visits, int32_t* __restrict__ scores,
+                        int32_t* __restrict__ best, int32_t* __restrict__ nodes, uint32_t* trees) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t width = (uint32_t)g.w();
+    const uint32_t stride = (uint32_t)g.h() + 1u;
+    const uint32_t node_words = width * 4u;
+    const int64_t i = root_base + (int64_t)blockIdx.x;       // (the grid holds exactly the trees of this launch)
+    uint32_t* const head = trees + (uint64_t)i * guided_tree_words((uint32_t)g.h(), width, capacity);
+    uint64_t* const head_planes = reinterpret_cast<uint64_t*>(head + 4);
+    uint32_t* const path = head + kGuidedHeaderWords;
+    uint32_t* const tree = path + g.cells_total;
+
+    Bits<NW> r0, r1;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        r0.w[j] = planes[(int64_t)j * n + i];
+        r1.w[j] = planes[(int64_t)(NW + j) * n + i];
+    }
+    const uint32_t rply = popcount(r0) + popcount(r1);
+    const bool running = status[i] == BGS_ST_RUNNING;
+    // lane c: the stones in column c of a position (h for a lane without a column: never legal)
+    const auto heights = [&](const Bits<NW>& occ) {
+        uint32_t height = (uint32_t)g.h();
+        if (lane < width) height = (uint32_t)__popcll(shr(occ, (int)(lane * stride)).w[0] & ((1ull << g.h()) - 1ull));
+        return height;
+    };
+
+    // ---- 1. the check (wave-uniform: every lane reads the same header); a tree that fails it is emptied
+    uint32_t used = head[0], pending = head[1], depth = head[2], expanded = head[3];
+    bool live = (flags & BGS_GUIDED_RESTART) == 0u && running && used >= 1u && used <= capacity;
+    if (live) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) live = live && head_planes[j] == r0.w[j] && head_planes[NW + j] == r1.w[j];
+    }
+    live = __builtin_amdgcn_readfirstlane((int)live) != 0;
+    if (!live) {
+        used = running ? 1u : 0u;
+        pending = kGuidedNone;
+        depth = 0;
+        expanded = 0;
+        if (running && lane < node_words) tree[lane] = 0;     // the root is node 0 (4 * width <= 64 words)
+        if (running && lane == 0) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) {
+                head_planes[j] = r0.w[j];
+                head_planes[NW + j] = r1.w[j];
+            }
+        }
+    }
+    used = (uint32_t)__builtin_amdgcn_readfirstlane((int)used);
+    pending = (uint32_t)__builtin_amdgcn_readfirstlane((int)pending);
+    depth = (uint32_t)__builtin_amdgcn_readfirstlane((int)depth);
+    depth = depth < g.cells_total ? depth : g.cells_total;
+    expanded = (uint32_t)__builtin_amdgcn_readfirstlane((int)expanded);
+
+    // ---- 2. the application of the pending evaluation
+    const uint32_t kind = pending & 255u;
+    if (kind != kGuidedNone) {
+        uint32_t sigma = kind == kGuidedWon ? 0u : 1024u;     // the leaf's value for its mover, 0 .. 2048
+        if (kind == kGuidedEvaluate) {
+            const float x = values[i];
+            int32_t v = 0;
+            if (x == x) v = (int32_t)(fminf(fmaxf(x, -1.0f), 1.0f) * 1024.0f);
+            sigma = (uint32_t)(1024 + v);
+            // the priors of the leaf's legal columns, lane c column c: 16-bit weights, then 16-bit shares
+            const uint32_t columns = pending >> 16;
+            const bool legal = lane < width && ((columns >> lane) & 1u) != 0u;
+            uint32_t weight = 0;
+            if (legal) {
+                const float pr = priors[i * (int64_t)width + lane];
+                if (pr > 0.0f) weight = (uint32_t)(fminf(pr, 1.0f) * 65536.0f);
+            }
+            uint32_t sum = 0;
+            for (uint32_t c = 0; c < width; ++c) sum += (uint32_t)__builtin_amdgcn_readlane((int)weight, (int)c);
+            if (sum == 0u) {
+                weight = legal ? 1u : 0u;
+                sum = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(legal));
+            }
+            const uint32_t share = legal ? guided_quotient((uint64_t)weight << 16, sum) : 0u;
+            if (depth == 0u) {                                // the root is the leaf: it only receives P
+                if (lane < width) tree[3u * width + lane] = share;
+                expanded = 1u;
+            } else {                                          // a node is made if the edge has no child and the tree has room
+                const uint32_t edge = path[depth - 1u];
+                const uint32_t pv = edge >> 4, pc = edge & 15u;
+                const bool known = pv < used && pc < width;
+                const uint32_t child = known ? tree[(uint64_t)pv * node_words + 2u * width + pc] : 1u;
+                if (__builtin_amdgcn_readfirstlane((int)child) == 0 && used < capacity) {
+                    uint32_t* const made = tree + (uint64_t)used * node_words;
+                    if (lane < 3u * width) made[lane] = 0;
+                    if (lane < width) made[3u * width + lane] = share;
+                    if (lane == 0) tree[(uint64_t)pv * node_words + 2u * width + pc] = used;
+                    used += 1u;
+                }
+            }
+        }
+        // lane k takes edge k of the path: node k's mover is the leaf's when depth - k is even
+        for (uint32_t k = lane; k < depth; k += BGS_WAVE) {
+            const uint32_t edge = path[k];
+            const uint32_t pv = edge >> 4, pc = edge & 15u;
+            if (pv < used && pc < width) {
+                uint32_t* const node = tree + (uint64_t)pv * node_words;
+                node[pc] += 1u;
+                node[width + pc] += ((depth - k) & 1u) ? 2048u - sigma : sigma;
+            }
+        }
+        pending = kGuidedNone;
+        depth = 0;
+    }
+    __syncthreads();                // the tree is whole: the report and the descent read what other lanes wrote
+
+    // ---- 3. the report (an illegal column was never played: its words of the root are zero)
+    uint32_t nv = 0, sv = 0;
+    if (used != 0u && lane < width) {
+        nv = tree[lane];
+        sv = tree[width + lane];
+    }
+    if (lane < width) {
+        if (visits) visits[i * (int64_t)width + lane] = (int32_t)nv;
+        if (scores) scores[i * (int64_t)width + lane] = (int32_t)sv;
+    }
+    uint32_t root_total = 0;
+    {
+        // the most visits, then the larger s, then the lower column
+        int32_t top = -1;
+        uint32_t top_n = 0, top_s = 0;
+        for (uint32_t c = 0; c < width; ++c) {
+            const uint32_t cn = (uint32_t)__builtin_amdgcn_readlane((int)nv, (int)c);
+            const uint32_t cs = (uint32_t)__builtin_amdgcn_readlane((int)sv, (int)c);
+            root_total += cn;
+            if (cn > 0u && (top < 0 || cn > top_n || (cn == top_n && cs > top_s))) {
+                top = (int32_t)c;
+                top_n = cn;
+                top_s = cs;
+            }
+        }
+        if (lane == 0) {
+            if (best) best[i] = top;
+            if (nodes) nodes[i] = (int32_t)(used ? used - 1u : 0u);
+        }
+    }
+
+    // ---- 4. the selection (wave-uniform): p is the position at node v, and the leaf's at the end
+    Bits<NW> p[2] = {r0, r1};
+    uint32_t ply = rply, out_kind = (uint32_t)BGS_GUIDED_IDLE;
+    if (used != 0u && (flags & BGS_GUIDED_FINISH) == 0u && root_total < (uint32_t)BGS_GUIDED_MAX_VISITS) {
+        if (expanded == 0u) {                                          // an unexpanded root is itself the leaf
+            const uint64_t columns = __builtin_amdgcn_ballot_w64(heights(p[0] | p[1]) < (uint32_t)g.h());
+            pending = kGuidedEvaluate | ((uint32_t)columns << 16);
+            out_kind = (uint32_t)BGS_GUIDED_EVALUATE;
+        } else {
+            uint32_t v = 0;
+            for (;;) {
+                const uint32_t height = heights(p[0] | p[1]);
+                const bool legal = height < (uint32_t)g.h();
+                if (__builtin_amdgcn_ballot_w64(legal) == 0) break;    // (a running position always has a column)
+                const uint32_t* const node = tree + (uint64_t)v * node_words;
+                uint32_t nc = 0, sc = 0, ch = 0, pc = 0;
+                if (legal) {
+                    nc = node[lane];
+                    sc = node[width + lane];
+                    ch = node[2u * width + lane];
+                    pc = node[3u * width + lane];
+                }
+                uint32_t total = 0;
+                for (uint32_t c = 0; c < width; ++c) total += (uint32_t)__builtin_amdgcn_readlane((int)nc, (int)c);
+                // (a node's N is at most the root's, which the selection bounds: the clamp changes no tree and keeps (N + 1) << 12
+                // in 32 bits whatever the memory held)
+                total = total < (uint32_t)BGS_GUIDED_MAX_VISITS ? total : (uint32_t)BGS_GUIDED_MAX_VISITS;
+                const uint32_t root = search_isqrt((total + 1u) << 12);
+                uint32_t key = 0;                                      // (U(c) << 4 | 15 - c) + 1: the largest U, then the lowest column
+                if (legal) {
+                    const uint32_t q = nc ? (2u * sc) / nc : 2048u;
+                    const uint32_t e = (uint32_t)(((uint64_t)(cpuct * pc) * root) >> 19) / (1u + nc);
+                    key = (((q + e) << 4) | (15u - lane)) + 1u;
+                }
+                uint32_t top = 0;
+                for (uint32_t c = 0; c < width; ++c) {
+                    const uint32_t other = (uint32_t)__builtin_amdgcn_readlane((int)key, (int)c);
+                    top = other > top ? other : top;
+                }
+                const uint32_t col = 15u - ((top - 1u) & 15u);
+                const uint32_t at = (uint32_t)__builtin_amdgcn_readlane((int)height, (int)col);
+                const uint32_t child = (uint32_t)__builtin_amdgcn_readlane((int)ch, (int)col);
+                if (lane == 0 && depth < g.cells_total) path[depth] = (v << 4) | col;   // (always: the position had room for a stone)
+                const uint32_t mover = ply & 1u;
+                Bits<NW>& mine = mover ? p[1] : p[0];
+                const bool won = __builtin_amdgcn_readfirstlane((int)drop_and_test(g, mine, col * stride + at, ~0u)) != 0;
+                ply += 1u;
+                depth += 1u;
+                if (won || ply >= g.cells_total) {                     // the leaf ended the game: its value is known
+                    pending = won ? kGuidedWon : kGuidedFull;
+                    out_kind = (uint32_t)BGS_GUIDED_TERMINAL;
+                    break;
+                }
+                if (child == 0u || child >= used) {                    // no node for p' yet: the caller evaluates it
+                    const uint64_t columns = __builtin_amdgcn_ballot_w64(heights(p[0] | p[1]) < (uint32_t)g.h());
+                    pending = kGuidedEvaluate | ((uint32_t)columns << 16);
+                    out_kind = (uint32_t)BGS_GUIDED_EVALUATE;
+                    break;
+                }
+                v = child;
+            }
+            if (out_kind == (uint32_t)BGS_GUIDED_IDLE) {               // (the descent found no column: nothing is pending)
+                p[0] = r0;
+                p[1] = r1;
+                ply = rply;
+                depth = 0;
+            }
+        }
+    }
+
+    // ---- the leaf goes out (an idle tree shows its root), in the encoding of bgs_read_grid: row 0 is the bottom
+    int8_t* const cells = leaf_grid + i * (int64_t)g.cells_total;
+    for (uint32_t j = lane; j < g.cells_total; j += BGS_WAVE) {
+        const uint32_t y = j / width, x = j - y * width;
+        const int bit = (int)(x * stride + y);
+        cells[j] = (int8_t)((int)test_bit(p[0], bit) + 2 * (int)test_bit(p[1], bit) - 1);
+    }
+    if (lane == 0) {
+        leaf_player[i] = (int8_t)(ply & 1u);
+        leaf_kind[i] = (int32_t)out_kind;
+        head[0] = used;             // the header: the planes were recorded when the tree was emptied
+        head[1] = pending;
+        head[2] = depth;
+        head[3] = expanded;
     }
 }
 
@@ -1564,6 +1846,39 @@ void connect_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations
                            int32_t* d_best, int32_t* d_nodes, int32_t* d_carried, void* d_forest) {
     search_any<true>(b, policy, {seed, (uint32_t)iterations, (uint32_t)leaf_playouts, (uint32_t)explore, (uint32_t)max_plies,
                                  (uint32_t)capacity, restart ? 1u : 0u, d_counts, d_visits, d_best, d_nodes, d_carried, d_forest});
+}
+
+uint64_t connect_guided_tree_bytes(int height, int width, int32_t capacity) {
+    return guided_tree_words((uint32_t)height, (uint32_t)width, (uint32_t)capacity) * sizeof(uint32_t);
+}
+
+template <int NW>
+static void launch_guided(const bgs_batch* b, const EvalGeom& g, int32_t capacity, int32_t cpuct, uint32_t flags, const float* d_priors,
+                          const float* d_values, int8_t* d_leaf_grid, int8_t* d_leaf_player, int32_t* d_leaf_kind, int32_t* d_visits,
+                          int32_t* d_scores, int32_t* d_best, int32_t* d_nodes, void* d_trees) {
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL((k_connect_search_guided<NW>), dim3((uint32_t)blocks), dim3(BGS_WAVE), 0, b->stream, g,
+                           (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status, b->n, i0, (uint32_t)capacity, (uint32_t)cpuct,
+                           flags, d_priors, d_values, d_leaf_grid, d_leaf_player, d_leaf_kind, d_visits, d_scores, d_best, d_nodes,
+                           static_cast<uint32_t*>(d_trees));
+    }
+}
+
+void connect_guided_step(const bgs_batch* b, int32_t capacity, int32_t cpuct, uint32_t flags, const float* d_priors,
+                         const float* d_values, int8_t* d_leaf_grid, int8_t* d_leaf_player, int32_t* d_leaf_kind, int32_t* d_visits,
+                         int32_t* d_scores, int32_t* d_best, int32_t* d_nodes, void* d_trees) {
+    const EvalGeom g = eval_geom(b);
+    const auto launch = [&](auto nw) {
+        launch_guided<decltype(nw)::value>(b, g, capacity, cpuct, flags, d_priors, d_values, d_leaf_grid, d_leaf_player, d_leaf_kind,
+                                           d_visits, d_scores, d_best, d_nodes, d_trees);
+    };
+    switch (b->cg.nw) {             // the words of a plane, as with_connect_form: no RNG contract and no policy here
+        case 1: launch(std::integral_constant<int, 1>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        default: launch(std::integral_constant<int, 3>{}); break;
+    }
 }
 
 void connect_forest_advance(const bgs_batch* b, const int32_t* d_columns, int32_t capacity, int32_t* d_kept, void* d_forest) {

@@ -28,6 +28,9 @@ SOLVE_NONE, SOLVE_LOSS, SOLVE_DRAW, SOLVE_WIN, SOLVE_UNKNOWN, SOLVE_BUDGET = -2,
 DEFAULT_SOLVE_NODES = 1 << 20
 # bgs_connect_search_actions: `explore` for a UCB1 constant of about 1.2 on rewards in [0, 1] (45426 * C * C)
 DEFAULT_EXPLORE = 65536
+# bgs_connect_guided_step: `cpuct` for c_puct = 1.25 (Q8), and the values of leaf_kind
+DEFAULT_CPUCT = 320
+GUIDED_EVALUATE, GUIDED_TERMINAL, GUIDED_IDLE = _abi.GUIDED_EVALUATE, _abi.GUIDED_TERMINAL, _abi.GUIDED_IDLE
 # bgs_bounce_solve_moves: the deepest horizon (BGS_BOUNCE_SOLVE_MAX_DEPTH) and the default one
 BOUNCE_SOLVE_MAX_DEPTH = 16
 DEFAULT_BOUNCE_SOLVE_DEPTH = 3
@@ -1010,6 +1013,17 @@ class ConnectBatch(_Batch):
         search to search (`SearchForest`).  The forest belongs to this batch's shape; close it before the batch."""
         return SearchForest(self, capacity)
 
+    def guided_bytes(self, capacity: int) -> int:
+        """bytes of device memory the guided trees of this batch take at `capacity` nodes a tree (bgs_connect_guided_bytes)"""
+        nbytes = ctypes.c_size_t()
+        _abi.check(_abi.lib().bgs_connect_guided_bytes(self._handle, ctypes.c_int32(capacity), ctypes.byref(nbytes)))
+        return nbytes.value
+
+    def guided_search(self, capacity: int, cpuct: int = DEFAULT_CPUCT) -> "GuidedSearch":
+        """A PUCT search of this batch whose leaves the caller evaluates, e.g. with a policy/value network: one tree per
+        board with room for `capacity` nodes, `cpuct` = c_puct in Q8 (`GuidedSearch`).  Close it before the batch."""
+        return GuidedSearch(self, capacity, cpuct)
+
     def solve_actions(self, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """Exact solve of every column of every board (bgs_connect_solve_actions), one launch: (codes int8[n, width],
         plies int16[n, width] or None).  Seen from the player to move; lines of at most `depth` plies from the board,
@@ -1166,6 +1180,86 @@ class SearchForest:
         return kept
 
 
+class GuidedSearch:
+    """PUCT tree search of a ConnectBatch with caller-evaluated leaves (bgs_connect_guided_step, include/bgs.h):
+    `ConnectBatch.guided_search(capacity, cpuct)` makes one.  One tree per board, `capacity` nodes a tree, the root
+    included; `cpuct` is c_puct in Q8 (320 = 1.25).
+
+    Every call is one launch on the batch's stream, with no synchronisation: it applies the evaluator's rows to the leaves
+    the previous call handed out, and hands out the next ones.  `begin()` empties the trees and returns the roots as
+    leaves; `step(priors, values)` is one simulation; `finish(priors, values)` applies the last evaluation and selects
+    nothing.  Each returns the same seven device tensors, allocated once and rewritten by every call:
+    (leaf_grid int8[n, h, w], leaf_player int8[n], leaf_kind int32[n], visits int32[n, w], scores int32[n, w],
+    best int32[n], nodes int32[n]).  `priors` float32[n, w] and `values` float32[n] are the evaluator's output for
+    (leaf_grid, leaf_player) of the previous call: a value is seen from the player to move at the leaf, in [-1, 1]; rows
+    whose leaf_kind is not GUIDED_EVALUATE are ignored.  A board that was stepped or reset between two calls restarts its
+    tree on its own.  The boards and `steps` are not modified.
+
+    The object owns the device buffer of the trees (a torch tensor) and belongs to the batch it was made from."""
+
+    def __init__(self, batch: "ConnectBatch", capacity: int, cpuct: int = DEFAULT_CPUCT):
+        self.batch = batch
+        self.capacity = int(capacity)
+        self.cpuct = int(cpuct)
+        if not 0 <= self.cpuct <= 4096:
+            raise ValueError(f"cpuct must be 0 .. 4096, c_puct in Q8 (got {cpuct})")
+        nbytes = batch.guided_bytes(self.capacity)         # (refuses Bounce, generic boards and a bad capacity)
+        t = batch._need_torch("guided_search")
+        n, h, w = batch.n, batch.height, batch.width
+        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")
+        self._outputs = tuple(batch._device_tensors("guided_search", [
+            ("leaf_grid", None, (n, h, w), "int8"), ("leaf_player", None, (n,), "int8"), ("leaf_kind", None, (n,)),
+            ("visits", None, (n, w)), ("scores", None, (n, w)), ("best", None, (n,)), ("nodes", None, (n,))]))
+        self._fresh = True
+
+    def close(self) -> None:
+        self._buffer = None
+
+    def _call(self, flags: int, priors, values):
+        if self._buffer is None:
+            raise RuntimeError("the guided search is closed")
+        if self._fresh and not flags & _abi.GUIDED_RESTART:
+            raise RuntimeError("begin() comes first: fresh memory holds no trees")
+        pointers = [None, None]
+        if not flags & _abi.GUIDED_RESTART:
+            n, w = self.batch.n, self.batch.width   # (inputs: "optional", so that they are checked and never allocated)
+            priors, values = self.batch._device_tensors("guided_search", [("priors", priors, (n, w), "float32", True),
+                                                                          ("values", values, (n,), "float32", True)])
+            if priors is None or values is None:
+                raise TypeError("priors and values are the evaluator's device tensors: float32[n, width] and float32[n]")
+            pointers = [ctypes.c_void_p(priors.data_ptr()), ctypes.c_void_p(values.data_ptr())]
+        _abi.check(_abi.lib().bgs_connect_guided_step(
+            self.batch._handle, ctypes.c_int32(self.capacity), ctypes.c_int32(self.cpuct), ctypes.c_uint32(flags), *pointers,
+            *(ctypes.c_void_p(x.data_ptr()) for x in self._outputs), ctypes.c_void_p(self._buffer.data_ptr()),
+            ctypes.c_size_t(self._buffer.numel())))
+        self._fresh = False
+        return self._outputs
+
+    def begin(self):
+        """Empty every tree (BGS_GUIDED_RESTART): the leaves that come back are the roots."""
+        return self._call(_abi.GUIDED_RESTART, None, None)
+
+    def step(self, priors, values):
+        """One simulation: apply (priors, values) to the leaves of the previous call, descend to the next leaves."""
+        return self._call(0, priors, values)
+
+    def finish(self, priors, values):
+        """Apply (priors, values) to the leaves of the previous call and select nothing (BGS_GUIDED_FINISH): every
+        leaf_kind comes back GUIDED_IDLE, and visits, scores, best and nodes are final."""
+        return self._call(_abi.GUIDED_FINISH, priors, values)
+
+    def run(self, evaluate, simulations: int):
+        """`begin`, `simulations` evaluations a tree, `finish`: evaluate(leaf_grid, leaf_player) -> (priors float32[n, w],
+        values float32[n]) is called once a simulation on the device tensors of the leaves (the first call sees the
+        roots) and returns device tensors.  Returns what `finish` returns."""
+        if simulations < 1:
+            raise ValueError(f"simulations must be >= 1 (got {simulations})")
+        outs = self.begin()
+        for _ in range(int(simulations) - 1):
+            outs = self.step(*evaluate(outs[0], outs[1]))
+        return self.finish(*evaluate(outs[0], outs[1]))
+
+
 class BounceBatch(_Batch):
     """N Bounce boards sharing one start grid: ``Config(grid)`` (reference bounce.cpp:26) times n."""
 
@@ -1258,6 +1352,12 @@ class BounceBatch(_Batch):
         raise ValueError("search_forest: Connect batches only (Bounce boards: search_moves)")
 
     forest_bytes = search_forest
+
+    def guided_search(self, *args, **kwargs):
+        """Not available for Bounce: the search with caller-evaluated leaves covers bit-packed Connect boards."""
+        raise ValueError("guided_search: Connect batches only")
+
+    guided_bytes = guided_search
 
     def solve_actions(self, *args, **kwargs):
         """Not available for Bounce: the exact solver covers bit-packed Connect boards (Bounce games can cycle)."""

@@ -30,6 +30,10 @@ POLICY_UNIFORM, POLICY_DECISIVE = 0, 1   # bgs_connect_evaluate_actions_policy, 
 CONNECT_FOREST_MAX_CAPACITY = 65536   # BGS_CONNECT_FOREST_MAX_CAPACITY: the nodes a tree of a forest may hold
 BOUNCE_FOREST_MAX_NODES = 65536   # BGS_BOUNCE_FOREST_MAX_NODES: the nodes a tree of a Bounce forest may hold
 BOUNCE_FOREST_MAX_EDGES = 1 << 29   # BGS_BOUNCE_FOREST_MAX_EDGES: the pool edges a tree of a Bounce forest may hold
+GUIDED_RESTART, GUIDED_FINISH = 1, 2   # BGS_GUIDED_RESTART / BGS_GUIDED_FINISH: the flags of bgs_connect_guided_step
+GUIDED_EVALUATE, GUIDED_TERMINAL, GUIDED_IDLE = 0, 1, 2   # BGS_GUIDED_*: the values of its leaf_kind
+GUIDED_MAX_CAPACITY = 1 << 20   # BGS_GUIDED_MAX_CAPACITY: the nodes a guided tree may hold
+GUIDED_MAX_VISITS = 1 << 19   # BGS_GUIDED_MAX_VISITS: the simulations a guided root takes
 HALVING_SHORT = -2   # bgs_bounce_evaluate_moves_halving: best[i] of a running board the budget is too small for
 
 GAME_CONNECT = 1
@@ -233,6 +237,12 @@ SIGNATURES = {
     ),
     "bgs_connect_forest_advance": (
         ctypes.c_int, [c_handle, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    ),
+    "bgs_connect_guided_bytes": (ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]),
+    "bgs_connect_guided_step": (
+        ctypes.c_int,
+        [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t],
     ),
     "bgs_bounce_forest_bytes": (ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]),
     "bgs_bounce_forest_search": (

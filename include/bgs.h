@@ -357,6 +357,69 @@ BGS_API int bgs_connect_forest_search(bgs_batch* b, uint64_t seed, int32_t itera
                                       int on_device);
 BGS_API int bgs_connect_forest_advance(bgs_batch* b, const int32_t* columns, int32_t capacity, int32_t* kept, void* forest,
                                        size_t forest_bytes, int on_device);
+/* PUCT tree search whose leaves the CALLER evaluates (Connect, bit-packed boards only): the search of a policy/value
+ * network.  One call is one simulation of every tree: it applies the caller's (priors, value) to the pending leaf of
+ * every tree, reports the root's statistics and descends to the next leaf, whose position it writes out; the caller runs
+ * its evaluator on that device tensor and calls again.  Integer arithmetic throughout, no RNG anywhere: the result is
+ * defined bit for bit.  The boards and bgs_steps are untouched.
+ * EVERY POINTER IS A DEVICE POINTER: `trees` 256-byte aligned, the rest 16-byte aligned; the call is an enqueue on the
+ * batch's stream with no synchronisation and no allocation, so the loop can sit in a stream or in a captured graph with
+ * the network.  There is no host variant, because the evaluator lives on the device.  visits, scores, best and nodes may
+ * be NULL; priors and values may be NULL only with BGS_GUIDED_RESTART.
+ * Tree and node.  One tree per board, in caller-owned opaque memory (bgs_connect_guided_bytes says how large), with room
+ * for `capacity` (C) nodes, the root included.  A node holds four values per column c: n[c], s[c], the child and P[c].
+ * The position is rebuilt during the descent.  Each tree's share also holds, between calls: the nodes in use; the root
+ * position, as the batch's planes; the pending leaf: its kind and its path of (node, column) pairs, at most h * w of
+ * them.  The share is rounded up to 256 bytes.
+ * One step, for board i, in this order:
+ *   1. Check.  The tree is LIVE if BGS_GUIDED_RESTART is not set, the board is running, the nodes in use are in [1, C]
+ *      and the recorded planes equal board i's.  Otherwise the tree is emptied and any pending evaluation is dropped; a
+ *      running board gets one unexpanded root and has board i recorded.  So a board that the caller stepped or reset
+ *      between two calls restarts on its own.  THE FIRST CALL ON FRESH MEMORY MUST PASS BGS_GUIDED_RESTART.
+ *   2. Apply, if an evaluation is pending.  A leaf of kind EVALUATE reads priors[i][0..w) and values[i]; kind TERMINAL
+ *      reads neither.
+ *      Priors.  For a legal column c of the leaf with x = priors[i][c]: w[c] = 0 unless x > 0 (NaN, zero and negatives
+ *      give 0), otherwise w[c] = floor(min(x, 1.0f) * 65536.0f), exact in float32.  Illegal columns are ignored.
+ *      W = the sum of w[c]; if W = 0, every legal w[c] = 1 (and W their number).  P[c] = floor(w[c] * 65536 / W).
+ *      Value, seen from the player to move at the leaf: NaN gives v = 0; otherwise x is clamped to [-1, 1] and
+ *      v = (int32)(x * 1024.0f), truncated toward zero.  sigma = 1024 + v.  A TERMINAL leaf has sigma = 0 if the last
+ *      edge won and sigma = 1024 if it filled the board.
+ *      The leaf is made a node -- n, s and child zeroed, its P set, the parent's child word linking it -- if and only
+ *      if the leaf is EVALUATE, is not the root, its edge has no child and the tree holds fewer than C nodes.  An edge
+ *      whose node did not fit is tried again later (the forest's rule).  An EVALUATE leaf that IS the root only
+ *      receives P.  Every edge k of the path gets n += 1, and s += sigma if node k's mover is the leaf's mover, else
+ *      s += 2048 - sigma.
+ *   3. Report, through the outputs that are not NULL: visits[i][c] = the root's n[c]; scores[i][c] = the root's s[c];
+ *      nodes[i] = the nodes in use, the root not counted; best[i] = the column with the most visits, then the larger s,
+ *      then the lower column; best[i] = -1 for an ended board or a root with no visit.  Illegal columns read as zeros.
+ *   4. Select, unless BGS_GUIDED_FINISH is set, the board has ended, or the sum of the root's n[c] has reached
+ *      BGS_GUIDED_MAX_VISITS: each of those three gives kind IDLE.  An unexpanded root is itself the leaf: EVALUATE,
+ *      with an empty path.  Otherwise, at node v with N = the sum of n[c] over the legal columns, take the legal column
+ *      with the largest U(c) = Q(c) + E(c), ties to the lowest column, where
+ *        Q(c) = floor(2 * s[c] / n[c]), or 2048 for n[c] = 0,
+ *        E(c) = floor(((cpuct * P[c] * isqrt((N + 1) << 12)) >> 19) / (1 + n[c])), computed in 64 bits (isqrt: the exact
+ *               floor square root); `cpuct` is c_puct in Q8, 0 .. 4096, and E stays below 2^25.
+ *      Play the column.  The game ended: the leaf is TERMINAL.  There is no child: the leaf is EVALUATE.  Otherwise
+ *      descend.  The path and the kind are recorded, and leaf_grid[i] (int8[h][w], in bgs_read_grid's encoding),
+ *      leaf_player[i] (the leaf's ply & 1) and leaf_kind[i] are written.  IDLE rows carry the root's grid and player.
+ * A tree's result depends only on its board and the rows it was fed, so any split of the batch gives the same trees.
+ * Refused (BGS_ERR_ARG, with a message; the outputs and the trees are untouched): a Bounce batch, a generic batch, C < 2
+ * or C > BGS_GUIDED_MAX_CAPACITY, cpuct outside [0, 4096], unknown flag bits, BGS_GUIDED_RESTART together with
+ * BGS_GUIDED_FINISH, NULL trees, leaf_grid, leaf_player or leaf_kind, NULL priors or values without BGS_GUIDED_RESTART, a
+ * misaligned pointer, trees_bytes too small. */
+#define BGS_GUIDED_RESTART 1u      /* empty every tree first; nothing is pending; priors/values are not read */
+#define BGS_GUIDED_FINISH  2u      /* apply the pending evaluation, select nothing */
+#define BGS_GUIDED_EVALUATE 0      /* leaf_kind: the caller's priors[i] / values[i] are wanted for this leaf */
+#define BGS_GUIDED_TERMINAL 1      /* the leaf ended the game: its value is known, the caller's row is ignored */
+#define BGS_GUIDED_IDLE     2      /* no simulation: ended board, FINISH, or the root at BGS_GUIDED_MAX_VISITS */
+#define BGS_GUIDED_MAX_CAPACITY (1 << 20)
+#define BGS_GUIDED_MAX_VISITS   (1 << 19)
+BGS_API int bgs_connect_guided_bytes(const bgs_batch* b, int32_t capacity, size_t* bytes);
+BGS_API int bgs_connect_guided_step(bgs_batch* b, int32_t capacity, int32_t cpuct, uint32_t flags,
+                                    const float* priors, const float* values,
+                                    int8_t* leaf_grid, int8_t* leaf_player, int32_t* leaf_kind,
+                                    int32_t* visits, int32_t* scores, int32_t* best, int32_t* nodes,
+                                    void* trees, size_t trees_bytes);
 /* Flat Monte-Carlo evaluation of every legal move of every board (Bounce, bit-packed boards only: at most 64 cells,
  * piece values <= 15).  counts int32[n][width][height * width][3]: entry [i][x][c] = (wins, draws, losses) of the
  * player to move at board i over `playouts` games that start with the move of the piece in column x of the active row
