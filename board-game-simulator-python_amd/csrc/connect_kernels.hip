@@ -738,6 +738,86 @@ struct WaveCodes {
     }
 };
 
+// The plies of a one-word nibble board (W <= 8, H <= 8), the one text of them for K2a, K2o and K2o's grouped form: the
+// wave constants of the geometry and, on a board held as two planes q, column nibbles h4 = (H + 7) - height and their
+// open flags op = (h4 >> 3) & ONES, the full ply, the opening ply and the outcome byte.  These are the Connect RNG
+// contract of the block-aligned rollouts: which column a draw names, and what a game leaves.
+template <class G>
+struct NibblePlies {
+    static constexpr uint32_t ONES = 0x11111111u;
+    const uint32_t top, columns, stride;
+    const uint32_t column_top;   // bit 3 of the nibbles of real columns only: the count stays <= W
+    const uint64_t eights;       // the addend of the column select's multiply-add, in a register pair
+    __device__ __forceinline__ explicit NibblePlies(const G& g)
+        : top((uint32_t)g.h() + 7u), columns(g.w() >= 8 ? ONES : (ONES & ((1u << (4 * g.w())) - 1u))),
+          stride((uint32_t)g.h() + 1u), column_top(8u * columns), eights(0x88888888ull) {}
+
+    // The mover (plane `mine`) drops a stone into the column `draw` names among the open ones and is tested for a run
+    // through it; returns whether there is one.  No control flow: a lane that is not playing (act = 0; all ones
+    // otherwise) executes the same instructions, the stone it drops is masked away and its nibbles stay.  Such a lane
+    // re-tests a plane that did not change: a running game holds no run, so the result can only be true there for the
+    // plane that ended this lane's game, or on a lane whose result is not stored any more.
+    __device__ __forceinline__ bool drop(const G& g, uint32_t draw, uint32_t act, uint64_t& mine, uint32_t& h4,
+                                         uint32_t& op) const {
+        const uint32_t cnt = (uint32_t)__popc(op);
+        const uint32_t idx = sample_index(draw, cnt);
+        // nibble x of cmp = 8 + idx - (open columns among 0..x): (idx - open) * ONES is idx * ONES - open * ONES, and
+        // (idx - open) * ONES + 0x88888888 is ONE v_mad_u64_u32 (hipcc, needing only the low word, picks v_mul_lo_u32 +
+        // v_add_u32: two instructions, 7.6 instead of 5.3 cycles)
+        uint64_t cmp64;
+        {
+            uint64_t carry;
+            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(cmp64), "=s"(carry) : "v"(idx - op), "s"(ONES), "v"(eights));
+        }
+        const uint32_t cmp = (uint32_t)cmp64;
+        uint32_t col = (uint32_t)__popc(cmp & column_top);  // columns whose prefix count is still <= idx
+        if (g.w() >= 8) col &= 7u;                         // (a full 8-wide board would give 8)
+        const uint32_t sh = col * 4u;
+        const uint32_t v = (h4 >> sh) & 15u;
+        uint32_t base = col * stride + top;
+        asm("" : "+v"(base));  // keep (col * stride + top) one multiply-add; then one subtract
+        uint32_t pos = base - v;
+        if ((uint32_t)g.w() * stride + top > 63u) pos &= 63u;  // only a lane that is not playing can exceed 63
+        // the stone of a lane that is not playing is masked away: (bit & act) | mine, one v_bitop3 per half
+        const uint64_t bit = 1ull << pos;
+        mine = ((uint64_t)and_or((uint32_t)(bit >> 32), act, (uint32_t)(mine >> 32)) << 32) |
+               and_or((uint32_t)bit, act, (uint32_t)mine);
+        h4 += act << sh;  // act is 0 or -1: one stone more in the column = its nibble one lower
+        op = (h4 >> 3) & ONES;
+        if (g.k() == 4) return ply_run_of_four(g, mine, pos);
+        Bits<1> b;
+        b.w[0] = mine;
+        return has_run(g, b);
+    }
+    // one full ply of sub-step J of a block of K2o: the mover is player J & 1, `alive` the lane mask of a running game.
+    // Neither the winner nor the env-steps are tracked ply by ply: a game's plies are the stones on its board, and when it
+    // has ended with a run the winner is whoever placed the last stone -- both read off the planes once, where the game ends
+    // (round 5: 8 VALU a block less than a per-ply winner select and step count).
+    template <uint32_t J>
+    __device__ __forceinline__ void full(const G& g, uint32_t draw, uint64_t (&q)[2], uint32_t& h4, uint32_t& op,
+                                         uint32_t& alive, bool& won_any) const {
+        const bool won = drop(g, draw, alive, q[J & 1u], h4, op);
+        won_any = won_any || won;   // (lane masks: scalar ORs)
+        alive = (won || op == 0u) ? 0u : alive;
+    }
+    // one opening ply: every column is open and nobody can win yet
+    __device__ __forceinline__ void cheap(const G& g, uint32_t j, uint32_t draw, uint64_t (&q)[2], uint32_t& h4) const {
+        const uint32_t col = sample_index(draw, (uint32_t)g.w());
+        const uint32_t sh = col * 4u;
+        const uint32_t v = (h4 >> sh) & 15u;
+        const uint32_t pos = col * stride + top - v;
+        q[j & 1u] |= 1ull << pos;
+        h4 -= 1u << sh;
+    }
+    // the outcome byte of a board that has just ended: its stones, and whether somebody holds a run (no cap: a board that
+    // stopped without one is full).  Status, reward, code and env-steps follow from it when the chunk is flushed
+    // (connect_unit.h: connect_outcome_byte).
+    __device__ __forceinline__ static uint32_t outcome_of(const uint64_t (&q)[2], bool won_any) {
+        const uint32_t stones = (uint32_t)__popcll(q[0]) + (uint32_t)__popcll(q[1]);
+        return connect_outcome_byte(stones, won_any);
+    }
+};
+
 // K2a: the same rollout for boards that start from the initial state on a one-word geometry (W <= 8, H <= 8),
 // written without per-ply control flow.  Every game starts at a 4-ply boundary, so inside a block the mover of
 // sub-step j is player j & 1: no plane swap, no ply counter.  A lane that is not playing executes the same
@@ -749,12 +829,9 @@ k_connect_rollout_aligned(G g, uint64_t* __restrict__ planes, uint8_t* __restric
                           int64_t n, uint64_t seed, uint64_t first_game, uint32_t max_plies,
                           unsigned long long* __restrict__ steps, uint32_t games_per_wave, uint32_t* __restrict__ codes_out) {
     extern __shared__ uint32_t code_lds[];  // CODES: games_per_wave / 16 dwords per wave
-    constexpr uint32_t ONES = 0x11111111u;
-    const uint32_t top = (uint32_t)g.h() + 7u;
-    const uint32_t columns = g.w() >= 8 ? ONES : (ONES & ((1u << (4 * g.w())) - 1u));
-    const uint32_t stride = (uint32_t)g.h() + 1u;
-    const uint32_t column_top = 8u * columns;  // bit 3 of the nibbles of real columns only: the count stays <= W
-    const uint64_t eights = 0x88888888ull;  // the addend of the column select's multiply-add, in a register pair
+    const NibblePlies<G> plies(g);
+    constexpr uint32_t ONES = NibblePlies<G>::ONES;
+    const uint32_t top = plies.top, columns = plies.columns, stride = plies.stride;
 
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (BGS_BLOCK / BGS_WAVE) + (threadIdx.x >> 6));
     const int64_t begin = (int64_t)wave * games_per_wave;
@@ -833,40 +910,10 @@ k_connect_rollout_aligned(G g, uint64_t* __restrict__ planes, uint8_t* __restric
         uint32_t open = (hts >> 3) & ONES;
 #pragma unroll
         for (uint32_t j = 0; j < 4; ++j) {
-            const uint32_t cnt = (uint32_t)__popc(open);
-            const uint32_t idx = sample_index(draws.draw(j), cnt);
-            // nibble x of cmp = 8 + idx - (open columns among 0..x): (idx - open) * ONES is idx * ONES - open * ONES
-            uint64_t cmp64, carry;  // (idx - open) * ONES + 0x88888888 as one v_mad_u64_u32 (hipcc would pick mul_lo + add)
-            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(cmp64), "=s"(carry) : "v"(idx - open), "s"(ONES), "v"(eights));
-            const uint32_t cmp = (uint32_t)cmp64;
-            uint32_t col = (uint32_t)__popc(cmp & column_top);  // columns whose prefix count is still <= idx
-            if (g.w() >= 8) col &= 7u;                         // (a full 8-wide board would give 8)
-            const uint32_t sh = col * 4u;
-            const uint32_t v = (hts >> sh) & 15u;
-            uint32_t base = col * stride + top;
-            asm("" : "+v"(base));  // keep (col * stride + top) one multiply-add; then one subtract
-            uint32_t pos = base - v;
-            if ((uint32_t)g.w() * stride + top > 63u) pos &= 63u;  // only a lane that is not playing can exceed 63
             const uint32_t act = (FROM_INITIAL || j >= skip) ? live : 0u;  // mask: this lane plays this sub-step
-            uint64_t& mine = p[j & 1u];
-            // the stone of a lane that is not playing is masked away: (bit & act) | mine, one v_bitop3 per half
-            const uint64_t bit = 1ull << pos;
-            mine = ((uint64_t)and_or((uint32_t)(bit >> 32), act, (uint32_t)(mine >> 32)) << 32) |
-                   and_or((uint32_t)bit, act, (uint32_t)mine);
-            hts += act << sh;  // act is 0 or -1: one stone more in the column = its nibble one lower
-            open = (hts >> 3) & ONES;
-            bool won;
-            if (g.k() == 4) {
-                won = ply_run_of_four(g, mine, pos);
-            } else {
-                Bits<1> b;
-                b.w[0] = mine;
-                won = has_run(g, b);
-            }
+            const bool won = plies.drop(g, draws.draw(j), act, p[j & 1u], hts, open);
             stepped -= act;
-            // no "act &&": a lane that is not playing re-tests a plane that did not change.  A running game holds no
-            // run, so `won` can only be true there for the plane that ended this lane's game -- it names the same
-            // winner again -- or on a lane whose result is not stored any more
+            // no "act &&": on a lane that is not playing `won` can only name the same winner again (see drop)
             st = won ? (j & 1u) + 1u : st;
             live = (won || open == 0u) ? 0u : live;
             if (CAPPED) live = (4u * blk + j + 1u < max_plies) ? live : 0u;
@@ -1046,6 +1093,132 @@ __device__ __forceinline__ void open_games_deferred(const G& g, Pool& pool, uint
     }
 }
 
+// ---- the per-ply opening of K2o and its grouped form (every setting and geometry the deferred one does not take): all
+// 64 lanes play blocks 0 .. OPEN_BLOCKS - 1 of 64 games in lock step and park them in their pool slots with the words of
+// their blocks to come.  The lane's game is game `og` of the wave's chunk of `avail` games, its RNG
+// stream (seed, id).  A game that ends inside the opening -- a win, or a small board is full -- leaves its byte in
+// `outcome` and, where the chunk's planes are given (BOARDS: they always are), its board in `plane0` and `plane1`, and is
+// parked as a dead slot; a lane past the end of the chunk played for nobody: nothing of it is stored or counted.
+// The draws of block b: sub-draws of its word, or (strict contract) the four words of its own philox call.
+template <bool PER_PLY, uint32_t J>
+__device__ __forceinline__ uint32_t opening_draw(const Philox4& own, uint32_t word) {
+    return PER_PLY ? own.v[J] : sub_draw<J>(word);
+}
+
+template <int OPEN_BLOCKS, bool PER_PLY, bool BOARDS, class G, class Pool>
+__device__ __forceinline__ void open_games_per_ply(const G& g, const NibblePlies<G>& plies, Pool& pool, uint64_t seed, uint64_t id,
+                                                   uint32_t og, uint32_t avail, uint64_t* plane0, uint64_t* plane1, uint8_t* outcome) {
+    using OW = OpenedWords<G, OPEN_BLOCKS, PER_PLY>;
+    uint64_t q[2] = {0, 0};
+    uint32_t h4 = plies.top * plies.columns, alive = ~0u, op = plies.columns;
+    bool won_any = false;
+    uint32_t words[12];   // the words of blocks 0 .. 11: three philox calls (fewer when the board cannot last that long)
+    Philox4 own = philox4x32_10(seed, id, 0u);
+    if constexpr (!PER_PLY) {
+        words[0] = own.v[0]; words[1] = own.v[1]; words[2] = own.v[2]; words[3] = own.v[3];
+#pragma unroll
+        for (int c = 1; c < 3; ++c) {
+            if (4 * c <= OW::LAST) {
+                const Philox4 d = philox4x32_10(seed, id, (uint32_t)c);
+                words[4 * c] = d.v[0]; words[4 * c + 1] = d.v[1]; words[4 * c + 2] = d.v[2]; words[4 * c + 3] = d.v[3];
+            } else {
+                words[4 * c] = words[4 * c + 1] = words[4 * c + 2] = words[4 * c + 3] = 0u;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 12; ++c) words[c] = 0u;
+    }
+    plies.cheap(g, 0u, opening_draw<PER_PLY, 0>(own, words[0]), q, h4);
+    plies.cheap(g, 1u, opening_draw<PER_PLY, 1>(own, words[0]), q, h4);
+    plies.cheap(g, 2u, opening_draw<PER_PLY, 2>(own, words[0]), q, h4);
+    plies.cheap(g, 3u, opening_draw<PER_PLY, 3>(own, words[0]), q, h4);
+    if (OPEN_BLOCKS >= 2) {
+        if constexpr (PER_PLY) own = philox4x32_10(seed, id, 1u);
+        plies.cheap(g, 0u, opening_draw<PER_PLY, 0>(own, words[1]), q, h4);
+        plies.cheap(g, 1u, opening_draw<PER_PLY, 1>(own, words[1]), q, h4);
+        op = (h4 >> 3) & plies.ONES;
+        plies.template full<2>(g, opening_draw<PER_PLY, 2>(own, words[1]), q, h4, op, alive, won_any);
+        plies.template full<3>(g, opening_draw<PER_PLY, 3>(own, words[1]), q, h4, op, alive, won_any);
+    }
+#pragma unroll
+    for (int ob = 2; ob < OPEN_BLOCKS; ++ob) {  // further blocks in lock step
+        if constexpr (PER_PLY) own = philox4x32_10(seed, id, (uint32_t)ob);
+        plies.template full<0>(g, opening_draw<PER_PLY, 0>(own, words[ob]), q, h4, op, alive, won_any);
+        plies.template full<1>(g, opening_draw<PER_PLY, 1>(own, words[ob]), q, h4, op, alive, won_any);
+        plies.template full<2>(g, opening_draw<PER_PLY, 2>(own, words[ob]), q, h4, op, alive, won_any);
+        plies.template full<3>(g, opening_draw<PER_PLY, 3>(own, words[ob]), q, h4, op, alive, won_any);
+    }
+    if (OPEN_BLOCKS >= 2 && og < avail && alive == 0) {
+        if (BOARDS || plane0) {
+            plane0[og] = q[0];
+            plane1[og] = q[1];
+        }
+        outcome[og] = (uint8_t)plies.outcome_of(q, won_any);
+    }
+    const uint32_t slot = og & (Pool::SLOTS - 1u);
+    pool.plane[0][slot] = q[0];
+    pool.plane[1][slot] = q[1];
+    pool.cols[slot] = alive ? h4 : 0u;
+#pragma unroll
+    for (int k = 0; k < OW::QUADS; ++k) {
+        auto at = [&](int i) { return OPEN_BLOCKS + i <= 11 ? words[OPEN_BLOCKS + i <= 11 ? OPEN_BLOCKS + i : 11] : 0u; };
+        pool.words[k][slot] = make_uint4(at(4 * k), at(4 * k + 1), at(4 * k + 2), at(4 * k + 3));
+    }
+}
+
+// an idle lane takes the board parked in `slot`: planes, column nibbles (0: a dead slot) and -- QUADS > 0 -- the words of its
+// blocks to come, the first into `wnext`, the others into the lane's column of lane_words
+template <int QUADS, class Pool>
+__device__ __forceinline__ void take_slot(const Pool& pool, uint32_t slot, uint64_t (&p)[2], uint32_t& hts, uint32_t& wnext,
+                                          uint32_t* my_words) {
+    p[0] = pool.plane[0][slot];
+    p[1] = pool.plane[1][slot];
+    hts = pool.cols[slot];
+#pragma unroll
+    for (int k = 0; k < QUADS; ++k) {
+        const uint4 v = pool.words[k][slot];
+        if (k == 0) wnext = v.x; else my_words[(4 * k) * BGS_WAVE] = v.x;
+        my_words[(4 * k + 1) * BGS_WAVE] = v.y;
+        my_words[(4 * k + 2) * BGS_WAVE] = v.z;
+        my_words[(4 * k + 3) * BGS_WAVE] = v.w;
+    }
+}
+
+// A chunk is done: four games per lane -- their outcome dword as it lies in LDS gives their status bytes, their reward
+// pairs (both only where `boards`: the step leaves boards), their byte of 2-bit codes for the hand-over (64 lanes: 64
+// contiguous bytes per store, into host memory when mapped) and their plies, which are returned summed over the lane's
+// games (connect_unit.h: connect_outcome4).  Bytes past `avail` are 0; the chunk's last dword takes the ragged tail.
+// ROLLED: the loop is not unrolled (two trips at 512 games a wave: unrolled by four, hipcc's choice, the codes' loop alone
+// took the grouped kernel past 80 VGPRs once its play_block held the refetch branch).
+template <bool CODES, bool ROLLED>
+__device__ __forceinline__ uint32_t flush_outcomes(const uint32_t* outcome, uint32_t lane, uint32_t avail, bool boards,
+                                                   uint8_t* status_out, uint16_t* reward_out, uint8_t* packed_out) {
+    uint32_t stepped = 0;
+    auto four_games = [&](uint32_t g4) {
+        const ConnectOutcome4 o = connect_outcome4(outcome[g4 >> 2]);
+        stepped += o.plies;
+        if (CODES) packed_out[g4 >> 2] = (uint8_t)o.codes;
+        if (!boards) return;
+        if (g4 + 4u <= avail) {
+            *reinterpret_cast<uint32_t*>(status_out + g4) = o.status;
+            *reinterpret_cast<uint2*>(reward_out + g4) = make_uint2(o.reward[0], o.reward[1]);
+        } else {
+            for (uint32_t k = 0; g4 + k < avail; ++k) {
+                status_out[g4 + k] = (uint8_t)(o.status >> (8u * k));
+                reward_out[g4 + k] = (uint16_t)((((uint64_t)o.reward[1] << 32) | o.reward[0]) >> (16u * k));
+            }
+        }
+    };
+    if constexpr (ROLLED) {
+#pragma unroll 1
+        for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) four_games(g4);
+    } else {
+        for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) four_games(g4);
+    }
+    return stepped;
+}
+
 // PER_PLY (round 6): the same kernel under the strict RNG contract -- a philox word per ply.  Nothing is parked beside a
 // board: a block makes its own philox call (its four words are its draws), the opening one per block.
 template <class G, int OPEN_BLOCKS, bool CODES, bool PER_PLY>
@@ -1065,12 +1238,7 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
     // registers the eight words had to move down one every block: 8 moves; this is an add, a min and an LDS read that is
     // issued a block ahead of its use.)
     __shared__ uint32_t lane_words[BGS_BLOCK / BGS_WAVE][NWORDS][BGS_WAVE];
-    constexpr uint32_t ONES = 0x11111111u;
-    const uint32_t top = (uint32_t)g.h() + 7u;
-    const uint32_t columns = g.w() >= 8 ? ONES : (ONES & ((1u << (4 * g.w())) - 1u));
-    const uint32_t stride = (uint32_t)g.h() + 1u;
-    const uint32_t column_top = 8u * columns;
-    const uint64_t eights = 0x88888888ull;  // the addend of the column select's multiply-add, in a register pair
+    const NibblePlies<G> plies(g);
 
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (BGS_BLOCK / BGS_WAVE) + (threadIdx.x >> 6));
     const uint32_t lane = threadIdx.x & 63u;
@@ -1099,64 +1267,6 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
     for (uint32_t i = lane; i < ((avail + 3u) >> 2); i += BGS_WAVE) reinterpret_cast<uint32_t*>(outcome)[i] = 0u;
     __builtin_amdgcn_wave_barrier();
 
-    // one full ply of sub-step J on (q, h4, op, alive, won_any); the body of K2a's block
-    // Neither the winner nor the env-steps are tracked ply by ply: a game's plies are the stones on its board, and when it
-    // has ended with a run the winner is whoever placed the last stone -- both read off the planes once, where the game ends
-    // (round 5: 8 VALU a block less than a per-ply winner select and step count).
-    auto full_ply = [&](auto j_tag, uint32_t draw, uint64_t (&q)[2], uint32_t& h4, uint32_t& op, uint32_t& alive,
-                        bool& won_any) {
-        constexpr uint32_t J = decltype(j_tag)::value;
-        const uint32_t cnt = (uint32_t)__popc(op);
-        const uint32_t idx = sample_index(draw, cnt);
-        // nibble x of cmp = 8 + idx - (open columns among 0..x): (idx - open) * ONES + 0x88888888 as ONE v_mad_u64_u32
-        // (hipcc, needing only the low word, picks v_mul_lo_u32 + v_add_u32: two instructions, 7.6 instead of 5.3 cycles)
-        uint64_t cmp64;
-        {
-            uint64_t carry;
-            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(cmp64), "=s"(carry) : "v"(idx - op), "s"(ONES), "v"(eights));
-        }
-        const uint32_t cmp = (uint32_t)cmp64;
-        uint32_t col = (uint32_t)__popc(cmp & column_top);
-        if (g.w() >= 8) col &= 7u;
-        const uint32_t sh = col * 4u;
-        const uint32_t v = (h4 >> sh) & 15u;
-        uint32_t base = col * stride + top;
-        asm("" : "+v"(base));
-        uint32_t pos = base - v;
-        if ((uint32_t)g.w() * stride + top > 63u) pos &= 63u;
-        const uint32_t act = alive;
-        uint64_t& mine = q[J & 1u];
-        const uint64_t bit = 1ull << pos;
-        mine = ((uint64_t)and_or((uint32_t)(bit >> 32), act, (uint32_t)(mine >> 32)) << 32) |
-               and_or((uint32_t)bit, act, (uint32_t)mine);
-        h4 += act << sh;
-        op = (h4 >> 3) & ONES;
-        bool won;
-        if (g.k() == 4) {
-            won = ply_run_of_four(g, mine, pos);
-        } else {
-            Bits<1> b;
-            b.w[0] = mine;
-            won = has_run(g, b);
-        }
-        won_any = won_any || won;   // (lane masks: scalar ORs)
-        alive = (won || op == 0u) ? 0u : alive;
-    };
-    // the outcome byte of a board that has just ended: its stones, and whether somebody holds a run (no cap: a board that
-    // stopped without one is full).  Status, reward, code and env-steps follow from it when the chunk is flushed.
-    auto outcome_of = [&](const uint64_t (&q)[2], bool won_any) -> uint32_t {
-        const uint32_t stones = (uint32_t)__popcll(q[0]) + (uint32_t)__popcll(q[1]);
-        return connect_outcome_byte(stones, won_any);
-    };
-    // one opening ply: every column is open and nobody can win yet
-    auto cheap_ply = [&](uint32_t j, uint32_t draw, uint64_t (&q)[2], uint32_t& h4) {
-        const uint32_t col = sample_index(draw, (uint32_t)g.w());
-        const uint32_t sh = col * 4u;
-        const uint32_t v = (h4 >> sh) & 15u;
-        const uint32_t pos = col * stride + top - v;
-        q[j & 1u] |= 1ull << pos;
-        h4 -= 1u << sh;
-    };
     // The deferred opening parks a replayed game with the words of blocks 1 .. 8; it can last to block 10.  Such a lane
     // carries kReplayRow in wrow until it is about to read its last row (the word of block 8): then, behind a wave-uniform
     // branch almost never taken, it makes philox call 2 of its own game, lays the words of blocks 8, 9 and 10 into rows
@@ -1192,36 +1302,22 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
             wnext = my_words[wrow * BGS_WAVE];   // (used by the NEXT block: the read has a whole block to arrive)
             wrow = wrow + 1u < (uint32_t)NWORDS - 1u ? wrow + 1u : (uint32_t)NWORDS - 1u;   // (a finished lane idles on the last row)
         }
-        uint32_t open = (hts >> 3) & ONES;
-        full_ply(std::integral_constant<uint32_t, 0>{}, PER_PLY ? four.v[0] : sub_draw<0>(word), p, hts, open, live, anywon);
-        full_ply(std::integral_constant<uint32_t, 1>{}, PER_PLY ? four.v[1] : sub_draw<1>(word), p, hts, open, live, anywon);
-        full_ply(std::integral_constant<uint32_t, 2>{}, PER_PLY ? four.v[2] : sub_draw<2>(word), p, hts, open, live, anywon);
-        full_ply(std::integral_constant<uint32_t, 3>{}, PER_PLY ? four.v[3] : sub_draw<3>(word), p, hts, open, live, anywon);
+        uint32_t open = (hts >> 3) & plies.ONES;
+        plies.template full<0>(g, opening_draw<PER_PLY, 0>(four, word), p, hts, open, live, anywon);
+        plies.template full<1>(g, opening_draw<PER_PLY, 1>(four, word), p, hts, open, live, anywon);
+        plies.template full<2>(g, opening_draw<PER_PLY, 2>(four, word), p, hts, open, live, anywon);
+        plies.template full<3>(g, opening_draw<PER_PLY, 3>(four, word), p, hts, open, live, anywon);
         if (was_live != 0 && live == 0) {
             *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(plane0) + (game * 8u)) = p[0];
             *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(plane1) + (game * 8u)) = p[1];
-            outcome[game] = (uint8_t)outcome_of(p, anywon);
+            outcome[game] = (uint8_t)plies.outcome_of(p, anywon);
         }
     };
     // an idle lane takes game `which` of the chunk out of the pool: board, column nibbles, the words of its blocks to come
     auto take = [&](uint32_t which) {
         game = which;
-        const uint32_t slot = which & (Pool::SLOTS - 1u);
-        p[0] = pool.plane[0][slot];
-        p[1] = pool.plane[1][slot];
-        hts = pool.cols[slot];
-        if constexpr (PER_PLY) {
-            myblk = (uint32_t)OPEN_BLOCKS;
-        } else {
-#pragma unroll
-            for (int k = 0; k < OW::QUADS; ++k) {
-                const uint4 v = pool.words[k][slot];
-                if (k == 0) wnext = v.x; else my_words[(4 * k) * BGS_WAVE] = v.x;
-                my_words[(4 * k + 1) * BGS_WAVE] = v.y;
-                my_words[(4 * k + 2) * BGS_WAVE] = v.z;
-                my_words[(4 * k + 3) * BGS_WAVE] = v.w;
-            }
-        }
+        take_slot<PER_PLY ? 0 : OW::QUADS>(pool, which & (Pool::SLOTS - 1u), p, hts, wnext, my_words);
+        if constexpr (PER_PLY) myblk = (uint32_t)OPEN_BLOCKS;
         wrow = DEFER ? 1u | ((hts << 3) & kReplayRow) : 1u;   // (kReplayMark moves up into kReplayRow)
         anywon = false;
         live = hts != 0u ? ~0u : 0u;  // (a dead slot: the opening stage has stored that game, or it lies past the chunk)
@@ -1230,70 +1326,8 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
     auto open_games = [&]() {
         const uint32_t og = opened + lane;
         const uint64_t id = first_game + (uint64_t)(begin + og);
-        if constexpr (DEFER) {
-            open_games_deferred(g, pool, og & (Pool::SLOTS - 1u), seed, id, og < avail);
-            opened += 64u;
-            return;
-        }
-        uint64_t q[2] = {0, 0};
-        uint32_t h4 = top * columns, alive = ~0u, op = columns;
-        bool won_any = false;
-        uint32_t words[12];   // the words of blocks 0 .. 11: three philox calls (fewer when the board cannot last that long)
-        // the draws of block b of the opening: sub-draws of its word, or (strict contract) the four words of its own call
-        Philox4 own = philox4x32_10(seed, id, 0u);
-        using J0 = std::integral_constant<uint32_t, 0>; using J1 = std::integral_constant<uint32_t, 1>;
-        using J2 = std::integral_constant<uint32_t, 2>; using J3 = std::integral_constant<uint32_t, 3>;
-#define BGS_DRAW_OF(JT, b) (PER_PLY ? own.v[JT::value] : sub_draw<JT::value>(words[b]))
-        if constexpr (!PER_PLY) {
-            words[0] = own.v[0]; words[1] = own.v[1]; words[2] = own.v[2]; words[3] = own.v[3];
-#pragma unroll
-            for (int c = 1; c < 3; ++c) {
-                if (4 * c <= OW::LAST) {
-                    const Philox4 d = philox4x32_10(seed, id, (uint32_t)c);
-                    words[4 * c] = d.v[0]; words[4 * c + 1] = d.v[1]; words[4 * c + 2] = d.v[2]; words[4 * c + 3] = d.v[3];
-                } else {
-                    words[4 * c] = words[4 * c + 1] = words[4 * c + 2] = words[4 * c + 3] = 0u;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 12; ++c) words[c] = 0u;
-        }
-        cheap_ply(0u, BGS_DRAW_OF(J0, 0), q, h4);
-        cheap_ply(1u, BGS_DRAW_OF(J1, 0), q, h4);
-        cheap_ply(2u, BGS_DRAW_OF(J2, 0), q, h4);
-        cheap_ply(3u, BGS_DRAW_OF(J3, 0), q, h4);
-        if (OPEN_BLOCKS >= 2) {
-            if constexpr (PER_PLY) own = philox4x32_10(seed, id, 1u);
-            cheap_ply(0u, BGS_DRAW_OF(J0, 1), q, h4);
-            cheap_ply(1u, BGS_DRAW_OF(J1, 1), q, h4);
-            op = (h4 >> 3) & ONES;
-            full_ply(J2{}, BGS_DRAW_OF(J2, 1), q, h4, op, alive, won_any);
-            full_ply(J3{}, BGS_DRAW_OF(J3, 1), q, h4, op, alive, won_any);
-        }
-#pragma unroll
-        for (int ob = 2; ob < OPEN_BLOCKS; ++ob) {  // further blocks in lock step
-            if constexpr (PER_PLY) own = philox4x32_10(seed, id, (uint32_t)ob);
-            full_ply(J0{}, BGS_DRAW_OF(J0, ob), q, h4, op, alive, won_any);
-            full_ply(J1{}, BGS_DRAW_OF(J1, ob), q, h4, op, alive, won_any);
-            full_ply(J2{}, BGS_DRAW_OF(J2, ob), q, h4, op, alive, won_any);
-            full_ply(J3{}, BGS_DRAW_OF(J3, ob), q, h4, op, alive, won_any);
-        }
-#undef BGS_DRAW_OF
-        if (OPEN_BLOCKS >= 2 && og < avail && alive == 0) {  // ended inside the opening: a win, or a small board is full
-            plane0[og] = q[0];
-            plane1[og] = q[1];
-            outcome[og] = (uint8_t)outcome_of(q, won_any);
-        }   // (a lane past the end of the chunk played for nobody: nothing of it is stored or counted)
-        const uint32_t slot = og & (Pool::SLOTS - 1u);
-        pool.plane[0][slot] = q[0];
-        pool.plane[1][slot] = q[1];
-        pool.cols[slot] = alive ? h4 : 0u;
-#pragma unroll
-        for (int k = 0; k < OW::QUADS; ++k) {
-            auto at = [&](int i) { return OPEN_BLOCKS + i <= 11 ? words[OPEN_BLOCKS + i <= 11 ? OPEN_BLOCKS + i : 11] : 0u; };
-            pool.words[k][slot] = make_uint4(at(4 * k), at(4 * k + 1), at(4 * k + 2), at(4 * k + 3));
-        }
+        if constexpr (DEFER) open_games_deferred(g, pool, og & (Pool::SLOTS - 1u), seed, id, og < avail);
+        else open_games_per_ply<OPEN_BLOCKS, PER_PLY, true>(g, plies, pool, seed, id, og, avail, plane0, plane1, outcome);
         opened += 64u;
     };
 
@@ -1326,30 +1360,11 @@ k_connect_rollout_opened(G g, uint64_t* __restrict__ planes, uint8_t* __restrict
     // ---- the drain: no games left to hand out, the boards in flight play to their end
     while (__builtin_amdgcn_ballot_w64(live != 0)) play_block();
 
-    // ---- the chunk is done: four games per lane -- their outcome dword as it lies in LDS gives their status bytes, their
-    // reward pairs, their byte of 2-bit codes for the hand-over (64 lanes: 64 contiguous bytes per store, into host memory
-    // when mapped) and their plies (connect_unit.h: connect_outcome4)
+    // ---- the chunk is done: what its games leave besides their boards, from their outcome bytes
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the byte stores of every lane before the reads below
     __builtin_amdgcn_wave_barrier();
-    uint8_t* __restrict__ const status_out = status + begin;
-    uint16_t* __restrict__ const reward_out = reward + begin;
-    uint8_t* __restrict__ const packed_out = reinterpret_cast<uint8_t*>(codes_out) + (begin >> 2);
-    uint32_t stepped = 0;
-    for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
-        const ConnectOutcome4 o = connect_outcome4(reinterpret_cast<const uint32_t*>(outcome)[g4 >> 2]);  // (bytes past avail are 0)
-        stepped += o.plies;
-        if (CODES) packed_out[g4 >> 2] = (uint8_t)o.codes;
-        if (g4 + 4u <= avail) {
-            *reinterpret_cast<uint32_t*>(status_out + g4) = o.status;
-            *reinterpret_cast<uint2*>(reward_out + g4) = make_uint2(o.reward[0], o.reward[1]);
-        } else {
-            for (uint32_t k = 0; g4 + k < avail; ++k) {
-                status_out[g4 + k] = (uint8_t)(o.status >> (8u * k));
-                reward_out[g4 + k] = (uint16_t)((((uint64_t)o.reward[1] << 32) | o.reward[0]) >> (16u * k));
-            }
-        }
-    }
-    add_steps(steps, stepped);
+    add_steps(steps, flush_outcomes<CODES, false>(reinterpret_cast<const uint32_t*>(outcome), lane, avail, true, status + begin,
+                                                  reward + begin, reinterpret_cast<uint8_t*>(codes_out) + (begin >> 2)));
 }
 
 // K2o over several pipeline steps in one launch (the executor's grouped form, bgs_pipeline.hip).  A launch's waves are
@@ -1380,12 +1395,7 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
     extern __shared__ uint32_t code_lds[];  // two outcome slices per wave, games_per_wave bytes each
     __shared__ Pool pools[BGS_BLOCK / BGS_WAVE];
     __shared__ uint32_t lane_words[BGS_BLOCK / BGS_WAVE][NWORDS][BGS_WAVE];
-    constexpr uint32_t ONES = 0x11111111u;
-    const uint32_t top = (uint32_t)g.h() + 7u;
-    const uint32_t columns = g.w() >= 8 ? ONES : (ONES & ((1u << (4 * g.w())) - 1u));
-    const uint32_t stride = (uint32_t)g.h() + 1u;
-    const uint32_t column_top = 8u * columns;
-    const uint64_t eights = 0x88888888ull;
+    const NibblePlies<G> plies(g);
 
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (BGS_BLOCK / BGS_WAVE) + (threadIdx.x >> 6));
     const uint32_t lane = threadIdx.x & 63u;
@@ -1427,58 +1437,7 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
     };
     zero_slice(0u);
 
-    // K2o's full ply, opening ply and block (see k_connect_rollout_opened)
-    auto full_ply = [&](auto j_tag, uint32_t draw, uint64_t (&q)[2], uint32_t& h4, uint32_t& op, uint32_t& alive,
-                        bool& won_any) {
-        constexpr uint32_t J = decltype(j_tag)::value;
-        const uint32_t cnt = (uint32_t)__popc(op);
-        const uint32_t idx = sample_index(draw, cnt);
-        uint64_t cmp64;
-        {
-            uint64_t carry;
-            asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(cmp64), "=s"(carry) : "v"(idx - op), "s"(ONES), "v"(eights));
-        }
-        const uint32_t cmp = (uint32_t)cmp64;
-        uint32_t col = (uint32_t)__popc(cmp & column_top);
-        if (g.w() >= 8) col &= 7u;
-        const uint32_t sh = col * 4u;
-        const uint32_t v = (h4 >> sh) & 15u;
-        uint32_t base = col * stride + top;
-        asm("" : "+v"(base));
-        uint32_t pos = base - v;
-        if ((uint32_t)g.w() * stride + top > 63u) pos &= 63u;
-        const uint32_t act = alive;
-        uint64_t& mine = q[J & 1u];
-        const uint64_t bit = 1ull << pos;
-        mine = ((uint64_t)and_or((uint32_t)(bit >> 32), act, (uint32_t)(mine >> 32)) << 32) |
-               and_or((uint32_t)bit, act, (uint32_t)mine);
-        h4 += act << sh;
-        op = (h4 >> 3) & ONES;
-        bool won;
-        if (g.k() == 4) {
-            won = ply_run_of_four(g, mine, pos);
-        } else {
-            Bits<1> b;
-            b.w[0] = mine;
-            won = has_run(g, b);
-        }
-        won_any = won_any || won;
-        alive = (won || op == 0u) ? 0u : alive;
-    };
-    // the outcome byte of a board that has just ended (connect_unit.h: connect_outcome_byte)
-    auto outcome_of = [&](const uint64_t (&q)[2], bool won_any) -> uint32_t {
-        const uint32_t stones = (uint32_t)__popcll(q[0]) + (uint32_t)__popcll(q[1]);
-        return connect_outcome_byte(stones, won_any);
-    };
-    auto cheap_ply = [&](uint32_t j, uint32_t draw, uint64_t (&q)[2], uint32_t& h4) {
-        const uint32_t col = sample_index(draw, (uint32_t)g.w());
-        const uint32_t sh = col * 4u;
-        const uint32_t v = (h4 >> sh) & 15u;
-        const uint32_t pos = col * stride + top - v;
-        q[j & 1u] |= 1ull << pos;
-        h4 -= 1u << sh;
-    };
-    // a replayed game's words of blocks 8 .. 10 (see k_connect_rollout_opened).  The lane's game is of step cur or of step
+    // a replayed game's words of blocks 8 .. 10 (K2o's refetch, for two steps).  The lane's game is of step cur or of step
     // cur - 1: a pass for each, so that the seed stays wave-uniform and philox's key schedule in SGPRs
     auto refetch = [&]() {
         const bool at = wrow == (kReplayRow | 7u);
@@ -1508,11 +1467,11 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
             wnext = my_words[wrow * BGS_WAVE];
             wrow = wrow + 1u < (uint32_t)NWORDS - 1u ? wrow + 1u : (uint32_t)NWORDS - 1u;
         }
-        uint32_t open = (hts >> 3) & ONES;
-        full_ply(std::integral_constant<uint32_t, 0>{}, sub_draw<0>(word), p, hts, open, live, anywon);
-        full_ply(std::integral_constant<uint32_t, 1>{}, sub_draw<1>(word), p, hts, open, live, anywon);
-        full_ply(std::integral_constant<uint32_t, 2>{}, sub_draw<2>(word), p, hts, open, live, anywon);
-        full_ply(std::integral_constant<uint32_t, 3>{}, sub_draw<3>(word), p, hts, open, live, anywon);
+        uint32_t open = (hts >> 3) & plies.ONES;
+        plies.template full<0>(g, sub_draw<0>(word), p, hts, open, live, anywon);
+        plies.template full<1>(g, sub_draw<1>(word), p, hts, open, live, anywon);
+        plies.template full<2>(g, sub_draw<2>(word), p, hts, open, live, anywon);
+        plies.template full<3>(g, sub_draw<3>(word), p, hts, open, live, anywon);
         if (was_live != 0 && live == 0) {
             // (wave-uniform: only a call's last step on a batch leaves boards, so most launches have no store to select)
             if (cur_planes != nullptr || prev_planes != nullptr) {
@@ -1523,25 +1482,14 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
                     *reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(planes + n) + at) = p[1];
                 }
             }
-            outcome_bytes[game] = (uint8_t)outcome_of(p, anywon);
+            outcome_bytes[game] = (uint8_t)plies.outcome_of(p, anywon);
         }
     };
     // an idle lane takes game `which` of step cur's chunk out of the pool
     auto take = [&](uint32_t which) {
         game = cur_at + which;
         old = 0u;
-        const uint32_t slot = which & (Pool::SLOTS - 1u);
-        p[0] = pool.plane[0][slot];
-        p[1] = pool.plane[1][slot];
-        hts = pool.cols[slot];
-#pragma unroll
-        for (int k = 0; k < OW::QUADS; ++k) {
-            const uint4 v = pool.words[k][slot];
-            if (k == 0) wnext = v.x; else my_words[(4 * k) * BGS_WAVE] = v.x;
-            my_words[(4 * k + 1) * BGS_WAVE] = v.y;
-            my_words[(4 * k + 2) * BGS_WAVE] = v.z;
-            my_words[(4 * k + 3) * BGS_WAVE] = v.w;
-        }
+        take_slot<OW::QUADS>(pool, which & (Pool::SLOTS - 1u), p, hts, wnext, my_words);
         wrow = DEFER ? 1u | ((hts << 3) & kReplayRow) : 1u;
         anywon = false;
         live = hts != 0u ? ~0u : 0u;
@@ -1550,62 +1498,9 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
     auto open_games = [&]() {
         const uint32_t og = opened + lane;
         const uint64_t id = cur_first + (uint64_t)(begin + og);
-        if constexpr (DEFER) {
-            open_games_deferred(g, pool, og & (Pool::SLOTS - 1u), cur_seed, id, og < avail);
-            opened += 64u;
-            return;
-        }
-        uint64_t q[2] = {0, 0};
-        uint32_t h4 = top * columns, alive = ~0u, op = columns;
-        bool won_any = false;
-        uint32_t words[12];
-        const Philox4 own = philox4x32_10(cur_seed, id, 0u);
-        using J2 = std::integral_constant<uint32_t, 2>; using J3 = std::integral_constant<uint32_t, 3>;
-        using J0 = std::integral_constant<uint32_t, 0>; using J1 = std::integral_constant<uint32_t, 1>;
-        words[0] = own.v[0]; words[1] = own.v[1]; words[2] = own.v[2]; words[3] = own.v[3];
-#pragma unroll
-        for (int c = 1; c < 3; ++c) {
-            if (4 * c <= OW::LAST) {
-                const Philox4 d = philox4x32_10(cur_seed, id, (uint32_t)c);
-                words[4 * c] = d.v[0]; words[4 * c + 1] = d.v[1]; words[4 * c + 2] = d.v[2]; words[4 * c + 3] = d.v[3];
-            } else {
-                words[4 * c] = words[4 * c + 1] = words[4 * c + 2] = words[4 * c + 3] = 0u;
-            }
-        }
-        cheap_ply(0u, sub_draw<0>(words[0]), q, h4);
-        cheap_ply(1u, sub_draw<1>(words[0]), q, h4);
-        cheap_ply(2u, sub_draw<2>(words[0]), q, h4);
-        cheap_ply(3u, sub_draw<3>(words[0]), q, h4);
-        if (OPEN_BLOCKS >= 2) {
-            cheap_ply(0u, sub_draw<0>(words[1]), q, h4);
-            cheap_ply(1u, sub_draw<1>(words[1]), q, h4);
-            op = (h4 >> 3) & ONES;
-            full_ply(J2{}, sub_draw<2>(words[1]), q, h4, op, alive, won_any);
-            full_ply(J3{}, sub_draw<3>(words[1]), q, h4, op, alive, won_any);
-        }
-#pragma unroll
-        for (int ob = 2; ob < OPEN_BLOCKS; ++ob) {
-            full_ply(J0{}, sub_draw<0>(words[ob]), q, h4, op, alive, won_any);
-            full_ply(J1{}, sub_draw<1>(words[ob]), q, h4, op, alive, won_any);
-            full_ply(J2{}, sub_draw<2>(words[ob]), q, h4, op, alive, won_any);
-            full_ply(J3{}, sub_draw<3>(words[ob]), q, h4, op, alive, won_any);
-        }
-        if (OPEN_BLOCKS >= 2 && og < avail && alive == 0) {
-            if (cur_planes) {
-                cur_planes[og] = q[0];
-                cur_planes[n + og] = q[1];
-            }
-            slice_of(cur)[og] = (uint8_t)outcome_of(q, won_any);
-        }
-        const uint32_t slot = og & (Pool::SLOTS - 1u);
-        pool.plane[0][slot] = q[0];
-        pool.plane[1][slot] = q[1];
-        pool.cols[slot] = alive ? h4 : 0u;
-#pragma unroll
-        for (int k = 0; k < OW::QUADS; ++k) {
-            auto at = [&](int i) { return OPEN_BLOCKS + i <= 11 ? words[OPEN_BLOCKS + i <= 11 ? OPEN_BLOCKS + i : 11] : 0u; };
-            pool.words[k][slot] = make_uint4(at(4 * k), at(4 * k + 1), at(4 * k + 2), at(4 * k + 3));
-        }
+        if constexpr (DEFER) open_games_deferred(g, pool, og & (Pool::SLOTS - 1u), cur_seed, id, og < avail);
+        else open_games_per_ply<OPEN_BLOCKS, false, false>(g, plies, pool, cur_seed, id, og, avail, cur_planes,
+                                                               cur_planes ? cur_planes + n : nullptr, slice_of(cur));
         opened += 64u;
     };
     // step s's chunk is done: status, reward pairs and codes as the one-step kernel stores them, and its env-steps -- all
@@ -1614,30 +1509,9 @@ k_connect_rollout_opened_steps(G g, const ConnectGroup tab, int64_t n, uint32_t 
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         const ConnectGroupStep& e = tab.step[s];
-        const uint32_t* const outcome = reinterpret_cast<const uint32_t*>(slice_of(s));
-        uint8_t* __restrict__ const status_out = e.status + begin;
-        uint16_t* __restrict__ const reward_out = e.reward + begin;
-        uint8_t* __restrict__ const packed_out = reinterpret_cast<uint8_t*>(e.codes) + (begin >> 2);
-        uint32_t stepped = 0;
-        // (two trips at 512 games a wave: unrolled by four, hipcc's choice, the codes' loop alone took the kernel past 80
-        // VGPRs once play_block held the refetch branch)
-#pragma unroll 1
-        for (uint32_t g4 = lane * 4u; g4 < avail; g4 += BGS_WAVE * 4u) {
-            const ConnectOutcome4 o = connect_outcome4(outcome[g4 >> 2]);
-            stepped += o.plies;
-            if (CODES) packed_out[g4 >> 2] = (uint8_t)o.codes;
-            if (e.planes) {
-                if (g4 + 4u <= avail) {
-                    *reinterpret_cast<uint32_t*>(status_out + g4) = o.status;
-                    *reinterpret_cast<uint2*>(reward_out + g4) = make_uint2(o.reward[0], o.reward[1]);
-                } else {
-                    for (uint32_t k = 0; g4 + k < avail; ++k) {
-                        status_out[g4 + k] = (uint8_t)(o.status >> (8u * k));
-                        reward_out[g4 + k] = (uint16_t)((((uint64_t)o.reward[1] << 32) | o.reward[0]) >> (16u * k));
-                    }
-                }
-            }
-        }
+        const uint32_t stepped = flush_outcomes<CODES, true>(reinterpret_cast<const uint32_t*>(slice_of(s)), lane, avail,
+                                                             e.planes != nullptr, e.status + begin, e.reward + begin,
+                                                             reinterpret_cast<uint8_t*>(e.codes) + (begin >> 2));
         add_steps(e.steps, stepped);
     };
     // step cur - 1 is flushed as soon as none of its games is playing any more
@@ -2369,6 +2243,19 @@ struct Tag {
     using type = T;
 };
 
+// run-time flags as compile-time tags: with_tags(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{})
+template <class F>
+void with_tags(F&& f) {
+    f();
+}
+template <class F, class... Flags>
+void with_tags(F&& f, bool flag, Flags... flags) {
+    if (flag) with_tags([&](auto... tags) { f(std::true_type{}, tags...); }, flags...);
+    else with_tags([&](auto... tags) { f(std::false_type{}, tags...); }, flags...);
+}
+
+static_assert(kRolloutWave == BGS_WAVE && kRolloutWavesPerBlock * BGS_WAVE == BGS_BLOCK, "connect_launch_shape's workgroup");
+
 template <class F>
 void dispatch(const ConnectGeom& cg, F&& f) {
     if (cg.h == 6 && cg.w == 7 && cg.k == 4) { f(Geo<1, 6, 7, 4>{6, 7, 4}); return; }
@@ -2395,11 +2282,10 @@ void connect_reset_ended(const bgs_batch* b) {
 // geometry + board policy: nibble column state where it applies (one word, W <= 8, H <= 8), generic otherwise
 template <class F>
 void dispatch_game(const ConnectGeom& cg, F&& f) {
-    const bool nibble_ok = cg.nw == 1 && cg.w <= 8 && cg.h <= 8;
     dispatch(cg, [&](auto g) {
         using G = decltype(g);
         if constexpr (G::NW == 1) {
-            if (nibble_ok) { f(g, Tag<NibbleGame<G>>{}); return; }
+            if (connect_nibble_ok(cg)) { f(g, Tag<NibbleGame<G>>{}); return; }
         }
         f(g, Tag<GenericGame<G>>{});
     });
@@ -2424,13 +2310,7 @@ void connect_step_random(const bgs_batch* b, uint64_t seed, uint32_t count) {
                                        b->stream, g, b->d_planes, b->d_status, reinterpret_cast<uint16_t*>(b->d_reward), b->n,
                                        seed, b->first_game, b->d_steps, count);
                 };
-                if (count == 1u) {
-                    if (b->rng_per_ply) launch(std::true_type{}, std::true_type{});
-                    else launch(std::true_type{}, std::false_type{});
-                } else {
-                    if (b->rng_per_ply) launch(std::false_type{}, std::true_type{});
-                    else launch(std::false_type{}, std::false_type{});
-                }
+                with_tags(launch, count == 1u, b->rng_per_ply != 0);
             }
         });
         return;
@@ -2480,182 +2360,116 @@ void status_to_ended(const bgs_batch* b, uint8_t* d_ended) {
 // k_pack_outcomes behind it)
 bool connect_rollout(const bgs_batch* b, uint64_t seed, int32_t max_plies, uint32_t flags, uint32_t* codes_out) {
     const uint32_t cap = max_plies < 0 ? 0u : (uint32_t)max_plies;
+    // a cap of height * width plies or more can never bind: drop the per-ply test
+    const bool capped = cap < (uint32_t)(b->cg.h * b->cg.w);
+    const bool initial = flags & 1u;
     // the RNG contract of this call: the batch's (bgs_set_rng_contract), or the strict one by flag (BGS_ROLLOUT_DRAW_PER_PLY)
     const bool per_ply = b->rng_per_ply || (flags & 4u);
-    auto with_rng = [&](auto&& f) {
-        if (per_ply) f(std::true_type{});
-        else f(std::false_type{});
-    };
-    // resident waves: CUs x 4 SIMDs x waves per SIMD; every wave gets an equal contiguous chunk of games, a multiple
-    // of 64 (whole dwords of outcome codes per wave, whole refill rounds)
-    const int64_t resident = (int64_t)b->num_cus * 4 * b->rollout_wps;
-    int64_t per_wave = b->rollout_chunk > 0 ? b->rollout_chunk : (b->n + resident - 1) / resident;
-    per_wave = (per_wave + BGS_WAVE - 1) / BGS_WAVE * BGS_WAVE;
-    const int64_t waves = (b->n + per_wave - 1) / per_wave;
-    // the wave-private LDS slices of the fused codes: 4 waves x per_wave / 16 dwords per workgroup
-    const size_t code_lds = (size_t)4 * (per_wave / 16) * sizeof(uint32_t);
-    const bool fuse_codes = codes_out != nullptr && code_lds <= (32u << 10);
+    const ConnectLaunchShape shape = connect_launch_shape(b->n, b->num_cus, b->rollout_wps, b->rollout_chunk);
+    const uint32_t per_wave = (uint32_t)shape.per_wave;
+    const bool fuse_codes = codes_out != nullptr && shape.code_lds <= kRolloutLdsLimit;
     bool fused = false;
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
-    const bool nibble_ok = b->cg.nw == 1 && b->cg.w <= 8 && b->cg.h <= 8;
     dispatch(b->cg, [&](auto g) {
         using G = decltype(g);
-        auto launch = [&](auto game_tag, auto initial_tag, auto capped_tag) {
-            using Game = typename decltype(game_tag)::type;
-            constexpr bool INITIAL = decltype(initial_tag)::value;
-            constexpr bool CAPPED = decltype(capped_tag)::value;
-            hipLaunchKernelGGL((k_connect_rollout<G, Game, INITIAL, CAPPED>), dim3(blocks), dim3(BGS_BLOCK), 0, b->stream,
-                               g, b->d_planes, b->d_status, reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed,
-                               b->first_game, cap, b->d_steps, (uint32_t)per_wave, per_ply ? 1u : 0u);
+        // every rollout kernel's arguments begin (g, planes, status, reward, n, seed, first_game): `tail` is what follows
+        auto launch = [&](auto kernel, size_t lds, auto... tail) {
+            hipLaunchKernelGGL(kernel, dim3(shape.blocks), dim3(BGS_BLOCK), lds, b->stream, g, b->d_planes, b->d_status,
+                               reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed, b->first_game, tail...);
         };
-        // a cap of height * width plies or more can never bind: drop the per-ply test
-        const bool capped = cap < (uint32_t)(b->cg.h * b->cg.w);
-        auto with_game = [&](auto game_tag) {
-            if (flags & 1u) {
-                if (capped) launch(game_tag, std::true_type{}, std::true_type{});
-                else launch(game_tag, std::true_type{}, std::false_type{});
-            } else {
-                if (capped) launch(game_tag, std::false_type{}, std::true_type{});
-                else launch(game_tag, std::false_type{}, std::false_type{});
-            }
+        // the lane-refill kernel on a board policy: any state, any cap, no codes
+        auto launch_game = [&](auto game_tag) {
+            using Game = typename decltype(game_tag)::type;
+            with_tags([&](auto initial_tag, auto capped_tag) {
+                launch(k_connect_rollout<G, Game, decltype(initial_tag)::value, decltype(capped_tag)::value>, 0, cap, b->d_steps,
+                       per_wave, per_ply ? 1u : 0u);
+            }, initial, capped);
         };
         if constexpr (G::NW == 1) {
-            if (nibble_ok && !b->rollout_generic) {
-                // one-word boards: the block-aligned, branch-free kernel (from the initial state or from memory)
-                auto launch_aligned = [&](auto capped_tag, auto initial_tag) {
-                    constexpr bool CAPPED = decltype(capped_tag)::value;
-                    constexpr bool INITIAL = decltype(initial_tag)::value;
-                    with_rng([&](auto rng_tag) {
-                        constexpr bool PER_PLY = decltype(rng_tag)::value;
-                        if (fuse_codes) {
-                            hipLaunchKernelGGL((k_connect_rollout_aligned<G, CAPPED, INITIAL, true, PER_PLY>), dim3(blocks), dim3(BGS_BLOCK),
-                                               code_lds, b->stream, g, b->d_planes, b->d_status,
-                                               reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed, b->first_game, cap, b->d_steps,
-                                               (uint32_t)per_wave, codes_out);
-                            fused = true;
-                        } else {
-                            hipLaunchKernelGGL((k_connect_rollout_aligned<G, CAPPED, INITIAL, false, PER_PLY>), dim3(blocks), dim3(BGS_BLOCK),
-                                               0, b->stream, g, b->d_planes, b->d_status, reinterpret_cast<uint16_t*>(b->d_reward),
-                                               b->n, seed, b->first_game, cap, b->d_steps, (uint32_t)per_wave, nullptr);
-                        }
-                    });
-                };
-                const size_t outcome_lds = (size_t)4 * per_wave;  // K2o: one outcome byte per game
-                // (boards of at most 48 cells: a game is at most 12 blocks of four plies, whose words three philox calls give)
-                if ((flags & 1u) && !capped && b->rollout_opening && b->cg.h >= 4 && b->cg.w >= 2 && b->cg.k >= 3 &&
-                    b->cg.h * b->cg.w <= 48 && outcome_lds <= (32u << 10)) {
+            if (connect_nibble_ok(b->cg) && !b->rollout_generic) {
+                if (connect_opened_ok(b->cg, initial, capped, b->rollout_opening, shape)) {
                     // from the initial state, no cap: the kernel with the lock-step opening stage (K2o)
-                    auto launch_opened = [&](auto blocks_tag, auto codes_tag) {
-                        constexpr int OPEN_BLOCKS = decltype(blocks_tag)::value;
-                        constexpr bool CODES = decltype(codes_tag)::value;
-                        with_rng([&](auto rng_tag) {
-                            constexpr bool PER_PLY = decltype(rng_tag)::value;
-                            hipLaunchKernelGGL((k_connect_rollout_opened<G, OPEN_BLOCKS, CODES, PER_PLY>), dim3(blocks), dim3(BGS_BLOCK),
-                                               outcome_lds, b->stream, g, b->d_planes, b->d_status,
-                                               reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed, b->first_game, b->d_steps,
-                                               (uint32_t)per_wave, CODES ? codes_out : nullptr);
-                        });
-                        fused = CODES;
+                    auto launch_opened = [&](auto blocks_tag) {
+                        with_tags([&](auto codes_tag, auto rng_tag) {
+                            constexpr bool CODES = decltype(codes_tag)::value;
+                            launch(k_connect_rollout_opened<G, decltype(blocks_tag)::value, CODES, decltype(rng_tag)::value>,
+                                   shape.outcome_lds, b->d_steps, per_wave, CODES ? codes_out : nullptr);
+                        }, fuse_codes, per_ply);
                     };
-                    const bool deep = b->cg.k >= 4 && b->cg.h >= 6;
-                    auto with_blocks = [&](auto blocks_tag) {
-                        if (fuse_codes) launch_opened(blocks_tag, std::true_type{});
-                        else launch_opened(blocks_tag, std::false_type{});
-                    };
-                    switch (deep ? b->rollout_opening : 1) {
-                        case 1: with_blocks(std::integral_constant<int, 1>{}); break;
-                        case 2: with_blocks(std::integral_constant<int, 2>{}); break;
-                        case 3: with_blocks(std::integral_constant<int, 3>{}); break;
-                        default: with_blocks(std::integral_constant<int, 4>{}); break;
+                    switch (connect_opened_blocks(b->cg, b->rollout_opening)) {
+                        case 1: launch_opened(std::integral_constant<int, 1>{}); break;
+                        case 2: launch_opened(std::integral_constant<int, 2>{}); break;
+                        case 3: launch_opened(std::integral_constant<int, 3>{}); break;
+                        default: launch_opened(std::integral_constant<int, 4>{}); break;
                     }
-                    return;
-                }
-                if (flags & 1u) {
-                    if (capped) launch_aligned(std::true_type{}, std::true_type{});
-                    else launch_aligned(std::false_type{}, std::true_type{});
                 } else {
-                    if (capped) launch_aligned(std::true_type{}, std::false_type{});
-                    else launch_aligned(std::false_type{}, std::false_type{});
+                    // one-word boards: the block-aligned, branch-free kernel (from the initial state or from memory)
+                    with_tags([&](auto capped_tag, auto initial_tag, auto codes_tag, auto rng_tag) {
+                        constexpr bool CODES = decltype(codes_tag)::value;
+                        launch(k_connect_rollout_aligned<G, decltype(capped_tag)::value, decltype(initial_tag)::value, CODES,
+                                                         decltype(rng_tag)::value>,
+                               CODES ? shape.code_lds : 0, cap, b->d_steps, per_wave, CODES ? codes_out : nullptr);
+                    }, capped, initial, fuse_codes, per_ply);
                 }
+                fused = fuse_codes;
                 return;
             }
-            if (nibble_ok) { with_game(Tag<NibbleGame<G>>{}); return; }
+            if (connect_nibble_ok(b->cg)) { launch_game(Tag<NibbleGame<G>>{}); return; }
         }
         if constexpr (LdsBoard<G>::fits && G::NW > 1) {
             if (!b->rollout_generic && !b->rollout_no_lds) {
                 // a compile-time multi-word geometry: boards staged in LDS, run test on the window around the stone --
                 // from the initial state or from memory, with or without a ply cap
-                const size_t tile = LdsBoard<G>::lds_bytes;
-                const OpenedBoard* heights = reinterpret_cast<const OpenedBoard*>(b->d_staging);
                 auto launch_lds = [&](auto capped_tag, auto entry_tag) {
-                    constexpr bool CAPPED = decltype(capped_tag)::value;
-                    constexpr int ENTRY = decltype(entry_tag)::value;
-                    with_rng([&](auto rng_tag) {
-                        constexpr bool PER_PLY = decltype(rng_tag)::value;
-                        if (fuse_codes) {
-                            hipLaunchKernelGGL((k_connect_rollout_lds<G, CAPPED, true, ENTRY, PER_PLY>), dim3(blocks), dim3(BGS_BLOCK),
-                                               tile + code_lds, b->stream, g, b->d_planes, b->d_status,
-                                               reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed, b->first_game, cap, b->d_steps,
-                                               (uint32_t)per_wave, codes_out, heights);
-                            fused = true;
-                        } else {
-                            hipLaunchKernelGGL((k_connect_rollout_lds<G, CAPPED, false, ENTRY, PER_PLY>), dim3(blocks), dim3(BGS_BLOCK), tile,
-                                               b->stream, g, b->d_planes, b->d_status, reinterpret_cast<uint16_t*>(b->d_reward),
-                                               b->n, seed, b->first_game, cap, b->d_steps, (uint32_t)per_wave, nullptr, heights);
-                        }
-                    });
+                    with_tags([&](auto codes_tag, auto rng_tag) {
+                        constexpr bool CODES = decltype(codes_tag)::value;
+                        launch(k_connect_rollout_lds<G, decltype(capped_tag)::value, CODES, decltype(entry_tag)::value,
+                                                     decltype(rng_tag)::value>,
+                               LdsBoard<G>::lds_bytes + (CODES ? shape.code_lds : 0), cap, b->d_steps, per_wave,
+                               CODES ? codes_out : nullptr, reinterpret_cast<const OpenedBoard*>(b->d_staging));
+                    }, fuse_codes, per_ply);
                 };
                 // the opening as a launch of its own: nobody can win and no column can fill in the first kOpenedPlies plies
                 constexpr bool can_open = G::STATIC_K > 0 && 2 * G::STATIC_K - 2 >= (int)kOpenedPlies &&
                                           G::STATIC_H >= (int)kOpenedPlies && G::STATIC_H <= 15;
-                if ((flags & 1u) && !capped && can_open && G::NW <= 3 && b->rollout_opening &&
+                if (initial && !capped && can_open && G::NW <= 3 && b->rollout_opening &&
                     b->staging_bytes >= (size_t)b->n * sizeof(OpenedBoard)) {
-                    with_rng([&](auto rng_tag) {
+                    with_tags([&](auto rng_tag) {
                         hipLaunchKernelGGL((k_connect_open_lds<G, decltype(rng_tag)::value>), dim3(grid_for(b->n)), dim3(BGS_BLOCK), 0,
                                            b->stream, g, reinterpret_cast<OpenedBoard*>(b->d_staging), b->n, seed, b->first_game,
                                            b->d_steps);
-                    });
+                    }, per_ply);
                     launch_lds(std::false_type{}, std::integral_constant<int, kEntryOpened>{});
-                } else if (flags & 1u) {
-                    if (capped) launch_lds(std::true_type{}, std::integral_constant<int, kEntryInitial>{});
-                    else launch_lds(std::false_type{}, std::integral_constant<int, kEntryInitial>{});
                 } else {
-                    if (capped) launch_lds(std::true_type{}, std::integral_constant<int, kEntryMemory>{});
-                    else launch_lds(std::false_type{}, std::integral_constant<int, kEntryMemory>{});
+                    with_tags([&](auto capped_tag, auto initial_tag) {
+                        launch_lds(capped_tag, std::integral_constant<int, decltype(initial_tag)::value ? kEntryInitial : kEntryMemory>{});
+                    }, capped, initial);
                 }
+                fused = fuse_codes;
                 return;
             }
         }
-        if ((flags & 1u) && !b->rollout_generic) {
-            if (capped)
-                hipLaunchKernelGGL((k_connect_rollout_aligned_wide<G, true>), dim3(blocks), dim3(BGS_BLOCK), 0, b->stream,
-                                   g, b->d_planes, b->d_status, reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed,
-                                   b->first_game, cap, b->d_steps, (uint32_t)per_wave, per_ply ? 1u : 0u);
-            else
-                hipLaunchKernelGGL((k_connect_rollout_aligned_wide<G, false>), dim3(blocks), dim3(BGS_BLOCK), 0, b->stream,
-                                   g, b->d_planes, b->d_status, reinterpret_cast<uint16_t*>(b->d_reward), b->n, seed,
-                                   b->first_game, cap, b->d_steps, (uint32_t)per_wave, per_ply ? 1u : 0u);
+        if (initial && !b->rollout_generic) {
+            with_tags([&](auto capped_tag) {
+                launch(k_connect_rollout_aligned_wide<G, decltype(capped_tag)::value>, 0, cap, b->d_steps, per_wave,
+                       per_ply ? 1u : 0u);
+            }, capped);
             return;
         }
-        with_game(Tag<GenericGame<G>>{});
+        launch_game(Tag<GenericGame<G>>{});
     });
     return fused;
 }
 
-// The steps connect_rollout_steps can take: the ones connect_rollout gives to K2o with the default opening on a compile-time
-// one-word geometry (6x7x4) -- from the initial state, no cap, the per-block contract -- delivering their codes to a
-// sink's slot (`codes`) or nothing.
+// The steps connect_rollout_steps can take: the ones connect_rollout gives to K2o (connect_opened_ok) with the default
+// opening on the compile-time geometry 6x7x4 under the per-block contract, whose chunk leaves LDS for the group's two
+// outcome slices a wave; they deliver their codes to a sink's slot (`codes`) or nothing.
 bool connect_steps_ok(const bgs_batch* b, int32_t max_plies, uint32_t flags, bool codes) {
     if (b->game != BGS_GAME_CONNECT || b->generic || !(b->cg.h == 6 && b->cg.w == 7 && b->cg.k == 4)) return false;
-    if (!(flags & 1u) || (flags & 4u) || b->rng_per_ply || b->rollout_generic || b->rollout_opening != kRolloutOpeningBlocks) return false;
-    if (max_plies < 0 || (uint32_t)max_plies < (uint32_t)(b->cg.h * b->cg.w)) return false;
-    const int64_t resident = (int64_t)b->num_cus * 4 * b->rollout_wps;
-    int64_t per_wave = b->rollout_chunk > 0 ? b->rollout_chunk : (b->n + resident - 1) / resident;
-    per_wave = (per_wave + BGS_WAVE - 1) / BGS_WAVE * BGS_WAVE;
-    // connect_rollout's own conditions for K2o and for its fused codes, with the group's two outcome slices a wave
-    if ((size_t)8 * per_wave > (32u << 10)) return false;
-    if (codes && (size_t)4 * (per_wave / 16) * sizeof(uint32_t) > (32u << 10)) return false;
-    return true;
+    if ((flags & 4u) || b->rng_per_ply || b->rollout_generic || b->rollout_opening != kRolloutOpeningBlocks) return false;
+    const ConnectLaunchShape shape = connect_launch_shape(b->n, b->num_cus, b->rollout_wps, b->rollout_chunk);
+    const bool capped = max_plies < 0 || (uint32_t)max_plies < (uint32_t)(b->cg.h * b->cg.w);
+    return connect_opened_ok(b->cg, flags & 1u, capped, b->rollout_opening, shape) && shape.outcome_lds2 <= kRolloutLdsLimit &&
+           (!codes || shape.code_lds <= kRolloutLdsLimit);
 }
 
 // `count` (1 .. kConnectGroupMax) steps in ONE launch on `stream`: step i plays every board of bs[i] (alike batches,
@@ -2664,11 +2478,7 @@ bool connect_steps_ok(const bgs_batch* b, int32_t max_plies, uint32_t flags, boo
 void connect_rollout_steps(const bgs_batch* const* bs, const uint64_t* seeds, uint32_t* const* codes, const bool* writes, int count,
                            hipStream_t stream) {
     const bgs_batch* b = bs[0];
-    const int64_t resident = (int64_t)b->num_cus * 4 * b->rollout_wps;
-    int64_t per_wave = b->rollout_chunk > 0 ? b->rollout_chunk : (b->n + resident - 1) / resident;
-    per_wave = (per_wave + BGS_WAVE - 1) / BGS_WAVE * BGS_WAVE;
-    const int64_t waves = (b->n + per_wave - 1) / per_wave;
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
+    const ConnectLaunchShape shape = connect_launch_shape(b->n, b->num_cus, b->rollout_wps, b->rollout_chunk);
     ConnectGroup tab = {};
     tab.count = count;
     for (int i = 0; i < count; ++i) {
@@ -2681,14 +2491,11 @@ void connect_rollout_steps(const bgs_batch* const* bs, const uint64_t* seeds, ui
         e.codes = codes ? codes[i] : nullptr;
         e.steps = bs[i]->d_steps;
     }
-    const size_t outcome_lds = (size_t)4 * 2 * per_wave;   // two slices of one outcome byte per game, four waves
     using G = Geo<1, 6, 7, 4>;
-    if (codes)
-        hipLaunchKernelGGL((k_connect_rollout_opened_steps<G, kRolloutOpeningBlocks, true>), dim3(blocks), dim3(BGS_BLOCK), outcome_lds,
-                           stream, G{6, 7, 4}, tab, b->n, (uint32_t)per_wave);
-    else
-        hipLaunchKernelGGL((k_connect_rollout_opened_steps<G, kRolloutOpeningBlocks, false>), dim3(blocks), dim3(BGS_BLOCK), outcome_lds,
-                           stream, G{6, 7, 4}, tab, b->n, (uint32_t)per_wave);
+    with_tags([&](auto codes_tag) {
+        hipLaunchKernelGGL((k_connect_rollout_opened_steps<G, kRolloutOpeningBlocks, decltype(codes_tag)::value>), dim3(shape.blocks),
+                           dim3(BGS_BLOCK), shape.outcome_lds2, stream, G{6, 7, 4}, tab, b->n, (uint32_t)shape.per_wave);
+    }, codes != nullptr);
 }
 
 void connect_unpack_grid(const bgs_batch* b, int8_t* d_grid) {

@@ -4,6 +4,7 @@
 // as that id stands, and an edit to the Bounce unit does not move it.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 struct ConnectGeom {
@@ -15,6 +16,52 @@ struct ConnectGeom {
 constexpr int kRolloutOpeningBlocks = 3;    // K2o: 4-ply blocks played in lock step before a board joins the refill loop
 constexpr int kGamesPerLaneOneWord = 8;     // one-word Connect boards: games per lane a launch aims for (512 per wave at 2^20)
 constexpr int kGamesPerLane = 4;            // every other rollout
+
+// The launch shape of the fused rollouts, computed here once for every launcher.  Resident waves: CUs x 4 SIMDs x waves
+// per SIMD (rollout_wps); every wave gets an equal contiguous chunk of games -- rollout_chunk when it is set -- a multiple
+// of 64: whole dwords of outcome codes per wave, whole refill rounds.  The LDS a workgroup of four waves needs besides a
+// kernel's static arrays: the wave-private slices of the fused 2-bit codes (K2a, the LDS-staged kernel), K2o's one outcome
+// byte per game, and the grouped kernel's two outcome slices a wave.
+constexpr int kRolloutWave = 64;             // lanes per wave (BGS_WAVE)
+constexpr int kRolloutWavesPerBlock = 4;     // waves per workgroup (BGS_BLOCK / BGS_WAVE)
+constexpr size_t kRolloutLdsLimit = 32u << 10;   // what a launch may ask for in dynamic LDS
+struct ConnectLaunchShape {
+    int64_t per_wave;        // games per wave
+    int64_t waves;
+    unsigned blocks;
+    size_t code_lds;         // bytes: per_wave / 16 dwords of 2-bit codes per wave
+    size_t outcome_lds;      // bytes: one outcome byte per game
+    size_t outcome_lds2;     // bytes: two outcome slices per wave
+};
+constexpr ConnectLaunchShape connect_launch_shape(int64_t n, int num_cus, int rollout_wps, int rollout_chunk) {
+    const int64_t resident = (int64_t)num_cus * 4 * rollout_wps;
+    const int64_t asked = rollout_chunk > 0 ? rollout_chunk : (n + resident - 1) / resident;
+    const int64_t per_wave = (asked + kRolloutWave - 1) / kRolloutWave * kRolloutWave;
+    const int64_t waves = (n + per_wave - 1) / per_wave;
+    return ConnectLaunchShape{per_wave,
+                              waves,
+                              (unsigned)((waves + kRolloutWavesPerBlock - 1) / kRolloutWavesPerBlock),
+                              (size_t)kRolloutWavesPerBlock * (size_t)(per_wave / 16) * sizeof(uint32_t),
+                              (size_t)kRolloutWavesPerBlock * (size_t)per_wave,
+                              (size_t)kRolloutWavesPerBlock * 2 * (size_t)per_wave};
+}
+
+// Which boards the one-word nibble rollouts (K2a, K2o) take, and which calls on them go to K2o, the kernel with the
+// lock-step opening stage: from the initial state, no ply cap that can bind, the opening not switched off
+// (rollout_opening = 0), a geometry on which nobody can win and no column can fill within the first four plies (H >= 4,
+// K >= 3, W >= 2), at most 48 cells (a game is at most 12 blocks of four plies, whose words three philox calls give), and a
+// chunk whose outcome bytes fit in LDS.  connect_opened_blocks: how many blocks that opening plays in lock step -- plies
+// 4 and 5 are cheap only with K >= 4 and H >= 6, else the opening is one block; a setting past 4 plays 4.
+constexpr bool connect_nibble_ok(const ConnectGeom& cg) { return cg.nw == 1 && cg.w <= 8 && cg.h <= 8; }
+constexpr bool connect_opened_ok(const ConnectGeom& cg, bool from_initial, bool capped, int rollout_opening,
+                                 const ConnectLaunchShape& shape) {
+    return connect_nibble_ok(cg) && from_initial && !capped && rollout_opening != 0 && cg.h >= 4 && cg.w >= 2 && cg.k >= 3 &&
+           cg.h * cg.w <= 48 && shape.outcome_lds <= kRolloutLdsLimit;
+}
+constexpr int connect_opened_blocks(const ConnectGeom& cg, int rollout_opening) {
+    const int blocks = cg.k >= 4 && cg.h >= 6 ? rollout_opening : 1;
+    return blocks >= 1 && blocks <= 3 ? blocks : 4;
+}
 
 // Where a four-in-a-row that is not vertical can start on a one-word board (bit(x, y) = x * (h + 1) + y): it spans four
 // columns, so its lowest cell lies in a column <= w - 4 and a row <= h - 1.  When that last start bit is below 32 the

@@ -1150,3 +1150,62 @@ def test_bounce_compile_time_geometry_equals_the_run_time_record(batch_mod, monk
         np.testing.assert_array_equal(out[0].plies[:m], orc.plies)
         for dev in out:
             dev.close()
+
+
+_SMALL_CHUNK_REFERENCE = {}
+
+
+def _small_chunk_run(batch_mod, h, w, k, contract, entry, codes):
+    """333 games in chunks of 128 through the rollout the knobs select; what they leave, as arrays."""
+    import torch
+
+    n = 333
+    dev = batch_mod.ConnectBatch(h, w, k, n)
+    dev.set_rng_contract(contract)
+    dev.set_first_game(3 << 34)
+    if entry.startswith("memory"):
+        dev.step_random(SEED ^ 77, plies=5)       # lanes then join in the middle of a block
+    cap = 17 if entry.endswith("capped") else 2**31 - 1
+    initial = entry.startswith("initial")
+    packed = torch.zeros((n + 63) // 64 * 16, dtype=torch.uint8, device="cuda")
+    if codes:
+        dev.rollout_outcomes_tensor(packed, SEED ^ 78, max_plies=cap, from_initial=initial)
+    else:
+        dev.rollout(SEED ^ 78, max_plies=cap, from_initial=initial)
+    out = {"grid": dev.grid.copy(), "winner": dev.winner.copy(), "ended": dev.has_ended.copy(), "plies": dev.plies.copy(),
+           "player": dev.player.copy(), "reward": dev.reward.copy(), "steps": dev.steps,
+           "codes": packed.cpu().numpy()[: (n + 3) // 4].copy()}
+    dev.close()
+    return out
+
+
+@pytest.mark.parametrize("contract", ["per-block", "per-ply"])
+@pytest.mark.parametrize("h,w,k", [(6, 7, 4), (6, 5, 4)], ids=["static", "runtime"])
+def test_connect_one_word_rollouts_equal_the_any_geometry_kernel_on_small_chunks(batch_mod, monkeypatch, h, w, k, contract):
+    """Every instantiation class of the block-aligned one-word rollouts against the any-geometry kernel (rollout_generic)
+    on the same seeds, bit for bit -- boards, status, rewards, env-steps and the 2-bit codes -- at the smallest shape that
+    still takes every path of a chunk: 333 games in chunks of 128 are three waves, the first two refill their pool of
+    opened boards once, the last holds 77 games and its flush takes the ragged tail.  K2o with 1 .. 4 opening blocks
+    (3 on 6x7x4 under the per-block contract is the deferred opening), with and without fused codes, on the compile-time
+    geometry and a run-time one; K2a (rollout_opening = 0, a cap, or boards from memory), capped and not."""
+    monkeypatch.setitem(knobs, "rollout_chunk", "128")
+    entries = ("initial", "initial-capped", "memory", "memory-capped")
+    for entry in entries:
+        key = (h, w, k, contract, entry)
+        if key not in _SMALL_CHUNK_REFERENCE:
+            monkeypatch.setitem(knobs, "rollout_generic", "1")
+            _SMALL_CHUNK_REFERENCE[key] = _small_chunk_run(batch_mod, h, w, k, contract, entry, codes=True)
+            monkeypatch.delitem(knobs, "rollout_generic")
+        want = _SMALL_CHUNK_REFERENCE[key]
+        assert want["steps"] > 0 and want["ended"].any()
+        for opening in ("0", "1", "2", "3", "4") if entry == "initial" else ("3",):
+            monkeypatch.setitem(knobs, "rollout_opening", opening)
+            for codes in (False, True):
+                got = _small_chunk_run(batch_mod, h, w, k, contract, entry, codes)
+                what = f"{h}x{w}x{k} {contract} {entry} opening {opening} codes {codes}"
+                for name in ("grid", "winner", "ended", "plies", "player", "reward"):
+                    np.testing.assert_array_equal(got[name], want[name], err_msg=f"{name} {what}")
+                assert got["steps"] == want["steps"], what
+                if codes:
+                    np.testing.assert_array_equal(got["codes"], want["codes"], err_msg=f"codes {what}")
+            monkeypatch.delitem(knobs, "rollout_opening")
