@@ -805,9 +805,24 @@ struct NibblePlies {
         const uint32_t col = sample_index(draw, (uint32_t)g.w());
         const uint32_t sh = col * 4u;
         const uint32_t v = (h4 >> sh) & 15u;
-        const uint32_t pos = col * stride + top - v;
+        uint32_t base = col * stride + top;
+        asm("" : "+v"(base));  // as in drop: one multiply-add and one subtract (hipcc: a multiply, a subtract and an add)
+        const uint32_t pos = base - v;
         q[j & 1u] |= 1ull << pos;
         h4 -= 1u << sh;
+    }
+    // ply 0, on the empty board: every nibble is `top`, so the stone lies at col * stride -- no nibble to extract (hipcc
+    // does not fold it: it shifts the constant h4 at run time).  Compile-time geometries only: with top, columns and stride
+    // in SGPRs the four-block run-time kernels without codes spill one SGPR more for it.
+    __device__ __forceinline__ void cheap_first(const G& g, uint32_t draw, uint64_t (&q)[2], uint32_t& h4) const {
+        if constexpr (G::STATIC_H <= 0) {
+            cheap(g, 0u, draw, q, h4);
+            return;
+        }
+        const uint32_t col = sample_index(draw, (uint32_t)g.w());
+        q[0] = 1ull << (col * stride);
+        q[1] = 0;
+        h4 = top * columns - (1u << (col * 4u));
     }
     // the outcome byte of a board that has just ended: its stones, and whether somebody holds a run (no cap: a board that
     // stopped without one is full).  Status, reward, code and env-steps follow from it when the chunk is flushed
@@ -1009,6 +1024,58 @@ constexpr bool deferred_opening() {
         return false;
 }
 
+// The three philox calls of an opening differ in counter word 2 only (the block): of round 1, p0 = M0 * c0, its low word (c3
+// of round 2) and n2 = hi(p0) ^ k1, and of round 2 p1 = M1 * n2 are the same value in all three.  PhiloxShared holds what
+// the later rounds read of them -- three VGPRs -- and philox_shared_10 is philox4x32_10 (bgs_common.h) from there on.
+struct PhiloxShared {
+    uint32_t c3;   // low word of round 1's p0
+    uint64_t p1;   // round 2's M1 * n2
+};
+__device__ __forceinline__ PhiloxShared philox_shared(uint64_t seed, uint64_t game) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * (uint32_t)game;
+    const uint32_t n2 = xor3((uint32_t)(p0 >> 32), 0u, (uint32_t)(seed >> 32));
+    PhiloxShared s;
+    s.c3 = (uint32_t)p0;
+    s.p1 = (uint64_t)0xCD9E8D57u * n2;
+    return s;
+}
+__device__ __forceinline__ Philox4 philox_shared_10(const PhiloxShared& s, uint64_t seed, uint64_t game, uint32_t block) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    // round 1: what depends on the block
+    const uint64_t q1 = (uint64_t)0xCD9E8D57u * block;
+    uint32_t c0 = xor3((uint32_t)(q1 >> 32), (uint32_t)(game >> 32), k0);
+    uint32_t c1 = (uint32_t)q1, c2, c3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+    {   // round 2: p1 is shared
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint32_t n0 = xor3((uint32_t)(s.p1 >> 32), c1, k0);
+        const uint32_t n2 = xor3((uint32_t)(p0 >> 32), s.c3, k1);
+        c1 = (uint32_t)s.p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+#pragma unroll
+    for (int r = 2; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
+        const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    Philox4 out;
+    out.v[0] = c0; out.v[1] = c1; out.v[2] = c2; out.v[3] = c3;
+    return out;
+}
+
 // all 64 lanes open 64 games into their pool slots; `mine`: the lane's game is inside the chunk (else: a dead slot)
 template <class G, class Pool>
 __device__ __forceinline__ void open_games_deferred(const G& g, Pool& pool, uint32_t slot, uint64_t seed, uint64_t id, bool mine) {
@@ -1022,7 +1089,9 @@ __device__ __forceinline__ void open_games_deferred(const G& g, Pool& pool, uint
         const uint32_t col = sample_index(draw, (uint32_t)g.w());
         const uint32_t sh = col * 4u;
         const uint32_t v = (h4 >> sh) & 15u;
-        uint32_t pos = col * stride + top - v;
+        uint32_t base = col * stride + top;
+        asm("" : "+v"(base));   // as in NibblePlies::drop: one multiply-add and one subtract
+        uint32_t pos = base - v;
         if (wrap) pos &= 63u;   // (a lane flagged before may have borrowed into the nibble above: garbage, but a defined shift)
         q[j & 1u] |= 1ull << pos;
         h4 -= 1u << sh;
@@ -1036,50 +1105,65 @@ __device__ __forceinline__ void open_games_deferred(const G& g, Pool& pool, uint
         cheap_ply(3u, sub_draw<3>(word), wrap);
         return closed;
     };
-    auto park = [&](uint32_t cols, const uint4& lo, const uint4& hi) {
+    auto park = [&](uint32_t cols) {
         pool.plane[0][slot] = q[0];
         pool.plane[1][slot] = q[1];
         pool.cols[slot] = cols;
-        pool.words[0][slot] = lo;
-        pool.words[1][slot] = hi;
     };
-    const Philox4 a = philox4x32_10(seed, id, 0u);   // the words of blocks 0 .. 3
-    cheap_ply(0u, sub_draw<0>(a.v[0]), false);
+    PhiloxShared shared = philox_shared(seed, id);
+    const Philox4 a = philox_shared_10(shared, seed, id, 0u);   // the words of blocks 0 .. 3
+    {   // ply 0, on the empty board: every nibble is `top`, the stone lies at col * stride
+        const uint32_t col = sample_index(sub_draw<0>(a.v[0]), (uint32_t)g.w());
+        q[0] = 1ull << (col * stride);
+        h4 -= 1u << (col * 4u);
+    }
     cheap_ply(1u, sub_draw<1>(a.v[0]), false);
     cheap_ply(2u, sub_draw<2>(a.v[0]), false);
     cheap_ply(3u, sub_draw<3>(a.v[0]), false);
     // The words do not stay in registers over the blind plies (the grouped kernel has none to spare): each goes to the slot
     // as soon as it is made, one philox call after the other, and a lane reads back what it parked -- LDS traffic, not VALU.
     // (The asm statements: hipcc would interleave the calls and forward the stored registers to the reads.)
-    uint32_t* const slot_words0 = reinterpret_cast<uint32_t*>(&pool.words[0][slot]);
-    uint32_t* const slot_words1 = reinterpret_cast<uint32_t*>(&pool.words[1][slot]);
+    // A slot's words are written and read in the pieces they lie in registers as -- single words where they come out of a
+    // philox call or move down by one word, 64-bit pairs where they move down by two -- so that no piece has to be put
+    // together first: for a 96- or 128-bit store of words from here and there hipcc spends a v_mov_b32 a word, and for a
+    // ds_read2 / ds_write2 past its 8-bit offsets a v_add_u32 on the address.  Hence volatile: the pieces stay pieces
+    // (and named as LDS: a volatile access through a generic pointer stays a flat one).  The LDS pipe has slack here, the
+    // VALU has none.
+    typedef volatile __attribute__((address_space(3))) uint32_t LdsWord;
+    typedef volatile __attribute__((address_space(3))) uint64_t LdsPair;
+    LdsWord* const slot_words0 = (LdsWord*)&pool.words[0][slot];
+    LdsWord* const slot_words1 = (LdsWord*)&pool.words[1][slot];
+    LdsPair* const slot_pairs0 = (LdsPair*)&pool.words[0][slot];
+    LdsPair* const slot_pairs1 = (LdsPair*)&pool.words[1][slot];
     slot_words0[0] = a.v[1]; slot_words0[1] = a.v[2]; slot_words0[2] = a.v[3];
     uint64_t id_after = id;
-    asm volatile("" : "+v"(id_after) : : "memory");
-    uint32_t word9, word10;
+    asm volatile("" : "+v"(id_after), "+v"(shared.c3), "+v"(shared.p1) : : "memory");
+    uint64_t words9_10;   // a register pair: it is parked as one 64-bit piece
     {
-        Philox4 c = philox4x32_10(seed, id_after, 2u);   // blocks 8 .. 10
+        Philox4 c = philox_shared_10(shared, seed, id_after, 2u);   // blocks 8 .. 10
         slot_words1[3] = c.v[0];
-        word9 = c.v[1];
-        word10 = c.v[2];
-        asm volatile("" : "+v"(id_after), "+v"(word9), "+v"(word10) : : "memory");
+        words9_10 = ((uint64_t)c.v[2] << 32) | c.v[1];
+        asm volatile("" : "+v"(id_after), "+v"(words9_10), "+v"(shared.c3), "+v"(shared.p1) : : "memory");
     }
     {
-        const Philox4 b = philox4x32_10(seed, id_after, 1u);   // blocks 4 .. 7
+        const Philox4 b = philox_shared_10(shared, seed, id_after, 1u);   // blocks 4 .. 7
         slot_words0[3] = b.v[0];
         slot_words1[0] = b.v[1]; slot_words1[1] = b.v[2]; slot_words1[2] = b.v[3];
     }
-    pool.plane[0][slot] = q[0];
-    pool.plane[1][slot] = q[1];
-    pool.cols[slot] = mine ? (h4 | kReplayMark) : 0u;
+    park(mine ? (h4 | kReplayMark) : 0u);
     asm volatile("" ::: "memory");
-    blind_block(slot_words0[0], false);
-    const bool closed = blind_block(slot_words0[1], false);
+    const uint64_t words1_2 = slot_pairs0[0];
+    blind_block((uint32_t)words1_2, false);
+    const bool closed = blind_block((uint32_t)(words1_2 >> 32), false);
     const uint32_t hits = four_in_a_row_low_hits(q[0], g.h()) | four_in_a_row_low_hits(q[1], g.h());
     const bool clean = mine && !closed && hits == 0u;
     if (clean) {   // words 1 .. 8 -> 3 .. 10
-        const uint4 lo = pool.words[0][slot], hi = pool.words[1][slot];
-        park(h4, make_uint4(lo.z, lo.w, hi.x, hi.y), make_uint4(hi.z, hi.w, word9, word10));
+        const uint64_t words3_4 = slot_pairs0[1], words5_6 = slot_pairs1[0], words7_8 = slot_pairs1[1];
+        park(h4);
+        slot_pairs0[0] = words3_4;
+        slot_pairs0[1] = words5_6;
+        slot_pairs1[0] = words7_8;
+        slot_pairs1[1] = words9_10;
     }
     if constexpr (kDeferredOpeningStages >= 2) {
         asm volatile("" ::: "memory");
@@ -1087,8 +1171,17 @@ __device__ __forceinline__ void open_games_deferred(const G& g, Pool& pool, uint
         const bool closed2 = blind_block(slot_words0[0], true);
         const uint32_t hits2 = four_in_a_row_low_hits(q[0], g.h()) | four_in_a_row_low_hits(q[1], g.h());
         if (clean && !closed2 && hits2 == 0u) {   // words 3 .. 10 -> 4 .. 10
-            const uint4 lo = pool.words[0][slot], hi = pool.words[1][slot];
-            park(h4, make_uint4(lo.y, lo.z, lo.w, hi.x), make_uint4(hi.y, hi.z, hi.w, 0u));
+            const uint32_t word4 = slot_words0[1];
+            const uint64_t words5_6 = slot_pairs0[1], words7_8 = slot_pairs1[0], words9_10_back = slot_pairs1[1];
+            park(h4);
+            slot_words0[0] = word4;
+            slot_words0[1] = (uint32_t)words5_6;
+            slot_words0[2] = (uint32_t)(words5_6 >> 32);
+            slot_words0[3] = (uint32_t)words7_8;
+            slot_words1[0] = (uint32_t)(words7_8 >> 32);
+            slot_words1[1] = (uint32_t)words9_10_back;
+            slot_words1[2] = (uint32_t)(words9_10_back >> 32);
+            slot_words1[3] = 0u;
         }
     }
 }
@@ -1129,7 +1222,7 @@ __device__ __forceinline__ void open_games_per_ply(const G& g, const NibblePlies
 #pragma unroll
         for (int c = 0; c < 12; ++c) words[c] = 0u;
     }
-    plies.cheap(g, 0u, opening_draw<PER_PLY, 0>(own, words[0]), q, h4);
+    plies.cheap_first(g, opening_draw<PER_PLY, 0>(own, words[0]), q, h4);
     plies.cheap(g, 1u, opening_draw<PER_PLY, 1>(own, words[0]), q, h4);
     plies.cheap(g, 2u, opening_draw<PER_PLY, 2>(own, words[0]), q, h4);
     plies.cheap(g, 3u, opening_draw<PER_PLY, 3>(own, words[0]), q, h4);
