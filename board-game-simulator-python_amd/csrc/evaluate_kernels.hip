@@ -86,11 +86,6 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
 #pragma unroll
     for (int j = 0; j < NW; ++j) p[0].w[j] = p[1].w[j] = c0.w[j] = c1.w[j] = 0;
 
-    auto count = [&](uint32_t s) {   // s: status of a finished game (0: capped, counted nowhere)
-        wins += (s != 0u && s != BGS_ST_DRAW && s - 1u == root_mover) ? 1u : 0u;
-        losses += (s != 0u && s != BGS_ST_DRAW && s - 1u != root_mover) ? 1u : 0u;
-        draws += s == BGS_ST_DRAW ? 1u : 0u;
-    };
     auto flush = [&]() {
         if (cur_seg >= 0 && (wins | draws | losses)) {
             uint32_t* t = tally + (uint32_t)(cur_seg - seg0) * 3u;
@@ -142,7 +137,7 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
                 if (child != kIllegal) {
                     stepped += 1u;   // the first move: a transition of the replicated board
                     if (child != BGS_ST_RUNNING) {
-                        count(child);
+                        wdl_count(child, root_mover, wins, draws, losses);
                     } else if (child_ply < max_plies) {
                         p[0] = c0;
                         p[1] = c1;
@@ -160,8 +155,9 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
         }
         if (!__builtin_amdgcn_ballot_w64(live != 0)) continue;
 
-        // ---- the block's draws: the strict contract's four words are one philox call a block; the default contract's
-        // call serves four blocks, so a lane makes one at a 16-ply boundary or for a new game only
+        // ---- the 4-ply block: a copy of connect_playout_block (playout.h), which the tree searches call and which says
+        // what the block is -- the same draws, the same ply code, kept equal by eye.  With the call in its place this
+        // kernel's launches came out above the parent's range in both orders (docs/EXPERIMENTS.md §41), so it keeps its text
         if (PER_PLY) {
             ph = philox4x32_10(seed, game, blk);
         } else {
@@ -196,7 +192,7 @@ k_connect_evaluate(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_
         }
         blk += 1u;
         skip = 0;
-        if (was_live && !live) count(st);
+        if (was_live && !live) wdl_count(st, root_mover, wins, draws, losses);
     }
     flush();
     __syncthreads();
@@ -373,7 +369,8 @@ k_connect_evaluate_halving(EvalGeom g, const uint64_t* __restrict__ planes, cons
             }
             if (!__builtin_amdgcn_ballot_w64(live != 0)) continue;
 
-            // ---- the 4-ply block of k_connect_evaluate: the same draws, the same ply code
+            // ---- the 4-ply block: a copy of connect_playout_block (playout.h): the same draws, the same ply code, kept
+            // equal by eye.  As in k_connect_evaluate, the call in its place was slower than the parent (EXPERIMENTS §41)
             if (PER_PLY) {
                 ph = philox4x32_10(seed, game, blk);
             } else {

@@ -3,8 +3,9 @@
 // solve unit (solve_kernels.hip: the exact solvers).  The Makefile hashes this header into the ids of all three.
 //
 // Connect: the geometry record the kernels take by value (EvalGeom), the stone drop with and without its win test, the
-// draw of a landing cell, the threat map and the ply of BGS_POLICY_DECISIVE.  Bounce: the W/D/L count,
-// the playout ply of the flat evaluation and the tree searches, and the most arms a root can have.  Last, the host's
+// draw of a landing cell, the threat map, the ply of BGS_POLICY_DECISIVE and the 4-ply playout block of the tree searches.
+// Bounce: the W/D/L count (Connect's kernels count with it too), the playout ply of the flat evaluation and the tree
+// searches, and the most arms a root can have.  Last, the host's
 // choice of instantiation, once a game.  Everything else lives with its only user (the first pass of the Bounce
 // evaluation and solver, which the search does not need: bounce_root_moves.h).
 #pragma once
@@ -163,6 +164,65 @@ __device__ __forceinline__ uint32_t decisive_position(const EvalGeom& g, const B
 #pragma unroll
     for (int j = 0; j < NW; ++j) set.w[j] = wins ? w.w[j] : (block ? b.w[j] : landing.w[j]);
     return draw_from_cells(g, set, draw);
+}
+
+// The Connect playout step of the tree searches (k_connect_search: plain, forest, proving); k_connect_evaluate and
+// k_connect_evaluate_halving play the same block from copies of their own, which say why.  The wave plays one 4-ply
+// block of every lane's game.  A lane's game is its kernel's own locals, taken by reference: the stones p[0] / p[1] of
+// player 0 / 1, the global game id, the block `blk` the game stands in, the plies of that block already on
+// the board (`skip`), the flags `live` (all ones: the lane holds a running game) and `fresh` (the game is new: ph holds
+// nothing of it), and the status st.  A lane that takes a new game at `ply` stones sets blk = ply >> 2, skip = ply & 3,
+// live = ~0u, fresh = 1 and st = 0.
+//   * The block's draws, DESIGN.md §3 ("RNG contract") at the game's absolute ply 4 * blk + j.  PER_PLY (the strict
+//     contract): word j of philox4x32_10(seed, game, blk), one call a block.  The default contract: sub-draw j of word
+//     blk & 3 of philox4x32_10(seed, game, blk >> 2) -- the call serves four blocks, so a lane makes one at a 16-ply
+//     boundary or for a new game only.
+//   * Four plies, player j & 1 to move at sub-step j; the first `skip` of a new game's block are on the board already and
+//     drop nothing.  BGS_POLICY_UNIFORM: a uniformly drawn landing cell and the win test.  BGS_POLICY_DECISIVE:
+//     decisive_position, which says itself whether its stone wins.
+//   * A game ends by a win, on the full board or at the cap of max_plies stones; `live` is then 0 and st says how (1 / 2
+//     the winner + 1, BGS_ST_DRAW, or 0 = BGS_ST_RUNNING at the cap: counted nowhere).
+// Returns "this lane's game has just finished".  What a kernel does with a finished game is all the kernels differ in
+// here, and stays in the kernel.  `stepped` grows by the plies the lane played.
+template <int NW, bool PER_PLY, int POLICY>
+__device__ __forceinline__ bool connect_playout_block(const EvalGeom& g, uint64_t seed, uint32_t max_plies, Bits<NW> (&p)[2],
+                                                      uint64_t game, uint32_t& blk, uint32_t& skip, uint32_t& live, uint32_t& st,
+                                                      uint32_t& fresh, Philox4& ph, uint32_t& stepped) {
+    if (PER_PLY) {
+        ph = philox4x32_10(seed, game, blk);
+    } else {
+        const bool want = live && (fresh || (blk & 3u) == 0u);
+        if (__builtin_amdgcn_ballot_w64(want)) {
+            if (want) ph = philox4x32_10(seed, game, blk >> 2);
+        }
+    }
+    fresh = 0;
+    const uint32_t word = PER_PLY ? 0u : philox_word(ph, blk);
+    const uint32_t was_live = live;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        const uint32_t draw = PER_PLY ? ph.v[j] : sub_draw(word, j);
+        const uint32_t act = j >= skip ? live : 0u;
+        const uint32_t ply = 4u * blk + j;          // stones before this sub-step; its mover is player j & 1
+        bool won;
+        if constexpr (POLICY == BGS_POLICY_DECISIVE) {
+            const uint32_t pos = decisive_position(g, p[j & 1u], p[(j & 1u) ^ 1u], draw, won);
+            drop(p[j & 1u], pos, act);
+            won = won && act;
+        } else {
+            const uint32_t pos = draw_position(g, p[0] | p[1], draw);
+            won = drop_and_test(g, p[j & 1u], pos, act);
+        }
+        const bool full = ply + 1u == g.cells_total;
+        if (act) {
+            st = won ? (j & 1u) + 1u : (full ? BGS_ST_DRAW : BGS_ST_RUNNING);
+            live = (won || full || ply + 1u >= max_plies) ? 0u : live;
+            stepped += 1u;
+        }
+    }
+    blk += 1u;
+    skip = 0;
+    return was_live && !live;
 }
 
 // ---- Bounce

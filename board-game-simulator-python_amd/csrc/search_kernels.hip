@@ -303,46 +303,8 @@ k_connect_search(EvalGeom g, const uint64_t* __restrict__ planes, const uint8_t*
                     taken = leaf_playouts - taken < wanted ? leaf_playouts : taken + wanted;
                 }
 
-                // ---- the 4-ply block of k_connect_evaluate: the same draws, the same ply code
-                if (PER_PLY) {
-                    ph = philox4x32_10(seed, game, blk);
-                } else {
-                    const bool want = live && (fresh || (blk & 3u) == 0u);
-                    if (__builtin_amdgcn_ballot_w64(want)) {
-                        if (want) ph = philox4x32_10(seed, game, blk >> 2);
-                    }
-                }
-                fresh = 0;
-                const uint32_t word = PER_PLY ? 0u : philox_word(ph, blk);
-                const uint32_t was_live = live;
-#pragma unroll
-                for (uint32_t j = 0; j < 4; ++j) {
-                    const uint32_t draw = PER_PLY ? ph.v[j] : sub_draw(word, j);
-                    const uint32_t act = j >= skip ? live : 0u;
-                    const uint32_t at = 4u * blk + j;          // stones before this sub-step; its mover is player j & 1
-                    bool won;
-                    if constexpr (POLICY == BGS_POLICY_DECISIVE) {
-                        const uint32_t pos = decisive_position(g, q[j & 1u], q[(j & 1u) ^ 1u], draw, won);
-                        drop(q[j & 1u], pos, act);
-                        won = won && act;
-                    } else {
-                        const uint32_t pos = draw_position(g, q[0] | q[1], draw);
-                        won = drop_and_test(g, q[j & 1u], pos, act);
-                    }
-                    const bool full = at + 1u == g.cells_total;
-                    if (act) {
-                        st = won ? (j & 1u) + 1u : (full ? BGS_ST_DRAW : BGS_ST_RUNNING);
-                        live = (won || full || at + 1u >= max_plies) ? 0u : live;
-                        played += 1u;
-                    }
-                }
-                blk += 1u;
-                skip = 0;
-                if (was_live && !live) {      // (st == 0: capped, counted nowhere)
-                    wins += (st != 0u && st != BGS_ST_DRAW && st - 1u == root_mover) ? 1u : 0u;
-                    losses += (st != 0u && st != BGS_ST_DRAW && st - 1u != root_mover) ? 1u : 0u;
-                    draws += st == BGS_ST_DRAW ? 1u : 0u;
-                }
+                const bool ended = connect_playout_block<NW, PER_PLY, POLICY>(g, seed, max_plies, q, game, blk, skip, live, st, fresh, ph, played);
+                if (ended) wdl_count(st, root_mover, wins, draws, losses);
             }
         }
         stepped += played;

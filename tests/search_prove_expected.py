@@ -223,6 +223,14 @@ def end_game_roots_6x7x4():
     return fc.take(layer, rows)
 
 
+@functools.lru_cache(maxsize=None)
+def spread_roots_12x13x5():
+    """12 x 13 x 5, three words: every third root of tests/search_expected.py's mix, eight running boards -- four in the
+    opening (2, 4, 5 and 18 stones: three of them inside a 4-ply block) and four a few plies before the board is full"""
+    mixed = se._case_roots(12, 13, 5)
+    return fc.take(mixed, np.arange(1, mixed[0].shape[0], 3))
+
+
 # ---- the cases of the GPU comparison: cases of tests/search_expected.py on its root mix, and the hand-made roots
 Case = namedtuple("Case", "name h w k iterations playouts explore cap first_game roots")
 BASE = (9, 8, 0, 1, 2, 10, 11)      # of search_expected.CASES: 2x5x3, 5x6x3, 6x7x4 (48 x 16, 200 x 1, 12 x 70 capped), 6x12x4, 12x13x5
@@ -232,11 +240,13 @@ CASES = tuple(Case(se.case_id(c), c.h, c.w, c.k, c.iterations, c.playouts, c.exp
     Case("hand-2x2x3-T24-P2", 2, 2, 3, 24, 2, 65536, None, 0, hand_roots_2x2x3),
     Case("hand-1x1x1-T4-P3", 1, 1, 1, 4, 3, 65536, None, 0, hand_roots_1x1x1),
     Case("ends-6x7x4-T96-P4", 6, 7, 4, 96, 4, 65536, None, 11, end_game_roots_6x7x4),
+    Case("spread-12x13x5-T16-P8-capped", 12, 13, 5, 16, 8, 65536, 12, 3, spread_roots_12x13x5),   # the cap cuts the opening roots' games
 )
 DECISIVE = (1, 2)                   # the cases that run under the decisive policy too: 5x6x3 and 6x7x4 48 x 16
 PER_PLY = (1,)                      # ... under the per-ply RNG contract too
+PER_PLY_BOTH = (11,)                # ... under the per-ply contract in both policies: the three-word spread
 RUNS = ([(j, "uniform", False) for j in range(len(CASES))] + [(j, "decisive", False) for j in DECISIVE]
-        + [(j, "uniform", True) for j in PER_PLY])
+        + [(j, "uniform", True) for j in PER_PLY] + [(j, policy, True) for j in PER_PLY_BOTH for policy in ("uniform", "decisive")])
 SOLVED_EMPTY = 12                   # roots with at most this many empty cells are checked against the exact solvers
 
 

@@ -12,7 +12,8 @@ Per variant: the launch time (median over the rounds, and the rounds' least and 
 (counted on the device, first moves included), env-steps/s, and the mean plies a playout (env-steps over the playouts
 played: halving, the sum of `given`).
 
-    python tools/evaluate_halving_rate.py [--rounds R] [--reps K] [--policy uniform] [--out profiles/evaluate_halving_rate.json]
+    python tools/evaluate_halving_rate.py [--rounds R] [--reps K] [--policy uniform] [--geometry H W K] [--out profiles/evaluate_halving_rate.json]
+--geometry H W K: that board at 4096 roots in place of the case list (a two-word board, say: 6 12 4).
 Prints one JSON object (and writes it to --out)."""
 import argparse
 import json
@@ -97,11 +98,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--policy", default="uniform", choices=("uniform", "decisive"))
+    ap.add_argument("--geometry", type=int, nargs=3, metavar=("H", "W", "K"))
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    cases = [(tuple(args.geometry), 4096)] if args.geometry else CASES
     res = {"tool": "tools/evaluate_halving_rate.py", "device": torch.cuda.get_device_name(0), "build_id": _abi.build_id(),
            "unit_ids": {**_abi.unit_ids(), **_abi.extra_unit_ids()}, "rounds": args.rounds, "reps": args.reps, "policy": args.policy,
-           "cases": [case(g, n, args.policy, args.rounds, args.reps) for g, n in CASES]}
+           "cases": [case(g, n, args.policy, args.rounds, args.reps) for g, n in cases]}
     text = json.dumps(res, indent=1)
     print(text)
     if args.out:

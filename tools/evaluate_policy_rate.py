@@ -13,7 +13,8 @@ env-steps of one launch (counted on the device, first moves included), env-steps
 over the playouts that start: legal columns of running roots x playouts).  A library without the policy entry point (the
 parent commit's, for the same-day comparison) gives uniform_old alone.
 
-    python tools/evaluate_policy_rate.py [--rounds R] [--reps K] [--out FILE]
+    python tools/evaluate_policy_rate.py [--rounds R] [--reps K] [--geometry H W K] [--out FILE]
+--geometry H W K: that board at 4096 roots x 256 playouts in place of the two shapes (a two-word board, say: 6 12 4).
 Prints one JSON object (and writes it to --out)."""
 import argparse
 import ctypes
@@ -114,12 +115,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=4)
+    ap.add_argument("--geometry", type=int, nargs=3, metavar=("H", "W", "K"))
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    cases = [(tuple(args.geometry), 4096, 256)] if args.geometry else CASES
     calls = variants(_abi.lib())
     res = {"tool": "tools/evaluate_policy_rate.py", "device": torch.cuda.get_device_name(0), "build_id": _abi.build_id(),
            "unit_ids": {**_abi.unit_ids(), **_abi.extra_unit_ids()}, "rounds": args.rounds, "reps": args.reps,
-           "variants": list(calls), "cases": [case(g, n, p, args.rounds, args.reps, calls) for g, n, p in CASES]}
+           "variants": list(calls), "cases": [case(g, n, p, args.rounds, args.reps, calls) for g, n, p in cases]}
     text = json.dumps(res, indent=1)
     print(text)
     if args.out:
