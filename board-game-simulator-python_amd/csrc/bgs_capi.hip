@@ -1608,6 +1608,65 @@ int bgs_bounce_forest_advance(bgs_batch* b, const int32_t* slots, int32_t nodes_
     });
 }
 
+// the checks of both Bounce guided entry points that need no device; *bytes: the trees of the batch
+static int bounce_guided_check(const bgs_batch* b, int32_t nodes_cap, int32_t edges, size_t* bytes) {
+    NEED(b->game == BGS_GAME_BOUNCE, "bounce_guided: Bounce batches only (Connect boards: bgs_connect_guided_step)");
+    NEED(!b->generic, "bounce_guided: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
+         BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
+    NEED(nodes_cap >= 2 && nodes_cap <= BGS_BOUNCE_FOREST_MAX_NODES, "nodes_cap must be 2 .. %d nodes a tree (got %d)",
+         BGS_BOUNCE_FOREST_MAX_NODES, nodes_cap);
+    const int32_t least = BGS_BOUNCE_SEARCH_MIN_EDGES(b->bg.h, b->bg.w);
+    NEED(edges >= least && edges <= BGS_BOUNCE_FOREST_MAX_EDGES,
+         "edges must be BGS_BOUNCE_SEARCH_MIN_EDGES(%d, %d) = %d, the most arms a position can have, .. %d (got %d)", b->bg.h, b->bg.w,
+         least, BGS_BOUNCE_FOREST_MAX_EDGES, edges);
+    const uint64_t tree = bgs::bounce_guided_tree_bytes(nodes_cap, edges);
+    NEED((uint64_t)b->n <= (uint64_t)(SIZE_MAX / 2) / tree, "the trees of %lld boards x %d nodes x %d edges overflow size_t",
+         (long long)b->n, nodes_cap, edges);
+    *bytes = (size_t)((uint64_t)b->n * tree);
+    return BGS_OK;
+}
+
+int bgs_bounce_guided_bytes(const bgs_batch* b, int32_t nodes, int32_t edges, size_t* bytes) {
+    NEED(b != nullptr, "batch is NULL");
+    NEED(bytes != nullptr, "bytes is NULL");
+    return bounce_guided_check(b, nodes, edges, bytes);
+}
+
+int bgs_bounce_guided_step(bgs_batch* b, int32_t nodes_cap, int32_t edges, int32_t cpuct, int32_t max_plies, uint32_t flags,
+                           const float* priors, const float* values, int8_t* leaf_grid, int8_t* leaf_player, int32_t* leaf_kind,
+                           uint64_t* leaf_targets, int32_t* visits, int32_t* scores, int32_t* best, int32_t* nodes, int32_t* used,
+                           void* trees, size_t trees_bytes) {
+    int rc = enter(b);
+    if (rc) return rc;
+    size_t need = 0;
+    rc = bounce_guided_check(b, nodes_cap, edges, &need);
+    if (rc) return rc;
+    NEED(cpuct >= 0 && cpuct <= 4096, "cpuct must be 0 .. 4096, c_puct in Q8 (got %d)", cpuct);
+    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
+    NEED((flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH)) == 0u, "unknown flag bits 0x%x (BGS_GUIDED_RESTART 0x%x, BGS_GUIDED_FINISH 0x%x)",
+         flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH), BGS_GUIDED_RESTART, BGS_GUIDED_FINISH);
+    NEED((flags & BGS_GUIDED_RESTART) == 0u || (flags & BGS_GUIDED_FINISH) == 0u,
+         "BGS_GUIDED_RESTART with BGS_GUIDED_FINISH: a restarted tree has nothing to finish");
+    NEED(trees != nullptr, "trees is NULL (the caller owns them; bgs_bounce_guided_bytes says how large)");
+    NEED(leaf_grid != nullptr, "leaf_grid is NULL");
+    NEED(leaf_player != nullptr, "leaf_player is NULL");
+    NEED(leaf_kind != nullptr, "leaf_kind is NULL");
+    NEED((flags & BGS_GUIDED_RESTART) != 0u || priors != nullptr, "priors is NULL (allowed with BGS_GUIDED_RESTART only)");
+    NEED((flags & BGS_GUIDED_RESTART) != 0u || values != nullptr, "values is NULL (allowed with BGS_GUIDED_RESTART only)");
+    NEED((reinterpret_cast<uintptr_t>(trees) & 255u) == 0, "trees must be 256-byte aligned");
+    const struct {
+        const char* name;
+        const void* ptr;
+    } rest[] = {{"priors", priors}, {"values", values}, {"leaf_grid", leaf_grid}, {"leaf_player", leaf_player},
+                {"leaf_kind", leaf_kind}, {"leaf_targets", leaf_targets}, {"visits", visits}, {"scores", scores},
+                {"best", best}, {"nodes", nodes}, {"used", used}};
+    for (const auto& p : rest) NEED((reinterpret_cast<uintptr_t>(p.ptr) & 15u) == 0, "device %s must be 16-byte aligned", p.name);
+    NEED(trees_bytes >= need, "the trees are too small: %zu bytes, %zu needed", trees_bytes, need);
+    bgs::bounce_guided_step(b, nodes_cap, edges, cpuct, max_plies, flags, priors, values, leaf_grid, leaf_player, leaf_kind, leaf_targets,
+                            visits, scores, best, nodes, used, trees);
+    return finish_launch();
+}
+
 int bgs_bounce_solve_moves(bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* codes, int16_t* plies, uint64_t* nodes,
                            int on_device) {
     int rc = enter(b);

@@ -198,6 +198,16 @@ void bounce_forest_search(const bgs_batch* b, uint64_t seed, int32_t iterations,
                           int32_t max_plies, int policy, int32_t capacity, int32_t edges, int restart, int32_t* d_counts,
                           int32_t* d_visits, int32_t* d_best, int32_t* d_nodes, int32_t* d_used, int32_t* d_carried, void* d_forest);
 void bounce_forest_advance(const bgs_batch* b, const int32_t* d_slots, int32_t capacity, int32_t edges, int32_t* d_kept, void* d_forest);
+// one simulation of the PUCT search whose leaves the caller evaluates, over packed Bounce boards (bgs_bounce_guided_step):
+// d_trees holds n * bounce_guided_tree_bytes(capacity, edges) bytes, 256-byte aligned; d_priors float[n][w * h * w] and
+// d_values float[n] are read for trees with a pending EVALUATE leaf only; d_leaf_targets uint64[n][w], d_visits and
+// d_scores int32[n][w * h * w] (the kernel zeroes the illegal slots), d_best, d_nodes and d_used int32[n] may be NULL; every pointer is a device
+// pointer; enqueued on the batch's stream, the boards are not touched
+uint64_t bounce_guided_tree_bytes(int32_t capacity, int32_t edges);
+void bounce_guided_step(const bgs_batch* b, int32_t capacity, int32_t edges, int32_t cpuct, int32_t max_plies, uint32_t flags,
+                        const float* d_priors, const float* d_values, int8_t* d_leaf_grid, int8_t* d_leaf_player, int32_t* d_leaf_kind,
+                        uint64_t* d_leaf_targets, int32_t* d_visits, int32_t* d_scores, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
+                        void* d_trees);
 // exact horizon search of every legal move of packed Bounce boards (bgs_bounce_solve_moves; solve_kernels.hip): codes int8[n][w][h * w] and
 // plies int16[n][w][h * w] (may be NULL) are filled here (illegal slots NONE / 0), *d_nodes = positions visited; scratch
 // as bounce_evaluate; depth 1 .. BGS_BOUNCE_SOLVE_MAX_DEPTH; device pointers, enqueued on the batch's stream

@@ -3,8 +3,8 @@
 // first half of this file, Bounce (bgs_bounce_search_moves and its forest and proving forms) in the second.  A search is
 // one kernel a game, k_connect_search / k_bounce_search; the forest and the proving search are template parameters of it
 // (FOREST, PROVE), and the re-rooting of a forest is a kernel of its own.  The PUCT search whose leaves the caller
-// evaluates (bgs_connect_guided_step, k_connect_search_guided) follows the Connect forest.  The section comments below
-// describe each.
+// evaluates (bgs_connect_guided_step, k_connect_search_guided) follows the Connect forest, and its Bounce sibling
+// (bgs_bounce_guided_step, k_bounce_search_guided) the Bounce forest.  The section comments below describe each.
 //
 // A unit of its own (bgs_kernel_unit_id(4)).  The leaves' playouts are the evaluation unit's (evaluate_kernels.hip): the
 // Connect 4-ply block is written out in k_connect_search, the Bounce ply is bounce_playout_ply of playout.h, which also
@@ -1715,7 +1715,421 @@ k_bounce_forest_advance(uint32_t height, uint32_t width, const int32_t* __restri
     }
 }
 
+// ================================================================================================================
+// PUCT tree search for Bounce with caller-evaluated leaves (bgs_bounce_guided_step, include/bgs.h): one launch is one
+// simulation of every tree, as k_connect_search_guided -- the caller's (priors, value) of the pending leaf go into the
+// tree, the root's statistics come out, a descent finds the next leaf -- over k_bounce_search's tree: an edge pool, a node
+// table, arms that are generated once (movable, reach) and replayed, the ended and capped sentinels.
+//
+// Shape: one wave a tree.  Lanes stride a node's arms, at most kGuidedLaneArms = 8 a lane; N and the selection key go
+// through wave_sum and wave_max64 (the key is (U << 9 | 511 - arm) + 1 with U < 2^25 + 4097: 64 bits).  A step is a short
+// chain of dependent loads a level, and a launch has thousands of trees: a wave a tree keeps four times the trees of a
+// 256-lane team resident on a CU (docs/EXPERIMENTS.md §42).  LDS holds the 8 * NC target words of the position whose arms
+// are being numbered, and nothing else.
+//
+// A tree's share, in 32-bit words, rounded up to 256 bytes:
+//     word 0         the nodes in use, the root counted (0: an emptied tree)
+//     word 1         the pool edges in use
+//     word 2         the absolute ply count of the position the root stands for
+//     word 3         the effective cap (min(max_plies, 65535)) the tree's kEdgeCapped sentinels were written under
+//     words 4 .. 11  the position the root stands for: the four 64-bit planes of the batch
+//     word 12        the pending leaf's kind (kGuidedNone, kGuidedEvaluate, kGuidedWon, kGuidedFull: sigma 1024, a draw or the cap)
+//     word 13        the edges of the pending path
+//     word 14        1 once the root's arms have their P
+//     word 15        the ply count of an EVALUATE leaf
+//     words 16 .. 23 the four planes of an EVALUATE leaf: the application makes its arms again from them
+//     words 32 ..    the E edges, four words each: n, s, child or sentinel (k_bounce_search's), P << 14 | source cell << 8 |
+//                    target cell (P <= 65536 takes 17 bits, the move 14)
+//     then           the C node-table entries (first edge, arms)
+//     then           the C words of the pending path, edge indices: a descent leaves every node at most once
+// Every word read back from the share is used only within its bounds: a path no longer than C, an edge below the edges
+// in use, a child below the nodes in use, a node's block inside the edges in use, a slot below S.  Memory that passes the
+// check by accident gives a wrong tree, never a store outside its own share or its own output rows.
+//
+// Ordering, all inside the one-wave workgroup.  Writers and readers of the tree:
+//   the emptying (strided lanes write the root's arms, lane 0 the table entry) and the application (strided lanes write a
+//   new node's arms or the root's P, lane 0 the table entry and the parent's child word, lane k edge k of the path)
+//     -- barrier (T) --
+//   the report (strided lanes read the root's arms) and the descent (strided lanes read a node's arms, every lane the
+//   table entry and the chosen edge).  The descent writes only an edge's sentinel and the path, which nothing of this
+//   launch reads afterwards; the header goes last, by lane 0, and is read by the next launch.
+// Writers of a row of visits and scores: the lanes zero every slot, strided, and behind barrier (Z) the lanes that hold
+// the root's arms store theirs.  (A memset by the entry point in front of the launch was two more enqueues a step: with
+// them a step of 64 trees took 22.9 us, docs/EXPERIMENTS.md §42.)
+// Writers and readers of node_targets: lane x writes word x, every lane reads every word; put() has a barrier on either
+// side of its store.
+// ================================================================================================================
+constexpr uint32_t kBounceGuidedHeaderWords = 32;
+constexpr uint32_t kGuidedMoveBits = 14, kGuidedMoveMask = (1u << kGuidedMoveBits) - 1u;
+constexpr uint32_t kGuidedLaneArms = kBounceHalvingMaxArms / BGS_WAVE;
+static_assert(kGuidedLaneArms * BGS_WAVE == kBounceHalvingMaxArms, "the lanes of a wave hold every arm of a node");
+static_assert((65536ull << kGuidedMoveBits) + kGuidedMoveMask < (1ull << 32), "P and the move share a word");
+static_assert((((uint64_t)BGS_GUIDED_MAX_VISITS + 1u) << 41) < (1ull << 63), "the key of `best` holds n above s above the arm");
+
+// words of a tree's share: the header, the pool, the node table and the path, rounded up to 256 bytes (below 2^32)
+__host__ __device__ __forceinline__ uint64_t bounce_guided_tree_words(uint32_t capacity, uint32_t edges) {
+    return (kBounceGuidedHeaderWords + (uint64_t)edges * kEdgeWords + (uint64_t)capacity * 3u + 63u) & ~(uint64_t)63u;
+}
+
+__device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, off, BGS_WAVE);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+template <class GEO, int NC>
+__global__ void __launch_bounds__(BGS_WAVE)
+k_bounce_search_guided(GEO g, const uint64_t* __restrict__ planes, const uint8_t* __restrict__ status, const uint16_t* __restrict__ plies_buf,
+                       int64_t n, int64_t root_base, uint32_t capacity, uint32_t edges, uint32_t cpuct, uint32_t cap, uint32_t flags,
+                       const float* __restrict__ priors, const float* __restrict__ values, int8_t* __restrict__ leaf_grid,
+                       int8_t* __restrict__ leaf_player, int32_t* __restrict__ leaf_kind, uint64_t* __restrict__ leaf_targets,
+                       int32_t* __restrict__ visits, int32_t* __restrict__ scores, int32_t* __restrict__ best, int32_t* __restrict__ nodes,
+                       int32_t* __restrict__ used_out, uint32_t* trees) {
+    __shared__ uint64_t node_targets[8 * NC];                      // targets of the piece in column x of the active row
+    const uint32_t lane = threadIdx.x;
+    const uint32_t width = (uint32_t)g.w, hw = (uint32_t)(g.h * g.w), slots = width * hw;
+    const int64_t i = root_base + (int64_t)blockIdx.x;             // (the grid holds exactly the trees of this launch)
+    uint32_t* const head = trees + (uint64_t)i * bounce_guided_tree_words(capacity, edges);
+    uint64_t* const head_planes = reinterpret_cast<uint64_t*>(head + 4);
+    uint64_t* const leaf_planes = reinterpret_cast<uint64_t*>(head + 16);
+    uint32_t* const pool = head + kBounceGuidedHeaderWords;
+    uint32_t* const node_tab = pool + (uint64_t)edges * kEdgeWords;             // node v: first edge, arms
+    uint32_t* const path = node_tab + (uint64_t)capacity * 2u;                  // edge k of the pending descent
+    const auto uniform = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+
+    // lane x: the targets of `player`'s piece in column x of its active row on `bd`; base: the cell of column 0 of that row
+    const auto spread = [&](const Board& bd, uint64_t occ, uint32_t player, bool live, uint32_t& base) {
+        const uint64_t sources = live ? movable(g, occ, player) : 0ull;
+        const uint32_t first_source = sources ? (uint32_t)(__ffsll((unsigned long long)sources) - 1) : 0u;
+        base = ((first_source * g.inv_w) >> 16) * (uint32_t)g.w;
+        const bool piece = lane < width && ((sources >> ((base + lane) & 63u)) & 1ull);
+        return piece ? reach(g, bd, occ, player, (int)(base + lane)) : 0ull;
+    };
+    // the lanes' masks into node_targets, for arm_move; returns the arms (uniform)
+    const auto put = [&](uint64_t mask) {
+        __syncthreads();
+        if (lane < 8 * NC) node_targets[lane] = mask;
+        __syncthreads();
+        return uniform(wave_sum((uint32_t)__popcll(mask)));
+    };
+    // arm a (canonical order, a < the arms put) of the position in node_targets: its move word and its slot
+    const auto arm_move = [&](uint32_t a, uint32_t base, uint32_t& slot) {
+        uint32_t j = a, x = 0;
+        for (; x < 8 * NC - 1; ++x) {
+            const uint32_t cnt = (uint32_t)__popcll(node_targets[x]);
+            if (j < cnt) break;
+            j -= cnt;
+        }
+        const uint32_t cell = select_bit64(node_targets[x], j);
+        slot = x * hw + cell;
+        return ((base + x) << 8) | cell;
+    };
+
+    // ---- the root: its arms say whether there is anything to search (an ended root and one that holds the most plies a
+    // board can have none, as in k_bounce_search)
+    const Board root = load_board(planes, n, i);
+    const uint32_t rply = plies_buf[i];
+    uint32_t root_cell = 0;
+    const uint64_t root_mask = spread(root, occupancy(root), rply & 1u, status[i] == BGS_ST_RUNNING && rply < kBounceMaxPlies, root_cell);
+    uint32_t root_arms = put(root_mask);
+    root_arms = root_arms <= edges ? root_arms : 0u;               // (never: E >= BGS_BOUNCE_SEARCH_MIN_EDGES)
+
+    // ---- 1. the check (wave-uniform: every lane reads the same header); a tree that fails it is emptied
+    uint32_t count = uniform(head[0]), used = uniform(head[1]), kind = uniform(head[12]), depth = uniform(head[13]);
+    uint32_t expanded = uniform(head[14]);
+    bool live = (flags & BGS_GUIDED_RESTART) == 0u && root_arms != 0u && count >= 1u && count <= capacity && used >= root_arms &&
+                used <= edges && head[2] == rply && head[3] == cap;
+    if (live) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) live = live && head_planes[j] == root.v[j];
+    }
+    live = uniform(live ? 1u : 0u) != 0u;
+    if (!live) {                        // node 0 and its arms, no P yet; board i recorded
+        kind = kGuidedNone;
+        depth = 0;
+        expanded = 0;
+        count = root_arms ? 1u : 0u;
+        used = root_arms;
+        for (uint32_t a = lane; a < root_arms; a += BGS_WAVE) {
+            uint32_t slot;
+            const uint32_t move = arm_move(a, root_cell, slot);
+            *reinterpret_cast<uint4*>(pool + (uint64_t)a * kEdgeWords) = make_uint4(0u, 0u, 0u, move);
+        }
+        if (root_arms != 0u && lane == 0) {
+            node_tab[0] = 0u;
+            node_tab[1] = root_arms;
+            head[2] = rply;
+            head[3] = cap;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) head_planes[j] = root.v[j];
+        }
+    }
+    depth = depth < capacity ? depth : capacity;
+
+    // ---- 2. the application of the pending evaluation
+    if (kind != kGuidedNone) {
+        uint32_t sigma = kind == kGuidedWon ? 0u : 1024u;         // the leaf's value for its mover, 0 .. 2048
+        if (kind == kGuidedEvaluate) {
+            const float x = values[i];
+            int32_t v = 0;
+            if (x == x) v = (int32_t)(fminf(fmaxf(x, -1.0f), 1.0f) * 1024.0f);
+            sigma = (uint32_t)(1024 + v);
+            // the leaf's arms again: the root's are in node_targets, any other leaf's come from its recorded planes
+            uint32_t arms = root_arms, base = root_cell;
+            if (depth != 0u) {
+                Board lp;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) lp.v[j] = leaf_planes[j];
+                arms = put(spread(lp, occupancy(lp), head[15] & 1u, true, base));
+                arms = arms < kBounceHalvingMaxArms ? arms : kBounceHalvingMaxArms;
+            }
+            // the priors of the leaf's arms, arm lane + 64 k by lane: 16-bit weights, then 16-bit shares
+            uint32_t move[kGuidedLaneArms], weight[kGuidedLaneArms], sum = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < kGuidedLaneArms; ++k) {
+                const uint32_t a = lane + k * BGS_WAVE;
+                move[k] = weight[k] = 0;
+                if (k * BGS_WAVE < arms && a < arms) {
+                    uint32_t slot;
+                    move[k] = arm_move(a, base, slot);
+                    const float pr = priors[i * (int64_t)slots + slot];
+                    if (pr > 0.0f) weight[k] = (uint32_t)(fminf(pr, 1.0f) * 65536.0f);
+                    sum += weight[k];
+                }
+            }
+            sum = uniform(wave_sum(sum));
+            const bool flat = sum == 0u;                           // no weight on a legal slot: equal shares
+            sum = flat ? arms : sum;
+            uint32_t first = 0;
+            bool place = false, fresh = false;
+            if (depth == 0u) {                                     // the root is the leaf: it only receives P
+                place = true;
+                expanded = 1u;
+            } else {            // a node is made if the edge has no child, the table has room and the pool has the arms
+                const uint32_t e = uniform(path[depth - 1u]);
+                const uint32_t child = e < used ? uniform(pool[(uint64_t)e * kEdgeWords + 2u]) : 1u;
+                if (child == 0u && arms != 0u && count < capacity && used + arms <= edges) {
+                    place = fresh = true;
+                    first = used;
+                    if (lane == 0) {
+                        node_tab[2u * count] = used;
+                        node_tab[2u * count + 1u] = arms;
+                        pool[(uint64_t)e * kEdgeWords + 2u] = count;
+                    }
+                    count += 1u;
+                    used += arms;
+                }
+            }
+            if (place) {
+#pragma unroll
+                for (uint32_t k = 0; k < kGuidedLaneArms; ++k) {
+                    const uint32_t a = lane + k * BGS_WAVE;
+                    if (k * BGS_WAVE < arms && a < arms) {
+                        const uint32_t share = guided_quotient((uint64_t)(flat ? 1u : weight[k]) << 16, sum);
+                        const uint32_t word = (share << kGuidedMoveBits) | move[k];
+                        uint32_t* const edge = pool + (uint64_t)(first + a) * kEdgeWords;
+                        if (fresh) *reinterpret_cast<uint4*>(edge) = make_uint4(0u, 0u, 0u, word);
+                        else edge[3] = word;
+                    }
+                }
+            }
+        }
+        // lane k takes edge k of the path: node k's mover is the leaf's when depth - k is even
+        for (uint32_t k = lane; k < depth; k += BGS_WAVE) {
+            const uint32_t e = path[k];
+            if (e < used) {
+                uint32_t* const edge = pool + (uint64_t)e * kEdgeWords;
+                edge[0] += 1u;
+                edge[1] += ((depth - k) & 1u) ? 2048u - sigma : sigma;
+            }
+        }
+        kind = kGuidedNone;
+        depth = 0;
+    }
+    __syncthreads();                // (T) the tree is whole: the report and the descent read what other lanes wrote
+
+    // ---- 3. the report: every slot of the row is zeroed, coalesced, and behind barrier (Z) the lanes that hold the root's
+    // arms store theirs -- a slot has two writers, and the barrier stands between them; the root's block starts at edge 0
+    const auto slot_of = [&](uint32_t word) { return (((word & kGuidedMoveMask) >> 8) - root_cell) * hw + (word & 255u); };
+    for (uint32_t s = lane; s < slots; s += BGS_WAVE) {
+        if (visits) visits[i * (int64_t)slots + s] = 0;
+        if (scores) scores[i * (int64_t)slots + s] = 0;
+    }
+    __syncthreads();                // (Z)
+    uint32_t root_total = 0;
+    {
+        uint64_t key = 0;           // n << 41 | s << 9 | 511 - arm: the most visits, then the larger s, then the lower slot
+        if (count != 0u) {
+            for (uint32_t a = lane; a < root_arms; a += BGS_WAVE) {
+                const uint4 edge = *reinterpret_cast<const uint4*>(pool + (uint64_t)a * kEdgeWords);
+                const uint32_t slot = slot_of(edge.w);
+                if (slot < slots) {
+                    if (visits) visits[i * (int64_t)slots + slot] = (int32_t)edge.x;
+                    if (scores) scores[i * (int64_t)slots + slot] = (int32_t)edge.y;
+                }
+                root_total += edge.x;
+                const uint64_t mine = ((uint64_t)edge.x << 41) | ((uint64_t)edge.y << 9) | (uint64_t)(511u - a);
+                key = (edge.x != 0u && mine > key) ? mine : key;
+            }
+        }
+        key = wave_max64(key);
+        root_total = uniform(wave_sum(root_total));
+        if (lane == 0) {
+            if (best) best[i] = key ? (int32_t)slot_of(pool[(uint64_t)(511u - ((uint32_t)key & 511u)) * kEdgeWords + 3u]) : -1;
+            if (nodes) nodes[i] = (int32_t)(count ? count - 1u : 0u);
+            if (used_out) used_out[i] = (int32_t)used;
+        }
+    }
+
+    // ---- 4. the selection (wave-uniform): p is the position at node v, and the leaf's at the end
+    Board p = root;
+    uint32_t ply = rply, out_kind = (uint32_t)BGS_GUIDED_IDLE;
+    uint64_t leaf_mask = 0;             // lane x: the targets of the piece in column x of an EVALUATE leaf's active row
+    if (count != 0u && (flags & BGS_GUIDED_FINISH) == 0u && root_total < (uint32_t)BGS_GUIDED_MAX_VISITS) {
+        if (expanded == 0u) {                                          // an unexpanded root is itself the leaf
+            leaf_mask = root_mask;
+            kind = kGuidedEvaluate;
+            out_kind = (uint32_t)BGS_GUIDED_EVALUATE;
+        } else {
+            uint32_t v = 0;
+            while (depth < capacity) {                                 // (always: a descent leaves every node at most once)
+                const uint32_t first = uniform(node_tab[2u * v]);
+                uint32_t arms = uniform(node_tab[2u * v + 1u]);
+                if (first > used || arms > used - first || arms == 0u) break;   // (never: a node's block lies inside the edges in use)
+                arms = arms < kBounceHalvingMaxArms ? arms : kBounceHalvingMaxArms;
+                const uint32_t* const node = pool + (uint64_t)first * kEdgeWords;
+                uint32_t na[kGuidedLaneArms], sa[kGuidedLaneArms], pa[kGuidedLaneArms], total = 0;
+#pragma unroll
+                for (uint32_t k = 0; k < kGuidedLaneArms; ++k) {
+                    const uint32_t a = lane + k * BGS_WAVE;
+                    na[k] = sa[k] = pa[k] = 0;
+                    if (k * BGS_WAVE < arms && a < arms) {
+                        const uint4 edge = *reinterpret_cast<const uint4*>(node + (uint64_t)a * kEdgeWords);
+                        na[k] = edge.x;
+                        sa[k] = edge.y;
+                        pa[k] = edge.w >> kGuidedMoveBits;
+                        total += edge.x;
+                    }
+                }
+                total = uniform(wave_sum(total));
+                // (a node's N is at most the root's, which the selection bounds: the clamp changes no tree and keeps (N + 1) << 12
+                // in 32 bits whatever the memory held)
+                total = total < (uint32_t)BGS_GUIDED_MAX_VISITS ? total : (uint32_t)BGS_GUIDED_MAX_VISITS;
+                const uint32_t sqrt_n = search_isqrt((total + 1u) << 12);
+                uint64_t key = 0;                                      // (U(a) << 9 | 511 - a) + 1: the largest U, then the lowest arm
+#pragma unroll
+                for (uint32_t k = 0; k < kGuidedLaneArms; ++k) {
+                    const uint32_t a = lane + k * BGS_WAVE;
+                    if (k * BGS_WAVE < arms && a < arms) {
+                        const uint32_t q = na[k] ? (2u * sa[k]) / na[k] : 2048u;
+                        const uint32_t e = (uint32_t)(((uint64_t)(cpuct * pa[k]) * sqrt_n) >> 19) / (1u + na[k]);
+                        const uint64_t mine = (((uint64_t)q + e) << 9 | (uint64_t)(511u - a)) + 1u;
+                        key = mine > key ? mine : key;
+                    }
+                }
+                key = wave_max64(key);
+                const uint32_t arm = uniform(511u - ((uint32_t)(key - 1u) & 511u));
+                const uint32_t e = first + arm;                        // (arm < arms: below the edges in use)
+                uint32_t* const edge = pool + (uint64_t)e * kEdgeWords;
+                const uint32_t child = uniform(edge[2]), word = uniform(edge[3]);
+                if (lane == 0) path[depth] = e;
+                const int s_cell = (int)((word >> 8) & 63u), t_cell = (int)(word & 63u);
+                const uint32_t mover = ply & 1u;
+                move_piece(p, s_cell, t_cell);
+                ply += 1u;
+                depth += 1u;
+                out_kind = (uint32_t)BGS_GUIDED_TERMINAL;
+                if (child == kEdgeCapped) {                            // p' runs and holds the cap
+                    kind = kGuidedFull;
+                    break;
+                }
+                if (child >= kEdgeEnded) {                             // the edge ends the game: its mover won, or a draw
+                    kind = (child & 15u) == (uint32_t)BGS_ST_DRAW ? kGuidedFull : kGuidedWon;
+                    break;
+                }
+                if (child != 0u && child < count) {
+                    out_kind = (uint32_t)BGS_GUIDED_IDLE;
+                    v = child;
+                    continue;
+                }
+                // ---- the edge has no child: what p' is
+                uint32_t code = 0;                                     // the edge's new third word, if any
+                if ((1ull << t_cell) & (g.goal_top | g.goal_bottom)) {
+                    kind = kGuidedWon;
+                    code = kEdgeEnded | (mover + 1u);
+                } else {
+                    const uint64_t occ = occupancy(p);
+                    uint32_t base;
+                    leaf_mask = spread(p, occ, ply & 1u, true, base);
+                    if (__builtin_amdgcn_ballot_w64(leaf_mask != 0ull) == 0) {   // the side to move is blocked: the mover wins if it could move
+                        const bool could = __builtin_amdgcn_ballot_w64(spread(p, occ, mover, true, base) != 0ull) != 0;
+                        kind = could ? kGuidedWon : kGuidedFull;
+                        code = kEdgeEnded | (could ? mover + 1u : (uint32_t)BGS_ST_DRAW);
+                    } else if (ply >= cap) {                           // no node, now or later
+                        kind = kGuidedFull;
+                        code = kEdgeCapped;
+                    } else {                                           // the caller evaluates p'
+                        kind = kGuidedEvaluate;
+                        out_kind = (uint32_t)BGS_GUIDED_EVALUATE;
+                    }
+                }
+                if (lane == 0 && code) edge[2] = code;
+                break;
+            }
+            if (out_kind == (uint32_t)BGS_GUIDED_IDLE) {               // (never: the descent left the tree's bounds; nothing is pending)
+                p = root;
+                ply = rply;
+                depth = 0;
+                kind = kGuidedNone;
+            }
+        }
+    }
+
+    // ---- the leaf goes out (an idle tree shows its root), in the encoding of bgs_read_grid: the piece values by cell
+    int8_t* const cells = leaf_grid + i * (int64_t)hw;
+    for (uint32_t j = lane; j < hw; j += BGS_WAVE) cells[j] = (int8_t)value_at(p, (int)j);
+    if (leaf_targets && lane < width) leaf_targets[i * (int64_t)width + lane] = out_kind == (uint32_t)BGS_GUIDED_EVALUATE ? leaf_mask : 0ull;
+    if (lane == 0) {
+        leaf_player[i] = (int8_t)(ply & 1u);
+        leaf_kind[i] = (int32_t)out_kind;
+        head[0] = count;            // the header: ply, cap and planes were recorded when the tree was emptied
+        head[1] = used;
+        head[12] = kind;
+        head[13] = depth;
+        head[14] = expanded;
+        head[15] = ply;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) leaf_planes[j] = p.v[j];
+    }
+}
+
 }  // namespace
+
+uint64_t bounce_guided_tree_bytes(int32_t capacity, int32_t edges) {
+    return bounce_guided_tree_words((uint32_t)capacity, (uint32_t)edges) * sizeof(uint32_t);
+}
+
+void bounce_guided_step(const bgs_batch* b, int32_t capacity, int32_t edges, int32_t cpuct, int32_t max_plies, uint32_t flags,
+                        const float* d_priors, const float* d_values, int8_t* d_leaf_grid, int8_t* d_leaf_player, int32_t* d_leaf_kind,
+                        uint64_t* d_leaf_targets, int32_t* d_visits, int32_t* d_scores, int32_t* d_best, int32_t* d_nodes, int32_t* d_used,
+                        void* d_trees) {
+    const uint32_t cap = (uint32_t)max_plies > kBounceMaxPlies ? kBounceMaxPlies : (uint32_t)max_plies;   // plies are stored as uint16
+    // (the kernel zeroes the rows of visits and scores itself: one enqueue a step, not three)
+    with_bounce_geom(b, [&](const auto& g, auto nc) {
+        constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+        for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+            const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+            hipLaunchKernelGGL((k_bounce_search_guided<std::decay_t<decltype(g)>, decltype(nc)::value>), dim3((uint32_t)blocks),
+                               dim3(BGS_WAVE), 0, b->stream, g, (const uint64_t*)b->d_planes, (const uint8_t*)b->d_status,
+                               (const uint16_t*)b->d_plies, b->n, i0, (uint32_t)capacity, (uint32_t)edges, (uint32_t)cpuct, cap, flags,
+                               d_priors, d_values, d_leaf_grid, d_leaf_player, d_leaf_kind, d_leaf_targets, d_visits, d_scores, d_best,
+                               d_nodes, d_used, static_cast<uint32_t*>(d_trees));
+        }
+    });
+}
 
 uint64_t bounce_search_root_bytes(int32_t iterations, int32_t edges) {
     return bounce_search_root_words((uint32_t)iterations, (uint32_t)edges) * sizeof(uint32_t);

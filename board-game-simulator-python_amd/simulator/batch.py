@@ -1354,10 +1354,32 @@ class BounceBatch(_Batch):
     forest_bytes = search_forest
 
     def guided_search(self, *args, **kwargs):
-        """Not available for Bounce: the search with caller-evaluated leaves covers bit-packed Connect boards."""
+        """Not available for Bounce: `guided_search` and `guided_bytes` are the Connect calls, a prior a column.  Bounce
+        has `guided_moves_search` and `guided_moves_bytes`, a prior a move slot."""
         raise ValueError("guided_search: Connect batches only")
 
     guided_bytes = guided_search
+
+    def guided_default_edges(self, nodes: int) -> int:
+        """the edge pool `guided_moves_search` takes with edges=None: `search_min_edges()` + 32 * (nodes - 1), the allowance
+        of `search_moves`: 32 edges a node that is not the root"""
+        return self.search_min_edges() + 32 * max(int(nodes) - 1, 0)
+
+    def guided_moves_bytes(self, nodes: int, edges: Optional[int] = None) -> int:
+        """bytes of device memory the guided trees of this batch take at `nodes` nodes and `edges` pool edges a tree (None:
+        `guided_default_edges(nodes)`; bgs_bounce_guided_bytes)"""
+        edges = self.guided_default_edges(nodes) if edges is None else int(edges)
+        nbytes = ctypes.c_size_t()
+        _abi.check(_abi.lib().bgs_bounce_guided_bytes(self._handle, ctypes.c_int32(nodes), ctypes.c_int32(edges), ctypes.byref(nbytes)))
+        return nbytes.value
+
+    def guided_moves_search(self, nodes: int, edges: Optional[int] = None, cpuct: int = DEFAULT_CPUCT,
+                            max_plies: int = 65535) -> "GuidedMovesSearch":
+        """A PUCT search of this batch whose leaves the caller evaluates, e.g. with a policy/value network: one tree per
+        board with room for `nodes` nodes, the root included, and `edges` pool edges (None: `guided_default_edges(nodes)`),
+        `cpuct` = c_puct in Q8; a position that holds `max_plies` plies is a draw (`GuidedMovesSearch`).  Close it before
+        the batch."""
+        return GuidedMovesSearch(self, nodes, edges, cpuct, max_plies)
 
     def solve_actions(self, *args, **kwargs):
         """Not available for Bounce: the exact solver covers bit-packed Connect boards (Bounce games can cycle)."""
@@ -1761,3 +1783,93 @@ class MovesForest:
                                                                     ("kept", kept, shape)], align=1)
         self._advance(slots.data_ptr(), kept.data_ptr(), 1)
         return kept
+
+
+class GuidedMovesSearch:
+    """PUCT tree search of a BounceBatch with caller-evaluated leaves (bgs_bounce_guided_step, include/bgs.h):
+    `BounceBatch.guided_moves_search(nodes, edges, cpuct, max_plies)` makes one.  One tree per board, `nodes` nodes a tree,
+    the root included, and `edges` pool edges; `cpuct` is c_puct in Q8 (320 = 1.25); `max_plies` is clamped to 65535.
+
+    The calls are those of `GuidedSearch`: `begin()` empties the trees and returns the roots as leaves, `step(priors,
+    values)` is one simulation, `finish(priors, values)` applies the last evaluation and selects nothing; each is one
+    launch on the batch's stream, with no synchronisation.  Each returns the same nine device tensors, allocated once and
+    rewritten by every call: (leaf_grid int8[n, H, W], leaf_player int8[n], leaf_kind int32[n], leaf_targets int64[n, W],
+    visits int32[n, W, H * W], scores int32[n, W, H * W], best int32[n], nodes int32[n], used int32[n]).  Entry [i, x, c]
+    is the move of the piece in column x of the active row to cell c = ty * W + tx, as in `BounceBatch.search_moves`;
+    `leaf_targets[i, x]` has bit c set for every legal one of an EVALUATE leaf (the bits of `BounceBatch.targets`, as
+    torch's signed 64-bit type) and is zero for every other kind: it is the mask of the evaluator's softmax.  `priors`
+    float32[n, W, H * W] and `values` float32[n] are the evaluator's output for the previous call's leaves: a value is seen
+    from the player to move at the leaf, in [-1, 1]; rows whose leaf_kind is not GUIDED_EVALUATE are ignored.  A board that
+    was stepped or reset between two calls restarts its tree on its own.  The boards and `steps` are not modified.
+
+    The object owns the device buffer of the trees (a torch tensor) and belongs to the batch it was made from."""
+
+    def __init__(self, batch: "BounceBatch", nodes: int, edges: Optional[int] = None, cpuct: int = DEFAULT_CPUCT,
+                 max_plies: int = 65535):
+        self.batch = batch
+        self.nodes = int(nodes)
+        self.edges = batch.guided_default_edges(self.nodes) if edges is None else int(edges)
+        self.cpuct = int(cpuct)
+        self.max_plies = int(max_plies)
+        if not 0 <= self.cpuct <= 4096:
+            raise ValueError(f"cpuct must be 0 .. 4096, c_puct in Q8 (got {cpuct})")
+        if self.max_plies < 1:
+            raise ValueError(f"max_plies must be >= 1 (got {max_plies})")
+        nbytes = batch.guided_moves_bytes(self.nodes, self.edges)     # (refuses Connect, generic boards, bad nodes or edges)
+        t = batch._need_torch("guided_moves_search")
+        n, h, w = batch.n, batch.height, batch.width
+        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")
+        self._outputs = tuple(batch._device_tensors("guided_moves_search", [
+            ("leaf_grid", None, (n, h, w), "int8"), ("leaf_player", None, (n,), "int8"), ("leaf_kind", None, (n,)),
+            ("leaf_targets", None, (n, w), "int64"), ("visits", None, (n, w, h * w)), ("scores", None, (n, w, h * w)),
+            ("best", None, (n,)), ("nodes", None, (n,)), ("used", None, (n,))]))
+        self._fresh = True
+
+    def close(self) -> None:
+        self._buffer = None
+
+    def _call(self, flags: int, priors, values):
+        if self._buffer is None:
+            raise RuntimeError("the guided search is closed")
+        if self._fresh and not flags & _abi.GUIDED_RESTART:
+            raise RuntimeError("begin() comes first: fresh memory holds no trees")
+        pointers = [None, None]
+        if not flags & _abi.GUIDED_RESTART:
+            n, w, hw = self.batch.n, self.batch.width, self.batch.height * self.batch.width
+            # (inputs: "optional", so that they are checked and never allocated)
+            priors, values = self.batch._device_tensors("guided_moves_search", [("priors", priors, (n, w, hw), "float32", True),
+                                                                                ("values", values, (n,), "float32", True)])
+            if priors is None or values is None:
+                raise TypeError("priors and values are the evaluator's device tensors: float32[n, W, H * W] and float32[n]")
+            pointers = [ctypes.c_void_p(priors.data_ptr()), ctypes.c_void_p(values.data_ptr())]
+        _abi.check(_abi.lib().bgs_bounce_guided_step(
+            self.batch._handle, ctypes.c_int32(self.nodes), ctypes.c_int32(self.edges), ctypes.c_int32(self.cpuct),
+            ctypes.c_int32(min(self.max_plies, 2**31 - 1)), ctypes.c_uint32(flags), *pointers,
+            *(ctypes.c_void_p(x.data_ptr()) for x in self._outputs), ctypes.c_void_p(self._buffer.data_ptr()),
+            ctypes.c_size_t(self._buffer.numel())))
+        self._fresh = False
+        return self._outputs
+
+    def begin(self):
+        """Empty every tree (BGS_GUIDED_RESTART): the leaves that come back are the roots."""
+        return self._call(_abi.GUIDED_RESTART, None, None)
+
+    def step(self, priors, values):
+        """One simulation: apply (priors, values) to the leaves of the previous call, descend to the next leaves."""
+        return self._call(0, priors, values)
+
+    def finish(self, priors, values):
+        """Apply (priors, values) to the leaves of the previous call and select nothing (BGS_GUIDED_FINISH): every
+        leaf_kind comes back GUIDED_IDLE, and visits, scores, best, nodes and used are final."""
+        return self._call(_abi.GUIDED_FINISH, priors, values)
+
+    def run(self, evaluate, simulations: int):
+        """`begin`, `simulations` evaluations a tree, `finish`: evaluate(leaf_grid, leaf_player, leaf_targets) -> (priors
+        float32[n, W, H * W], values float32[n]) is called once a simulation on the device tensors of the leaves (the first
+        call sees the roots) and returns device tensors.  Returns what `finish` returns."""
+        if simulations < 1:
+            raise ValueError(f"simulations must be >= 1 (got {simulations})")
+        outs = self.begin()
+        for _ in range(int(simulations) - 1):
+            outs = self.step(*evaluate(outs[0], outs[1], outs[3]))
+        return self.finish(*evaluate(outs[0], outs[1], outs[3]))

@@ -255,6 +255,13 @@ SIGNATURES = {
         ctypes.c_int,
         [c_handle, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int],
     ),
+    "bgs_bounce_guided_bytes": (ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]),
+    "bgs_bounce_guided_step": (
+        ctypes.c_int,
+        [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t],
+    ),
     "bgs_bounce_search_workspace_bytes": (
         ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
     ),

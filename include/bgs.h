@@ -665,6 +665,62 @@ BGS_API int bgs_bounce_forest_search(bgs_batch* b, uint64_t seed, int32_t iterat
                                      int32_t* carried, void* forest, size_t forest_bytes, int on_device);
 BGS_API int bgs_bounce_forest_advance(bgs_batch* b, const int32_t* slots, int32_t nodes_cap, int32_t edges, int32_t* kept,
                                       void* forest, size_t forest_bytes, int on_device);
+/* PUCT tree search whose leaves the CALLER evaluates (Bounce, bit-packed boards only), the sibling of
+ * bgs_connect_guided_step: what that text says holds here unless restated -- one call is one simulation of every tree,
+ * EVERY POINTER IS A DEVICE POINTER (`trees` 256-byte aligned, the rest 16-byte aligned), the call is one enqueue on the
+ * batch's stream with no synchronisation, no allocation and no RNG, there is no host variant, the boards and bgs_steps
+ * are untouched, the flags and kinds are the BGS_GUIDED_* values and BGS_GUIDED_MAX_VISITS bounds the root's N.
+ * Slots and arms are those of bgs_bounce_search_moves.  With S = width * height * width, slot x * height * width + c is
+ * the piece in column x of the active row moving to cell c, and a position's arms are its legal moves in ascending slot
+ * order.  priors float32[n][S], values float32[n].
+ * Tree.  `nodes_cap` (C) nodes, the root included, 2 <= C <= BGS_BOUNCE_FOREST_MAX_NODES, and a pool of `edges` (E)
+ * edges, BGS_BOUNCE_SEARCH_MIN_EDGES(height, width) <= E <= BGS_BOUNCE_FOREST_MAX_EDGES; a node with A arms takes A pool
+ * edges when it is made, the root its own first.  An edge holds n, s, the child (or the sentinel of an edge that ends the
+ * game, or of one whose position holds the cap), its move and P.  Opaque; bgs_bounce_guided_bytes says how large; a
+ * tree's share is rounded up to 256 bytes and holds, between calls: the nodes and the edges in use; the root position
+ * (four planes), its ply count and the effective cap min(max_plies, 65535); whether the root has its P; the pending
+ * leaf: its kind, its path of edge indices (at most C) and, for an EVALUATE leaf, its four planes and its ply count.
+ * One step, for board i, in this order:
+ *   1. Check.  The tree is LIVE if BGS_GUIDED_RESTART is not set, the board is running, has arms and holds fewer than
+ *      65535 plies, the nodes in use are in [1, C], the edges in use are in [the arms of the root, E], and the recorded
+ *      planes, ply count and cap equal board i's and this call's.  Otherwise the tree is emptied and the pending leaf is
+ *      dropped; a running board with arms gets node 0 with its arms (P = 0, not expanded) and is recorded.  THE FIRST
+ *      CALL ON FRESH MEMORY MUST PASS BGS_GUIDED_RESTART.  Every word read back from a share is used only within its
+ *      bounds: memory that passes the check by accident may give a wrong tree, never a store outside its own share.
+ *   2. Apply.  The value and the priors are quantised as in bgs_connect_guided_step, word for word, over the leaf's
+ *      legal slots in place of its legal columns: w = floor(min(x, 1.0f) * 65536.0f) for x > 0, else 0; W = the sum; if
+ *      W = 0 every legal arm gets w = 1; P = floor(w * 65536 / W).  sigma = 1024 + v.  A TERMINAL leaf has sigma = 0 if
+ *      the last edge won for its mover (a move into the goal row; a side to move without a move while the mover has
+ *      one) and sigma = 1024 for a draw and for a leaf that runs but holds the cap.  An EVALUATE leaf that is not the
+ *      root becomes a node if and only if its edge has no child, fewer than C nodes are in use and (edges in use) +
+ *      A(leaf) <= E; a node that does not fit is tried again the next time the edge is taken (the forest's rule).  An
+ *      EVALUATE leaf that IS the root only receives P.  Every edge k of the path gets n += 1, and s += sigma if node k's
+ *      mover is the leaf's mover, else s += 2048 - sigma.
+ *   3. Report, through the outputs that are not NULL: visits and scores int32[n][S] = the root's n and s by slot, zeros
+ *      on illegal slots; best[i] = the slot with the most visits, then the larger s, then the lower slot, -1 for an
+ *      emptied tree or a root with no visit; nodes[i] = the nodes in use, the root not counted; used[i] = the pool edges
+ *      in use.
+ *   4. Select, unless BGS_GUIDED_FINISH is set, the tree is emptied or the root's N has reached BGS_GUIDED_MAX_VISITS:
+ *      each gives IDLE.  An unexpanded root is the leaf: EVALUATE with an empty path.  Otherwise take the arm with the
+ *      largest U = Q + E, ties to the lowest arm; Q, E, isqrt((N + 1) << 12), the clamp on N and the range of `cpuct`
+ *      are the Connect text's (there is no unplayed-arm-first rule).  Play the stored move; then, the first that applies:
+ *      the edge word is an ended or a capped sentinel: TERMINAL, with no move search; the new position ended: the ended
+ *      sentinel is written, TERMINAL; it runs and its ply count is at or beyond the cap: the capped sentinel is written,
+ *      TERMINAL, and no node is made for it, now or later; the edge has a child: descend; otherwise EVALUATE.
+ *      leaf_grid int8[n][h][w] in bgs_read_grid's Bounce encoding, leaf_player[i] = the leaf's ply & 1, leaf_kind[i];
+ *      leaf_targets uint64[n][w] (may be NULL): for an EVALUATE leaf the target masks of the pieces in columns 0 .. w - 1
+ *      of the leaf's active row, in the bit layout of bgs_bounce_read_targets -- what a caller needs to mask its softmax
+ *      --, zeros for every other kind.  IDLE rows carry the root's grid and player.
+ * Refused (BGS_ERR_ARG, with a message that names the argument; the outputs and the trees are untouched): a Connect batch,
+ * a generic batch, C or E out of range, cpuct outside [0, 4096], max_plies < 1, unknown flag bits, BGS_GUIDED_RESTART
+ * together with BGS_GUIDED_FINISH, NULL trees, leaf_grid, leaf_player or leaf_kind, NULL priors or values without
+ * BGS_GUIDED_RESTART, a misaligned pointer, trees_bytes too small. */
+BGS_API int bgs_bounce_guided_bytes(const bgs_batch* b, int32_t nodes, int32_t edges, size_t* bytes);
+BGS_API int bgs_bounce_guided_step(bgs_batch* b, int32_t nodes_cap, int32_t edges, int32_t cpuct, int32_t max_plies,
+                                   uint32_t flags, const float* priors, const float* values,
+                                   int8_t* leaf_grid, int8_t* leaf_player, int32_t* leaf_kind, uint64_t* leaf_targets,
+                                   int32_t* visits, int32_t* scores, int32_t* best, int32_t* nodes, int32_t* used,
+                                   void* trees, size_t trees_bytes);
 /* Exact solve of every column of every board (Connect, bit-packed boards only): a depth-first alpha-beta search a
  * (board, column), no RNG.  Entry [i][c] is seen from the player to move at board i; the lines searched are at most
  * `depth` plies long, column c itself counted (depth >= height * width: a full solve).
