@@ -83,12 +83,31 @@ class GuidedMoves:
         self.expanded = [False] * n         # the root's arms have their P
         self.pending = [None] * n           # (kind, path, sigma of a TERMINAL leaf, (position, actions) of an EVALUATE leaf)
         self.restarts = [0] * n             # how often the tree was emptied
+        self.made = []                      # (tree, node): every node made by an application, in order, for the tests
         self.seen = new_seen()
+
+    # the four rules below are methods so that tests/test_guided_shares.py can state a wrong version of each
+    @staticmethod
+    def stopped(total):
+        """the root selects nothing once it holds this many visits"""
+        return total >= MAX_VISITS
+
+    @staticmethod
+    def credit(sigma, own, depth):
+        """what edge `depth` of the path (0: the root's) receives: own, the edge's mover is the leaf's"""
+        return sigma if own else 2048 - sigma
+
+    @staticmethod
+    def accumulate(s, x):
+        return s + x
+
+    def explore(self, share, total, n):
+        return e_term(self.cpuct, share, total, n)
 
     def select(self, node):
         """the arm the descent takes at `node`: the largest U, ties to the lowest arm"""
         total = min(sum(node.n), MAX_VISITS)
-        u = [q_term(node.s[a], node.n[a]) + e_term(self.cpuct, node.P[a], total, node.n[a]) for a in range(len(node.actions))]
+        u = [q_term(node.s[a], node.n[a]) + self.explore(node.P[a], total, node.n[a]) for a in range(len(node.actions))]
         return u.index(max(u))
 
     def step(self, roots, priors=None, values=None, flags=0, max_plies=None):
@@ -153,10 +172,11 @@ class GuidedMoves:
                                 self.count[i] += 1
                                 self.used[i] += len(leaf_acts)
                                 self.seen["made"] += 1
+                                self.made.append((i, node))
                 leaf_mover = (root.position[2] + len(path)) & 1
-                for node, a in path:
+                for depth, (node, a) in enumerate(path):
                     node.n[a] += 1
-                    node.s[a] += sigma if (node.position[2] & 1) == leaf_mover else 2048 - sigma
+                    node.s[a] = self.accumulate(node.s[a], self.credit(sigma, (node.position[2] & 1) == leaf_mover, depth))
             # 3. the report
             if root is not None:
                 visits[i, root.slots], scores[i, root.slots] = root.n, root.s
@@ -165,7 +185,7 @@ class GuidedMoves:
                 if ranked:
                     best[i] = root.slots[ranked[0]]
             # 4. the selection
-            if root is None or flags & FINISH or sum(root.n) >= MAX_VISITS:
+            if root is None or flags & FINISH or self.stopped(sum(root.n)):
                 continue
             if not self.expanded[i]:
                 self.pending[i] = (EVALUATE, [], None, (root.position, root.actions))
@@ -206,13 +226,18 @@ class GuidedMoves:
         shape = (n, w, h * w)
         return out_grid, out_player, out_kind, out_targets, visits.reshape(shape), scores.reshape(shape), best, nodes, used
 
-    def run(self, roots, evaluate, simulations):
+    def run(self, roots, evaluate, simulations, after_call=None):
         """GuidedMovesSearch.run: RESTART, simulations - 1 plain steps and FINISH, `evaluate` between them; returns every
-        call's outputs"""
+        call's outputs.  after_call(number of the call, 0 for begin): called behind every call, for the tests that look at
+        the trees"""
         calls = [self.step(roots, flags=RESTART)]
+        if after_call:
+            after_call(0)
         for t in range(simulations):
             priors, values = evaluate(calls[-1][0], calls[-1][1], calls[-1][3])
             calls.append(self.step(roots, priors, values, flags=FINISH if t == simulations - 1 else 0))
+            if after_call:
+                after_call(t + 1)
         return calls
 
 
@@ -310,17 +335,34 @@ def sweep_arguments(key, sweep):
     return case.grid, case.roots, nodes, edges, cpuct, case.max_plies[0] if capped else MAX_PLIES
 
 
+TREE_CALLS = (0, SIMULATIONS // 2, SIMULATIONS)       # the calls after which the GPU comparison reads the whole trees back
+
+
+def run_with_trees(model, roots, evaluate, simulations, tree_calls=TREE_CALLS):
+    """model.run, with model.trees[call] = every tree after call number `call` (0: begin) in the decoded form of
+    tests/guided_shares.py"""
+    from tests import guided_shares as gs       # (it imports this module)
+
+    model.trees = {}
+
+    def keep(call):
+        if call in tree_calls:
+            model.trees[call] = [gs.model_tree_bounce(model, i) for i in range(roots[0].shape[0])]
+
+    return model.run(roots, evaluate, simulations, after_call=keep)
+
+
 _SWEEPS_DONE = {}
 
 
 def sweep_expected(key, sweep):
     """(the GuidedMoves, every call's outputs) of the run under fake_network_moves, computed once a session and shared:
-    treat everything as read-only"""
+    treat everything as read-only.  model.trees: the whole trees after the calls of TREE_CALLS"""
     if (key, sweep) not in _SWEEPS_DONE:
         grid, roots, nodes, edges, cpuct, max_plies = sweep_arguments(key, sweep)
         model = GuidedMoves(grid, roots[0].shape[0], nodes, edges, cpuct, max_plies)
         before = dict(SEEN)
-        calls = model.run(roots, fake_network_moves, SIMULATIONS)
+        calls = run_with_trees(model, roots, fake_network_moves, SIMULATIONS)
         model.served = {name: SEEN[name] - before[name] for name in SPECIALS}     # the special rows this run was fed
         _SWEEPS_DONE[key, sweep] = (model, calls)
     return _SWEEPS_DONE[key, sweep]

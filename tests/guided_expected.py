@@ -77,10 +77,28 @@ class Guided:
         self.made = []                      # (tree, node): every node made by an application, for the tests
         self.refused = 0                    # EVALUATE leaves whose node did not fit
 
+    # the four rules below are methods so that tests/test_guided_shares.py can state a wrong version of each
+    @staticmethod
+    def stopped(total):
+        """the root selects nothing once it holds this many visits"""
+        return total >= MAX_VISITS
+
+    @staticmethod
+    def credit(sigma, own, depth):
+        """what edge `depth` of the path (0: the root's) receives: own, the edge's mover is the leaf's"""
+        return sigma if own else 2048 - sigma
+
+    @staticmethod
+    def accumulate(s, x):
+        return s + x
+
+    def explore(self, share, total, n):
+        return e_term(self.cpuct, share, total, n)
+
     def select(self, node):
         """the column the descent takes at `node`: the largest U, ties to the lowest column"""
         total = sum(node.n[c] for c in node.legal)
-        u = [q_term(node.s[c], node.n[c]) + e_term(self.cpuct, node.P[c], total, node.n[c]) for c in node.legal]
+        u = [q_term(node.s[c], node.n[c]) + self.explore(node.P[c], total, node.n[c]) for c in node.legal]
         return node.legal[u.index(max(u))]
 
     def step(self, roots, priors=None, values=None, flags=0):
@@ -133,9 +151,9 @@ class Guided:
                 if path:
                     self.applied[i] += 1
                 leaf_mover = (root.position[2] + len(path)) & 1
-                for node, c in path:
+                for depth, (node, c) in enumerate(path):
                     node.n[c] += 1
-                    node.s[c] += sigma if (node.position[2] & 1) == leaf_mover else 2048 - sigma
+                    node.s[c] = self.accumulate(node.s[c], self.credit(sigma, (node.position[2] & 1) == leaf_mover, depth))
             # 3. the report
             if root is not None:
                 visits[i], scores[i] = root.n, root.s
@@ -143,7 +161,7 @@ class Guided:
                 if sum(root.n) > 0:
                     best[i] = sorted(range(w), key=lambda c: (-root.n[c], -root.s[c], c))[0]
             # 4. the selection
-            if root is None or flags & FINISH or sum(root.n) >= MAX_VISITS:
+            if root is None or flags & FINISH or self.stopped(sum(root.n)):
                 continue
             if not self.expanded[i]:
                 self.pending[i] = (EVALUATE, [], None, root.position, list(root.legal))
@@ -169,12 +187,17 @@ class Guided:
             out_grid[i], out_player[i] = after[0], (root.position[2] + len(path)) & 1
         return out_grid, out_player, out_kind, visits, scores, best, nodes
 
-    def run(self, roots, evaluate, simulations):
-        """GuidedSearch.run: RESTART, simulations - 1 plain steps and FINISH, `evaluate` between them; returns every call's outputs"""
+    def run(self, roots, evaluate, simulations, after_call=None):
+        """GuidedSearch.run: RESTART, simulations - 1 plain steps and FINISH, `evaluate` between them; returns every call's
+        outputs.  after_call(number of the call, 0 for begin): called behind every call, for the tests that look at the trees"""
         calls = [self.step(roots, flags=RESTART)]
+        if after_call:
+            after_call(0)
         for t in range(simulations):
             priors, values = evaluate(calls[-1][0], calls[-1][1])
             calls.append(self.step(roots, priors, values, flags=FINISH if t == simulations - 1 else 0))
+            if after_call:
+                after_call(t + 1)
         return calls
 
 

@@ -3,7 +3,9 @@ BounceGuidedSearchAgent) against the CPU statement of tests/bounce_guided_expect
 leaf_targets, visits, scores, best, nodes and used bit for bit after every call, over the corner boards of
 tests/fuzz_cases.py from tree memory that holds 0xA5 in every byte.  The device is fed the rows `fake_network_moves`
 computes from the device's own leaves.  tests/test_bounce_guided_expected.py states what the CPU statement holds and that
-the sweeps here meet every branch.
+the sweeps here meet every branch.  After `begin`, a call in the middle and the last call of every run the whole trees
+are read back from the caller's tensor and compared with the statement's (tests/guided_shares.py): header, edges, node
+table and path in use.
 
 Every launch is one wave a root over at most 20 roots; the CPU model, computed once a run and shared, is the slower side.
 
@@ -18,6 +20,8 @@ import pytest
 from oracle import oracle
 from tests import bounce_guided_expected as bg
 from tests import fuzz_cases as fc
+from tests import guided_shares as gs
+from tests.guided_torch import torch_evaluator_moves as torch_evaluator
 from tests.search_bounce_expected import _actions, min_edges
 
 pytestmark = pytest.mark.gpu
@@ -68,6 +72,22 @@ def poisoned(b, nodes, edges, cpuct=320, max_plies=65535):
     return guided
 
 
+def device_trees(guided):
+    """every tree of a GuidedMovesSearch, read back and decoded (tests/guided_shares.py)"""
+    b = guided.batch
+    stride = b.guided_moves_bytes(guided.nodes, guided.edges) // b.n
+    assert stride == 4 * gs.bounce_share_words(guided.nodes, guided.edges)
+    words = guided._buffer.cpu().numpy().view(np.uint32).reshape(b.n, stride // 4)
+    return [gs.decode_bounce(words[i], guided.nodes, guided.edges) for i in range(b.n)]
+
+
+def assert_same_trees(guided, want, what):
+    got = device_trees(guided)
+    assert len(got) == len(want)
+    for i, (device, model) in enumerate(zip(got, want)):
+        gs.assert_same_tree(device, model, f"{what} tree {i}")
+
+
 def run_against(key, sweep):
     grid, roots, nodes, edges, cpuct, max_plies = bg.sweep_arguments(key, sweep)
     model, want = bg.sweep_expected(key, sweep)
@@ -76,10 +96,14 @@ def run_against(key, sweep):
     guided = poisoned(b, nodes, edges, cpuct, max_plies)
     got = host(guided.begin())
     assert_equal(got, want[0], f"{key} {sweep} begin")
+    assert_same_trees(guided, model.trees[0], f"{key} {sweep} begin")
     for t in range(SIMULATIONS):
         call = guided.finish if t == SIMULATIONS - 1 else guided.step
         got = host(call(*rows(got)))
         assert_equal(got, want[t + 1], f"{key} {sweep} call {t + 1}")
+        if t + 1 in model.trees:                    # the whole trees: in the middle and after the last call
+            assert_same_trees(guided, model.trees[t + 1], f"{key} {sweep} call {t + 1}")
+    assert sorted(model.trees) == list(bg.TREE_CALLS)
     print(f"bounce corner {key!r} {sweep}: C = {nodes}, E = {edges}, cpuct = {cpuct}, cap = {max_plies}, nodes {got[7].tolist()}, "
           f"used {got[8].tolist()}, best {got[6].tolist()}, met {model.seen}")
     assert snapshot(b) == before and b.steps == 0               # the boards and bgs_steps are untouched
@@ -298,23 +322,6 @@ def test_every_refusal_leaves_outputs_and_trees_untouched():
         own.begin()
     for batch in (b, connect, generic):
         batch.close()
-
-
-def torch_evaluator(grid, player, targets):
-    """a deterministic evaluator on the device: a softmax over the legal slots of `targets`, a value from the grid"""
-    import torch
-
-    n, h, w = grid.shape
-    x = grid.to(torch.float32)
-    weights = torch.arange(1, h * w + 1, dtype=torch.float32, device=grid.device).view(1, h, w)
-    cells = torch.arange(h * w, device=grid.device, dtype=torch.int64).view(1, 1, h * w)
-    legal = ((targets.view(n, w, 1) >> cells) & 1).bool()
-    logits = (torch.arange(w, device=grid.device, dtype=torch.float32).view(1, w, 1) * 0.25
-              + cells.to(torch.float32) * 0.0625 + (x * weights).sum(dim=(1, 2)).view(n, 1, 1) * 0.001)
-    logits = torch.where(legal, logits, torch.full_like(logits, -1e30))
-    priors = torch.softmax(logits.view(n, -1), dim=1).view(n, w, h * w) * legal
-    values = torch.tanh((x * weights).sum(dim=(1, 2)) * 0.003) * (1 - 2 * player.to(torch.float32))
-    return priors.contiguous(), values.contiguous()
 
 
 def test_the_agent_equals_the_batch_call():

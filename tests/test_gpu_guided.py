@@ -1,7 +1,9 @@
 """The PUCT search with caller-evaluated leaves (bgs_connect_guided_step, ConnectBatch.guided_search, GuidedSearchAgent)
 against the CPU statement of tests/guided_expected.py: leaf_grid, leaf_player, leaf_kind, visits, scores, best and nodes
 bit for bit after every call, over the corner boards of tests/fuzz_cases.py.  The device is fed the rows `fake_network`
-computes from the device's own leaves.  tests/test_guided_expected.py states what the CPU statement holds.
+computes from the device's own leaves.  tests/test_guided_expected.py states what the CPU statement holds.  After
+`begin`, a call in the middle and the last call of every run the whole trees are read back from the caller's tensor and
+compared with the statement's (tests/guided_shares.py): header, path and every node in use.
 
 Everything here needs a real MI355X: `pytest -m gpu`.
 """
@@ -15,6 +17,8 @@ import pytest
 from oracle import oracle
 from tests import fuzz_cases as fc
 from tests import guided_expected as ge
+from tests import guided_shares as gs
+from tests.guided_torch import torch_evaluator
 
 pytestmark = pytest.mark.gpu
 
@@ -63,24 +67,62 @@ def poisoned(b, capacity, cpuct):
     return guided
 
 
+TREE_CALLS = (0, SIMULATIONS // 2, SIMULATIONS)       # the calls after which the whole trees are read back
+
+
 @functools.lru_cache(maxsize=None)
-def expected(key, capacity, cpuct):
+def expected_run(key, capacity, cpuct):
+    """(every call's outputs, {call: every tree after it, decoded} for TREE_CALLS) of Guided.run"""
     case = fc.connect_case(key)
-    return ge.Guided(case.h, case.w, case.k, case.roots[0].shape[0], capacity, cpuct).run(case.roots, ge.fake_network, SIMULATIONS)
+    n = case.roots[0].shape[0]
+    model = ge.Guided(case.h, case.w, case.k, n, capacity, cpuct)
+    trees = {}
+
+    def keep(call):
+        if call in TREE_CALLS:
+            trees[call] = [gs.model_tree_connect(model, i) for i in range(n)]
+
+    calls = model.run(case.roots, ge.fake_network, SIMULATIONS, after_call=keep)
+    return calls, trees
+
+
+def expected(key, capacity, cpuct):
+    return expected_run(key, capacity, cpuct)[0]
+
+
+def device_trees(guided):
+    """every tree of a GuidedSearch, read back and decoded (tests/guided_shares.py)"""
+    b = guided.batch
+    h, w = b.height, b.width
+    stride = b.guided_bytes(guided.capacity) // b.n
+    assert stride == 4 * gs.connect_share_words(h, w, guided.capacity)
+    words = guided._buffer.cpu().numpy().view(np.uint32).reshape(b.n, stride // 4)
+    return [gs.decode_connect(words[i], h, w, (w * (h + 1) + 63) // 64, guided.capacity) for i in range(b.n)]
+
+
+def assert_same_trees(guided, want, what):
+    got = device_trees(guided)
+    assert len(got) == len(want)
+    for i, (device, model) in enumerate(zip(got, want)):
+        gs.assert_same_tree(device, model, f"{what} tree {i}")
 
 
 def run_against(key, capacity, cpuct):
     case = fc.connect_case(key)
-    want = expected(key, capacity, cpuct)
+    want, trees = expected_run(key, capacity, cpuct)
     b = load(case.h, case.w, case.k, case.roots)
     before = snapshot(b)
     guided = poisoned(b, capacity, cpuct)
     got = host(guided.begin())
     assert_equal(got, want[0], f"{key} begin")
+    assert_same_trees(guided, trees[0], f"{key} C = {capacity} begin")
     for t in range(SIMULATIONS):
         call = guided.finish if t == SIMULATIONS - 1 else guided.step
         got = host(call(*rows(got)))
         assert_equal(got, want[t + 1], f"{key} C = {capacity} call {t + 1}")
+        if t + 1 in trees:                          # the whole trees: in the middle and after the last call
+            assert_same_trees(guided, trees[t + 1], f"{key} C = {capacity} call {t + 1}")
+    assert sorted(trees) == list(TREE_CALLS)
     print(f"{fc.describe(case)}: C = {capacity}, cpuct = {cpuct}, nodes {got[6].tolist()}, best {got[5].tolist()}")
     assert snapshot(b) == before and b.steps == 0               # the boards and bgs_steps are untouched
     guided.close()
@@ -249,17 +291,6 @@ def test_every_refusal_leaves_outputs_and_trees_untouched():
         own.begin()
     for batch in (b, bounce, generic):
         batch.close()
-
-
-def torch_evaluator(grid, player):
-    """a deterministic evaluator on the device: any function of the leaves will do, both callers see the same rows"""
-    import torch
-
-    x = grid.to(torch.float32)
-    weights = torch.arange(1, grid.shape[1] * grid.shape[2] + 1, dtype=torch.float32, device=grid.device).view(1, grid.shape[1], grid.shape[2])
-    priors = torch.softmax((x * weights).sum(dim=1) * 0.125, dim=1)
-    values = torch.tanh((x * weights).sum(dim=(1, 2)) * 0.03125) * (1 - 2 * player.to(torch.float32))
-    return priors.contiguous(), values.contiguous()
 
 
 def test_the_agent_equals_the_batch_call():
