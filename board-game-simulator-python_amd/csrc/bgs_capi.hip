@@ -1347,6 +1347,33 @@ int bgs_connect_guided_bytes(const bgs_batch* b, int32_t capacity, size_t* bytes
     return connect_guided_check(b, capacity, bytes);
 }
 
+// What both guided steps check once their game's size check has said `need`.  `max_plies` is Bounce's (NULL: Connect has
+// none).  `named` are the device pointers of the call but the trees, in the order of its arguments: priors and values, which
+// may be NULL with BGS_GUIDED_RESTART only, then leaf_grid, leaf_player and leaf_kind, which may not, then the game's other
+// outputs.  `sizing` is the call that says how large the trees are.
+struct GuidedPointer {
+    const char* name;
+    const void* ptr;
+};
+static int guided_step_check(int32_t cpuct, const int32_t* max_plies, uint32_t flags, const GuidedPointer* named, size_t count,
+                             const void* trees, size_t trees_bytes, size_t need, const char* sizing) {
+    NEED(cpuct >= 0 && cpuct <= 4096, "cpuct must be 0 .. 4096, c_puct in Q8 (got %d)", cpuct);
+    NEED(max_plies == nullptr || *max_plies >= 1, "max_plies must be >= 1 (got %d)", *max_plies);
+    NEED((flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH)) == 0u, "unknown flag bits 0x%x (BGS_GUIDED_RESTART 0x%x, BGS_GUIDED_FINISH 0x%x)",
+         flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH), BGS_GUIDED_RESTART, BGS_GUIDED_FINISH);
+    NEED((flags & BGS_GUIDED_RESTART) == 0u || (flags & BGS_GUIDED_FINISH) == 0u,
+         "BGS_GUIDED_RESTART with BGS_GUIDED_FINISH: a restarted tree has nothing to finish");
+    NEED(trees != nullptr, "trees is NULL (the caller owns them; %s says how large)", sizing);
+    for (size_t i = 2; i < 5; ++i) NEED(named[i].ptr != nullptr, "%s is NULL", named[i].name);
+    for (size_t i = 0; i < 2; ++i)
+        NEED((flags & BGS_GUIDED_RESTART) != 0u || named[i].ptr != nullptr, "%s is NULL (allowed with BGS_GUIDED_RESTART only)", named[i].name);
+    NEED((reinterpret_cast<uintptr_t>(trees) & 255u) == 0, "trees must be 256-byte aligned");
+    for (size_t i = 0; i < count; ++i)
+        NEED((reinterpret_cast<uintptr_t>(named[i].ptr) & 15u) == 0, "device %s must be 16-byte aligned", named[i].name);
+    NEED(trees_bytes >= need, "the trees are too small: %zu bytes, %zu needed", trees_bytes, need);
+    return BGS_OK;
+}
+
 int bgs_connect_guided_step(bgs_batch* b, int32_t capacity, int32_t cpuct, uint32_t flags, const float* priors, const float* values,
                             int8_t* leaf_grid, int8_t* leaf_player, int32_t* leaf_kind, int32_t* visits, int32_t* scores,
                             int32_t* best, int32_t* nodes, void* trees, size_t trees_bytes) {
@@ -1355,25 +1382,10 @@ int bgs_connect_guided_step(bgs_batch* b, int32_t capacity, int32_t cpuct, uint3
     size_t need = 0;
     rc = connect_guided_check(b, capacity, &need);
     if (rc) return rc;
-    NEED(cpuct >= 0 && cpuct <= 4096, "cpuct must be 0 .. 4096, c_puct in Q8 (got %d)", cpuct);
-    NEED((flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH)) == 0u, "unknown flag bits 0x%x (BGS_GUIDED_RESTART 0x%x, BGS_GUIDED_FINISH 0x%x)",
-         flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH), BGS_GUIDED_RESTART, BGS_GUIDED_FINISH);
-    NEED((flags & BGS_GUIDED_RESTART) == 0u || (flags & BGS_GUIDED_FINISH) == 0u,
-         "BGS_GUIDED_RESTART with BGS_GUIDED_FINISH: a restarted tree has nothing to finish");
-    NEED(trees != nullptr, "trees is NULL (the caller owns them; bgs_connect_guided_bytes says how large)");
-    NEED(leaf_grid != nullptr, "leaf_grid is NULL");
-    NEED(leaf_player != nullptr, "leaf_player is NULL");
-    NEED(leaf_kind != nullptr, "leaf_kind is NULL");
-    NEED((flags & BGS_GUIDED_RESTART) != 0u || priors != nullptr, "priors is NULL (allowed with BGS_GUIDED_RESTART only)");
-    NEED((flags & BGS_GUIDED_RESTART) != 0u || values != nullptr, "values is NULL (allowed with BGS_GUIDED_RESTART only)");
-    NEED((reinterpret_cast<uintptr_t>(trees) & 255u) == 0, "trees must be 256-byte aligned");
-    const struct {
-        const char* name;
-        const void* ptr;
-    } rest[] = {{"priors", priors},   {"values", values}, {"leaf_grid", leaf_grid}, {"leaf_player", leaf_player}, {"leaf_kind", leaf_kind},
-                {"visits", visits},   {"scores", scores}, {"best", best},           {"nodes", nodes}};
-    for (const auto& p : rest) NEED((reinterpret_cast<uintptr_t>(p.ptr) & 15u) == 0, "device %s must be 16-byte aligned", p.name);
-    NEED(trees_bytes >= need, "the trees are too small: %zu bytes, %zu needed", trees_bytes, need);
+    const GuidedPointer named[] = {{"priors", priors}, {"values", values}, {"leaf_grid", leaf_grid}, {"leaf_player", leaf_player},
+                                   {"leaf_kind", leaf_kind}, {"visits", visits}, {"scores", scores}, {"best", best}, {"nodes", nodes}};
+    rc = guided_step_check(cpuct, nullptr, flags, named, sizeof(named) / sizeof(named[0]), trees, trees_bytes, need, "bgs_connect_guided_bytes");
+    if (rc) return rc;
     bgs::connect_guided_step(b, capacity, cpuct, flags, priors, values, leaf_grid, leaf_player, leaf_kind, visits, scores, best, nodes,
                              trees);
     return finish_launch();
@@ -1546,10 +1558,11 @@ int bgs_bounce_search_moves_proving(bgs_batch* b, uint64_t seed, int32_t iterati
                                visits, best, nodes, used, proved, done, workspace, workspace_bytes, on_device);
 }
 
-// the checks of the three Bounce forest entry points that need no device; *bytes: the forest of the batch
-static int bounce_forest_check(const bgs_batch* b, int32_t nodes_cap, int32_t edges, size_t* bytes) {
-    NEED(b->game == BGS_GAME_BOUNCE, "bounce_forest: Bounce batches only (Connect boards: bgs_connect_forest_search)");
-    NEED(!b->generic, "bounce_forest: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
+// the game, board, nodes_cap and edges checks of the Bounce forest and guided entry points; `what` begins the messages about
+// the batch, `connect_call` is where they send a Connect batch
+static int bounce_trees_check(const bgs_batch* b, const char* what, const char* connect_call, int32_t nodes_cap, int32_t edges) {
+    NEED(b->game == BGS_GAME_BOUNCE, "%s: Bounce batches only (Connect boards: %s)", what, connect_call);
+    NEED(!b->generic, "%s: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic", what,
          BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
     NEED(nodes_cap >= 2 && nodes_cap <= BGS_BOUNCE_FOREST_MAX_NODES, "nodes_cap must be 2 .. %d nodes a tree (got %d)",
          BGS_BOUNCE_FOREST_MAX_NODES, nodes_cap);
@@ -1557,6 +1570,13 @@ static int bounce_forest_check(const bgs_batch* b, int32_t nodes_cap, int32_t ed
     NEED(edges >= least && edges <= BGS_BOUNCE_FOREST_MAX_EDGES,
          "edges must be BGS_BOUNCE_SEARCH_MIN_EDGES(%d, %d) = %d, the most arms a position can have, .. %d (got %d)", b->bg.h, b->bg.w,
          least, BGS_BOUNCE_FOREST_MAX_EDGES, edges);
+    return BGS_OK;
+}
+
+// the checks of the three Bounce forest entry points that need no device; *bytes: the forest of the batch
+static int bounce_forest_check(const bgs_batch* b, int32_t nodes_cap, int32_t edges, size_t* bytes) {
+    const int rc = bounce_trees_check(b, "bounce_forest", "bgs_connect_forest_search", nodes_cap, edges);
+    if (rc) return rc;
     const uint64_t tree = bgs::bounce_forest_tree_bytes(nodes_cap, edges);
     NEED((uint64_t)b->n <= (uint64_t)(SIZE_MAX / 2) / tree, "the forest of %lld boards x %d nodes x %d edges overflows size_t",
          (long long)b->n, nodes_cap, edges);
@@ -1610,15 +1630,8 @@ int bgs_bounce_forest_advance(bgs_batch* b, const int32_t* slots, int32_t nodes_
 
 // the checks of both Bounce guided entry points that need no device; *bytes: the trees of the batch
 static int bounce_guided_check(const bgs_batch* b, int32_t nodes_cap, int32_t edges, size_t* bytes) {
-    NEED(b->game == BGS_GAME_BOUNCE, "bounce_guided: Bounce batches only (Connect boards: bgs_connect_guided_step)");
-    NEED(!b->generic, "bounce_guided: bit-packed Bounce boards only (up to %d cells, piece values up to %d); this %dx%d board is generic",
-         BGS_BOUNCE_MAX_CELLS, BGS_BOUNCE_MAX_VALUE, b->gen_h, b->gen_w);
-    NEED(nodes_cap >= 2 && nodes_cap <= BGS_BOUNCE_FOREST_MAX_NODES, "nodes_cap must be 2 .. %d nodes a tree (got %d)",
-         BGS_BOUNCE_FOREST_MAX_NODES, nodes_cap);
-    const int32_t least = BGS_BOUNCE_SEARCH_MIN_EDGES(b->bg.h, b->bg.w);
-    NEED(edges >= least && edges <= BGS_BOUNCE_FOREST_MAX_EDGES,
-         "edges must be BGS_BOUNCE_SEARCH_MIN_EDGES(%d, %d) = %d, the most arms a position can have, .. %d (got %d)", b->bg.h, b->bg.w,
-         least, BGS_BOUNCE_FOREST_MAX_EDGES, edges);
+    const int rc = bounce_trees_check(b, "bounce_guided", "bgs_connect_guided_step", nodes_cap, edges);
+    if (rc) return rc;
     const uint64_t tree = bgs::bounce_guided_tree_bytes(nodes_cap, edges);
     NEED((uint64_t)b->n <= (uint64_t)(SIZE_MAX / 2) / tree, "the trees of %lld boards x %d nodes x %d edges overflow size_t",
          (long long)b->n, nodes_cap, edges);
@@ -1641,27 +1654,11 @@ int bgs_bounce_guided_step(bgs_batch* b, int32_t nodes_cap, int32_t edges, int32
     size_t need = 0;
     rc = bounce_guided_check(b, nodes_cap, edges, &need);
     if (rc) return rc;
-    NEED(cpuct >= 0 && cpuct <= 4096, "cpuct must be 0 .. 4096, c_puct in Q8 (got %d)", cpuct);
-    NEED(max_plies >= 1, "max_plies must be >= 1 (got %d)", max_plies);
-    NEED((flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH)) == 0u, "unknown flag bits 0x%x (BGS_GUIDED_RESTART 0x%x, BGS_GUIDED_FINISH 0x%x)",
-         flags & ~(BGS_GUIDED_RESTART | BGS_GUIDED_FINISH), BGS_GUIDED_RESTART, BGS_GUIDED_FINISH);
-    NEED((flags & BGS_GUIDED_RESTART) == 0u || (flags & BGS_GUIDED_FINISH) == 0u,
-         "BGS_GUIDED_RESTART with BGS_GUIDED_FINISH: a restarted tree has nothing to finish");
-    NEED(trees != nullptr, "trees is NULL (the caller owns them; bgs_bounce_guided_bytes says how large)");
-    NEED(leaf_grid != nullptr, "leaf_grid is NULL");
-    NEED(leaf_player != nullptr, "leaf_player is NULL");
-    NEED(leaf_kind != nullptr, "leaf_kind is NULL");
-    NEED((flags & BGS_GUIDED_RESTART) != 0u || priors != nullptr, "priors is NULL (allowed with BGS_GUIDED_RESTART only)");
-    NEED((flags & BGS_GUIDED_RESTART) != 0u || values != nullptr, "values is NULL (allowed with BGS_GUIDED_RESTART only)");
-    NEED((reinterpret_cast<uintptr_t>(trees) & 255u) == 0, "trees must be 256-byte aligned");
-    const struct {
-        const char* name;
-        const void* ptr;
-    } rest[] = {{"priors", priors}, {"values", values}, {"leaf_grid", leaf_grid}, {"leaf_player", leaf_player},
-                {"leaf_kind", leaf_kind}, {"leaf_targets", leaf_targets}, {"visits", visits}, {"scores", scores},
-                {"best", best}, {"nodes", nodes}, {"used", used}};
-    for (const auto& p : rest) NEED((reinterpret_cast<uintptr_t>(p.ptr) & 15u) == 0, "device %s must be 16-byte aligned", p.name);
-    NEED(trees_bytes >= need, "the trees are too small: %zu bytes, %zu needed", trees_bytes, need);
+    const GuidedPointer named[] = {{"priors", priors}, {"values", values}, {"leaf_grid", leaf_grid}, {"leaf_player", leaf_player},
+                                   {"leaf_kind", leaf_kind}, {"leaf_targets", leaf_targets}, {"visits", visits}, {"scores", scores},
+                                   {"best", best}, {"nodes", nodes}, {"used", used}};
+    rc = guided_step_check(cpuct, &max_plies, flags, named, sizeof(named) / sizeof(named[0]), trees, trees_bytes, need, "bgs_bounce_guided_bytes");
+    if (rc) return rc;
     bgs::bounce_guided_step(b, nodes_cap, edges, cpuct, max_plies, flags, priors, values, leaf_grid, leaf_player, leaf_kind, leaf_targets,
                             visits, scores, best, nodes, used, trees);
     return finish_launch();

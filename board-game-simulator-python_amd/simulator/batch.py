@@ -48,6 +48,13 @@ def playout_policy(name) -> int:
     return PLAYOUT_POLICIES[name]
 
 
+def _playout_args(seed: int, policy, *int32s) -> list:
+    """(seed, *int32s, the code of `policy`): the scalars every entry point that plays playouts begins with.  An unknown
+    policy is refused here, before its caller allocates anything or reaches the library."""
+    code = playout_policy(policy)
+    return [ctypes.c_uint64(seed), *(ctypes.c_int32(x) for x in int32s), code]
+
+
 def _ptr(a: np.ndarray, ctype):
     return a.ctypes.data_as(ctypes.POINTER(ctype))
 
@@ -718,6 +725,73 @@ class _Batch:
             raise TypeError("workspace must be a contiguous uint8 device tensor")
         return workspace
 
+    def _size_query(self, entry: str, *sizes) -> int:
+        """what the `*_bytes` entry point `entry` answers for the int32 `sizes`"""
+        nbytes = ctypes.c_size_t()
+        _abi.check(getattr(_abi.lib(), entry)(self._handle, *(ctypes.c_int32(x) for x in sizes), ctypes.byref(nbytes)))
+        return nbytes.value
+
+    def _analysis(self, who: str, entry: str, scalars, specs, tensors=None, workspace=None, sizing=None):
+        """The one body of every analysis call, host and tensor form: `entry`(handle, *scalars, the outputs[, a workspace
+        and its bytes], on_device), once; returns the outputs in the order of `specs`.  specs are (name, shape[, dtype
+        name[, optional]]) in ABI order, what `_device_tensors` takes less the tensor: the one place where a call's output
+        shapes and dtypes are written.  tensors None is the host form, numpy arrays made here; else they are the caller's
+        device tensors in that order (None: allocated), checked by `_device_tensors` under the name `who`.  An optional
+        output that is not there goes to the library as NULL.  sizing is the (size_query, cache_key) of a search
+        (`_search_workspace`): its tensor form takes `workspace` or the batch's cached one, its host form passes None, 0
+        and the library allocates.  A `workspace` without sizing (a forest's buffer) is passed as it is."""
+        if tensors is None:
+            outs = []
+            for _, shape, *rest in specs:
+                dtype, optional = rest + ["int32", False][len(rest):]
+                outs.append(None if optional else np.empty(shape, dtype=dtype))
+            pointers = [None if x is None else ctypes.c_void_p(x.ctypes.data) for x in outs]
+        else:
+            outs = self._device_tensors(who, [(name, x, *rest) for (name, *rest), x in zip(specs, tensors)])
+            pointers = [None if x is None else ctypes.c_void_p(x.data_ptr()) for x in outs]
+            if sizing is not None:
+                workspace = self._search_workspace(who, workspace, *sizing)
+        if workspace is not None:
+            pointers += [ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel())]
+        elif sizing is not None:
+            pointers += [None, 0]
+        _abi.check(getattr(_abi.lib(), entry)(self._handle, *scalars, *pointers, 0 if tensors is None else 1))
+        return tuple(outs)
+
+    def _search_specs(self, proving: bool = False, carried: bool = False):
+        """the outputs of a tree search of this batch, a proving one or a forest's, as `_analysis` takes them"""
+        n, row = (self.n,), self._per_action()
+        specs = [("counts", row + (3,)), ("visits", row)] + [(name, n) for name in self._search_counters]
+        if proving:
+            specs += [("proved", row, "int8"), ("done", n)]
+        if carried:
+            specs += [("carried", n)]
+        return specs
+
+    def _evaluate(self, who: str, entry: str, tensors, seed: int, playouts: int, max_plies: int, policy: str):
+        """the flat evaluation of `policy`, host or tensor form: "uniform" is `entry` itself (bgs_connect_evaluate_actions,
+        bgs_bounce_evaluate_moves), any other policy goes through `entry`_policy, which takes the policy's code as well"""
+        scalars = _playout_args(seed, policy, playouts, max_plies)
+        if scalars[-1] == _abi.POLICY_UNIFORM:
+            scalars.pop()
+        else:
+            entry += "_policy"
+        return self._analysis(who, entry, scalars, [("out", self._per_action() + (3,))], tensors)[0]
+
+    def _halving(self, who: str, entry: str, tensors, seed: int, budget: int, max_plies: int, policy: str):
+        """the sequential-halving evaluation, host or tensor form"""
+        row = self._per_action()
+        return self._analysis(who, entry, _playout_args(seed, policy, budget, max_plies),
+                              [("counts", row + (3,)), ("given", row), ("best", (self.n,))], tensors)
+
+    def _solve(self, who: str, entry: str, tensors, depth: int, max_nodes: int, with_plies: bool):
+        """the exact solve, host or tensor form: (codes, plies or None).  The node counter, the third output of the entry
+        point, is never asked for: it goes as NULL"""
+        row = self._per_action()
+        specs = [("codes", row, "int8"), ("plies", row, "int16", not with_plies), ("nodes", (1,), "uint64", True)]
+        return self._analysis(who, entry, [ctypes.c_int32(int(depth)), ctypes.c_int64(max_nodes)], specs,
+                              None if tensors is None else tensors + (None,))[:2]
+
     # ---- snapshot / restore in the reference's wire format (State.to_json / State.from_json) -------------------
     def to_json_states(self) -> list:
         """The batch as a list of reference-shaped State JSON dicts {"grid", "player", "winner"}
@@ -810,11 +884,118 @@ class OneBoardCall:
         return int(self.status[0])
 
 
+class _Forest:
+    """What SearchForest and MovesForest share: the device buffer, the first-search rule and one body a call.  The
+    per-game part: `_search_entry` and `_advance_entry`, `_maker` (the batch's method that makes the forest, for the
+    missing-torch message), `_moves` (the name of the `advance` input) and `_sizes()`, the size arguments of both entry
+    points; the outputs are the batch's `_search_specs(carried=True)`."""
+
+    def _open(self, nbytes: int) -> None:
+        t = self.batch._need_torch(self._maker)
+        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{self.batch.device}")   # (zeros: every tree empty)
+        self._fresh = True
+
+    def close(self) -> None:
+        self._buffer = None
+
+    def _search(self, tensors, seed, iterations, leaf_playouts, explore, max_plies, policy, restart):
+        if self._buffer is None:
+            raise RuntimeError("the forest is closed")
+        scalars = _playout_args(seed, policy, iterations, leaf_playouts, explore, max_plies)
+        scalars += [*(ctypes.c_int32(x) for x in self._sizes()), 1 if restart or self._fresh else 0]
+        outs = self.batch._analysis("search_tensor", self._search_entry, scalars, self.batch._search_specs(carried=True), tensors,
+                                    self._buffer)
+        self._fresh = False
+        return outs
+
+    def _advance(self, moves, kept=None, on_device: bool = False):
+        n = self.batch.n
+        if on_device:   # (moves is an input: "optional", so that it is checked and never allocated)
+            moves, kept = self.batch._device_tensors("advance_tensor", [(self._moves, moves, (n,), "int32", True), ("kept", kept, (n,))],
+                                                     align=1)
+            pointers = moves.data_ptr(), kept.data_ptr()
+        else:
+            moves = np.ascontiguousarray(moves, dtype=np.int32)
+            if moves.shape != (n,):
+                raise TypeError(f"{self._moves} must be int32[{n}]")
+            kept = np.empty(n, dtype=np.int32)
+            pointers = moves.ctypes.data, kept.ctypes.data
+        if self._buffer is None:
+            raise RuntimeError("the forest is closed")
+        _abi.check(getattr(_abi.lib(), self._advance_entry)(
+            self.batch._handle, ctypes.c_void_p(pointers[0]), *(ctypes.c_int32(x) for x in self._sizes()), ctypes.c_void_p(pointers[1]),
+            ctypes.c_void_p(self._buffer.data_ptr()), ctypes.c_size_t(self._buffer.numel()), 1 if on_device else 0))
+        return kept
+
+
+class _Guided:
+    """What GuidedSearch and GuidedMovesSearch share: the trees' buffer, the output tensors made once, the "begin() comes
+    first" rule and one body a call.  The per-game part: `_entry`, `_maker` (the batch's method that makes the object, for
+    the messages about tensors), `_scalars()` (the int32 arguments in front of `flags`: the size arguments, `cpuct` and,
+    for Bounce, `max_plies`), `_priors` (the shape of `priors` as the TypeError names it; the shape itself is an entry a
+    column or move slot of every board), `_leaves` (the indices of the outputs `run` passes to `evaluate`) and the output
+    specs, which the constructor hands to `_open` once it has checked its ranges."""
+
+    def _check_cpuct(self, given) -> None:
+        if not 0 <= self.cpuct <= 4096:
+            raise ValueError(f"cpuct must be 0 .. 4096, c_puct in Q8 (got {given})")
+
+    def _open(self, nbytes: int, specs) -> None:
+        batch = self.batch
+        t = batch._need_torch(self._maker)
+        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")
+        self._outputs = tuple(batch._device_tensors(self._maker, [(name, None, *rest) for name, *rest in specs]))
+        self._fresh = True
+
+    def close(self) -> None:
+        self._buffer = None
+
+    def _call(self, flags: int, priors, values):
+        if self._buffer is None:
+            raise RuntimeError("the guided search is closed")
+        if self._fresh and not flags & _abi.GUIDED_RESTART:
+            raise RuntimeError("begin() comes first: fresh memory holds no trees")
+        pointers = [None, None]
+        if not flags & _abi.GUIDED_RESTART:   # (inputs: "optional", so that they are checked and never allocated)
+            priors, values = self.batch._device_tensors(self._maker, [("priors", priors, self.batch._per_action(), "float32", True),
+                                                                      ("values", values, (self.batch.n,), "float32", True)])
+            if priors is None or values is None:
+                raise TypeError(f"priors and values are the evaluator's device tensors: {self._priors} and float32[n]")
+            pointers = [ctypes.c_void_p(priors.data_ptr()), ctypes.c_void_p(values.data_ptr())]
+        _abi.check(getattr(_abi.lib(), self._entry)(
+            self.batch._handle, *(ctypes.c_int32(x) for x in self._scalars()), ctypes.c_uint32(flags), *pointers,
+            *(ctypes.c_void_p(x.data_ptr()) for x in self._outputs), ctypes.c_void_p(self._buffer.data_ptr()),
+            ctypes.c_size_t(self._buffer.numel())))
+        self._fresh = False
+        return self._outputs
+
+    def begin(self):
+        """Empty every tree (BGS_GUIDED_RESTART): the leaves that come back are the roots."""
+        return self._call(_abi.GUIDED_RESTART, None, None)
+
+    def step(self, priors, values):
+        """One simulation: apply (priors, values) to the leaves of the previous call, descend to the next leaves."""
+        return self._call(0, priors, values)
+
+    def _run(self, evaluate, simulations: int):
+        if simulations < 1:
+            raise ValueError(f"simulations must be >= 1 (got {simulations})")
+        outs = self.begin()
+        for _ in range(int(simulations) - 1):
+            outs = self.step(*evaluate(*(outs[i] for i in self._leaves)))
+        return self.finish(*evaluate(*(outs[i] for i in self._leaves)))
+
+
 class ConnectBatch(_Batch):
     """N Connect-k boards: ``Config(height, width, count)`` (reference connect.cpp:26) times n."""
 
     game = _abi.GAME_CONNECT
     _action_width = 1
+    _search_counters = ("best", "nodes")   # the int32[n] outputs of a tree search
+
+    def _per_action(self):
+        """the shape of an entry a column of every board"""
+        return (self.n, self.width)
 
     def _empty_legal(self):
         return np.empty((self.n, self.width), dtype=np.uint8)
@@ -837,16 +1018,6 @@ class ConnectBatch(_Batch):
         """columns int32[n]; a negative entry skips the board.  Returns per-board status (0 / -2 illegal)."""
         return self._step_actions(columns, 1, want_status)
 
-    def _evaluate(self, seed: int, playouts: int, max_plies: int, policy: str, pointer: int, on_device: int) -> None:
-        """the evaluation call of `policy`: "uniform" is bgs_connect_evaluate_actions itself, any other policy goes through
-        bgs_connect_evaluate_actions_policy"""
-        code = playout_policy(policy)
-        args = (self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts), ctypes.c_int32(max_plies))
-        if code == _abi.POLICY_UNIFORM:
-            _abi.check(_abi.lib().bgs_connect_evaluate_actions(*args, ctypes.c_void_p(pointer), on_device))
-        else:
-            _abi.check(_abi.lib().bgs_connect_evaluate_actions_policy(*args, code, ctypes.c_void_p(pointer), on_device))
-
     def evaluate_actions(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1,
                          policy: str = "uniform") -> np.ndarray:
         """Flat Monte-Carlo evaluation of every column of every board (bgs_connect_evaluate_actions), one launch:
@@ -857,19 +1028,13 @@ class ConnectBatch(_Batch):
         policy="decisive" (bgs_connect_evaluate_actions_policy): the same games and draws, but a ply takes a winning
         column when there is one, else blocks the opponent's winning column when there is one, else plays uniformly --
         the ply's draw indexes the winning, else the blocking, else the legal columns."""
-        playout_policy(policy)   # (an unknown name: before anything is allocated)
-        out = np.empty((self.n, self.width, 3), dtype=np.int32)
-        self._evaluate(seed, playouts, max_plies, policy, out.ctypes.data, 0)
-        return out
+        return self._evaluate("evaluate_actions", "bgs_connect_evaluate_actions", None, seed, playouts, max_plies, policy)
 
     def evaluate_actions_tensor(self, out=None, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1,
                                 policy: str = "uniform"):
         """`evaluate_actions` into a device tensor int32[n, width, 3] (allocated when None), enqueued on the batch's stream
         with no synchronisation.  Every entry is written."""
-        playout_policy(policy)
-        out, = self._device_tensors("evaluate_actions_tensor", [("out", out, (self.n, self.width, 3))])
-        self._evaluate(seed, playouts, max_plies, policy, out.data_ptr(), 1)
-        return out
+        return self._evaluate("evaluate_actions_tensor", "bgs_connect_evaluate_actions", (out,), seed, playouts, max_plies, policy)
 
     def halving_min_budget(self) -> int:
         """the least budget of `evaluate_actions_halving`: width * max(1, ceil(log2 width)), a playout a column a round"""
@@ -886,32 +1051,18 @@ class ConnectBatch(_Batch):
         move.  Playout p of column c of board i is game ((first_game + i) * width + c) * budget + p, played as
         `evaluate_actions(playouts=budget, policy=policy)` plays it: a column's counts are those of its first `given`
         playouts there.  The boards are not modified."""
-        code = playout_policy(policy)
-        counts = np.empty((self.n, self.width, 3), dtype=np.int32)
-        given = np.empty((self.n, self.width), dtype=np.int32)
-        best = np.empty(self.n, dtype=np.int32)
-        _abi.check(_abi.lib().bgs_connect_evaluate_actions_halving(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
-            ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(given.ctypes.data), ctypes.c_void_p(best.ctypes.data), 0))
-        return counts, given, best
+        return self._halving("evaluate_actions_halving", "bgs_connect_evaluate_actions_halving", None, seed, budget, max_plies, policy)
 
     def evaluate_actions_halving_tensor(self, counts=None, given=None, best=None, seed: int = DEFAULT_SEED, budget: int = 1024,
                                         max_plies: int = 2**31 - 1, policy: str = "uniform"):
         """`evaluate_actions_halving` into device tensors int32[n, width, 3], int32[n, width] and int32[n] (allocated when
         None), enqueued on the batch's stream with no synchronisation: (counts, given, best).  Every entry is written."""
-        code = playout_policy(policy)
-        outs = self._device_tensors("evaluate_actions_halving_tensor", [
-            ("counts", counts, (self.n, self.width, 3)), ("given", given, (self.n, self.width)), ("best", best, (self.n,))])
-        _abi.check(_abi.lib().bgs_connect_evaluate_actions_halving(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
-            *(ctypes.c_void_p(x.data_ptr()) for x in outs), 1))
-        return tuple(outs)
+        return self._halving("evaluate_actions_halving_tensor", "bgs_connect_evaluate_actions_halving", (counts, given, best), seed, budget,
+                             max_plies, policy)
 
     def search_workspace_bytes(self, iterations: int = 256) -> int:
         """bytes of device memory `search_actions` needs for its trees at `iterations` (bgs_connect_search_workspace_bytes)"""
-        nbytes = ctypes.c_size_t()
-        _abi.check(_abi.lib().bgs_connect_search_workspace_bytes(self._handle, ctypes.c_int32(iterations), ctypes.byref(nbytes)))
-        return nbytes.value
+        return self._size_query("bgs_connect_search_workspace_bytes", iterations)
 
     def search_actions(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE,
                        max_plies: int = 2**31 - 1, policy: str = "uniform"):
@@ -924,16 +1075,7 @@ class ConnectBatch(_Batch):
         to move, `best` the column with the most visits (-1 for an ended board), `nodes` the nodes made.  Playout j of
         iteration t of board i is game ((first_game + i) * iterations + t) * leaf_playouts + j of the batch's RNG contract.
         The boards are not modified; the library allocates the trees' memory around the call."""
-        code = playout_policy(policy)
-        counts = np.empty((self.n, self.width, 3), dtype=np.int32)
-        visits = np.empty((self.n, self.width), dtype=np.int32)
-        best = np.empty(self.n, dtype=np.int32)
-        nodes = np.empty(self.n, dtype=np.int32)
-        _abi.check(_abi.lib().bgs_connect_search_actions(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(visits.ctypes.data),
-            ctypes.c_void_p(best.ctypes.data), ctypes.c_void_p(nodes.ctypes.data), None, 0, 0))
-        return counts, visits, best, nodes
+        return self._search("search_actions", False, None, None, seed, iterations, leaf_playouts, explore, max_plies, policy)
 
     def search_actions_tensor(self, counts=None, visits=None, best=None, nodes=None, seed: int = DEFAULT_SEED, iterations: int = 256,
                               leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1,
@@ -943,20 +1085,14 @@ class ConnectBatch(_Batch):
         written.  `workspace`: a contiguous, 256-byte aligned uint8 device tensor of at least
         `search_workspace_bytes(iterations)` bytes; None: a tensor of the batch's own, allocated on first use and kept per
         `iterations`.  The workspace needs no preparation, and calls on one stream may share it."""
-        code = playout_policy(policy)
-        outs = self._device_tensors("search_actions_tensor", self._search_specs(counts, visits, best, nodes))
-        workspace = self._search_workspace("search_actions_tensor", workspace, lambda: self.search_workspace_bytes(iterations),
-                                           lambda: int(iterations))
-        _abi.check(_abi.lib().bgs_connect_search_actions(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, *(ctypes.c_void_p(x.data_ptr()) for x in outs),
-            ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
-        return tuple(outs)
+        return self._search("search_actions_tensor", False, (counts, visits, best, nodes), workspace, seed, iterations, leaf_playouts,
+                            explore, max_plies, policy)
 
-    def _search_specs(self, counts, visits, best, nodes):
-        """the four outputs every tree search of this batch has, as `_device_tensors` takes them"""
-        return [("counts", counts, (self.n, self.width, 3)), ("visits", visits, (self.n, self.width)), ("best", best, (self.n,)),
-                ("nodes", nodes, (self.n,))]
+    def _search(self, who: str, proving: bool, tensors, workspace, seed, iterations, leaf_playouts, explore, max_plies, policy):
+        """the plain or the proving tree search, host or tensor form; both share the workspaces cached per `iterations`"""
+        return self._analysis(who, "bgs_connect_search_actions_proving" if proving else "bgs_connect_search_actions",
+                              _playout_args(seed, policy, iterations, leaf_playouts, explore, max_plies), self._search_specs(proving),
+                              tensors, workspace, (lambda: self.search_workspace_bytes(iterations), lambda: int(iterations)))
 
     def search_actions_proving(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
                                explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1, policy: str = "uniform"):
@@ -969,19 +1105,7 @@ class ConnectBatch(_Batch):
         undecided, 0 for an ended board).  `best` is the proved win if there is one, else the most visited column among
         those not proved lost.  A root whose search tags nothing returns what `search_actions` returns.  The workspace is
         `search_actions`'s."""
-        code = playout_policy(policy)
-        counts = np.empty((self.n, self.width, 3), dtype=np.int32)
-        visits = np.empty((self.n, self.width), dtype=np.int32)
-        best = np.empty(self.n, dtype=np.int32)
-        nodes = np.empty(self.n, dtype=np.int32)
-        proved = np.empty((self.n, self.width), dtype=np.int8)
-        done = np.empty(self.n, dtype=np.int32)
-        _abi.check(_abi.lib().bgs_connect_search_actions_proving(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(visits.ctypes.data),
-            ctypes.c_void_p(best.ctypes.data), ctypes.c_void_p(nodes.ctypes.data), ctypes.c_void_p(proved.ctypes.data),
-            ctypes.c_void_p(done.ctypes.data), None, 0, 0))
-        return counts, visits, best, nodes, proved, done
+        return self._search("search_actions_proving", True, None, None, seed, iterations, leaf_playouts, explore, max_plies, policy)
 
     def search_actions_proving_tensor(self, counts=None, visits=None, best=None, nodes=None, proved=None, done=None,
                                       seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
@@ -991,22 +1115,12 @@ class ConnectBatch(_Batch):
         as in `search_actions_tensor`), enqueued on the batch's stream with no synchronisation: (counts, visits, best,
         nodes, proved, done).  Every entry is written.  `workspace` is `search_actions_tensor`'s, and the batch's own
         cached workspace serves both."""
-        code = playout_policy(policy)
-        outs = self._device_tensors("search_actions_proving_tensor", self._search_specs(counts, visits, best, nodes) + [
-            ("proved", proved, (self.n, self.width), "int8"), ("done", done, (self.n,))])
-        workspace = self._search_workspace("search_actions_proving_tensor", workspace,
-                                           lambda: self.search_workspace_bytes(iterations), lambda: int(iterations))
-        _abi.check(_abi.lib().bgs_connect_search_actions_proving(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, *(ctypes.c_void_p(x.data_ptr()) for x in outs),
-            ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
-        return tuple(outs)
+        return self._search("search_actions_proving_tensor", True, (counts, visits, best, nodes, proved, done), workspace, seed, iterations,
+                            leaf_playouts, explore, max_plies, policy)
 
     def forest_bytes(self, capacity: int) -> int:
         """bytes of device memory a forest of this batch takes at `capacity` nodes a tree (bgs_connect_forest_bytes)"""
-        nbytes = ctypes.c_size_t()
-        _abi.check(_abi.lib().bgs_connect_forest_bytes(self._handle, ctypes.c_int32(capacity), ctypes.byref(nbytes)))
-        return nbytes.value
+        return self._size_query("bgs_connect_forest_bytes", capacity)
 
     def search_forest(self, capacity: int) -> "SearchForest":
         """A forest for this batch: one search tree per board with room for `capacity` nodes, kept on the device from
@@ -1015,9 +1129,7 @@ class ConnectBatch(_Batch):
 
     def guided_bytes(self, capacity: int) -> int:
         """bytes of device memory the guided trees of this batch take at `capacity` nodes a tree (bgs_connect_guided_bytes)"""
-        nbytes = ctypes.c_size_t()
-        _abi.check(_abi.lib().bgs_connect_guided_bytes(self._handle, ctypes.c_int32(capacity), ctypes.byref(nbytes)))
-        return nbytes.value
+        return self._size_query("bgs_connect_guided_bytes", capacity)
 
     def guided_search(self, capacity: int, cpuct: int = DEFAULT_CPUCT) -> "GuidedSearch":
         """A PUCT search of this batch whose leaves the caller evaluates, e.g. with a policy/value network: one tree per
@@ -1031,26 +1143,15 @@ class ConnectBatch(_Batch):
         winner fastest, the loser slowest), SOLVE_DRAW 0 (plies: the board's empty cells), SOLVE_UNKNOWN 2 (the horizon
         cut some lines), SOLVE_BUDGET 3 (the search of that column visited more than `max_nodes` positions),
         SOLVE_NONE -2 (an illegal column or an ended board).  The boards and `steps` are not modified."""
-        depth = self.height * self.width if depth is None else int(depth)
-        codes = np.empty((self.n, self.width), dtype=np.int8)
-        plies = np.empty((self.n, self.width), dtype=np.int16) if with_plies else None
-        _abi.check(_abi.lib().bgs_connect_solve_actions(
-            self._handle, ctypes.c_int32(depth), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.ctypes.data),
-            None if plies is None else ctypes.c_void_p(plies.ctypes.data), None, 0))
-        return codes, plies
+        depth = self.height * self.width if depth is None else depth
+        return self._solve("solve_actions", "bgs_connect_solve_actions", None, depth, max_nodes, with_plies)
 
     def solve_actions_tensor(self, codes=None, plies=None, depth: Optional[int] = None, max_nodes: int = DEFAULT_SOLVE_NODES,
                              with_plies: bool = True):
         """`solve_actions` into device tensors int8[n, width] and int16[n, width] (allocated when None; plies only
         `with_plies` or when given), enqueued on the batch's stream with no synchronisation: (codes, plies or None)."""
-        shape = (self.n, self.width)
-        codes, plies = self._device_tensors("solve_actions_tensor", [("codes", codes, shape, "int8"),
-                                                                     ("plies", plies, shape, "int16", not with_plies)])
-        depth = self.height * self.width if depth is None else int(depth)
-        _abi.check(_abi.lib().bgs_connect_solve_actions(
-            self._handle, ctypes.c_int32(depth), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.data_ptr()),
-            None if plies is None else ctypes.c_void_p(plies.data_ptr()), None, 1))
-        return codes, plies
+        depth = self.height * self.width if depth is None else depth
+        return self._solve("solve_actions_tensor", "bgs_connect_solve_actions", (codes, plies), depth, max_nodes, with_plies)
 
     def solve_moves(self, *args, **kwargs):
         """Not available for Connect: solve_moves is the Bounce horizon search; Connect has `solve_actions`."""
@@ -1092,7 +1193,7 @@ class ConnectBatch(_Batch):
         return out
 
 
-class SearchForest:
+class SearchForest(_Forest):
     """One UCT tree per board of a ConnectBatch, kept on the device from search to search (bgs_connect_forest_search /
     bgs_connect_forest_advance, include/bgs.h): `ConnectBatch.search_forest(capacity)` makes one.  A tree has room for
     `capacity` nodes, the root included.
@@ -1105,27 +1206,16 @@ class SearchForest:
     The object owns the device buffer (a torch tensor) and belongs to the batch it was made from; its first search
     restarts every tree, whatever `restart` says, because fresh memory holds no trees."""
 
+    _search_entry, _advance_entry = "bgs_connect_forest_search", "bgs_connect_forest_advance"
+    _maker, _moves = "search_forest", "columns"
+
     def __init__(self, batch: ConnectBatch, capacity: int):
         self.batch = batch
         self.capacity = int(capacity)
-        nbytes = batch.forest_bytes(self.capacity)         # (refuses Bounce, generic boards and a bad capacity)
-        t = batch._need_torch("search_forest")
-        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")   # (zeros: every tree empty)
-        self._fresh = True
+        self._open(batch.forest_bytes(self.capacity))      # (refuses Bounce, generic boards and a bad capacity)
 
-    def close(self) -> None:
-        self._buffer = None
-
-    def _call(self, seed, iterations, leaf_playouts, explore, max_plies, policy, restart, pointers, on_device):
-        if self._buffer is None:
-            raise RuntimeError("the forest is closed")
-        code = playout_policy(policy)
-        _abi.check(_abi.lib().bgs_connect_forest_search(
-            self.batch._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts),
-            ctypes.c_int32(explore), ctypes.c_int32(max_plies), code, ctypes.c_int32(self.capacity),
-            1 if restart or self._fresh else 0, *(ctypes.c_void_p(p) for p in pointers), ctypes.c_void_p(self._buffer.data_ptr()),
-            ctypes.c_size_t(self._buffer.numel()), on_device))
-        self._fresh = False
+    def _sizes(self):
+        return (self.capacity,)
 
     def search(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE,
                max_plies: int = 2**31 - 1, policy: str = "uniform", restart: bool = False):
@@ -1135,52 +1225,29 @@ class SearchForest:
         the nodes it started with, the root not counted in either.  Vary `seed` from call to call: playout j of iteration
         t of board i is game ((first_game + i) * iterations + t) * leaf_playouts + j of every call.  `restart` empties
         every tree first."""
-        n, w = self.batch.n, self.batch.width
-        outs = (np.empty((n, w, 3), dtype=np.int32), np.empty((n, w), dtype=np.int32), np.empty(n, dtype=np.int32),
-                np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32))
-        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [o.ctypes.data for o in outs], 0)
-        return outs
+        return self._search(None, seed, iterations, leaf_playouts, explore, max_plies, policy, restart)
 
     def search_tensor(self, counts=None, visits=None, best=None, nodes=None, carried=None, seed: int = DEFAULT_SEED,
                       iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1,
                       policy: str = "uniform", restart: bool = False):
         """`search` into device tensors int32[n, width, 3], int32[n, width] and three int32[n] (allocated when None),
         enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes, carried)."""
-        outs = self.batch._device_tensors("search_tensor", self.batch._search_specs(counts, visits, best, nodes) + [
-            ("carried", carried, (self.batch.n,))])
-        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [x.data_ptr() for x in outs], 1)
-        return tuple(outs)
-
-    def _advance(self, columns: int, kept: int, on_device: int) -> None:
-        if self._buffer is None:
-            raise RuntimeError("the forest is closed")
-        _abi.check(_abi.lib().bgs_connect_forest_advance(
-            self.batch._handle, ctypes.c_void_p(columns), ctypes.c_int32(self.capacity), ctypes.c_void_p(kept),
-            ctypes.c_void_p(self._buffer.data_ptr()), ctypes.c_size_t(self._buffer.numel()), on_device))
+        return self._search((counts, visits, best, nodes, carried), seed, iterations, leaf_playouts, explore, max_plies, policy, restart)
 
     def advance(self, columns) -> np.ndarray:
         """Re-root every tree by its board's column (bgs_connect_forest_advance): columns int32[n], a negative entry
         leaves the tree as it is.  Returns kept int32[n], the nodes a tree holds afterwards, the root not counted: the
         subtree under the column, or 0 where there was none (the next search starts that tree anew).  The boards are
         neither read nor stepped: play the same columns with `ConnectBatch.step_actions`."""
-        columns = np.ascontiguousarray(columns, dtype=np.int32)
-        if columns.shape != (self.batch.n,):
-            raise TypeError(f"columns must be int32[{self.batch.n}]")
-        kept = np.empty(self.batch.n, dtype=np.int32)
-        self._advance(columns.ctypes.data, kept.ctypes.data, 0)
-        return kept
+        return self._advance(columns)
 
     def advance_tensor(self, columns, kept=None):
         """`advance` with `columns` and `kept` as int32[n] device tensors (kept allocated when None), enqueued on the
         batch's stream with no synchronisation: kept."""
-        shape = (self.batch.n,)   # (columns is an input: "optional", so that it is checked and never allocated)
-        columns, kept = self.batch._device_tensors("advance_tensor", [("columns", columns, shape, "int32", True),
-                                                                      ("kept", kept, shape)], align=1)
-        self._advance(columns.data_ptr(), kept.data_ptr(), 1)
-        return kept
+        return self._advance(columns, kept, on_device=True)
 
 
-class GuidedSearch:
+class GuidedSearch(_Guided):
     """PUCT tree search of a ConnectBatch with caller-evaluated leaves (bgs_connect_guided_step, include/bgs.h):
     `ConnectBatch.guided_search(capacity, cpuct)` makes one.  One tree per board, `capacity` nodes a tree, the root
     included; `cpuct` is c_puct in Q8 (320 = 1.25).
@@ -1197,51 +1264,20 @@ class GuidedSearch:
 
     The object owns the device buffer of the trees (a torch tensor) and belongs to the batch it was made from."""
 
+    _entry, _maker, _priors, _leaves = "bgs_connect_guided_step", "guided_search", "float32[n, width]", (0, 1)
+
     def __init__(self, batch: "ConnectBatch", capacity: int, cpuct: int = DEFAULT_CPUCT):
         self.batch = batch
         self.capacity = int(capacity)
         self.cpuct = int(cpuct)
-        if not 0 <= self.cpuct <= 4096:
-            raise ValueError(f"cpuct must be 0 .. 4096, c_puct in Q8 (got {cpuct})")
-        nbytes = batch.guided_bytes(self.capacity)         # (refuses Bounce, generic boards and a bad capacity)
-        t = batch._need_torch("guided_search")
+        self._check_cpuct(cpuct)
         n, h, w = batch.n, batch.height, batch.width
-        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")
-        self._outputs = tuple(batch._device_tensors("guided_search", [
-            ("leaf_grid", None, (n, h, w), "int8"), ("leaf_player", None, (n,), "int8"), ("leaf_kind", None, (n,)),
-            ("visits", None, (n, w)), ("scores", None, (n, w)), ("best", None, (n,)), ("nodes", None, (n,))]))
-        self._fresh = True
+        self._open(batch.guided_bytes(self.capacity),      # (refuses Bounce, generic boards and a bad capacity)
+                   [("leaf_grid", (n, h, w), "int8"), ("leaf_player", (n,), "int8"), ("leaf_kind", (n,)), ("visits", (n, w)),
+                    ("scores", (n, w)), ("best", (n,)), ("nodes", (n,))])
 
-    def close(self) -> None:
-        self._buffer = None
-
-    def _call(self, flags: int, priors, values):
-        if self._buffer is None:
-            raise RuntimeError("the guided search is closed")
-        if self._fresh and not flags & _abi.GUIDED_RESTART:
-            raise RuntimeError("begin() comes first: fresh memory holds no trees")
-        pointers = [None, None]
-        if not flags & _abi.GUIDED_RESTART:
-            n, w = self.batch.n, self.batch.width   # (inputs: "optional", so that they are checked and never allocated)
-            priors, values = self.batch._device_tensors("guided_search", [("priors", priors, (n, w), "float32", True),
-                                                                          ("values", values, (n,), "float32", True)])
-            if priors is None or values is None:
-                raise TypeError("priors and values are the evaluator's device tensors: float32[n, width] and float32[n]")
-            pointers = [ctypes.c_void_p(priors.data_ptr()), ctypes.c_void_p(values.data_ptr())]
-        _abi.check(_abi.lib().bgs_connect_guided_step(
-            self.batch._handle, ctypes.c_int32(self.capacity), ctypes.c_int32(self.cpuct), ctypes.c_uint32(flags), *pointers,
-            *(ctypes.c_void_p(x.data_ptr()) for x in self._outputs), ctypes.c_void_p(self._buffer.data_ptr()),
-            ctypes.c_size_t(self._buffer.numel())))
-        self._fresh = False
-        return self._outputs
-
-    def begin(self):
-        """Empty every tree (BGS_GUIDED_RESTART): the leaves that come back are the roots."""
-        return self._call(_abi.GUIDED_RESTART, None, None)
-
-    def step(self, priors, values):
-        """One simulation: apply (priors, values) to the leaves of the previous call, descend to the next leaves."""
-        return self._call(0, priors, values)
+    def _scalars(self):
+        return (self.capacity, self.cpuct)
 
     def finish(self, priors, values):
         """Apply (priors, values) to the leaves of the previous call and select nothing (BGS_GUIDED_FINISH): every
@@ -1252,12 +1288,7 @@ class GuidedSearch:
         """`begin`, `simulations` evaluations a tree, `finish`: evaluate(leaf_grid, leaf_player) -> (priors float32[n, w],
         values float32[n]) is called once a simulation on the device tensors of the leaves (the first call sees the
         roots) and returns device tensors.  Returns what `finish` returns."""
-        if simulations < 1:
-            raise ValueError(f"simulations must be >= 1 (got {simulations})")
-        outs = self.begin()
-        for _ in range(int(simulations) - 1):
-            outs = self.step(*evaluate(outs[0], outs[1]))
-        return self.finish(*evaluate(outs[0], outs[1]))
+        return self._run(evaluate, simulations)
 
 
 class BounceBatch(_Batch):
@@ -1265,6 +1296,11 @@ class BounceBatch(_Batch):
 
     game = _abi.GAME_BOUNCE
     _action_width = 4
+    _search_counters = ("best", "nodes", "used")   # the int32[n] outputs of a tree search
+
+    def _per_action(self):
+        """the shape of an entry a move slot of every board: [i, x, c] is the move of column x's piece to cell c"""
+        return (self.n, self.width, self.height * self.width)
 
     def _empty_legal(self):
         if self.generic:  # wide record: int32 active row, then uint8 flags[W][H * W] (include/bgs.h, bgs_legal_bytes)
@@ -1368,10 +1404,7 @@ class BounceBatch(_Batch):
     def guided_moves_bytes(self, nodes: int, edges: Optional[int] = None) -> int:
         """bytes of device memory the guided trees of this batch take at `nodes` nodes and `edges` pool edges a tree (None:
         `guided_default_edges(nodes)`; bgs_bounce_guided_bytes)"""
-        edges = self.guided_default_edges(nodes) if edges is None else int(edges)
-        nbytes = ctypes.c_size_t()
-        _abi.check(_abi.lib().bgs_bounce_guided_bytes(self._handle, ctypes.c_int32(nodes), ctypes.c_int32(edges), ctypes.byref(nbytes)))
-        return nbytes.value
+        return self._size_query("bgs_bounce_guided_bytes", nodes, self.guided_default_edges(nodes) if edges is None else int(edges))
 
     def guided_moves_search(self, nodes: int, edges: Optional[int] = None, cpuct: int = DEFAULT_CPUCT,
                             max_plies: int = 65535) -> "GuidedMovesSearch":
@@ -1387,16 +1420,6 @@ class BounceBatch(_Batch):
 
     solve_actions_tensor = solve_actions
 
-    def _evaluate_moves(self, seed: int, playouts: int, max_plies: int, policy: str, pointer: int, on_device: int) -> None:
-        """the evaluation call of `policy`: "uniform" is bgs_bounce_evaluate_moves itself, any other policy goes through
-        bgs_bounce_evaluate_moves_policy"""
-        code = playout_policy(policy)
-        args = (self._handle, ctypes.c_uint64(seed), ctypes.c_int32(playouts), ctypes.c_int32(max_plies))
-        if code == _abi.POLICY_UNIFORM:
-            _abi.check(_abi.lib().bgs_bounce_evaluate_moves(*args, ctypes.c_void_p(pointer), on_device))
-        else:
-            _abi.check(_abi.lib().bgs_bounce_evaluate_moves_policy(*args, code, ctypes.c_void_p(pointer), on_device))
-
     def evaluate_moves(self, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1,
                        policy: str = "uniform") -> np.ndarray:
         """Flat Monte-Carlo evaluation of every legal move of every board (bgs_bounce_evaluate_moves), one launch:
@@ -1408,19 +1431,13 @@ class BounceBatch(_Batch):
         policy="decisive" (bgs_bounce_evaluate_moves_policy): the same games and draws, but a ply whose side to move can
         land in its goal row does so -- the ply's draw indexes the winning moves, else all moves.  There is no blocking
         step."""
-        playout_policy(policy)   # (an unknown name: before anything is allocated)
-        out = np.empty((self.n, self.width, self.height * self.width, 3), dtype=np.int32)
-        self._evaluate_moves(seed, playouts, max_plies, policy, out.ctypes.data, 0)
-        return out
+        return self._evaluate("evaluate_moves", "bgs_bounce_evaluate_moves", None, seed, playouts, max_plies, policy)
 
     def evaluate_moves_tensor(self, out=None, seed: int = DEFAULT_SEED, playouts: int = 256, max_plies: int = 2**31 - 1,
                               policy: str = "uniform"):
         """`evaluate_moves` into a device tensor int32[n, W, H * W, 3] (allocated when None), enqueued on the batch's stream
         with no synchronisation.  Every entry is written."""
-        playout_policy(policy)
-        out, = self._device_tensors("evaluate_moves_tensor", [("out", out, (self.n, self.width, self.height * self.width, 3))])
-        self._evaluate_moves(seed, playouts, max_plies, policy, out.data_ptr(), 1)
-        return out
+        return self._evaluate("evaluate_moves_tensor", "bgs_bounce_evaluate_moves", (out,), seed, playouts, max_plies, policy)
 
     @staticmethod
     def halving_min_budget(moves: int) -> int:
@@ -1442,29 +1459,15 @@ class BounceBatch(_Batch):
         Playout p of slot s of board i is game ((first_game + i) * W * H * W + s) * budget + p, played as
         `evaluate_moves(playouts=budget, policy=policy)` plays it: a move's counts are those of its first `given`
         playouts there.  The boards are not modified."""
-        code = playout_policy(policy)
-        shape = (self.n, self.width, self.height * self.width)
-        counts = np.empty(shape + (3,), dtype=np.int32)
-        given = np.empty(shape, dtype=np.int32)
-        best = np.empty(self.n, dtype=np.int32)
-        _abi.check(_abi.lib().bgs_bounce_evaluate_moves_halving(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
-            ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(given.ctypes.data), ctypes.c_void_p(best.ctypes.data), 0))
-        return counts, given, best
+        return self._halving("evaluate_moves_halving", "bgs_bounce_evaluate_moves_halving", None, seed, budget, max_plies, policy)
 
     def evaluate_moves_halving_tensor(self, counts=None, given=None, best=None, seed: int = DEFAULT_SEED, budget: int = 1024,
                                       max_plies: int = 2**31 - 1, policy: str = "uniform"):
         """`evaluate_moves_halving` into device tensors int32[n, W, H * W, 3], int32[n, W, H * W] and int32[n] (allocated
         when None), enqueued on the batch's stream with no synchronisation: (counts, given, best).  Every entry is
         written."""
-        code = playout_policy(policy)
-        slots = (self.n, self.width, self.height * self.width)
-        outs = self._device_tensors("evaluate_moves_halving_tensor", [
-            ("counts", counts, slots + (3,)), ("given", given, slots), ("best", best, (self.n,))])
-        _abi.check(_abi.lib().bgs_bounce_evaluate_moves_halving(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(budget), ctypes.c_int32(max_plies), code,
-            *(ctypes.c_void_p(x.data_ptr()) for x in outs), 1))
-        return tuple(outs)
+        return self._halving("evaluate_moves_halving_tensor", "bgs_bounce_evaluate_moves_halving", (counts, given, best), seed, budget,
+                             max_plies, policy)
 
     def search_min_edges(self) -> int:
         """BGS_BOUNCE_SEARCH_MIN_EDGES(H, W): the most arms a position of this geometry can have, W * W * (H - 2)"""
@@ -1481,10 +1484,7 @@ class BounceBatch(_Batch):
         """bytes of device memory `search_moves` needs for its trees at `iterations` and `edges` (None: the default pool;
         bgs_bounce_search_workspace_bytes)"""
         edges = self.search_default_edges(iterations) if edges is None else int(edges)
-        nbytes = ctypes.c_size_t()
-        _abi.check(_abi.lib().bgs_bounce_search_workspace_bytes(self._handle, ctypes.c_int32(iterations), ctypes.c_int32(edges),
-                                                                ctypes.byref(nbytes)))
-        return nbytes.value
+        return self._size_query("bgs_bounce_search_workspace_bytes", iterations, edges)
 
     def search_moves(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE,
                      max_plies: int = 2**31 - 1, policy: str = "uniform", edges: Optional[int] = None):
@@ -1502,18 +1502,7 @@ class BounceBatch(_Batch):
         not made and its edge is tried again later: used + (the arms of some position) > edges says the pool ran dry.
         Playout j of iteration t of board i is game ((first_game + i) * iterations + t) * leaf_playouts + j; `max_plies`
         is clamped to 65535.  The boards are not modified; the library allocates the trees' memory around the call."""
-        code = playout_policy(policy)
-        edges = self.search_default_edges(iterations) if edges is None else int(edges)
-        shape = (self.n, self.width, self.height * self.width)
-        counts = np.empty(shape + (3,), dtype=np.int32)
-        visits = np.empty(shape, dtype=np.int32)
-        best, nodes, used = (np.empty(self.n, dtype=np.int32) for _ in range(3))
-        _abi.check(_abi.lib().bgs_bounce_search_moves(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), ctypes.c_void_p(counts.ctypes.data),
-            ctypes.c_void_p(visits.ctypes.data), ctypes.c_void_p(best.ctypes.data), ctypes.c_void_p(nodes.ctypes.data),
-            ctypes.c_void_p(used.ctypes.data), None, 0, 0))
-        return counts, visits, best, nodes, used
+        return self._search("search_moves", False, None, None, seed, iterations, leaf_playouts, explore, max_plies, policy, edges)
 
     def search_moves_tensor(self, counts=None, visits=None, best=None, nodes=None, used=None, seed: int = DEFAULT_SEED,
                             iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1,
@@ -1523,24 +1512,17 @@ class BounceBatch(_Batch):
         is written.  `workspace`: a contiguous, 256-byte aligned uint8 device tensor of at least
         `search_moves_workspace_bytes(iterations, edges)` bytes; None: a tensor of the batch's own, allocated on first use
         and kept per (iterations, edges).  The workspace needs no preparation, and calls on one stream may share it."""
-        code = playout_policy(policy)
-        self._need_torch("search_moves_tensor")
-        edges = self.search_default_edges(iterations) if edges is None else int(edges)
-        outs = self._device_tensors("search_moves_tensor", self._search_specs(counts, visits, best, nodes, used))
-        workspace = self._search_workspace("search_moves_tensor", workspace,
-                                           lambda: self.search_moves_workspace_bytes(iterations, edges),
-                                           lambda: (int(iterations), edges))
-        _abi.check(_abi.lib().bgs_bounce_search_moves(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), *(ctypes.c_void_p(x.data_ptr()) for x in outs),
-            ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
-        return tuple(outs)
+        return self._search("search_moves_tensor", False, (counts, visits, best, nodes, used), workspace, seed, iterations, leaf_playouts,
+                            explore, max_plies, policy, edges)
 
-    def _search_specs(self, counts, visits, best, nodes, used):
-        """the five outputs every tree search of this batch has, as `_device_tensors` takes them"""
-        slots = (self.n, self.width, self.height * self.width)
-        return [("counts", counts, slots + (3,)), ("visits", visits, slots), ("best", best, (self.n,)), ("nodes", nodes, (self.n,)),
-                ("used", used, (self.n,))]
+    def _search(self, who: str, proving: bool, tensors, workspace, seed, iterations, leaf_playouts, explore, max_plies, policy, edges):
+        """the plain or the proving tree search, host or tensor form, with the default edge pool for edges=None; both share
+        the workspaces cached per (iterations, edges)"""
+        scalars = _playout_args(seed, policy, iterations, leaf_playouts, explore, max_plies)
+        edges = self.search_default_edges(iterations) if edges is None else int(edges)
+        return self._analysis(who, "bgs_bounce_search_moves_proving" if proving else "bgs_bounce_search_moves",
+                              scalars + [ctypes.c_int32(edges)], self._search_specs(proving), tensors, workspace,
+                              (lambda: self.search_moves_workspace_bytes(iterations, edges), lambda: (int(iterations), edges)))
 
     def search_moves_proving(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
                              explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1, policy: str = "uniform",
@@ -1555,19 +1537,7 @@ class BounceBatch(_Batch):
         moves).  `best` is the proved win if there is one, else the most visited move among those not proved lost.  A
         move whose position holds the cap proves nothing.  A root whose search plays no move that ends the game returns
         what `search_moves` returns.  The workspace and `edges` are `search_moves`'s."""
-        code = playout_policy(policy)
-        edges = self.search_default_edges(iterations) if edges is None else int(edges)
-        shape = (self.n, self.width, self.height * self.width)
-        counts = np.empty(shape + (3,), dtype=np.int32)
-        visits = np.empty(shape, dtype=np.int32)
-        best, nodes, used, done = (np.empty(self.n, dtype=np.int32) for _ in range(4))
-        proved = np.empty(shape, dtype=np.int8)
-        _abi.check(_abi.lib().bgs_bounce_search_moves_proving(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), ctypes.c_void_p(counts.ctypes.data),
-            ctypes.c_void_p(visits.ctypes.data), ctypes.c_void_p(best.ctypes.data), ctypes.c_void_p(nodes.ctypes.data),
-            ctypes.c_void_p(used.ctypes.data), ctypes.c_void_p(proved.ctypes.data), ctypes.c_void_p(done.ctypes.data), None, 0, 0))
-        return counts, visits, best, nodes, used, proved, done
+        return self._search("search_moves_proving", True, None, None, seed, iterations, leaf_playouts, explore, max_plies, policy, edges)
 
     def search_moves_proving_tensor(self, counts=None, visits=None, best=None, nodes=None, used=None, proved=None, done=None,
                                     seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64,
@@ -1577,27 +1547,14 @@ class BounceBatch(_Batch):
         as in `search_moves_tensor`), enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes,
         used, proved, done).  Every entry is written.  `workspace` is `search_moves_tensor`'s, and the batch's own cached
         workspace serves both."""
-        code = playout_policy(policy)
-        self._need_torch("search_moves_proving_tensor")
-        edges = self.search_default_edges(iterations) if edges is None else int(edges)
-        outs = self._device_tensors("search_moves_proving_tensor", self._search_specs(counts, visits, best, nodes, used) + [
-            ("proved", proved, (self.n, self.width, self.height * self.width), "int8"), ("done", done, (self.n,))])
-        workspace = self._search_workspace("search_moves_proving_tensor", workspace,
-                                           lambda: self.search_moves_workspace_bytes(iterations, edges),
-                                           lambda: (int(iterations), edges))
-        _abi.check(_abi.lib().bgs_bounce_search_moves_proving(
-            self._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts), ctypes.c_int32(explore),
-            ctypes.c_int32(max_plies), code, ctypes.c_int32(edges), *(ctypes.c_void_p(x.data_ptr()) for x in outs),
-            ctypes.c_void_p(workspace.data_ptr()), ctypes.c_size_t(workspace.numel()), 1))
-        return tuple(outs)
+        return self._search("search_moves_proving_tensor", True, (counts, visits, best, nodes, used, proved, done), workspace, seed,
+                            iterations, leaf_playouts, explore, max_plies, policy, edges)
 
     def moves_forest_bytes(self, nodes: int, edges: Optional[int] = None) -> int:
         """bytes of device memory a forest of this batch takes at `nodes` nodes and `edges` pool edges a tree (None: the
         default pool of `search_moves_forest`; bgs_bounce_forest_bytes)"""
         edges = self.search_default_edges(int(nodes) - 1) if edges is None else int(edges)
-        nbytes = ctypes.c_size_t()
-        _abi.check(_abi.lib().bgs_bounce_forest_bytes(self._handle, ctypes.c_int32(nodes), ctypes.c_int32(edges), ctypes.byref(nbytes)))
-        return nbytes.value
+        return self._size_query("bgs_bounce_forest_bytes", nodes, edges)
 
     def search_moves_forest(self, nodes: int, edges: Optional[int] = None) -> "MovesForest":
         """A forest for this batch: one search tree per board with room for `nodes` nodes, the root included, and `edges`
@@ -1647,25 +1604,13 @@ class BounceBatch(_Batch):
         itself ends the game as a draw; plies 1), SOLVE_UNKNOWN 2 (neither side can force a win within the horizon),
         SOLVE_BUDGET 3 (the search of that move visited more than `max_nodes` positions), SOLVE_NONE -2 (an illegal slot,
         an ended board).  The boards and `steps` are not modified."""
-        shape = (self.n, self.width, self.height * self.width)
-        codes = np.empty(shape, dtype=np.int8)
-        plies = np.empty(shape, dtype=np.int16) if with_plies else None
-        _abi.check(_abi.lib().bgs_bounce_solve_moves(
-            self._handle, ctypes.c_int32(int(depth)), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.ctypes.data),
-            None if plies is None else ctypes.c_void_p(plies.ctypes.data), None, 0))
-        return codes, plies
+        return self._solve("solve_moves", "bgs_bounce_solve_moves", None, depth, max_nodes, with_plies)
 
     def solve_moves_tensor(self, codes=None, plies=None, depth: int = DEFAULT_BOUNCE_SOLVE_DEPTH,
                            max_nodes: int = DEFAULT_SOLVE_NODES, with_plies: bool = True):
         """`solve_moves` into device tensors int8[n, W, H * W] and int16[n, W, H * W] (allocated when None; plies only
         `with_plies` or when given), enqueued on the batch's stream with no synchronisation: (codes, plies or None)."""
-        shape = (self.n, self.width, self.height * self.width)
-        codes, plies = self._device_tensors("solve_moves_tensor", [("codes", codes, shape, "int8"),
-                                                                   ("plies", plies, shape, "int16", not with_plies)])
-        _abi.check(_abi.lib().bgs_bounce_solve_moves(
-            self._handle, ctypes.c_int32(int(depth)), ctypes.c_int64(max_nodes), ctypes.c_void_p(codes.data_ptr()),
-            None if plies is None else ctypes.c_void_p(plies.data_ptr()), None, 1))
-        return codes, plies
+        return self._solve("solve_moves_tensor", "bgs_bounce_solve_moves", (codes, plies), depth, max_nodes, with_plies)
 
     def step_actions(self, moves, want_status: bool = True):
         """moves int32[n, 4] = source x, y, target x, y; a negative first entry skips the board."""
@@ -1691,7 +1636,7 @@ class BounceBatch(_Batch):
         return out
 
 
-class MovesForest:
+class MovesForest(_Forest):
     """One UCT tree per board of a BounceBatch, kept on the device from search to search (bgs_bounce_forest_search /
     bgs_bounce_forest_advance, include/bgs.h): `BounceBatch.search_moves_forest(nodes, edges)` makes one.  A tree has room
     for `nodes` nodes, the root included, and `edges` pool edges.
@@ -1706,28 +1651,17 @@ class MovesForest:
     The object owns the device buffer (a torch tensor) and belongs to the batch it was made from; its first search
     restarts every tree, whatever `restart` says, because fresh memory holds no trees."""
 
+    _search_entry, _advance_entry = "bgs_bounce_forest_search", "bgs_bounce_forest_advance"
+    _maker, _moves = "search_moves_forest", "slots"
+
     def __init__(self, batch: BounceBatch, nodes: int, edges: Optional[int] = None):
         self.batch = batch
         self.nodes = int(nodes)
         self.edges = batch.search_default_edges(self.nodes - 1) if edges is None else int(edges)
-        nbytes = batch.moves_forest_bytes(self.nodes, self.edges)     # (refuses Connect, generic boards, bad nodes or edges)
-        t = batch._need_torch("search_moves_forest")
-        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")   # (zeros: every tree empty)
-        self._fresh = True
+        self._open(batch.moves_forest_bytes(self.nodes, self.edges))     # (refuses Connect, generic boards, bad nodes or edges)
 
-    def close(self) -> None:
-        self._buffer = None
-
-    def _call(self, seed, iterations, leaf_playouts, explore, max_plies, policy, restart, pointers, on_device):
-        if self._buffer is None:
-            raise RuntimeError("the forest is closed")
-        code = playout_policy(policy)
-        _abi.check(_abi.lib().bgs_bounce_forest_search(
-            self.batch._handle, ctypes.c_uint64(seed), ctypes.c_int32(iterations), ctypes.c_int32(leaf_playouts),
-            ctypes.c_int32(explore), ctypes.c_int32(max_plies), code, ctypes.c_int32(self.nodes), ctypes.c_int32(self.edges),
-            1 if restart or self._fresh else 0, *(ctypes.c_void_p(p) for p in pointers), ctypes.c_void_p(self._buffer.data_ptr()),
-            ctypes.c_size_t(self._buffer.numel()), on_device))
-        self._fresh = False
+    def _sizes(self):
+        return (self.nodes, self.edges)
 
     def search(self, seed: int = DEFAULT_SEED, iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE,
                max_plies: int = 2**31 - 1, policy: str = "uniform", restart: bool = False):
@@ -1739,28 +1673,15 @@ class MovesForest:
         node count.  Vary `seed` from call to call: playout j of iteration t of board i is game ((first_game + i) *
         iterations + t) * leaf_playouts + j of every call.  `max_plies` is clamped to 65535, and a tree grown under
         another cap is started anew.  `restart` empties every tree first."""
-        n, w, hw = self.batch.n, self.batch.width, self.batch.height * self.batch.width
-        outs = (np.empty((n, w, hw, 3), dtype=np.int32), np.empty((n, w, hw), dtype=np.int32)) + tuple(
-            np.empty(n, dtype=np.int32) for _ in range(4))
-        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [o.ctypes.data for o in outs], 0)
-        return outs
+        return self._search(None, seed, iterations, leaf_playouts, explore, max_plies, policy, restart)
 
     def search_tensor(self, counts=None, visits=None, best=None, nodes=None, used=None, carried=None, seed: int = DEFAULT_SEED,
                       iterations: int = 256, leaf_playouts: int = 64, explore: int = DEFAULT_EXPLORE, max_plies: int = 2**31 - 1,
                       policy: str = "uniform", restart: bool = False):
         """`search` into device tensors int32[n, W, H * W, 3], int32[n, W, H * W] and four int32[n] (allocated when None),
         enqueued on the batch's stream with no synchronisation: (counts, visits, best, nodes, used, carried)."""
-        outs = self.batch._device_tensors("search_tensor", self.batch._search_specs(counts, visits, best, nodes, used) + [
-            ("carried", carried, (self.batch.n,))])
-        self._call(seed, iterations, leaf_playouts, explore, max_plies, policy, restart, [x.data_ptr() for x in outs], 1)
-        return tuple(outs)
-
-    def _advance(self, slots: int, kept: int, on_device: int) -> None:
-        if self._buffer is None:
-            raise RuntimeError("the forest is closed")
-        _abi.check(_abi.lib().bgs_bounce_forest_advance(
-            self.batch._handle, ctypes.c_void_p(slots), ctypes.c_int32(self.nodes), ctypes.c_int32(self.edges), ctypes.c_void_p(kept),
-            ctypes.c_void_p(self._buffer.data_ptr()), ctypes.c_size_t(self._buffer.numel()), on_device))
+        return self._search((counts, visits, best, nodes, used, carried), seed, iterations, leaf_playouts, explore, max_plies, policy,
+                            restart)
 
     def advance(self, slots) -> np.ndarray:
         """Re-root every tree by its board's move (bgs_bounce_forest_advance): slots int32[n] in the encoding of `best`
@@ -1768,24 +1689,15 @@ class MovesForest:
         kept int32[n], the nodes a tree holds afterwards, the root not counted: the subtree under the move, or 0 where
         there was none (the next search starts that tree anew).  The boards are neither read nor stepped: play the same
         moves with `BounceBatch.step_actions`."""
-        slots = np.ascontiguousarray(slots, dtype=np.int32)
-        if slots.shape != (self.batch.n,):
-            raise TypeError(f"slots must be int32[{self.batch.n}]")
-        kept = np.empty(self.batch.n, dtype=np.int32)
-        self._advance(slots.ctypes.data, kept.ctypes.data, 0)
-        return kept
+        return self._advance(slots)
 
     def advance_tensor(self, slots, kept=None):
         """`advance` with `slots` and `kept` as int32[n] device tensors (kept allocated when None), enqueued on the
         batch's stream with no synchronisation: kept."""
-        shape = (self.batch.n,)   # (slots is an input: "optional", so that it is checked and never allocated)
-        slots, kept = self.batch._device_tensors("advance_tensor", [("slots", slots, shape, "int32", True),
-                                                                    ("kept", kept, shape)], align=1)
-        self._advance(slots.data_ptr(), kept.data_ptr(), 1)
-        return kept
+        return self._advance(slots, kept, on_device=True)
 
 
-class GuidedMovesSearch:
+class GuidedMovesSearch(_Guided):
     """PUCT tree search of a BounceBatch with caller-evaluated leaves (bgs_bounce_guided_step, include/bgs.h):
     `BounceBatch.guided_moves_search(nodes, edges, cpuct, max_plies)` makes one.  One tree per board, `nodes` nodes a tree,
     the root included, and `edges` pool edges; `cpuct` is c_puct in Q8 (320 = 1.25); `max_plies` is clamped to 65535.
@@ -1804,6 +1716,8 @@ class GuidedMovesSearch:
 
     The object owns the device buffer of the trees (a torch tensor) and belongs to the batch it was made from."""
 
+    _entry, _maker, _priors, _leaves = "bgs_bounce_guided_step", "guided_moves_search", "float32[n, W, H * W]", (0, 1, 3)
+
     def __init__(self, batch: "BounceBatch", nodes: int, edges: Optional[int] = None, cpuct: int = DEFAULT_CPUCT,
                  max_plies: int = 65535):
         self.batch = batch
@@ -1811,52 +1725,16 @@ class GuidedMovesSearch:
         self.edges = batch.guided_default_edges(self.nodes) if edges is None else int(edges)
         self.cpuct = int(cpuct)
         self.max_plies = int(max_plies)
-        if not 0 <= self.cpuct <= 4096:
-            raise ValueError(f"cpuct must be 0 .. 4096, c_puct in Q8 (got {cpuct})")
+        self._check_cpuct(cpuct)
         if self.max_plies < 1:
             raise ValueError(f"max_plies must be >= 1 (got {max_plies})")
-        nbytes = batch.guided_moves_bytes(self.nodes, self.edges)     # (refuses Connect, generic boards, bad nodes or edges)
-        t = batch._need_torch("guided_moves_search")
         n, h, w = batch.n, batch.height, batch.width
-        self._buffer = t.zeros(nbytes, dtype=t.uint8, device=f"cuda:{batch.device}")
-        self._outputs = tuple(batch._device_tensors("guided_moves_search", [
-            ("leaf_grid", None, (n, h, w), "int8"), ("leaf_player", None, (n,), "int8"), ("leaf_kind", None, (n,)),
-            ("leaf_targets", None, (n, w), "int64"), ("visits", None, (n, w, h * w)), ("scores", None, (n, w, h * w)),
-            ("best", None, (n,)), ("nodes", None, (n,)), ("used", None, (n,))]))
-        self._fresh = True
+        self._open(batch.guided_moves_bytes(self.nodes, self.edges),     # (refuses Connect, generic boards, bad nodes or edges)
+                   [("leaf_grid", (n, h, w), "int8"), ("leaf_player", (n,), "int8"), ("leaf_kind", (n,)), ("leaf_targets", (n, w), "int64"),
+                    ("visits", (n, w, h * w)), ("scores", (n, w, h * w)), ("best", (n,)), ("nodes", (n,)), ("used", (n,))])
 
-    def close(self) -> None:
-        self._buffer = None
-
-    def _call(self, flags: int, priors, values):
-        if self._buffer is None:
-            raise RuntimeError("the guided search is closed")
-        if self._fresh and not flags & _abi.GUIDED_RESTART:
-            raise RuntimeError("begin() comes first: fresh memory holds no trees")
-        pointers = [None, None]
-        if not flags & _abi.GUIDED_RESTART:
-            n, w, hw = self.batch.n, self.batch.width, self.batch.height * self.batch.width
-            # (inputs: "optional", so that they are checked and never allocated)
-            priors, values = self.batch._device_tensors("guided_moves_search", [("priors", priors, (n, w, hw), "float32", True),
-                                                                                ("values", values, (n,), "float32", True)])
-            if priors is None or values is None:
-                raise TypeError("priors and values are the evaluator's device tensors: float32[n, W, H * W] and float32[n]")
-            pointers = [ctypes.c_void_p(priors.data_ptr()), ctypes.c_void_p(values.data_ptr())]
-        _abi.check(_abi.lib().bgs_bounce_guided_step(
-            self.batch._handle, ctypes.c_int32(self.nodes), ctypes.c_int32(self.edges), ctypes.c_int32(self.cpuct),
-            ctypes.c_int32(min(self.max_plies, 2**31 - 1)), ctypes.c_uint32(flags), *pointers,
-            *(ctypes.c_void_p(x.data_ptr()) for x in self._outputs), ctypes.c_void_p(self._buffer.data_ptr()),
-            ctypes.c_size_t(self._buffer.numel())))
-        self._fresh = False
-        return self._outputs
-
-    def begin(self):
-        """Empty every tree (BGS_GUIDED_RESTART): the leaves that come back are the roots."""
-        return self._call(_abi.GUIDED_RESTART, None, None)
-
-    def step(self, priors, values):
-        """One simulation: apply (priors, values) to the leaves of the previous call, descend to the next leaves."""
-        return self._call(0, priors, values)
+    def _scalars(self):
+        return (self.nodes, self.edges, self.cpuct, min(self.max_plies, 2**31 - 1))
 
     def finish(self, priors, values):
         """Apply (priors, values) to the leaves of the previous call and select nothing (BGS_GUIDED_FINISH): every
@@ -1867,9 +1745,4 @@ class GuidedMovesSearch:
         """`begin`, `simulations` evaluations a tree, `finish`: evaluate(leaf_grid, leaf_player, leaf_targets) -> (priors
         float32[n, W, H * W], values float32[n]) is called once a simulation on the device tensors of the leaves (the first
         call sees the roots) and returns device tensors.  Returns what `finish` returns."""
-        if simulations < 1:
-            raise ValueError(f"simulations must be >= 1 (got {simulations})")
-        outs = self.begin()
-        for _ in range(int(simulations) - 1):
-            outs = self.step(*evaluate(outs[0], outs[1], outs[3]))
-        return self.finish(*evaluate(outs[0], outs[1], outs[3]))
+        return self._run(evaluate, simulations)
