@@ -1391,6 +1391,25 @@ int bgs_connect_guided_step(bgs_batch* b, int32_t capacity, int32_t cpuct, uint3
     return finish_launch();
 }
 
+int bgs_connect_guided_advance(bgs_batch* b, const int32_t* columns, int32_t capacity, int32_t* kept, void* trees, size_t trees_bytes) {
+    int rc = enter(b);
+    if (rc) return rc;
+    size_t need = 0;
+    rc = connect_guided_check(b, capacity, &need);
+    if (rc) return rc;
+    NEED(capacity <= BGS_GUIDED_ADVANCE_MAX_CAPACITY,
+         "capacity must be at most %d nodes a tree for an advance: the re-rooting keeps its scratch on the chip (got %d)",
+         BGS_GUIDED_ADVANCE_MAX_CAPACITY, capacity);
+    NEED(columns != nullptr, "columns is NULL");
+    NEED(trees != nullptr, "trees is NULL (the caller owns them; bgs_connect_guided_bytes says how large)");
+    NEED((reinterpret_cast<uintptr_t>(trees) & 255u) == 0, "trees must be 256-byte aligned");
+    NEED((reinterpret_cast<uintptr_t>(columns) & 15u) == 0, "device columns must be 16-byte aligned");
+    NEED((reinterpret_cast<uintptr_t>(kept) & 15u) == 0, "device kept must be 16-byte aligned");
+    NEED(trees_bytes >= need, "the trees are too small: %zu bytes, %zu needed", trees_bytes, need);
+    bgs::connect_guided_advance(b, columns, capacity, kept, trees);
+    return finish_launch();
+}
+
 // the outputs of both solvers; d[2], the node counter, keeps its 8-byte rule, and without a caller's counter the total
 // goes to the batch's own scratch word (behind the work-queue head)
 static void add_solve_outputs(bgs::OutputPlan& plan, size_t cells, int8_t* codes, int16_t* plies, uint64_t* nodes) {

@@ -162,6 +162,9 @@ uint64_t connect_guided_tree_bytes(int height, int width, int32_t capacity);
 void connect_guided_step(const bgs_batch* b, int32_t capacity, int32_t cpuct, uint32_t flags, const float* d_priors,
                          const float* d_values, int8_t* d_leaf_grid, int8_t* d_leaf_player, int32_t* d_leaf_kind, int32_t* d_visits,
                          int32_t* d_scores, int32_t* d_best, int32_t* d_nodes, void* d_trees);
+// the re-rooting of those trees (bgs_connect_guided_advance): d_columns int32[n] on the device, d_kept int32[n] may be
+// NULL, capacity <= BGS_GUIDED_ADVANCE_MAX_CAPACITY; enqueued on the batch's stream, the boards are not touched
+void connect_guided_advance(const bgs_batch* b, const int32_t* d_columns, int32_t capacity, int32_t* d_kept, void* d_trees);
 // exact alpha-beta solve of every column of packed Connect boards (bgs_connect_solve_actions; solve_kernels.hip): codes int8[n][w], plies
 // int16[n][w] (may be NULL), *d_nodes = positions visited; device pointers, enqueued on the batch's stream
 void connect_solve(const bgs_batch* b, int32_t depth, int64_t max_nodes, int8_t* d_codes, int16_t* d_plies,

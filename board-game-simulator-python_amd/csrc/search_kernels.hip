@@ -852,6 +852,148 @@ k_connect_search_guided(EvalGeom g, const uint64_t* __restrict__ planes, const u
     }
 }
 
+// The re-rooting of the guided trees (bgs_connect_guided_advance): k_connect_forest_advance on the guided share -- one
+// wave a tree, in place, one launch over exactly the trees of the launch, with that kernel's mark, number, move and header
+// passes on nodes of 4 * width words, of which words 2 * width .. 3 * width - 1 are the child words.  The three passes are a
+// second text: one `__device__` function for both kernels changed the forest kernel's instruction order (same size, same
+// registers, other bytes), and that kernel stays byte for byte what it was (docs/EXPERIMENTS.md).  What differs is the
+// header: the planes stand at word 4, and a tree that was advanced has nothing pending (words 1 and 2 cleared: the
+// pending path named nodes by their old indices) and a root that has its P (word 3: the new root was made by an
+// application, which gave it P).  An emptied tree has words 0 .. 3 zero, as the step's check leaves it.  c < 0 touches
+// nothing, a pending leaf included.
+// Bounds: the count is used only up to `capacity`, the child word of the root's edge only below the count, the column only
+// below the width, the stone's cell only below the height, a child word only above its node and below the count (so a
+// store goes to a slot at or below the node it moves): memory that passes the step's check by accident gives a wrong
+// tree, never a wild store.
+// LDS: the two mask arrays (`capacity` bits and a 32nd of a word a node, each rounded up to 16 bytes) and a chunk of 64
+// nodes: 2 * 8 KB + 16 KB = 32 KB at capacity 65536 and width 16 (BGS_GUIDED_ADVANCE_MAX_CAPACITY).
+static_assert(BGS_GUIDED_ADVANCE_MAX_CAPACITY <= BGS_GUIDED_MAX_CAPACITY, "an advanced tree is a guided tree");
+static_assert((2u * ((BGS_GUIDED_ADVANCE_MAX_CAPACITY + 31u) / 32u + 3u) + 64u * 16u * 4u) * sizeof(uint32_t) <= 64u * 1024u,
+              "the masks and a chunk of 64 nodes of 64 words fit the LDS of a workgroup");
+__global__ void __launch_bounds__(BGS_WAVE)
+k_connect_guided_advance(uint32_t height, uint32_t width, uint32_t nw, const int32_t* __restrict__ columns, uint32_t capacity,
+                         uint32_t* trees, int32_t* __restrict__ kept, int64_t root_base) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t guided_lds[];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t node_words = width * 4u;
+    const uint32_t mask_room = (((capacity + 31u) >> 5) + 3u) & ~3u;
+    uint32_t* const mask = guided_lds;              // bit v: node v stays
+    uint32_t* const below = mask + mask_room;       // the marked nodes in the mask words before this one
+    uint32_t* const chunk = below + mask_room;      // 64 nodes
+    const int64_t i = root_base + (int64_t)blockIdx.x;
+    uint32_t* const head = trees + (uint64_t)i * guided_tree_words(height, width, capacity);
+    uint32_t* const planes = head + 4;              // the recorded position, counted in 32-bit words
+    uint32_t* const tree = head + kGuidedHeaderWords + height * width;
+
+    const int32_t c = columns[i];
+    uint32_t used = head[0];
+    used = (uint32_t)__builtin_amdgcn_readfirstlane((int)(used <= capacity ? used : 0u));
+    if (c < 0) {                                    // untouched, a pending leaf included
+        if (kept && lane == 0) kept[i] = (int32_t)(used ? used - 1u : 0u);
+        return;
+    }
+    // the new root: the child of the root's edge c (0: never played, terminal, did not fit, a full column)
+    uint32_t r = (used != 0u && (uint32_t)c < width) ? tree[2u * width + (uint32_t)c] : 0u;
+    r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(r < used ? r : 0u));
+    // the cell the stone takes on the recorded position, and its mover
+    const uint32_t plane_words = 2u * nw;           // 32-bit words a player
+    uint32_t stones = lane < 2u * plane_words ? (uint32_t)__popc(planes[lane]) : 0u;
+    for (int d = 32; d >= 1; d >>= 1) stones += (uint32_t)__shfl_xor((int)stones, d);
+    uint32_t at = 0;
+    if ((uint32_t)c < width) {
+        for (uint32_t y0 = 0; y0 < height; y0 += BGS_WAVE) {
+            const uint32_t bit = (uint32_t)c * (height + 1u) + y0 + lane;
+            const bool taken = y0 + lane < height &&
+                               (((planes[bit >> 5] | planes[plane_words + (bit >> 5)]) >> (bit & 31u)) & 1u) != 0u;
+            at += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(taken));
+        }
+    }
+    if (r == 0u || at >= height) {                  // emptied: the next step starts the tree anew from the batch's board
+        if (lane < 4u) head[lane] = 0;
+        if (kept && lane == 0) kept[i] = 0;
+        return;
+    }
+
+    // ---- mark
+    const uint32_t mask_words = (used + 31u) >> 5;
+    for (uint32_t k = lane; k < mask_words; k += BGS_WAVE) mask[k] = 0;
+    __syncthreads();
+    if (lane == 0) mask[r >> 5] = 1u << (r & 31u);
+    __syncthreads();
+    for (uint32_t base = r & ~63u; base < used; base += 64u) {
+        const uint32_t m0 = mask[base >> 5], m1 = (base >> 5) + 1u < mask_words ? mask[(base >> 5) + 1u] : 0u;
+        if ((m0 | m1) == 0u) continue;              // (uniform) nothing of this chunk is in the subtree
+        const uint32_t count = used - base < 64u ? used - base : 64u;
+        for (uint32_t k = lane; k < count * node_words; k += BGS_WAVE) chunk[k] = tree[(uint64_t)base * node_words + k];
+        __syncthreads();
+        bool done = false;
+        for (;;) {
+            const uint32_t v = base + lane;
+            const bool go = !done && lane < count && ((mask[v >> 5] >> (v & 31u)) & 1u) != 0u;
+            if (__builtin_amdgcn_ballot_w64(go) == 0) break;
+            if (go) {
+                for (uint32_t x = 0; x < width; ++x) {
+                    const uint32_t ch = chunk[lane * node_words + 2u * width + x];
+                    if (ch > v && ch < used) atomicOr(mask + (ch >> 5), 1u << (ch & 31u));
+                }
+                done = true;
+            }
+            __syncthreads();
+        }
+        __syncthreads();                            // the chunk is free for the next one
+    }
+
+    // ---- number
+    uint32_t total = 0;
+    for (uint32_t k0 = 0; k0 < mask_words; k0 += BGS_WAVE) {
+        const uint32_t k = k0 + lane;
+        const uint32_t bits = k < mask_words ? (uint32_t)__popc(mask[k]) : 0u;
+        uint32_t upto = bits;                       // the inclusive scan of the wave
+        for (int d = 1; d < BGS_WAVE; d <<= 1) {
+            const uint32_t other = (uint32_t)__shfl_up((int)upto, d);
+            upto += lane >= (uint32_t)d ? other : 0u;
+        }
+        if (k < mask_words) below[k] = total + upto - bits;
+        total += (uint32_t)__shfl((int)upto, BGS_WAVE - 1);
+    }
+    __syncthreads();
+
+    // ---- move
+    for (uint32_t base = r & ~63u; base < used; base += 64u) {
+        const uint32_t m0 = mask[base >> 5], m1 = (base >> 5) + 1u < mask_words ? mask[(base >> 5) + 1u] : 0u;
+        if ((m0 | m1) == 0u) continue;
+        const uint32_t count = used - base < 64u ? used - base : 64u;
+        for (uint32_t k = lane; k < count * node_words; k += BGS_WAVE) chunk[k] = tree[(uint64_t)base * node_words + k];
+        __syncthreads();                            // every word of the chunk is read before one is written
+        for (uint32_t l = 0; l < count; ++l) {
+            const uint32_t v = base + l;
+            const uint32_t word = mask[v >> 5];
+            if (((word >> (v & 31u)) & 1u) == 0u) continue;
+            const uint32_t to = below[v >> 5] + (uint32_t)__popc(word & ((1u << (v & 31u)) - 1u));
+            if (lane < node_words) {
+                uint32_t x = chunk[l * node_words + lane];
+                if (lane - 2u * width < width) {    // a child word: the child's new index (a kept node's children are kept)
+                    x = (x > v && x < used) ? below[x >> 5] + (uint32_t)__popc(mask[x >> 5] & ((1u << (x & 31u)) - 1u)) : 0u;
+                }
+                tree[(uint64_t)to * node_words + lane] = x;
+            }
+        }
+        __syncthreads();                            // the chunk is free for the next one
+    }
+
+    // ---- header (the tree's writes are issued; the count and the stone go last)
+    __syncthreads();
+    if (lane == 0) {
+        const uint32_t bit = (uint32_t)c * (height + 1u) + at;
+        head[0] = total;
+        head[1] = kGuidedNone;                      // the pending leaf is dropped
+        head[2] = 0;
+        head[3] = 1u;                               // the new root was made with its P
+        planes[((stones & 1u) ? plane_words : 0u) + (bit >> 5)] |= 1u << (bit & 31u);
+        if (kept) kept[i] = (int32_t)(total - 1u);
+    }
+}
+
 // ================================================================================================================
 // UCT tree search for Bounce (bgs_bounce_search_moves, include/bgs.h): k_connect_search's iteration with "column" read as
 // "arm", for a game whose nodes have 1 .. 512 arms and whose descents have no h * w bound.
@@ -2254,6 +2396,19 @@ void connect_guided_step(const bgs_batch* b, int32_t capacity, int32_t cpuct, ui
         case 1: launch(std::integral_constant<int, 1>{}); break;
         case 2: launch(std::integral_constant<int, 2>{}); break;
         default: launch(std::integral_constant<int, 3>{}); break;
+    }
+}
+
+void connect_guided_advance(const bgs_batch* b, const int32_t* d_columns, int32_t capacity, int32_t* d_kept, void* d_trees) {
+    const uint32_t width = (uint32_t)b->cg.w, room = (uint32_t)capacity;
+    // LDS: as connect_forest_advance, with nodes of 4 * width words
+    const uint32_t mask_room = (((room + 31u) >> 5) + 3u) & ~3u;
+    const size_t lds = ((size_t)2 * mask_room + (size_t)64 * width * 4u) * sizeof(uint32_t);
+    constexpr int64_t kMaxBlocks = (int64_t)1 << 30;
+    for (int64_t i0 = 0; i0 < b->n; i0 += kMaxBlocks) {
+        const int64_t blocks = b->n - i0 < kMaxBlocks ? b->n - i0 : kMaxBlocks;
+        hipLaunchKernelGGL(k_connect_guided_advance, dim3((uint32_t)blocks), dim3(BGS_WAVE), lds, b->stream, (uint32_t)b->cg.h, width,
+                           (uint32_t)b->cg.nw, d_columns, room, static_cast<uint32_t*>(d_trees), d_kept, i0);
     }
 }
 

@@ -1291,6 +1291,91 @@ class GuidedSearch(_Guided):
         return self._run(evaluate, simulations)
 
 
+class GuidedForest(GuidedSearch):
+    """A GuidedSearch whose trees are kept from move to move (bgs_connect_guided_advance, include/bgs.h):
+    `GuidedForest(batch, capacity, cpuct)` makes one for a ConnectBatch -- the batch has no maker method for it.  The
+    re-rooting bounds the room of a tree: `capacity` <= GUIDED_ADVANCE_MAX_CAPACITY.
+
+    The loop of self-play: `run(evaluate, simulations)` once, then per move: pick a column a board from `visits`, play
+    it (`ConnectBatch.step_actions` or `step_actions_observe`), `advance` by the same columns -- the subtree under the
+    column played becomes the tree, with every evaluation in it --, and `run(evaluate, simulations, carry=True)`, which
+    searches on from what was kept.  A tree whose column had no subtree, or whose board is not at the recorded position
+    when the next step looks (it was not stepped, or stepped elsewhere, or reset), starts anew on its own.  `visits`,
+    `scores` and `nodes` of a carried tree include what was carried.
+
+    `begin`, `step`, `finish` and `close` are GuidedSearch's."""
+
+    def __init__(self, batch: "ConnectBatch", capacity: int, cpuct: int = DEFAULT_CPUCT):
+        if capacity > _abi.GUIDED_ADVANCE_MAX_CAPACITY:
+            raise ValueError(f"capacity must be at most {_abi.GUIDED_ADVANCE_MAX_CAPACITY} nodes a tree for trees that are advanced "
+                             f"(got {capacity})")
+        super().__init__(batch, capacity, cpuct)
+        t = batch._torch
+        # what `resume` hands the step: rows that no tree reads, because no tree has a leaf pending
+        self._no_rows = (t.zeros(batch._per_action(), dtype=t.float32, device=f"cuda:{batch.device}"),
+                         t.zeros((batch.n,), dtype=t.float32, device=f"cuda:{batch.device}"))
+        self._last = None       # the last call: "begin", "step", "finish", "advance", "resume"; None: fresh memory
+
+    def _call(self, flags: int, priors, values):
+        outs = super()._call(flags, priors, values)
+        self._last = "begin" if flags & _abi.GUIDED_RESTART else "finish" if flags & _abi.GUIDED_FINISH else "step"
+        return outs
+
+    def advance(self, columns, kept=None):
+        """Re-root every tree by its board's column (bgs_connect_guided_advance), enqueued on the batch's stream with no
+        synchronisation: `columns` is an int32[n] device tensor, a negative entry leaves the tree as it is.  Returns
+        `kept`, an int32[n] device tensor (allocated when None): the nodes a tree holds afterwards, the root not counted
+        -- the subtree under the column, or 0 where there was none (the next step starts that tree anew).  The boards
+        are neither read nor stepped: play the same columns with `ConnectBatch.step_actions` before the next step.
+        RuntimeError while an evaluation is pending (the last call was `begin` or `step`): `finish` comes first."""
+        if self._buffer is None:
+            raise RuntimeError("the guided search is closed")
+        if self._last is None:
+            raise RuntimeError("begin() comes first: fresh memory holds no trees")
+        if self._last in ("begin", "step"):
+            raise RuntimeError("finish() comes first: an evaluation is pending, and an advance would drop it")
+        n = self.batch.n    # (columns is an input: "optional", so that it is checked and never allocated)
+        columns, kept = self.batch._device_tensors("GuidedForest.advance", [("columns", columns, (n,), "int32", True), ("kept", kept, (n,))])
+        if columns is None:
+            raise TypeError(f"columns must be an int32 device tensor of shape ({n},)")
+        _abi.check(_abi.lib().bgs_connect_guided_advance(
+            self.batch._handle, ctypes.c_void_p(columns.data_ptr()), ctypes.c_int32(self.capacity), ctypes.c_void_p(kept.data_ptr()),
+            ctypes.c_void_p(self._buffer.data_ptr()), ctypes.c_size_t(self._buffer.numel())))
+        self._last = "advance"
+        return kept
+
+    def resume(self):
+        """The step with nothing to apply, on rows the object holds itself: every tree reports and selects its next
+        leaf, a carried tree from what it holds, an emptied one from its board.  Returns the seven outputs; `step` or
+        `finish` take the evaluator's rows for them, as after `begin`.  (A second `resume` in their place would feed
+        those leaves the object's own rows: zeros, that is flat priors and a value of 0.)
+        RuntimeError unless the last call was `finish`, `advance` or `resume`."""
+        if self._buffer is None:
+            raise RuntimeError("the guided search is closed")
+        if self._last not in ("finish", "advance", "resume"):
+            raise RuntimeError("resume() follows finish(), advance() or resume()" +
+                               (": begin() comes first, fresh memory holds no trees" if self._last is None else
+                                ": an evaluation is pending, finish() comes first"))
+        outs = self._call(0, *self._no_rows)
+        self._last = "resume"
+        return outs
+
+    def run(self, evaluate, simulations: int, carry: bool = False):
+        """`GuidedSearch.run`, and with `carry` the same on the trees as they are: `resume` in place of `begin`, then
+        `simulations` evaluations a tree and `finish`.  A carried root has its P, so all `simulations` evaluations go
+        below it.  RuntimeError with `carry` on fresh memory."""
+        if not carry:
+            return self._run(evaluate, simulations)
+        if simulations < 1:
+            raise ValueError(f"simulations must be >= 1 (got {simulations})")
+        if self._last is None:
+            raise RuntimeError("carry=True on fresh memory: there are no trees to carry")
+        outs = self.resume()
+        for _ in range(int(simulations) - 1):
+            outs = self.step(*evaluate(*(outs[i] for i in self._leaves)))
+        return self.finish(*evaluate(*(outs[i] for i in self._leaves)))
+
+
 class BounceBatch(_Batch):
     """N Bounce boards sharing one start grid: ``Config(grid)`` (reference bounce.cpp:26) times n."""
 

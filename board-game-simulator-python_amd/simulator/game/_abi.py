@@ -34,6 +34,7 @@ GUIDED_RESTART, GUIDED_FINISH = 1, 2   # BGS_GUIDED_RESTART / BGS_GUIDED_FINISH:
 GUIDED_EVALUATE, GUIDED_TERMINAL, GUIDED_IDLE = 0, 1, 2   # BGS_GUIDED_*: the values of its leaf_kind
 GUIDED_MAX_CAPACITY = 1 << 20   # BGS_GUIDED_MAX_CAPACITY: the nodes a guided tree may hold
 GUIDED_MAX_VISITS = 1 << 19   # BGS_GUIDED_MAX_VISITS: the simulations a guided root takes
+GUIDED_ADVANCE_MAX_CAPACITY = 65536   # BGS_GUIDED_ADVANCE_MAX_CAPACITY: the nodes a guided tree may hold to be advanced
 HALVING_SHORT = -2   # bgs_bounce_evaluate_moves_halving: best[i] of a running board the budget is too small for
 
 GAME_CONNECT = 1
@@ -243,6 +244,9 @@ SIGNATURES = {
         ctypes.c_int,
         [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t],
+    ),
+    "bgs_connect_guided_advance": (
+        ctypes.c_int, [c_handle, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
     ),
     "bgs_bounce_forest_bytes": (ctypes.c_int, [c_handle, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]),
     "bgs_bounce_forest_search": (

@@ -20,8 +20,10 @@ from __future__ import annotations
 
 from typing import Callable, Dict, List, Optional, Sequence
 
-from .agents import _Agent, _Bounce, _Connect, _only
-from .batch import DEFAULT_CPUCT
+import numpy as np
+
+from .agents import TreeSearchAgent, _Agent, _Bounce, _Connect, _only
+from .batch import DEFAULT_CPUCT, GuidedForest
 
 
 class _Guided(_Agent):
@@ -110,6 +112,60 @@ class GuidedSearchAgent(_Guided):
         """the search over `states` (Connect states that share one Config): the host copies of (visits int32[n, w],
         scores int32[n, w], best int32[n], nodes int32[n])"""
         return self._run(states)
+
+
+class GuidedReuseAgent(GuidedSearchAgent):
+    """``GuidedSearchAgent`` that keeps its trees from call to call (``simulator.batch.GuidedForest``,
+    bgs_connect_guided_advance): the evaluations under the moves played are not paid for twice.  The agent holds a forest
+    per (Config, number of states) and remembers the grids it last searched there.  Before a search it advances the tree
+    at index k by the one or two stones that lead from the remembered grid k to the new one
+    (``TreeSearchAgent.stones_between``: the remembered mover's stone first), in two ``advance`` calls; an equal grid is
+    searched on, and any other difference passes -1, where the step's own check starts the tree anew.  So the states of
+    successive calls must keep their indices.  Then ``simulations`` evaluations a tree go on top of what was kept.
+
+    ``predict`` gives shares of the root's visits, carried ones included (they still sum to 1); ``search`` returns
+    ``kept`` -- the nodes every tree held after the last advance, the root not counted; zeros on the first search -- as a
+    fifth element.  ``capacity`` is the room of a tree in nodes; None: ``2 * simulations + 1``, the nodes one search can
+    make plus as many carried ones.  That is the forest agent's allowance and not a measurement: a tree that is full
+    stops growing until the next advance frees room."""
+
+    _who = "GuidedReuseAgent values"
+
+    def __init__(self, evaluate: Callable, simulations: int = 128, cpuct: int = DEFAULT_CPUCT, capacity: Optional[int] = None,
+                 device: int = 0):
+        super().__init__(evaluate, simulations, cpuct, capacity, device)
+        if capacity is None:
+            self.capacity = 2 * self.simulations + 1
+        self._searched: Dict[tuple, tuple] = {}       # key of the batch -> (grids, movers) of its last search
+
+    def _make(self, b):
+        return GuidedForest(b, self.capacity, self.cpuct)
+
+    def search(self, states: Sequence):
+        """the search over `states` (Connect states that share one Config), on the trees of the last search there: the
+        host copies of (visits int32[n, w], scores int32[n, w], best int32[n], nodes int32[n], kept int32[n])"""
+        _only(self._game, states[0], self._who, self._elsewhere)
+        b, arrays = self._loaded(states, self._who, self._game)
+        key = self._game.key(states[0].config, len(states))
+        forest = self._searches.get(key)
+        if forest is None:
+            forest = self._searches[key] = self._make(b)
+        last = self._searched.get(key)
+        kept = np.zeros(len(states), dtype=np.int32)
+        if last is not None:
+            t = b._need_torch("GuidedReuseAgent")
+            plies = np.array([TreeSearchAgent.stones_between(last[0][k], int(last[1][k]), arrays[0][k]) for k in range(len(states))],
+                             dtype=np.int32)
+            for ply in (plies[:, 0], plies[:, 1]):      # the own move, then the reply: two calls
+                kept = forest.advance(t.from_numpy(np.ascontiguousarray(ply)).to(f"cuda:{b.device}"))
+            kept = kept.cpu().numpy()
+        out = forest.run(self.evaluate, self.simulations, carry=last is not None)
+        self._searched[key] = (arrays[0].copy(), arrays[1].copy())
+        return tuple(x.cpu().numpy() for x in out[self._report:]) + (kept,)
+
+    def close(self) -> None:
+        self._searched.clear()
+        super().close()
 
 
 class BounceGuidedSearchAgent(_Guided):

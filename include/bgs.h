@@ -403,10 +403,36 @@ BGS_API int bgs_connect_forest_advance(bgs_batch* b, const int32_t* columns, int
  *      descend.  The path and the kind are recorded, and leaf_grid[i] (int8[h][w], in bgs_read_grid's encoding),
  *      leaf_player[i] (the leaf's ply & 1) and leaf_kind[i] are written.  IDLE rows carry the root's grid and player.
  * A tree's result depends only on its board and the rows it was fed, so any split of the batch gives the same trees.
+ * A call with flags 0 on a tree with nothing pending -- one that BGS_GUIDED_FINISH or bgs_connect_guided_advance left --
+ * applies nothing and reads neither that tree's priors row nor its values entry: it reports and selects.  That is how a
+ * search RESUMES on trees that were carried; it needs no flag of its own (priors and values must still be device
+ * pointers).
  * Refused (BGS_ERR_ARG, with a message; the outputs and the trees are untouched): a Bounce batch, a generic batch, C < 2
  * or C > BGS_GUIDED_MAX_CAPACITY, cpuct outside [0, 4096], unknown flag bits, BGS_GUIDED_RESTART together with
  * BGS_GUIDED_FINISH, NULL trees, leaf_grid, leaf_player or leaf_kind, NULL priors or values without BGS_GUIDED_RESTART, a
- * misaligned pointer, trees_bytes too small. */
+ * misaligned pointer, trees_bytes too small.
+ * bgs_connect_guided_advance re-roots every tree, so that a loop that searches, plays and searches again keeps the
+ * evaluations under the move it played: columns int32[n], for tree i with c = columns[i]:
+ *   c < 0: the share is untouched, a pending leaf included; kept[i] = the nodes in use, the root not counted (0 for an
+ *     emptied tree).
+ *   The root's edge c has a child r, c < width, and column c of the recorded position has room: the subtree of r becomes
+ *     the tree and r becomes node 0; the kept nodes stay in the order they were made; n, s, P and the parent/child
+ *     relations of every kept node are unchanged; the recorded position gets the stone of column c (a plain drop by the
+ *     side to move, no win test); the pending leaf is dropped (kind none, a path of no edge) and the root counts as one
+ *     that has its P.  kept[i] = the nodes after the call, the root not counted.
+ *   Anything else -- an edge never played, a terminal edge, a node that did not fit, a full column, c >= width, a tree
+ *     that is already empty, a node count above C --: the tree is emptied (no node, nothing pending, a root without P),
+ *     kept[i] = 0, and the next step starts the tree anew from the batch's board, by its check.
+ * The call neither reads nor modifies the boards or bgs_steps: the caller plays the same columns with bgs_step_actions
+ * before the next bgs_connect_guided_step; if it does not, that step's check finds other planes and empties the tree.
+ * Two plies (the own move, then the reply) are two calls.
+ * Every pointer is a device pointer, as in the step: `trees` 256-byte aligned, columns and kept 16-byte aligned, kept may
+ * be NULL; an enqueue on the batch's stream with no synchronisation and no allocation, so it can sit in a captured graph;
+ * there is no host variant.  trees, capacity and trees_bytes are those of bgs_connect_guided_step and
+ * bgs_connect_guided_bytes.  The re-rooting keeps its scratch on the chip, as the forest's does, which bounds C here:
+ * C <= BGS_GUIDED_ADVANCE_MAX_CAPACITY; larger trees can be searched, not advanced.
+ * Refused (BGS_ERR_ARG, with a message; kept and the trees are untouched): what bgs_connect_guided_bytes refuses,
+ * C > BGS_GUIDED_ADVANCE_MAX_CAPACITY, NULL columns, NULL trees, a misaligned pointer, trees_bytes too small. */
 #define BGS_GUIDED_RESTART 1u      /* empty every tree first; nothing is pending; priors/values are not read */
 #define BGS_GUIDED_FINISH  2u      /* apply the pending evaluation, select nothing */
 #define BGS_GUIDED_EVALUATE 0      /* leaf_kind: the caller's priors[i] / values[i] are wanted for this leaf */
@@ -420,6 +446,9 @@ BGS_API int bgs_connect_guided_step(bgs_batch* b, int32_t capacity, int32_t cpuc
                                     int8_t* leaf_grid, int8_t* leaf_player, int32_t* leaf_kind,
                                     int32_t* visits, int32_t* scores, int32_t* best, int32_t* nodes,
                                     void* trees, size_t trees_bytes);
+#define BGS_GUIDED_ADVANCE_MAX_CAPACITY 65536/* = BGS_CONNECT_FOREST_MAX_CAPACITY: the same scratch on the chip */
+BGS_API int bgs_connect_guided_advance(bgs_batch* b, const int32_t* columns, int32_t capacity,
+                                       int32_t* kept, void* trees, size_t trees_bytes);
 /* Flat Monte-Carlo evaluation of every legal move of every board (Bounce, bit-packed boards only: at most 64 cells,
  * piece values <= 15).  counts int32[n][width][height * width][3]: entry [i][x][c] = (wins, draws, losses) of the
  * player to move at board i over `playouts` games that start with the move of the piece in column x of the active row
